@@ -2,7 +2,7 @@
 """Headline benchmark: frames/s of VideoDepthAnything.forward on synthetic 1x32x518x518, ViT-L, fp16
 operands (BASELINE.json metric / configs[2]), on N MI355X of one node.
 
-  python bench.py [--gpus N --steps K --warmup W] [--encoder vitl|vits] [--video N_FRAMES]
+  python bench.py [--gpus N --steps K --warmup W] [--encoder vitl|vits] [--video N_FRAMES] [--dump-outputs DIR] [--full]
   N > 1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
               --master-port P bench.py --gpus N --steps K --warmup W
           (a bare `python bench.py --gpus N` starts exactly that command as a CHILD process and relays its one JSON line)
@@ -14,9 +14,14 @@ A step = one forward pass over one 32-frame clip (one sliding window) per rank, 
 Windows are independent units: ranks shard them with no data-path collective; for N > 1
 each step's depth maps are all-gathered (what the stitcher needs) asynchronously under the next step's compute; the timed region
 ends when every gather has completed. Rank 0 prints
-ONE JSON line; `value` is whole-job frames/s. `roofline` is for the dominant kernel, from HIP events
-recorded on the launch stream around each of its launches inside the timed region; `cpu_baseline` is
+ONE JSON line; `value` is whole-job frames/s, `ms_per_step` the time of one timed step.
+--dump-outputs DIR: after the timed steps, rank 0 writes what its last step returned as DIR/depth.npy (float32; the inputs are
+          seeded, so two builds run with the same arguments can be compared output for output).
+--full: also what the headline figure does not need. `roofline` is for the dominant kernel, from HIP events
+recorded on the launch stream around each of its launches inside the timed region, with per-kernel figures in `kernels`;
+`two_clips_in_flight` is an extra pass with two clips on two HIP streams; `cpu_baseline` is
 the CPU oracle (oracle/vda_oracle.py, the checker) timed on a bounded sample on rank 0 at N=1.
+Without --full these are not measured (`roofline` is null) and the timed steps carry no profiling events.
 """
 import argparse
 import json
@@ -24,6 +29,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -31,6 +37,18 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 # algorithmic FLOPs per 32-frame clip (2*MAC, matmul/conv only, reference op count)
 CLIP_TFLOP = {"vitl": 44.95, "vits": 3.881}
 MFMA_PEAK_TFLOPS = 2500.0      # MI355X dense fp16/bf16 (MI355X_MICROARCH.md)
+DUMP_BYTES = 64_000_000        # --dump-outputs: at most this much in all
+
+
+def dump_outputs(d, name, a):
+    """--dump-outputs: the timed path's result `a` (frames on the leading axis) as d/<name>.npy in float32. An output larger
+    than DUMP_BYTES is written as evenly spaced frames - the same frames for the same arguments."""
+    os.makedirs(d, exist_ok=True)
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if a.nbytes > DUMP_BYTES:
+        keep = DUMP_BYTES // (a.nbytes // a.shape[0])
+        a = a[np.linspace(0, a.shape[0] - 1, keep).round().astype(np.int64)]
+    np.save(os.path.join(d, name + ".npy"), a)
 
 
 def physical_cores():
@@ -133,7 +151,6 @@ def video_bench(args, model, dist, backend, world, rank, dev):
     """BASELINE.json configs[3] / SURVEY.md section 8(d): infer_video_depth (video_depth.py:166-254) over N synthetic 518x518 frames.
     Windows are sharded round-robin over the ranks with no data-path collective; one all-gather per round delivers the windows to
     the stitcher (rank 0 returns the video, the other ranks return None). A step = one pass over the whole video."""
-    import numpy as np
     from video_depth_anything_amd.scheduler import plan_windows
     n = args.video
     frames = np.random.default_rng(0).integers(0, 256, (n, 518, 518, 3), dtype=np.uint8)      # SURVEY 8(d): the same video on every rank
@@ -165,6 +182,8 @@ def video_bench(args, model, dist, backend, world, rank, dev):
     if rank != 0:
         return
     assert out is not None and out.shape == (n, 518, 518) and out.dtype == np.float32 and np.isfinite(out).all() and (out >= 0).all()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "depth", out)
     nw = len(plan_windows(n))
     prec = "fp32" if args.fp32 else "fp16"
     peak = 157.3 if args.fp32 else MFMA_PEAK_TFLOPS
@@ -202,7 +221,12 @@ def main():
     ap.add_argument("--video", type=int, default=0, metavar="N_FRAMES",
                     help="configs[3]: time infer_video_depth over N synthetic 518x518 frames (output frames/s) instead of the clip forward")
     ap.add_argument("--exchange", default="windows", choices=["windows", "keys"], help="--video, N > 1: what the ranks exchange per round")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the depth maps of the last one as DIR/depth.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the dominant kernel's roofline and per-kernel times, the two-clips-in-flight pass and the CPU baseline")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))                 # the parent touches no GPU; the ranks are its grandchildren
@@ -263,11 +287,12 @@ def main():
         dist.all_gather(parts, outs[s].cpu())
         gathered[s].copy_(torch.stack(parts))
         return None
-    # 1 in 8 GEMM / conv launches of each shape with at least 40 GFLOP is bracketed by HIP events on the launch stream (an event pair
-    # costs ~10 us of dispatch: every launch bracketed is ~1 ms per ViT-L clip, this is < 0.15 ms; the small launches of the head
-    # cannot be the dominant kernel and are only counted)
-    model.engine.set_option("profile_min_gflop", 40 if args.encoder == "vitl" else 4)
-    model.engine.profile_start(every=8)
+    # --full: 1 in 8 GEMM / conv launches of each shape with at least 40 GFLOP is bracketed by HIP events on the launch stream (an
+    # event pair costs ~10 us of dispatch: every launch bracketed is ~1 ms per ViT-L clip, this is < 0.15 ms; the small launches of
+    # the head cannot be the dominant kernel and are only counted)
+    if args.full:
+        model.engine.set_option("profile_min_gflop", 40 if args.encoder == "vitl" else 4)
+        model.engine.profile_start(every=8)
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
@@ -284,17 +309,19 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    prof = model.engine.profile_stop()          # {kernel: launches, flops, timed, timed_ms, timed_flops}
+    prof = model.engine.profile_stop() if args.full else None      # {kernel: launches, flops, timed, timed_ms, timed_flops}
 
     if dist is not None:
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, "depth", outs[args.steps - 1].cpu().numpy())   # before the extra pass reuses `outs`
 
     # Extra pass, NOT part of `value`: the same K forwards with TWO clips in flight per GPU (two HIP streams, two workspace slots) -
     # what infer_video_depth does with a video's independent windows. Reported beside the one-at-a-time headline number.
     inflight2 = None
-    if world == 1 and not args.no_inflight2:
+    if args.full and world == 1 and not args.no_inflight2:
         lanes = [torch.cuda.Stream(device=dev) for _ in range(2)]
         for j in range(2):
             with torch.cuda.stream(lanes[j]):
@@ -310,24 +337,6 @@ def main():
                      "note": "same K forwards, two clips in flight on two HIP streams (the video scheduler's mode); not `value`"}
 
     if rank == 0:
-        # ---- dominant kernel: per-launch durations from the events recorded in the timed region
-        # (1 launch in 8 of each large shape is bracketed; totals = sampled rate x all launches' algorithmic flops)
-        agg = {k: [v["timed"], v["timed_ms"] * 1e-3, v["timed_flops"]] for k, v in prof.items() if v["timed"] > 0}
-        launches = {k: (v["launches"], v["flops"]) for k, v in prof.items()}
-        est = {k: launches[k][1] / (v[2] / v[1]) for k, v in agg.items()}      # estimated seconds in the timed region
-        dom = max(est, key=est.get)
-        sampled, secs, flops = agg[dom]
-        calls = launches[dom][0]
-        # HBM bytes per launch of that kernel: cannot be read live (needs rocprofv3 --pmc passes); taken from the
-        # committed PMC summary of the same command (tools/pmc_bench.sh -> profiles/), null when absent.
-        traffic = None
-        for rnd in ("r04", "r03", "r02", "r01"):
-            pmc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", rnd, f"{args.encoder}_pmc_hbm_traffic.json")
-            if os.path.exists(pmc) and not args.fp32:
-                traffic = json.load(open(pmc))["kernels"].get(dom, {}).get("hbm_bytes_per_launch")
-                if traffic is not None:
-                    break
-        achieved = flops / secs / 1e12
         fps = world * args.steps * T / dt
         peak = 157.3 if args.fp32 else MFMA_PEAK_TFLOPS          # fp32-input MFMA runs at 1/16 of the fp16 rate (MI355X_MICROARCH.md)
         prec = "fp32" if args.fp32 else "fp16"
@@ -340,19 +349,39 @@ def main():
                                    f"(BASELINE.json configs[{2 if args.encoder == 'vitl' else 1}])",
                        "clips_per_step_per_gpu": 1, "parallelism": f"independent windows x{world}" + (", per-step all-gather of depth overlapped with compute" if world > 1 else ""),
                        "world": (dist.get_world_size() if dist is not None else 1), "backend": (dist.get_backend() if dist is not None else None)},
-            "roofline": {"bound": "mfma", "kernel": dom, "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
-                         "frac": achieved / peak, "traffic": traffic, "launches": calls,
-                         "launches_timed": sampled, "avg_launch_us": secs / sampled * 1e6,
-                         "algorithmic_gflop_per_launch": flops / sampled / 1e9, "share_of_step_time": est[dom] / dt},
+            "roofline": None,
             "model_tflops": CLIP_TFLOP[args.encoder] * world * args.steps / dt,
             "model_mfma_frac": CLIP_TFLOP[args.encoder] * world * args.steps / dt / (peak * world),
-            "kernels": {k: {"launches": launches[k][0], "launches_timed": v[0], "ms_per_step": est[k] / args.steps * 1e3,
-                            "tflops": v[2] / v[1] / 1e12} for k, v in agg.items()},
         }
-        if inflight2 is not None:
-            line["two_clips_in_flight"] = inflight2
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(args.encoder, full=not args.cpu_sample)
+        if args.full:
+            # ---- dominant kernel: per-launch durations from the events recorded in the timed region
+            # (1 launch in 8 of each large shape is bracketed; totals = sampled rate x all launches' algorithmic flops)
+            agg = {k: [v["timed"], v["timed_ms"] * 1e-3, v["timed_flops"]] for k, v in prof.items() if v["timed"] > 0}
+            launches = {k: (v["launches"], v["flops"]) for k, v in prof.items()}
+            est = {k: launches[k][1] / (v[2] / v[1]) for k, v in agg.items()}      # estimated seconds in the timed region
+            dom = max(est, key=est.get)
+            sampled, secs, flops = agg[dom]
+            calls = launches[dom][0]
+            # HBM bytes per launch of that kernel: cannot be read live (needs rocprofv3 --pmc passes); taken from the
+            # committed PMC summary of the same command (tools/pmc_bench.sh -> profiles/), null when absent.
+            traffic = None
+            for rnd in ("r04", "r03", "r02", "r01"):
+                pmc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", rnd, f"{args.encoder}_pmc_hbm_traffic.json")
+                if os.path.exists(pmc) and not args.fp32:
+                    traffic = json.load(open(pmc))["kernels"].get(dom, {}).get("hbm_bytes_per_launch")
+                    if traffic is not None:
+                        break
+            achieved = flops / secs / 1e12
+            line["roofline"] = {"bound": "mfma", "kernel": dom, "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
+                                "frac": achieved / peak, "traffic": traffic, "launches": calls,
+                                "launches_timed": sampled, "avg_launch_us": secs / sampled * 1e6,
+                                "algorithmic_gflop_per_launch": flops / sampled / 1e9, "share_of_step_time": est[dom] / dt}
+            line["kernels"] = {k: {"launches": launches[k][0], "launches_timed": v[0], "ms_per_step": est[k] / args.steps * 1e3,
+                                   "tflops": v[2] / v[1] / 1e12} for k, v in agg.items()}
+            if inflight2 is not None:
+                line["two_clips_in_flight"] = inflight2
+            if world == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline(args.encoder, full=not args.cpu_sample)
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.destroy_process_group()

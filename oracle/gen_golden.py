@@ -322,6 +322,21 @@ def main():
                         depth_autocast_fp16=autocast_fp16(lambda: model.forward(x)).float().numpy(), sd_seed=0, sd_checksum=sd_checksum(sd))
     print("vits_forward", depth.shape, float(depth.mean()))
 
+    # ---- 3b. the same clip through the outlier state dicts of tests/_outliers.py: depth and its fp16 anchor per kind ----
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    from _outliers import outlier_state_dict
+    ref_root = os.path.dirname(os.path.dirname(os.path.abspath(sys.modules["video_depth_anything.video_depth"].__file__)))
+    out = {}
+    for kind in ("channels", "offset", "both"):
+        osd = outlier_state_dict(cfg, seed=21, kind=kind)
+        omodel = build_reference(cfg, osd, ref_root)                        # (section 4 goes on with `model` and `sd` above)
+        with torch.no_grad():
+            out[f"{kind}_depth"] = omodel.forward(x).numpy()
+        out[f"{kind}_depth_autocast_fp16"] = autocast_fp16(lambda: omodel.forward(x)).float().numpy()
+        out[f"{kind}_sd_checksum"] = sd_checksum(osd)
+    np.savez_compressed(os.path.join(OUT, "vits_outlier_forward.npz"), x_seed=102, sd_seed=21, **out)
+    print("vits_outlier_forward", ", ".join(f"{k} {float(v.mean())}" for k, v in out.items() if k.endswith("_depth")))
+
     # ---- 4. real ViT-S, one 518x518 frame (stored pos_embed path, 1370 tokens) ----
     g = torch.Generator().manual_seed(103)
     x = torch.randn(1, 1, 3, 518, 518, generator=g)

@@ -36,3 +36,9 @@ def test_self_launch_starts_the_launcher_as_a_child_and_relays_its_exit_code(tmp
 def test_launcher_world_size_must_match_gpus():
     r = _run(["--gpus", "4", "--steps", "1"], env={"WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode != 0 and "started 2 rank(s)" in (r.stdout + r.stderr)
+
+
+def test_steps_must_be_positive():
+    """`ms_per_step` and --dump-outputs (the last timed step's depth) need at least one timed step: rejected before any GPU call."""
+    r = _run(["--steps", "0", "--warmup", "0", "--encoder", "vits"])
+    assert r.returncode != 0 and "--steps must be at least 1" in r.stderr, r.stderr[-2000:]

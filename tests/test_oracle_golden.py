@@ -26,7 +26,9 @@ def load(golden_dir, name):
 def seeded_sd(cfg, z):
     sd = synthetic_state_dict(cfg, seed=int(z["sd_seed"]))
     chk = np.array([float(v.double().abs().sum()) for v in sd.values()])
-    np.testing.assert_allclose(chk, z["sd_checksum"], rtol=1e-12, err_msg="seeded state dict drifted from the fixture's")
+    # torch.randn's CPU kernels differ in the last bit between instruction sets (scalar / AVX2 / AVX-512: up to 9e-8 of a sum),
+    # so the same seed gives a host-dependent ulp here and there; a changed seeding moves these sums by orders of magnitude more
+    np.testing.assert_allclose(chk, z["sd_checksum"], rtol=1e-6, err_msg="seeded state dict drifted from the fixture's")
     return sd
 
 
