@@ -335,7 +335,9 @@ int vda_affine_clamp_f32(const float* in, const float* scale_shift, float* out, 
  * Allocation / synchronisation: vda_load_weight copies synchronously (host or device source); vda_finalize_weights packs
  * the fp16 layouts on the device and synchronises; the FIRST vda_forward of a new (shape, precision) - or vda_prepare -
  * may allocate (the fp32 weight pack, the positional embedding at that grid, the handle's own workspace when the caller
- * gave none). After that vda_forward only enqueues kernels on `stream`. */
+ * gave none). After that vda_forward only enqueues kernels on `stream` - and, with option "enc_split" (default on; fp16, not while
+ * `stream` is capturing), on one stream the handle owns per caller stream, forked from `stream` and joined back into it before
+ * anything later on `stream` runs: completion of `stream`'s work still means the forward is done. */
 typedef struct vda_model vda_model;
 
 typedef struct vda_config {

@@ -354,11 +354,13 @@ extern "C" int vda_gemm_row_range(const vda_gemm_args* args, int r0, int rows, v
     return 0;
 }
 
-static int vda_gemm_f16_impl(const vda_gemm_args* args, vda_stream_t stream, bool may_split);
+static int vda_gemm_f16_impl(const vda_gemm_args* args, vda_stream_t stream, bool may_split, int m_plan);
 
-extern "C" int vda_gemm_f16(const vda_gemm_args* args, vda_stream_t stream) { return vda_gemm_f16_impl(args, stream, true); }
+extern "C" int vda_gemm_f16(const vda_gemm_args* args, vda_stream_t stream) { return vda_gemm_f16_impl(args, stream, true, 0); }
 
-static int vda_gemm_f16_impl(const vda_gemm_args* args, vda_stream_t stream, bool may_split) {
+int vda_gemm_f16_planned(const vda_gemm_args* args, vda_stream_t stream, int m_plan) { return vda_gemm_f16_impl(args, stream, true, m_plan); }
+
+static int vda_gemm_f16_impl(const vda_gemm_args* args, vda_stream_t stream, bool may_split, int m_plan) {
     VDA_REQUIRE(args != nullptr, "vda_gemm_f16: null args");
     vda_gemm_args a = *args;
     VDA_REQUIRE(a.A && a.W && a.out, "vda_gemm_f16: null operand");
@@ -425,6 +427,7 @@ static int vda_gemm_f16_impl(const vda_gemm_args* args, vda_stream_t stream, boo
             break;
     }
     hipStream_t s = (hipStream_t)stream;
+    const int Mp = m_plan > a.M ? m_plan : a.M;      // the rows the shape decisions below are taken for (vda_gemm_f16_planned)
     // Narrow-output 3x3 convs (Cout <= 64: the ViT-S head) run as a patch-in-LDS direct convolution instead of an implicit GEMM
     // (variant 7 forces it, any other explicit variant or VDA_CONV_LDS=0 keeps the GEMM: A/B and cross-checks).
     static const int conv_lds = getenv("VDA_CONV_LDS") ? atoi(getenv("VDA_CONV_LDS")) : 1;
@@ -451,7 +454,7 @@ static int vda_gemm_f16_impl(const vda_gemm_args* args, vda_stream_t stream, boo
         big = 128;
     }
     static const int big_min_n = getenv("VDA_GEMM_BIG_MIN_N") ? atoi(getenv("VDA_GEMM_BIG_MIN_N")) : 192;      // A/B hook
-    if (g_gemm_variant < 0 && a.N >= big_min_n && a.M >= 2048) {
+    if (g_gemm_variant < 0 && a.N >= big_min_n && Mp >= 2048) {
         // large-tile kernel; BN picked for the smaller padded width
         const int pad256 = (a.N + 255) / 256 * 256, pad128 = (a.N + 127) / 128 * 128;
         big = pad128 < pad256 ? 128 : 256;
@@ -478,7 +481,7 @@ static int vda_gemm_f16_impl(const vda_gemm_args* args, vda_stream_t stream, boo
         // Non-temporal output stores (8-phase kernel, fp16 row stores) for outputs that no cache will hand to the next kernel:
         // VDA_GEMM_NT_MB (default 192; 0 = never) megabytes and up. ViT-L: qkv, hid, the GEGLU hidden, the 148^2 conv maps; ViT-S: none.
         static const long long nt_mb = getenv("VDA_GEMM_NT_MB") ? atoll(getenv("VDA_GEMM_NT_MB")) : 192;
-        if (nt_mb > 0 && (long long)a.M * a.N * 2 >= nt_mb * 1000000ll) a8.relu_in |= 1 << 24;
+        if (nt_mb > 0 && (long long)Mp * a.N * 2 >= nt_mb * 1000000ll) a8.relu_in |= 1 << 24;
         const int sched8 = (eight && g_gemm_variant > 0) ? ((g_gemm_variant >> 5) & 3) : 0;   // A/B: variant 5 + 32 * sched
         // 192-row tiles when they quantise better on this device: rounds of 256-row tiles against 3/4-size rounds of 192-row tiles
         // (ViT-S proj / fc2: 3 against 2.25; variant 8 forces them). Only the one-barrier 256 x 128 family has the shape.
@@ -486,7 +489,7 @@ static int vda_gemm_f16_impl(const vda_gemm_args* args, vda_stream_t stream, boo
         const int ncu = device_cus();
         if (g_gemm_variant < 0 && !eight && big == 128 && a.a_mode == VDA_A_DENSE) {
             const long long nbn = (a.N + 127) / 128;
-            const long long r256 = (((a.M + 255) / 256) * nbn + ncu - 1) / ncu, r192 = (((a.M + 191) / 192) * nbn + ncu - 1) / ncu;
+            const long long r256 = (((Mp + 255) / 256) * nbn + ncu - 1) / ncu, r192 = (((Mp + 191) / 192) * nbn + ncu - 1) / ncu;
             static const int allow192 = getenv("VDA_GEMM_BM192") ? atoi(getenv("VDA_GEMM_BM192")) : 1;
             tall192 = allow192 && r192 * 3 * 100 < r256 * 4 * 85;                 // at least 15 % fewer tile-time units (a 192-row tile costs ~0.8, not 0.75, of a 256-row one)
         }
@@ -494,7 +497,7 @@ static int vda_gemm_f16_impl(const vda_gemm_args* args, vda_stream_t stream, boo
         // 128-row kernel (four times the tiles, two workgroups per CU) is faster - the head's 19x19 maps: rn4 (46 tiles, K = 9216)
         // 223 -> 133 us, the refinenet4 convs 62 -> 39 us (tools/gemm_ab.py, AB_SHAPES=small). VDA_GEMM_SMALL_GRID=0 switches it off.
         static const int small_grid = getenv("VDA_GEMM_SMALL_GRID") ? atoi(getenv("VDA_GEMM_SMALL_GRID")) : 1;
-        if (g_gemm_variant < 0 && small_grid && ((long long)(a.M + 255) / 256) * ((a.N + big - 1) / big) * 2 <= ncu) {
+        if (g_gemm_variant < 0 && small_grid && ((long long)(Mp + 255) / 256) * ((a.N + big - 1) / big) * 2 <= ncu) {
             g_last_kernel = a.a_mode == VDA_A_DENSE ? (a.N <= 64 ? "gemm_kernel<128, 64, 0>" : "gemm_kernel<128, 128, 0>")
                                                     : (a.N <= 64 ? "gemm_kernel<128, 64, 1>" : "gemm_kernel<128, 128, 1>");
             return launch_small(a, s);
@@ -532,14 +535,16 @@ static int vda_gemm_f16_impl(const vda_gemm_args* args, vda_stream_t stream, boo
         }
         // Row split (vda_gemm_plan_split): whole rounds of 256-row tiles + one launch of 192-row tiles for the remainder. Applied here
         // when the caller left it to the dispatcher (no per-launch sched counters: those belong to ONE launch).
-        if (eight && big == 256 && a.a_mode == VDA_A_DENSE && g_gemm_variant < 0 && may_split && a.tile_rows == 0 && a.sched == nullptr && a.lda != 0) {
+        // (Not for a row range planned as part of a larger GEMM, vda_gemm_f16_planned: its other rows run beside it.)
+        if (eight && big == 256 && a.a_mode == VDA_A_DENSE && g_gemm_variant < 0 && may_split && Mp == a.M && a.tile_rows == 0 && a.sched == nullptr &&
+            a.lda != 0) {
             const int m1 = vda_gemm_plan_split(a.M, a.N, a.K, a.epilogue, a.a_mode);
             if (m1 < a.M) {
                 vda_gemm_args p1 = row_range(a, 0, m1), p2 = row_range(a, m1, a.M - m1);
                 p2.tile_rows = 192;
-                const int rc1 = vda_gemm_f16_impl(&p1, stream, false);
+                const int rc1 = vda_gemm_f16_impl(&p1, stream, false, m_plan);
                 if (rc1 != 0) return rc1;
-                return vda_gemm_f16_impl(&p2, stream, false);
+                return vda_gemm_f16_impl(&p2, stream, false, m_plan);
             }
         }
         if (eight && big == 256 && a.a_mode == VDA_A_DENSE && (a.tile_rows == 192 || g_gemm_variant == 5 + 16 * 64)) {

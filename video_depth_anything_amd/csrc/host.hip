@@ -177,6 +177,13 @@ struct vda_model {
         hipEvent_t fork = nullptr, join = nullptr;
     };
     std::map<hipStream_t, Side> sides;        // one side stream + event pair per caller stream (two forwards may be in flight on two)
+    // vda_set_option("enc_split") (environment default VDA_ENC_SPLIT): the fp16 ln_fold encoder runs as two frame halves, half B on a
+    // LANE stream (one per caller stream) forked after the token rows exist and joined back before the head - see Run::forward
+    // Not while a forward of this handle on ANOTHER caller stream is still in flight (two windows / clips in flight already fill each
+    // other's idle time; splitting them too measured -4 %): `tails` holds the end of the last forward enqueued on each caller stream.
+    int enc_split = 1;
+    std::map<hipStream_t, Side> lanes;
+    std::map<hipStream_t, hipEvent_t> tails;
     int mlp_fused = 0;                        // vda_set_option("mlp_fused"): fc1 + GELU + fc2 + residual in one kernel where built (D = 384; needs ln_fold).
                                               // OFF: measured slower than the two GEMM launches (ViT-S clip 8.69 -> 9.00 ms, mlp_fused.hip's header)
     // Split-stream overflow report (ln_fold): one sticky word in pinned host memory, set by the device at the end of a forward whose
@@ -534,6 +541,7 @@ struct Run {
     size_t ab;                // bytes per activation element
     int32_t* sched = nullptr; // dynamic-schedule counters: 8 per GEMM launch of the forward, zeroed at its start
     int nsched = 0;           // launches so far (dry pass: the count that sizes the block)
+    int mplan = 0;            // != 0: the GEMMs are row ranges of an mplan-row GEMM, dispatched as it would be (vda_gemm_f16_planned)
 
     void* buf(const std::string& name, size_t elems, size_t esize) {
         const size_t bytes = (elems * esize + 255) & ~(size_t)255;
@@ -558,8 +566,10 @@ struct Run {
     // A large dense GEMM runs as two launches when that quantises better on this device (vda_gemm_plan_split: whole rounds of
     // 256-row tiles + the remainder on 192-row tiles). Split HERE rather than inside vda_gemm_f16 so that each launch has its own
     // dynamic-schedule counters and its own profile bracket (kernel name, FLOPs of its rows).
+    // A half of enc_split (mplan != 0) runs as ONE launch: the remainder launch pays only when the GEMM has the chip to itself, and
+    // beside the other half it lost (ViT-L fc2, in-process A/B: 50.52 -> 50.13 ms per clip without it, profiles/r05).
     int gemm(vda_gemm_args a) {
-        if (prec == VDA_PREC_F16) {
+        if (prec == VDA_PREC_F16 && mplan == 0) {
             const int m1 = vda_gemm_plan_split(a.M, a.N, a.K, a.epilogue, a.a_mode);
             if (m1 < a.M) {
                 if (dry) {
@@ -588,7 +598,7 @@ struct Run {
         if (a.lda == 0) a.lda = a.K;
         if (a.ldc == 0) a.ldc = a.N;
         Profile& pf = h->prof;
-        if (pf.every <= 0) return prec == VDA_PREC_F32 ? vda_gemm_f32(&a, s) : vda_gemm_f16(&a, s);
+        if (pf.every <= 0) return prec == VDA_PREC_F32 ? vda_gemm_f32(&a, s) : vda_gemm_f16_planned(&a, s, mplan);
         const std::array<int, 5> key = {a.M, a.N, a.K, a.epilogue, a.a_mode};
         const int n = pf.seen[key]++;
         const bool timed = n % pf.every == 0 && 2.0 * a.M * a.N * a.K >= pf.min_flops;
@@ -598,7 +608,7 @@ struct Run {
             VDA_HIP(hipEventCreate(&smp.e1));
             VDA_HIP(hipEventRecord(smp.e0, s));
         }
-        VDA_TRY(prec == VDA_PREC_F32 ? vda_gemm_f32(&a, s) : vda_gemm_f16(&a, s));
+        VDA_TRY(prec == VDA_PREC_F32 ? vda_gemm_f32(&a, s) : vda_gemm_f16_planned(&a, s, mplan));
         const std::string name = prec == VDA_PREC_F32 ? std::string("gemm_f32_kernel") : std::string(vda_gemm_last_kernel());
         const double flops = 2.0 * a.M * a.N * a.K;
         auto& tot = pf.launches[name];
@@ -720,6 +730,15 @@ struct Run {
         const vda_config& c = h->cfg;
         const int BT = B * T, ph = H / PATCH, pw = Wd / PATCH;
         const int P = ph * pw, D = c.embed_dim, NH = c.num_heads, Nt = P + 1, rows = BT * Nt;
+        bool capturing = false;              // (a captured forward stays one linear stream)
+        if (!dry) {
+            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+            if (hipStreamIsCapturing(s, &cs) != hipSuccess) {
+                (void)hipGetLastError();          // (e.g. the legacy stream while another stream captures): treated as capturing
+                cs = hipStreamCaptureStatusActive;
+            }
+            capturing = cs != hipStreamCaptureStatusNone;
+        }
         // dynamic-schedule counters of every GEMM launch below: sized by the dry pass, zeroed here once per forward
         if (prec == VDA_PREC_F16 && h->dyn_sched) {
             const int cap = dry ? 4096 : lay->gemm_launches;
@@ -777,28 +796,98 @@ struct Run {
         // spread whatever offset the stream carries (tests/_outliers.py "offset": mean / sigma ~ 20 cost 15x the standalone
         // LayerNorm's error before this). Every reader of the stream is a LayerNorm - invariant to a per-row shift.
         if (fold && !dry) VDA_TRY(vda_split_center_stats_f32(tok, thi, tlo, lnstat, ENC_LN_EPS, rows, D, s));
-        auto ln_gemm = [&](const std::string& wk, void* out, int epi, int N) -> int {         // LayerNorm(x) @ W^T + b on the hi plane
-            vda_gemm_args a = {};
-            a.A = thi, a.W = W(wk + ".weight.ln"), a.out = out, a.bias = V(wk + ".c2"), a.gamma = V(wk + ".c1"), a.stats = lnstat;
-            a.M = rows, a.N = N, a.K = D, a.a_mode = VDA_A_DENSE, a.epilogue = epi;
-            return gemm(a);
+        // ---- frame halves (option enc_split; fp16 ln_fold path). The encoder is exactly per frame: attention mixes the tokens of one
+        // frame only and every GEMM / LayerNorm row is independent. So frames [0, F) and [F, BT) run as two launch chains, half A on the
+        // caller's stream and half B on the handle's lane stream, and each chain's kernels fill the tail rounds, launch boundaries and
+        // small launches the other leaves idle. Every op is a row range of the same buffers, and each GEMM half is dispatched as the
+        // whole-clip GEMM would be (mplan): the result is bit-identical to one chain. The head (its motion modules mix frames) runs
+        // after the join at full T. A captured forward keeps one stream (a linear graph); the dry pass takes the uncaptured decision
+        // (the larger launch count, which sizes the dynamic-schedule counters).
+        struct Part {
+            int f0, nf;
+            hipStream_t st;
         };
-        auto res_gemm = [&](const void* A, const std::string& wk, const std::string& gk, int K, bool stats_next) -> int {   // x += gamma * (A @ W^T + b)
+        Part parts[2] = {{0, BT, s}, {0, 0, nullptr}};
+        int nparts = 1;
+        vda_model::Side* lane = nullptr;
+        bool split = fold && !mlp1 && h->enc_split != 0 && BT >= 2;
+        if (split && !dry) {
+            split = !capturing;
+            for (auto& kv : h->tails) {
+                if (!split) break;
+                if (kv.first == s || kv.second == nullptr) continue;
+                if (hipEventQuery(kv.second) != hipSuccess) {
+                    (void)hipGetLastError();      // (hipErrorNotReady: that forward is still running)
+                    split = false;
+                }
+            }
+        }
+        if (split) {
+            parts[0] = {0, BT / 2, s};
+            parts[1] = {BT / 2, BT - BT / 2, s};
+            nparts = 2;
+            if (!dry) {
+                vda_model::Side& ln = h->lanes[s];
+                if (ln.stream == nullptr) {
+                    VDA_HIP(hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking));
+                    VDA_HIP(hipEventCreateWithFlags(&ln.fork, hipEventDisableTiming));
+                    VDA_HIP(hipEventCreateWithFlags(&ln.join, hipEventDisableTiming));
+                }
+                lane = &ln;
+                parts[1].st = ln.stream;
+                VDA_HIP(hipEventRecord(ln.fork, s));                   // the centred token planes and their statistics exist
+                VDA_HIP(hipStreamWaitEvent(ln.stream, ln.fork, 0));
+            }
+        }
+        // fn(part) for every part, each on its own stream; the callers go op by op (A.qkv, B.qkv, A.attention, B.attention, ...) so
+        // that neither queue runs dry on the host side
+        auto each = [&](auto&& fn) -> int {
+            const hipStream_t keep = s;
+            int rc = 0;
+            for (int j = 0; j < nparts && rc == 0; ++j) {
+                s = parts[j].st;
+                rc = fn(parts[j]);
+            }
+            s = keep;
+            return rc;
+        };
+        auto ln_gemm = [&](const std::string& wk, void* out, int epi, int N, const Part& p) -> int {   // LayerNorm(x) @ W^T + b on the hi plane
+            const size_t r0 = (size_t)p.f0 * Nt;
             vda_gemm_args a = {};
-            a.A = A, a.W = W(wk + ".weight"), a.out = thi, a.out2 = tlo, a.res = thi, a.res2 = tlo, a.bias = V(wk + ".bias"), a.gamma = V(gk);
-            a.stats = lnpart;
-            a.pos = lnstat;                      // re-centre by the mean the LayerNorm before this branch saw
-            a.M = rows, a.N = D, a.K = K, a.a_mode = VDA_A_DENSE, a.epilogue = VDA_EPI_SCALE_RES_SPLIT;
-            VDA_TRY(gemm(a));
+            a.A = (const h16*)thi + r0 * D, a.W = W(wk + ".weight.ln"), a.out = (h16*)out + r0 * N, a.bias = V(wk + ".c2"), a.gamma = V(wk + ".c1");
+            a.stats = lnstat + r0 * 2;
+            a.M = p.nf * Nt, a.N = N, a.K = D, a.a_mode = VDA_A_DENSE, a.epilogue = epi;
+            mplan = nparts > 1 ? rows : 0;
+            const int rc = gemm(a);
+            mplan = 0;
+            return rc;
+        };
+        auto res_gemm = [&](const void* A, const std::string& wk, const std::string& gk, int K, bool stats_next, const Part& p) -> int {   // x += gamma * (A @ W^T + b)
+            const size_t r0 = (size_t)p.f0 * Nt;
+            const int nr = p.nf * Nt, np = D / 64;
+            vda_gemm_args a = {};
+            a.A = (const h16*)A + r0 * K, a.W = W(wk + ".weight"), a.bias = V(wk + ".bias"), a.gamma = V(gk);
+            a.out = (h16*)thi + r0 * D, a.out2 = (h16*)tlo + r0 * D, a.res = a.out, a.res2 = a.out2;
+            a.stats = lnpart + r0 * np * 2;      // the part's own [np, nr, 2] block of partial statistics
+            a.pos = lnstat + r0 * 2;             // re-centre by the mean the LayerNorm before this branch saw
+            a.M = nr, a.N = D, a.K = K, a.a_mode = VDA_A_DENSE, a.epilogue = VDA_EPI_SCALE_RES_SPLIT;
+            mplan = nparts > 1 ? rows : 0;
+            const int rc = gemm(a);
+            mplan = 0;
+            VDA_TRY(rc);
             // (after the last block nothing reads the statistics: that finalize runs for its overflow check alone, 5 us per clip)
             (void)stats_next;
-            if (!dry) VDA_TRY(vda_ln_stats_finalize(lnpart, lnstat, ENC_LN_EPS, rows, D / 64, ovf, s));
+            if (!dry) VDA_TRY(vda_ln_stats_finalize(lnpart + r0 * np * 2, lnstat + r0 * 2, ENC_LN_EPS, nr, np, ovf, s));
             return 0;
         };
-        auto tap_ln = [&](void* out, int group, int skip) -> int {
+        // final norm of the part's rows; out is the whole tensor (group > 0: compacted, group - skip rows per frame)
+        auto tap_ln = [&](void* out, int group, int skip, const Part& p) -> int {
             if (dry) return 0;
-            return fold ? vda_layernorm_split_f16(thi, tlo, out, V("norm.w"), V("norm.b"), ENC_LN_EPS, rows, D, group, skip, s)
-                        : vda_layernorm_f32_f16(tok, out, V("norm.w"), V("norm.b"), ENC_LN_EPS, rows, D, group, skip, nullptr, 0, 0, s);
+            const size_t r0 = (size_t)p.f0 * Nt, o0 = group > 0 ? (size_t)p.f0 * (Nt / group) * (group - skip) : r0;
+            const int nr = p.nf * Nt;
+            return fold ? vda_layernorm_split_f16((const h16*)thi + r0 * D, (const h16*)tlo + r0 * D, (h16*)out + o0 * D, V("norm.w"), V("norm.b"), ENC_LN_EPS, nr, D,
+                                                  group, skip, s)
+                        : vda_layernorm_f32_f16(tok + r0 * D, (h16*)out + o0 * D, V("norm.w"), V("norm.b"), ENC_LN_EPS, nr, D, group, skip, nullptr, 0, 0, s);
         };
         void* yb = defer ? act("ybuf", (size_t)rows * D) : nullptr;
         auto ln_res = [&](const float* gamma, void* out, const float* w, const float* b, int group, int skip) -> int {
@@ -852,15 +941,20 @@ struct Run {
         for (int i = 0; i < c.depth; ++i) {
             const std::string k = "b" + std::to_string(i) + ".";
             if (fold) {
-                VDA_TRY(ln_gemm(k + "attn.qkv", qkv, VDA_EPI_LN_BIAS_F16, 3 * D));
+                VDA_TRY(each([&](const Part& p) { return ln_gemm(k + "attn.qkv", qkv, VDA_EPI_LN_BIAS_F16, 3 * D, p); }));
             } else {
                 if (!xn_ready) VDA_TRY(layernorm(tok, xn, V(k + "norm1.weight"), V(k + "norm1.bias"), ENC_LN_EPS, rows, D));
                 xn_ready = false;
                 VDA_TRY(dense(xn, W(k + "attn.qkv.weight"), qkv, VDA_EPI_BIAS_F16, rows, 3 * D, D, V(k + "attn.qkv.bias")));
             }
-            if (!dry) VDA_TRY(prec == VDA_PREC_F32 ? vda_attention_f32((const float*)qkv, (float*)ao, BT, Nt, NH, s) : vda_attention_f16(qkv, ao, BT, Nt, NH, s));
+            if (!dry)
+                VDA_TRY(each([&](const Part& p) {
+                    const size_t r0 = (size_t)p.f0 * Nt;
+                    return prec == VDA_PREC_F32 ? vda_attention_f32((const float*)qkv + r0 * 3 * D, (float*)ao + r0 * D, p.nf, Nt, NH, s)
+                                                : vda_attention_f16((const h16*)qkv + r0 * 3 * D, (h16*)ao + r0 * D, p.nf, Nt, NH, s);
+                }));
             if (fold) {
-                VDA_TRY(res_gemm(ao, k + "attn.proj", k + "ls1.gamma", D, true));
+                VDA_TRY(each([&](const Part& p) { return res_gemm(ao, k + "attn.proj", k + "ls1.gamma", D, true, p); }));
             } else if (defer) {
                 VDA_TRY(dense(ao, W(k + "attn.proj.weight"), yb, VDA_EPI_BIAS_F16, rows, D, D, V(k + "attn.proj.bias")));
                 VDA_TRY(ln_res(V(k + "ls1.gamma"), xn, V(k + "norm2.weight"), V(k + "norm2.bias"), 0, 0));
@@ -872,7 +966,7 @@ struct Run {
                 if (!dry)
                     VDA_TRY(vda_mlp_fused_f16(thi, lnstat, W(k + "mlp.fc1.weight.ln"), V(k + "mlp.fc1.c1"), V(k + "mlp.fc1.c2"), W(k + "mlp.fc2.weight.perm"),
                                               V(k + "mlp.fc2.bias"), V(k + "ls2.gamma"), thi, tlo, lnpart, rows, D, 4 * D, rows, s));
-            } else if (fold) VDA_TRY(ln_gemm(k + "mlp.fc1", hid, VDA_EPI_LN_GELU_F16, 4 * D));
+            } else if (fold) VDA_TRY(each([&](const Part& p) { return ln_gemm(k + "mlp.fc1", hid, VDA_EPI_LN_GELU_F16, 4 * D, p); }));
             else VDA_TRY(dense(xn, W(k + "mlp.fc1.weight"), hid, VDA_EPI_BIAS_GELU_F16, rows, 4 * D, D, V(k + "mlp.fc1.bias")));
             bool is_tap = false;
             for (int t = 0; t < 4; ++t) is_tap = is_tap || c.taps[t] == i;
@@ -882,9 +976,9 @@ struct Run {
                 if (mlp1) {
                     if (!dry) VDA_TRY(vda_ln_stats_finalize(lnpart, lnstat, ENC_LN_EPS, rows, D / 64, ovf, s));
                 } else {
-                    VDA_TRY(res_gemm(hid, k + "mlp.fc2", k + "ls2.gamma", 4 * D, !last));
+                    VDA_TRY(each([&](const Part& p) { return res_gemm(hid, k + "mlp.fc2", k + "ls2.gamma", 4 * D, !last, p); }));
                 }
-                if (tp != nullptr) VDA_TRY(tap_ln(tp, Nt, 1));                                             // final norm, cls dropped
+                if (tp != nullptr) VDA_TRY(each([&](const Part& p) { return tap_ln(tp, Nt, 1, p); }));     // final norm, cls dropped
             } else if (defer) {
                 VDA_TRY(dense(hid, W(k + "mlp.fc2.weight"), yb, VDA_EPI_BIAS_F16, rows, D, 4 * D, V(k + "mlp.fc2.bias")));
                 if (last && tp != nullptr) {
@@ -904,13 +998,20 @@ struct Run {
                     // dpt_temporal.py:56-59: the tap becomes GELU(Linear([patch token, cls])); the final norm above dropped the cls
                     // row, so norm the whole token matrix again (cls kept) and gather [patch | cls] rows for one K = 2D GEMM
                     void* full = act("rd_full", (size_t)rows * D);
-                    VDA_TRY(fold ? tap_ln(full, 0, 0) : layernorm(tok, full, V("norm.w"), V("norm.b"), ENC_LN_EPS, rows, D));
                     void* cat = act("rd_cat", (size_t)BT * P * 2 * D);
-                    if (!dry)
-                        VDA_TRY(prec == VDA_PREC_F32 ? vda_readout_concat_f32((const float*)full, (float*)cat, BT, P, D, s)
-                                                     : vda_readout_concat_f16(full, cat, BT, P, D, s));
                     const std::string kr = "readout" + std::to_string(ntap);
-                    VDA_TRY(dense(cat, W(kr + ".w"), tp, VDA_EPI_BIAS_GELU_F16, BT * P, D, 2 * D, V(kr + ".b")));
+                    VDA_TRY(each([&](const Part& p) -> int {
+                        const size_t r0 = (size_t)p.f0 * Nt, q0 = (size_t)p.f0 * P;      // (token rows, patch rows) before the part
+                        VDA_TRY(fold ? tap_ln(full, 0, 0, p) : layernorm(tok, full, V("norm.w"), V("norm.b"), ENC_LN_EPS, rows, D));
+                        if (!dry)
+                            VDA_TRY(prec == VDA_PREC_F32 ? vda_readout_concat_f32((const float*)full + r0 * D, (float*)cat + q0 * 2 * D, p.nf, P, D, s)
+                                                         : vda_readout_concat_f16((const h16*)full + r0 * D, (h16*)cat + q0 * 2 * D, p.nf, P, D, s));
+                        mplan = nparts > 1 ? BT * P : 0;
+                        const int rc = dense((const char*)cat + q0 * 2 * D * ab, W(kr + ".w"), (char*)tp + q0 * D * ab, VDA_EPI_BIAS_GELU_F16, p.nf * P, D, 2 * D,
+                                             V(kr + ".b"));
+                        mplan = 0;
+                        return rc;
+                    }));
                 }
                 taps[ntap++] = tp;
                 if (ntap == 3 && !last && !early_done) {
@@ -930,6 +1031,10 @@ struct Run {
                         side = &sd;
                         VDA_HIP(hipEventRecord(sd.fork, s));               // taps 0..2 are behind this point of the caller's stream
                         VDA_HIP(hipStreamWaitEvent(sd.stream, sd.fork, 0));
+                        if (lane != nullptr) {                              // ... and of the lane's (enc_split: half B's tap rows)
+                            VDA_HIP(hipEventRecord(lane->join, lane->stream));
+                            VDA_HIP(hipStreamWaitEvent(sd.stream, lane->join, 0));
+                        }
                         hipStream_t main_stream = s;
                         s = sd.stream;
                         const int rc = head_early();
@@ -940,6 +1045,10 @@ struct Run {
                     }
                 }
             }
+        }
+        if (lane != nullptr) {                 // half B's encoder is done before anything later on the caller's stream
+            VDA_HIP(hipEventRecord(lane->join, lane->stream));
+            VDA_HIP(hipStreamWaitEvent(s, lane->join, 0));
         }
         if (ntap != 4) {
             vda_set_error("vda_forward: the configuration's taps are not four distinct block indices below depth");
@@ -989,6 +1098,11 @@ struct Run {
             hipLaunchKernelGGL(poison_on_overflow_kernel, dim3(256), dim3(256), 0, s, (const int*)ovf, depth, (long long)BT * H * Wd, (volatile int*)h->ovf_host);
             VDA_LAUNCH_CHECK();
         }
+        if (!dry && !capturing) {
+            hipEvent_t& tail = h->tails[s];
+            if (tail == nullptr) VDA_HIP(hipEventCreateWithFlags(&tail, hipEventDisableTiming));
+            VDA_HIP(hipEventRecord(tail, s));
+        }
         return 0;
     }
 };
@@ -1021,6 +1135,11 @@ int check_shape(const vda_model* h, int B, int T, int H, int W, int prec) {
     VDA_REQUIRE(T <= h->cfg.num_frames, "vda_forward: T=%d exceeds temporal_max_len=%d", T, h->cfg.num_frames);
     VDA_REQUIRE((long long)B * T * ((H / PATCH) * (W / PATCH) + 1) * 4 * h->cfg.embed_dim < (1ll << 31), "vda_forward: clip too large for 32-bit row offsets (B*T*tokens*4*embed_dim)");
     return 0;
+}
+
+int enc_split_default() {
+    static const int v = getenv("VDA_ENC_SPLIT") ? atoi(getenv("VDA_ENC_SPLIT")) : 1;      // (A/B through an unmodified caller)
+    return v != 0;
 }
 
 }  // namespace
@@ -1063,6 +1182,7 @@ extern "C" int vda_create(const vda_config* cfg, vda_model** out) {
     }
     memset(ring, 0, 64);
     h->ovf_host = (volatile int32_t*)ring;
+    h->enc_split = enc_split_default();
     *out = h;
     return 0;
 }
@@ -1070,11 +1190,14 @@ extern "C" int vda_create(const vda_config* cfg, vda_model** out) {
 extern "C" int vda_destroy(vda_model* h) {
     if (h == nullptr) return 0;
     if (h->ovf_host) (void)hipHostFree((void*)h->ovf_host);
-    for (auto& kv : h->sides) {
-        if (kv.second.fork) (void)hipEventDestroy(kv.second.fork);
-        if (kv.second.join) (void)hipEventDestroy(kv.second.join);
-        if (kv.second.stream) (void)hipStreamDestroy(kv.second.stream);
-    }
+    for (auto& kv : h->tails)
+        if (kv.second) (void)hipEventDestroy(kv.second);
+    for (auto* m : {&h->sides, &h->lanes})
+        for (auto& kv : *m) {
+            if (kv.second.fork) (void)hipEventDestroy(kv.second.fork);
+            if (kv.second.join) (void)hipEventDestroy(kv.second.join);
+            if (kv.second.stream) (void)hipStreamDestroy(kv.second.stream);
+        }
     for (void* p : h->owned) (void)hipFree(p);
     delete h;
     return 0;
@@ -1244,7 +1367,7 @@ static int vda_debug_copy_impl(vda_model* h, const char* name, void* dst, int64_
 }
 
 // Tuning / A-B switches of the launch sequence: "residual_in_ln" (default 0), "ln_fold" (default 1), "dyn_sched" (default 0), "oc1_fused"
-// (default 1), "mlp_fused" (default 0), "head_overlap" (default 0): see Run::forward.
+// (default 1), "mlp_fused" (default 0), "head_overlap" (default 0), "enc_split" (default 1, or VDA_ENC_SPLIT): see Run::forward.
 extern "C" int vda_set_option(vda_model* h, const char* name, int value) {
     VDA_REQUIRE(h && name, "vda_set_option: null argument");
     if (strcmp(name, "residual_in_ln") == 0) {
@@ -1268,6 +1391,11 @@ extern "C" int vda_set_option(vda_model* h, const char* name, int value) {
     }
     if (strcmp(name, "head_overlap") == 0) {
         h->head_overlap = value != 0;
+        return 0;
+    }
+    if (strcmp(name, "enc_split") == 0) {                // (< 0: the default, VDA_ENC_SPLIT or 1)
+        h->enc_split = value < 0 ? enc_split_default() : value != 0;
+        h->layouts.clear();                  // the GEMM launch count (dynamic-schedule counters) depends on it
         return 0;
     }
     if (strcmp(name, "mlp_fused") == 0) {

@@ -207,6 +207,12 @@ struct VdaKernelDeviceState {
 // take HALF the chip were measured against two full-grid sequences interleaving freely (tools/two_stream.py, round 4): the capped
 // form loses (ViT-L 2 x 16 frames: 619 against 630 frames/s; two clips: 636 against 652), so nothing in the product sets it.
 extern int g_vda_max_wgs;
+// vda_gemm_f16 with the dispatcher's shape decisions (tile family, 192-row tiles, the small-grid fallback, non-temporal stores) taken
+// for m_plan rows instead of args->M (0: args->M). The forward's encoder runs each GEMM as two frame halves on two streams: each half
+// launch picks the kernel the whole-clip launch would have picked - same family, same per-row arithmetic, same store policy for what
+// the two halves write together. A planned row range is never row-split further (its other rows fill the chip beside it).
+// Library-internal (not part of the C ABI).
+int vda_gemm_f16_planned(const vda_gemm_args* args, vda_stream_t stream, int m_plan);
 inline int vda_prepare_kernel(const void* fn, int dyn_lds_bytes, VdaKernelDeviceState& st) {
     int dev = 0;
     (void)hipGetDevice(&dev);

@@ -42,6 +42,7 @@ class ModelHandle:
             _check(lib.vda_create(C.byref(c), C.byref(h)), "vda_create")
         self._h = h
         self._ws = {}                            # workspace blocks by slot (a caller keeping two forwards in flight uses two)
+        self.options = {}                        # what set_option set (an option not in it has the library's default)
         if os.environ.get("VDA_RESIDUAL_IN_LN") is not None:          # A/B switch for tools / bench runs
             _check(lib.vda_set_option(h, b"residual_in_ln", int(os.environ["VDA_RESIDUAL_IN_LN"])), "vda_set_option")
         if os.environ.get("VDA_DYN_SCHED") is not None:
@@ -165,6 +166,7 @@ class ModelHandle:
 
     def set_option(self, name, value):
         _check(lib.vda_set_option(self._h, name.encode(), int(value)), "vda_set_option")
+        self.options[name] = int(value)
 
     def profile_start(self, every=4):
         _check(lib.vda_profile_start(self._h, every), "vda_profile_start")

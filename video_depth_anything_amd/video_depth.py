@@ -115,8 +115,15 @@ class VideoDepthAnything:
         if torch.device(device).type != 'cuda':
             raise RuntimeError("video_depth_anything_amd runs on an MI355X HIP device only (got device=%r)" % (device,))
         eng = self._ensure_engine()
-        with torch.cuda.device(eng.device):
-            return self._infer_video_depth(eng, frames, target_fps, input_size, bool(fp32))
+        # two windows in flight on two lanes already fill each other's idle time: the encoder's frame-half split (vda_set_option
+        # "enc_split") measured -2 % on a 1024-frame video on top of them (profiles/r05), so it is off for the video and restored after
+        keep = eng.options.get("enc_split", -1)           # (-1: the library's default)
+        eng.set_option("enc_split", 0)
+        try:
+            with torch.cuda.device(eng.device):
+                return self._infer_video_depth(eng, frames, target_fps, input_size, bool(fp32))
+        finally:
+            eng.set_option("enc_split", keep)
 
     def _infer_video_depth(self, eng, frames, target_fps, input_size, fp32):
         import torch.distributed as dist
