@@ -319,6 +319,10 @@ int vda_stitch_window_f32(const float* win, const float* scale_shift, float* chu
 /* out[i] = aff(in[i]) for n elements, the same arithmetic as the stitch (video_depth.py:238,243,249): aligns key frames another rank
  * computed (the key-frame exchange of the multi-rank schedule). in == out is allowed. */
 int vda_affine_clamp_f32(const float* in, const float* scale_shift, float* out, long long n, vda_stream_t stream);
+/* Running range of a streamed video: minmax[0] = min(minmax[0], min x[0..n)), minmax[1] = max(minmax[1], max x[0..n)); minmax is
+ * device fp32 [2] that the caller starts at (+inf, -inf). Exact (min / max do not round), deterministic, one workgroup, no atomics
+ * and no workspace; x needs 4-byte alignment only. A NaN in x is never taken. Calls that share `minmax` must be stream-ordered. */
+int vda_minmax_accum_f32(const float* x, long long n, float* minmax, vda_stream_t stream);
 
 /* ================================================================ handle API: the model behind one pointer
  * What a C / C++ host binds in place of the reference's Python class (the seam of SURVEY.md section 8b):

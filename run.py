@@ -5,15 +5,65 @@ Frame I/O is utils/dc_utils.py (same two helpers as the reference's): `--input_v
 of uint8 [N,H,W,3] RGB frames, a directory of images, a GIF, or a video file when decord or cv2 is importable; the
 visualisations are mp4 through imageio when present and animated GIFs otherwise; `--save_npz` adds <name>_depths.npz.
 `--metric` selects the metric-depth variant (metric_depth/run.py: ViT-L, no scale/shift alignment).
+`--stream` runs infer_video_depth_stream instead: the frames (a memory map for .npy) are fed to the stream, the depths go piece by
+piece into <name>_depths.npy on disk and the visualisation is made from that file block by block, so neither the video nor its
+depth is ever held in memory as one array.
 """
 import argparse
 import os
+import struct
 
 import numpy as np
 import torch
 
 from utils.dc_utils import read_video_frames, save_video
 from video_depth_anything_amd.video_depth import MetricVideoDepthAnything, VideoDepthAnything
+
+
+class GrowingNpy:
+    """A float32 .npy written piece by piece when the number of frames is not known up front: a fixed 128-byte header is reserved,
+    the pieces are appended raw, and close() writes the header for the shape that arrived and returns the file memory-mapped."""
+    HEADER = 128
+
+    def __init__(self, path):
+        self.path, self.n, self.frame_shape = path, 0, None
+        self.f = open(path, "wb")
+        self.f.write(b"\0" * self.HEADER)
+
+    def append(self, piece):
+        piece = np.ascontiguousarray(piece, dtype=np.float32)
+        if self.frame_shape is None:
+            self.frame_shape = tuple(piece.shape[1:])
+        assert tuple(piece.shape[1:]) == self.frame_shape
+        self.f.write(piece.tobytes())
+        self.n += piece.shape[0]
+
+    def close(self):
+        d = "{'descr': %r, 'fortran_order': False, 'shape': %r, }" % (np.lib.format.dtype_to_descr(np.dtype(np.float32)), (self.n,) + self.frame_shape)
+        pad = self.HEADER - 10 - len(d) - 1
+        assert pad >= 0
+        self.f.seek(0)
+        self.f.write(b"\x93NUMPY\x01\x00" + struct.pack("<H", self.HEADER - 10) + (d + " " * pad + "\n").encode("latin1"))
+        self.f.close()
+        return np.load(self.path, mmap_mode="r")
+
+
+def write_depth_stream(stream, path, n_frames=None):
+    """Every piece of an infer_video_depth_stream into the .npy at `path`; returns it memory-mapped. n_frames known (an array
+    source): np.lib.format.open_memmap of the final shape; unknown (an iterable): a growing file whose header is fixed up at the end."""
+    sink = None
+    for first, d in stream:
+        if n_frames is None:
+            sink = sink or GrowingNpy(path)
+            sink.append(d)
+        else:
+            if sink is None:
+                sink = np.lib.format.open_memmap(path, mode="w+", dtype=np.float32, shape=(n_frames,) + d.shape[1:])
+            sink[first:first + d.shape[0]] = d
+    if n_frames is None:
+        return sink.close()
+    sink.flush()
+    return np.load(path, mmap_mode="r")
 
 
 if __name__ == '__main__':
@@ -30,6 +80,7 @@ if __name__ == '__main__':
     parser.add_argument('--save_npz', action='store_true', help='save depths as npz')
     parser.add_argument('--save_exr', action='store_true', help='save depths as exr')
     parser.add_argument('--metric', action='store_true', help='metric-depth checkpoint and stitching (metric_depth/run.py)')
+    parser.add_argument('--stream', action='store_true', help='bounded memory: infer_video_depth_stream, depths written to <name>_depths.npy piece by piece')
     parser.add_argument('--checkpoint', type=str, default=None, help='override ./checkpoints/<name>.pth; "synthetic" = seeded random weights')
     args = parser.parse_args()
 
@@ -51,14 +102,21 @@ if __name__ == '__main__':
     video_depth_anything = video_depth_anything.to(DEVICE).eval()
 
     frames, target_fps = read_video_frames(args.input_video, args.max_len, args.target_fps, args.max_res)   # run.py:53
-    depths, fps = video_depth_anything.infer_video_depth(frames, target_fps, input_size=args.input_size, device=DEVICE, fp32=args.fp32)
-
     video_name = os.path.basename(args.input_video)
     os.makedirs(args.output_dir, exist_ok=True)
     stem = os.path.join(args.output_dir, os.path.splitext(video_name)[0])
+    d_range = {}
+    if args.stream:
+        stream = video_depth_anything.infer_video_depth_stream(frames, target_fps, input_size=args.input_size, device=DEVICE, fp32=args.fp32)
+        depths = write_depth_stream(stream, stem + '_depths.npy', len(frames) if isinstance(frames, np.ndarray) else None)
+        fps = stream.fps
+        d_range = dict(d_min=stream.depth_min, d_max=stream.depth_max)      # the stream kept the range: no second pass over the file
+    else:
+        depths, fps = video_depth_anything.infer_video_depth(frames, target_fps, input_size=args.input_size, device=DEVICE, fp32=args.fp32)
+
     # run.py:57-62: <name>_src.mp4 and <name>_vis.mp4 (GIFs when no H.264 encoder is importable)
     src_path = save_video(frames, stem + '_src.mp4', fps=fps)
-    vis_path = save_video(depths, stem + '_vis.mp4', fps=fps, is_depths=True, grayscale=args.grayscale)
+    vis_path = save_video(depths, stem + '_vis.mp4', fps=fps, is_depths=True, grayscale=args.grayscale, **d_range)
     if args.save_npz:
         np.savez_compressed(stem + '_depths.npz', depths=depths)
     if args.save_exr:

@@ -113,16 +113,38 @@ def _inferno(u8):
     return (np.clip(rgb, 0, 1) * 255).astype(np.uint8)
 
 
-def save_video(frames, output_video_path, fps=10, is_depths=False, grayscale=False):
+SAVE_BLOCK = 32                                        # frames mapped to uint8 / colour at a time by save_video
+
+
+def save_video(frames, output_video_path, fps=10, is_depths=False, grayscale=False, d_min=None, d_max=None):
     """dc_utils.py:73-88. Depth is mapped through its GLOBAL min / max to uint8 (then inferno unless `grayscale`).
-    Returns the path written (the reference returns None): the .mp4 asked for, or a .gif when there is no encoder."""
-    frames = np.asarray(frames)
+    Returns the path written (the reference returns None): the .mp4 asked for, or a .gif when there is no encoder.
+    Works SAVE_BLOCK frames at a time and hands each frame to the writer as it is mapped, so `frames` may be a memory map of a video
+    that does not fit in RAM (run.py --stream); d_min / d_max: the global range when the caller knows it already
+    (infer_video_depth_stream's depth_min / depth_max) - otherwise one block-wise pass finds it. Element by element the same
+    arithmetic as mapping the whole array at once: the bytes written do not depend on the block size."""
+    if not isinstance(frames, np.ndarray):
+        frames = np.asarray(frames)
+    n = frames.shape[0]
+    blocks = [slice(i, min(i + SAVE_BLOCK, n)) for i in range(0, n, SAVE_BLOCK)]
     if is_depths:
-        d_min, d_max = frames.min(), frames.max()
-        norm = ((frames - d_min) / max(float(d_max - d_min), 1e-12) * 255).astype(np.uint8)
-        vis = norm if grayscale else _inferno(norm)
-    else:
-        vis = frames
+        if d_min is None:
+            d_min = min(frames[b].min() for b in blocks)
+        if d_max is None:
+            d_max = max(frames[b].max() for b in blocks)
+        d_min, d_max = frames.dtype.type(d_min), frames.dtype.type(d_max)
+        span = max(float(d_max - d_min), 1e-12)
+
+    def mapped():
+        for b in blocks:
+            if is_depths:
+                norm = ((frames[b] - d_min) / span * 255).astype(np.uint8)
+                vis = norm if grayscale else _inferno(norm)
+            else:
+                vis = frames[b]
+            for f in vis:
+                yield f
+
     try:
         import imageio
     except ImportError:
@@ -130,13 +152,13 @@ def save_video(frames, output_video_path, fps=10, is_depths=False, grayscale=Fal
     if imageio is not None:
         # an encoder that IS installed and fails (bad path, codec error) raises: the failure must not turn into a silent GIF
         writer = imageio.get_writer(output_video_path, fps=fps, macro_block_size=1, codec='libx264', ffmpeg_params=['-crf', '18'])
-        for f in vis:
+        for f in mapped():
             writer.append_data(f)
         writer.close()
         return output_video_path
     else:
         from PIL import Image
         path = os.path.splitext(output_video_path)[0] + ".gif"
-        ims = [Image.fromarray(f) for f in vis]
-        ims[0].save(path, save_all=True, append_images=ims[1:], duration=max(int(round(1000.0 / max(fps, 1e-6))), 1), loop=0)
+        ims = (Image.fromarray(f) for f in mapped())
+        next(ims).save(path, save_all=True, append_images=ims, duration=max(int(round(1000.0 / max(fps, 1e-6))), 1), loop=0)
         return path

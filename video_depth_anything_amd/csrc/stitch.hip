@@ -137,3 +137,66 @@ extern "C" int vda_stitch_window_f32(const float* win, const float* scale_shift,
     VDA_LAUNCH_CHECK();
     return 0;
 }
+
+// ---- running depth range of a streamed video (infer_video_depth_stream): minmax = (min(minmax[0], min x), max(minmax[1], max x)).
+// ONE workgroup: the entry point takes no workspace and uses no atomics, so there is nowhere for several workgroups to meet. It runs
+// on the consumer's stream beside two windows' forwards and reads one 22-frame chunk per window (26 MB at 518x518, well under a
+// millisecond from one CU against ~50 ms of forward), so it is latency, not throughput, that it must not add to. Min and max are
+// exact in any order: the result does not depend on the reduction tree. Comparisons, not fminf / fmaxf: a NaN is never taken (the
+// stream raises on an overflowed window before its frames could reach this kernel).
+namespace {
+
+constexpr int MM_T = 1024;
+
+__device__ __forceinline__ void mm_take(float v, float& lo, float& hi) {
+    lo = v < lo ? v : lo;
+    hi = v > hi ? v : hi;
+}
+
+__global__ void __launch_bounds__(MM_T) minmax_accum_kernel(const float* __restrict__ x, long long n, float* __restrict__ minmax) {
+    float lo = __builtin_inff(), hi = -__builtin_inff();
+    // elements before the first 16-byte boundary, then float4 loads, then the remainder: every index is < n
+    long long head = (long long)(((16u - (unsigned)((uintptr_t)x & 15u)) & 15u) >> 2);
+    if (head > n) head = n;
+    if ((long long)threadIdx.x < head) mm_take(x[threadIdx.x], lo, hi);
+    const f32x4* __restrict__ x4 = reinterpret_cast<const f32x4*>(x + head);
+    const long long n4 = (n - head) >> 2;
+#pragma unroll 4
+    for (long long i = threadIdx.x; i < n4; i += MM_T) {
+        const f32x4 v = x4[i];
+        mm_take(v[0], lo, hi);
+        mm_take(v[1], lo, hi);
+        mm_take(v[2], lo, hi);
+        mm_take(v[3], lo, hi);
+    }
+    const long long rest = head + (n4 << 2) + threadIdx.x;          // at most 3 elements
+    if (rest < n) mm_take(x[rest], lo, hi);
+    __shared__ float red[2][MM_T];
+    red[0][threadIdx.x] = lo;
+    red[1][threadIdx.x] = hi;
+    __syncthreads();
+    for (int w = MM_T / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            const float a = red[0][threadIdx.x + w], b = red[1][threadIdx.x + w];
+            red[0][threadIdx.x] = a < red[0][threadIdx.x] ? a : red[0][threadIdx.x];
+            red[1][threadIdx.x] = b > red[1][threadIdx.x] ? b : red[1][threadIdx.x];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float lo0 = minmax[0], hi0 = minmax[1];                // the running values (the caller starts them at +inf, -inf)
+        minmax[0] = red[0][0] < lo0 ? red[0][0] : lo0;
+        minmax[1] = red[1][0] > hi0 ? red[1][0] : hi0;
+    }
+}
+
+}  // namespace
+
+extern "C" int vda_minmax_accum_f32(const float* x, long long n, float* minmax, vda_stream_t stream) {
+    VDA_REQUIRE(x && minmax, "vda_minmax_accum_f32: null pointer");
+    VDA_REQUIRE(n > 0, "vda_minmax_accum_f32: bad size %lld", n);
+    VDA_REQUIRE(((uintptr_t)x & 3) == 0 && ((uintptr_t)minmax & 3) == 0, "vda_minmax_accum_f32: pointers must be 4-byte aligned");
+    hipLaunchKernelGGL(minmax_accum_kernel, dim3(1), dim3(MM_T), 0, (hipStream_t)stream, x, n, minmax);
+    VDA_LAUNCH_CHECK();
+    return 0;
+}

@@ -335,6 +335,16 @@ def affine_clamp(x, scale_shift, out):
     check(lib.vda_affine_clamp_f32(_p(x), _p(scale_shift), _p(out), x.numel(), _stream(x)), "vda_affine_clamp_f32")
 
 
+def minmax_accum(x, minmax, n=None):
+    """minmax[0] = min(minmax[0], x[:n].min()), minmax[1] = max(minmax[1], x[:n].max()) over the first n elements of x (all of them
+    when n is None); minmax: device fp32 [2], started at (+inf, -inf) by the caller. Exact; see include/vda.h."""
+    _req(x, F32, "x"), _req(minmax, F32, "minmax")
+    n = x.numel() if n is None else int(n)
+    if n <= 0 or n > x.numel() or minmax.numel() < 2:
+        raise ValueError("minmax_accum: bad sizes")
+    check(lib.vda_minmax_accum_f32(_p(x), n, _p(minmax), _stream(x)), "vda_minmax_accum_f32")
+
+
 # ---------------------------------------------------------------------------
 # Weight layouts the kernels expect (done once at load time, on the host or device)
 # ---------------------------------------------------------------------------

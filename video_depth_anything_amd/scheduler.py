@@ -324,6 +324,210 @@ def stitch_windows(window_depths: Sequence[np.ndarray], n_frames: int, metric: b
     return np.stack(aligned[:n_frames], axis=0)
 
 
+# ------------------------------------------------------------------ a video of unknown length: incremental plan, frame ring
+STEP = INFER_LEN - OVERLAP                       # 22 new frames per window
+# The streamed path (infer_video_depth_stream) keeps the single-rank issue order of drive_windows: window k is queued on its lane,
+# window k + 1's frames are uploaded under it, and only then is window k - 1's finished piece taken. So when a piece is handed out,
+# frames through the end of the window TWO ahead of it have been drawn: window k + 1 ends at frame STEP (k + 1) + INFER_LEN - 1 and
+# piece k - 1 ends at frame STEP (k - 1) + PIECE_FRAMES - 1.
+READ_AHEAD = 2 * STEP + INFER_LEN - (INFER_LEN - INTERP_LEN)                      # 52 frames drawn beyond the last one handed out
+# Frames that must be resident in HBM at that moment: windows k - 1 and k may still be running (their gathers read the ring), window
+# k + 1 is being uploaded. The oldest frame any of them reads (frame 0 aside) is window k - 1's key frame STEP (k - 2) + KEYFRAMES[1],
+# the newest is STEP (k + 1) + INFER_LEN - 1: a contiguous run of 2 STEP + INFER_LEN + (STEP - KEYFRAMES[1]) frames, plus the slot frame 0
+# keeps for the whole video. Independent of the video's length.
+RING_SPAN = 2 * STEP + INFER_LEN + (STEP - KEYFRAMES[1])                          # 86
+RING_FRAMES = 1 + RING_SPAN                                                       # 87 slots
+assert KEYFRAMES[0] == 0 and KEYFRAMES[2:] == list(range(INFER_LEN - INTERP_LEN, INFER_LEN)), "frame 0, one key frame, the previous tail"
+assert READ_AHEAD <= 3 * INFER_LEN and RING_FRAMES <= 4 * INFER_LEN
+
+
+class WindowPlanner:
+    """plan_windows for a video whose length is not known yet: told how many frames have arrived (and, finally, that there are no
+    more), it returns each window as soon as it is decidable - all of its 32 source frames have arrived (frames through
+    STEP k + INFER_LEN - 1: nothing is padded, whatever the final length turns out to be), or the end is known (padded slots map to
+    the last real frame). For every n the windows returned, in order, are exactly plan_windows(n)."""
+
+    def __init__(self):
+        self.arrived = 0
+        self.ended = False
+        self.emitted = 0                 # windows returned so far
+        self._prev = None
+
+    def decidable(self) -> int:
+        """Number of windows decidable from what is known now."""
+        if self.ended:
+            return (self.arrived + STEP - 1) // STEP
+        return 0 if self.arrived < INFER_LEN else (self.arrived - INFER_LEN) // STEP + 1
+
+    def feed(self, count: int = 0, end: bool = False) -> List[List[int]]:
+        """`count` more frames have arrived; end=True: the stream is exhausted. Returns the windows that became decidable."""
+        if self.ended:
+            raise RuntimeError("WindowPlanner.feed after the end of the stream")
+        if count < 0:
+            raise ValueError("negative frame count")
+        self.arrived += count
+        if end:
+            if self.arrived <= 0:
+                raise ValueError("empty video")
+            self.ended = True
+        out = []
+        while self.emitted < self.decidable():
+            start = STEP * self.emitted
+            last = self.arrived - 1                  # clips only once the end is known: before that start + 31 <= last
+            cur = [min(start + i, last) for i in range(INFER_LEN)]
+            if self._prev is not None:
+                cur[:OVERLAP] = [self._prev[k] for k in KEYFRAMES]
+            out.append(cur)
+            self._prev = cur
+            self.emitted += 1
+        return out
+
+
+class FrameRing:
+    """Slot allocator of the fixed-capacity uint8 frame ring in HBM that stands in for the whole-video buffer of infer_video_depth.
+    Frame 0 is pinned to slot 0; frame f > 0 lives in slot 1 + (f - 1) % (capacity - 1), so placing frame f evicts frame
+    f - (capacity - 1). Host bookkeeping only; it ASSERTS what the schedule promises instead of trusting it:
+
+      reserve(k, window)   before window k's frames are uploaded: places the frames that are not resident, returns
+                           ([(frame, slot)] to upload, newest window that READ an evicted frame or -1). A frame may only be evicted
+                           when no reserved window still waits to be issued with it, and never frame 0.
+      issued(k, window)    window k's slot-consuming kernel (the gather) has been queued on its lane.
+
+    What makes the reuse safe ON THE DEVICE is the caller's business: the upload stream has to be ordered behind the gathers of the
+    windows that read an evicted slot. RING_FRAMES is sized so that when window k + 1 is reserved those are windows <= k - 2
+    (returned for the caller to assert), whose `freed` event - recorded by the consumer behind the stitch of window k - 2, hence behind
+    its forward and its gather - the upload stream waits for. Stream order on a lane is NOT enough: uploads run on their own stream."""
+
+    def __init__(self, capacity: int = RING_FRAMES):
+        assert capacity >= 2
+        self.capacity = capacity
+        self.frame_at = [None] * capacity        # slot -> frame
+        self.slot_of = {}                        # resident frame -> slot
+        self.waiting = {}                        # frame -> reserved, not yet issued windows that read it
+        self.reader = {}                         # resident frame -> newest issued window that read it
+        self.peak = 0
+
+    def _slot(self, f):
+        return 0 if f == 0 else 1 + (f - 1) % (self.capacity - 1)
+
+    def in_use(self) -> int:
+        return len(self.slot_of)
+
+    def reserve(self, k, window):
+        need = sorted(set(window))
+        todo, evicted_reader = [], -1
+        for f in need:
+            if f not in self.slot_of:
+                s = self._slot(f)
+                old = self.frame_at[s]
+                if old is not None:
+                    assert old != 0, "frame 0 is pinned"
+                    assert self.waiting.get(old, 0) == 0, f"frame {old} evicted by {f} while a reserved window still needs it"
+                    evicted_reader = max(evicted_reader, self.reader.pop(old, -1))
+                    del self.slot_of[old]
+                    self.waiting.pop(old, None)
+                self.frame_at[s] = f
+                self.slot_of[f] = s
+                todo.append((f, s))
+        for f in need:                           # after every placement: a window's own frames must not have evicted each other
+            assert f in self.slot_of and self.frame_at[self.slot_of[f]] == f, f"window {k}: frame {f} lost its slot to another of its frames"
+            self.waiting[f] = self.waiting.get(f, 0) + 1
+        self.peak = max(self.peak, len(self.slot_of))
+        assert len(self.slot_of) <= self.capacity
+        return todo, evicted_reader
+
+    def issued(self, k, window):
+        for f in set(window):
+            self.waiting[f] -= 1
+            self.reader[f] = k
+
+    def slots(self, window):
+        return [self.slot_of[f] for f in window]
+
+
+class HostStitcher:
+    """stitch_windows one window at a time (the same numpy operations on the same operands, so bit-equal): push(window) returns the
+    frames that became final - 24 after window 0, 22 after each later one -, tail() the last 8 once no window follows."""
+
+    def __init__(self, metric: bool = False):
+        self.metric = metric
+        self.k = 0
+        self._tail = None
+        self._ref = None
+
+    def push(self, wd: np.ndarray) -> List[np.ndarray]:
+        align_len = OVERLAP - INTERP_LEN
+        kf_align = KEYFRAMES[:align_len]
+        frames = [wd[i] for i in range(INFER_LEN)]
+        if self.k == 0:
+            out = frames[:INFER_LEN - INTERP_LEN]
+            self._tail = frames[INFER_LEN - INTERP_LEN:]
+            self._ref = [frames[kf] for kf in kf_align]
+        else:
+            if self.metric:
+                scale, shift = 1.0, 0.0
+            else:
+                scale, shift = compute_scale_and_shift(np.concatenate(frames[:align_len]), np.concatenate(self._ref))
+            post = [_clamped_affine(frames[i], scale, shift) for i in range(align_len, OVERLAP)]
+            rest = [_clamped_affine(frames[i], scale, shift) for i in range(OVERLAP, INFER_LEN)]
+            out = crossfade(self._tail, post) + rest[:-INTERP_LEN]
+            self._tail = rest[-INTERP_LEN:]
+            self._ref = self._ref[:1] + [_clamped_affine(frames[kf], scale, shift) for kf in kf_align[1:]]
+        self.k += 1
+        return out
+
+    def tail(self) -> List[np.ndarray]:
+        return self._tail
+
+
+def _as_block(block) -> np.ndarray:
+    """One item of a frame iterable as a [m,H,W,3] array: a single [H,W,3] frame becomes a block of one."""
+    block = np.asarray(block) if not isinstance(block, np.ndarray) else block
+    if block.ndim == 3:
+        block = block[None]
+    return block
+
+
+def run_windows_stream(frames_iter, window_fn: Callable[[np.ndarray], np.ndarray], metric: bool = False):
+    """infer_video_depth_stream's host logic without a GPU (the twin of run_windows for one rank): frames arrive as [H,W,3] frames or
+    [m,H,W,3] blocks from an iterable of unknown length, the incremental planner decides the windows, the stitcher runs window by
+    window. Yields (first output frame, float32 [c,H0,W0]) pieces - in order, contiguous, trimmed to the video's length once that
+    is known; their concatenation is bit-equal to run_windows on the concatenated frames. Only the frames a later window can still
+    read are kept."""
+    planner = WindowPlanner()
+    st = HostStitcher(metric)
+    held = {}                                    # frame index -> [H0,W0,3]
+    done = 0                                     # windows computed
+    it = iter(frames_iter)
+    ended = False
+    while not ended:
+        try:
+            block = _as_block(next(it))
+            base = planner.arrived
+            for i in range(block.shape[0]):
+                held[base + i] = block[i]
+            windows = planner.feed(block.shape[0])
+        except StopIteration:
+            windows = planner.feed(end=True)
+            ended = True
+        for win in windows:
+            w = np.ascontiguousarray(window_fn(np.stack([held[f] for f in win])), dtype=np.float32)
+            out = st.push(w)
+            pos, _ = piece_position(done)
+            done += 1
+            # a window decided before the end is known lies wholly inside the video: only the end can trim
+            hi = min(pos + len(out), planner.arrived) if planner.ended else pos + len(out)
+            if hi > pos:
+                yield pos, np.stack(out[:hi - pos])
+            oldest = STEP * (done - 1) + KEYFRAMES[1]           # the next window's key frame: nothing older (frame 0 aside) is read again
+            for f in [f for f in held if 0 < f < oldest]:
+                del held[f]
+    n = planner.arrived
+    pos = STEP * (done - 1) + PIECE_FRAMES
+    if n > pos:
+        yield pos, np.stack(st.tail()[:n - pos])
+
+
 # ------------------------------------------------------------------ host driver (CPU rehearsal of the multi-rank schedule)
 def run_windows(frames: np.ndarray, window_fn: Callable[[np.ndarray], np.ndarray], metric: bool = False, group=None, exchange: str = "windows",
                 result_ranks=None):

@@ -125,6 +125,29 @@ class VideoDepthAnything:
         finally:
             eng.set_option("enc_split", keep)
 
+    def infer_video_depth_stream(self, frames, target_fps, input_size=518, device='cuda', fp32=False):
+        """infer_video_depth for a video of unknown length, in bounded memory (stream.py):
+
+            stream = model.infer_video_depth_stream(frames, target_fps)
+            for first, depths in stream:      # depths: np.float32 [c, H0, W0] = frames first .. first + c - 1, the caller's own array
+                ...
+            stream.n_frames, stream.depth_min, stream.depth_max, stream.fps      # valid once exhausted
+
+        frames: an [N,H,W,3] array or memory map (as infer_video_depth takes it), or any iterable of [H,W,3] frames or [m,H,W,3]
+        blocks. The pieces are what the stitcher makes final - 24 frames, then 22 per window, then the 8-frame tail, trimmed to the
+        video -, in order; concatenated they are bit-identical to infer_video_depth's result. A bad block raises infer_video_depth's
+        ValueError / TypeError when it is drawn, a source without frames ValueError("empty video"), a window whose residual stream
+        left fp16's range RuntimeError before any of its frames is handed out. stream.close() (also on garbage collection) stops
+        early; on every way out the lanes are joined and the handle's options restored. One rank only."""
+        import torch.distributed as dist
+        from .stream import DepthStream
+        if torch.device(device).type != 'cuda':
+            raise RuntimeError("video_depth_anything_amd runs on an MI355X HIP device only (got device=%r)" % (device,))
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("infer_video_depth_stream runs on one rank: sharding a video of unknown length is not built; "
+                                      "with torch.distributed initialised use infer_video_depth, which shards the windows of an array")
+        return DepthStream(self, self._ensure_engine(), frames, target_fps, input_size, bool(fp32))
+
     def _infer_video_depth(self, eng, frames, target_fps, input_size, fp32):
         import torch.distributed as dist
         from . import ops
