@@ -36,6 +36,20 @@ def network_size(height: int, width: int, input_size: int = 518) -> Tuple[int, i
 
 
 # ------------------------------------------------------------------ window schedule
+STEP = INFER_LEN - OVERLAP                       # 22 new frames per window
+PIECE_FRAMES = INFER_LEN - INTERP_LEN            # 24: the frames window 0 makes final, the largest piece; later windows fill STEP of it
+
+
+def piece_position(k: int) -> Tuple[int, int]:
+    """(first output frame, frame count) of the piece window k makes final (the device stitcher's chunk, its owner's piece)."""
+    return (0, PIECE_FRAMES) if k == 0 else (STEP * k + (OVERLAP - INTERP_LEN), STEP)
+
+
+def tail_position(n_windows: int) -> int:
+    """First output frame of the INTERP_LEN-frame tail that is final once no window follows the n_windows-th."""
+    return STEP * (n_windows - 1) + PIECE_FRAMES
+
+
 def plan_windows(n_frames: int) -> List[List[int]]:
     """Source-frame index of every input slot of every window.
 
@@ -44,10 +58,9 @@ def plan_windows(n_frames: int) -> List[List[int]]:
     slots KEYFRAMES. Padded positions map back to the last real frame."""
     if n_frames <= 0:
         raise ValueError("empty video")
-    step = INFER_LEN - OVERLAP
     windows: List[List[int]] = []
     prev = None
-    for start in range(0, n_frames, step):
+    for start in range(0, n_frames, STEP):
         cur = [min(start + i, n_frames - 1) for i in range(INFER_LEN)]
         if prev is not None:
             cur[:OVERLAP] = [prev[k] for k in KEYFRAMES]
@@ -130,12 +143,6 @@ def drive_windows(n_windows: int, world: int, rank: int, send, recv, compute, ga
 # Per round and rank: 11 frames all-gathered + 22..24 sent to each result rank, against 32 all-gathered; a rank that is not a
 # result rank receives 7 x 11 instead of 7 x 32 frames on 8 GPUs, and the stitch work is spread over the ranks.
 KEY_SLOTS = (0, 1, 12, 24, 25, 26, 27, 28, 29, 30, 31)
-PIECE_FRAMES = INFER_LEN - INTERP_LEN            # 24: the largest piece (window 0); later windows fill 22 of it
-
-
-def piece_position(k: int) -> Tuple[int, int]:
-    """(first output frame, frame count) of the piece window k's owner finalises."""
-    return (0, PIECE_FRAMES) if k == 0 else ((INFER_LEN - OVERLAP) * k + (OVERLAP - INTERP_LEN), INFER_LEN - OVERLAP)
 
 
 def drive_windows_keys(n_windows: int, world: int, rank: int, ops, result_ranks=None):
@@ -187,7 +194,7 @@ def drive_windows_keys(n_windows: int, world: int, rank: int, ops, result_ranks=
     last = n_windows - 1
     tail = ops.last_tail(last, last % world)
     if wanted and tail is not None:
-        yield (INFER_LEN - OVERLAP) * last + PIECE_FRAMES, INTERP_LEN, tail
+        yield tail_position(n_windows), INTERP_LEN, tail
 
 
 class HostKeyOps:
@@ -325,7 +332,6 @@ def stitch_windows(window_depths: Sequence[np.ndarray], n_frames: int, metric: b
 
 
 # ------------------------------------------------------------------ a video of unknown length: incremental plan, frame ring
-STEP = INFER_LEN - OVERLAP                       # 22 new frames per window
 # The streamed path (infer_video_depth_stream) keeps the single-rank issue order of drive_windows: window k is queued on its lane,
 # window k + 1's frames are uploaded under it, and only then is window k - 1's finished piece taken. So when a piece is handed out,
 # frames through the end of the window TWO ahead of it have been drawn: window k + 1 ends at frame STEP (k + 1) + INFER_LEN - 1 and
@@ -523,7 +529,7 @@ def run_windows_stream(frames_iter, window_fn: Callable[[np.ndarray], np.ndarray
             for f in [f for f in held if 0 < f < oldest]:
                 del held[f]
     n = planner.arrived
-    pos = STEP * (done - 1) + PIECE_FRAMES
+    pos = tail_position(done)
     if n > pos:
         yield pos, np.stack(st.tail()[:n - pos])
 

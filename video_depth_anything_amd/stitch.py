@@ -10,15 +10,18 @@ and as the cross-check of this one). Here the per-window depth maps never leave 
 
 so a window contributes 22 final frames (24 for the first) and the host receives each frame exactly once.
 """
+import collections
+
 import numpy as np
 import torch
 
 from . import ops
 from .config import INFER_LEN, INTERP_LEN, KEYFRAMES, OVERLAP
+from .lanes import HostCopyRing
+from .scheduler import PIECE_FRAMES as FIRST   # 24 frames final after window 0
+from .scheduler import STEP, piece_position, tail_position
 
 ALIGN_LEN = OVERLAP - INTERP_LEN
-STEP = INFER_LEN - OVERLAP                     # 22 new frames per window
-FIRST = INFER_LEN - INTERP_LEN                 # 24 frames final after window 0
 assert (INFER_LEN, OVERLAP, INTERP_LEN, ALIGN_LEN) == (32, 10, 8, 2) and tuple(KEYFRAMES[:2]) == (0, 12), \
     "vda_stitch_window_f32 is built for the released schedule (32-frame windows, 10 overlap, 8 interpolated, key frames 0 and 12)"
 
@@ -58,13 +61,6 @@ class DeviceStitcher:
         self.k += 1
         return n
 
-    def first_frame_of(self, k):
-        """Output position of chunk[0] of window k."""
-        return 0 if k == 0 else STEP * k + ALIGN_LEN
-
-    def tail_position(self):
-        return STEP * (self.k - 1) + FIRST
-
 
 def stitch_stream(windows, n_frames, H0, W0, device, metric=False):
     """Stitch an iterator of device windows (fp32 [32,H0,W0], window order) into a host float32 [n_frames,H0,W0] array.
@@ -72,41 +68,28 @@ def stitch_stream(windows, n_frames, H0, W0, device, metric=False):
     queues for window k+1 on the current stream."""
     st = DeviceStitcher(H0, W0, device, metric)
     out = np.empty((n_frames, H0, W0), dtype=np.float32)
-    compute = torch.cuda.current_stream(device)
-    copy_stream = torch.cuda.Stream(device=device)
+    ring = HostCopyRing(2, FIRST, H0, W0, device)
     chunk = [torch.empty(FIRST, H0, W0, dtype=torch.float32, device=device) for _ in range(2)]
-    pinned = [torch.empty(FIRST, H0, W0, dtype=torch.float32, pin_memory=True) for _ in range(2)]
-    done = [torch.cuda.Event() for _ in range(2)]
-    pending = None                                  # (slot, first output frame, count)
+    pending = None                                  # (copy in flight, first output frame)
 
     def harvest(p):
-        s, lo, cnt = p
-        done[s].synchronize()
-        hi = min(lo + cnt, n_frames)
+        token, lo = p
+        view = ring.wait(token)
+        hi = min(lo + view.shape[0], n_frames)
         if hi > lo:
-            out[lo:hi] = pinned[s][:hi - lo].numpy()
+            out[lo:hi] = view[:hi - lo].numpy()
 
-    def send(src, s, lo, cnt):
-        copy_stream.wait_stream(compute)
-        with torch.cuda.stream(copy_stream):
-            pinned[s][:cnt].copy_(src[:cnt], non_blocking=True)
-            done[s].record(copy_stream)
-        return (s, lo, cnt)
-
-    k = 0
-    for win in windows:
-        s = k & 1
-        cnt = st.push(win, chunk[s])
-        nxt = send(chunk[s], s, st.first_frame_of(k), cnt)
+    for k, win in enumerate(windows):
+        cnt = st.push(win, chunk[k & 1])
+        nxt = ring.start(chunk[k & 1], cnt), piece_position(k)[0]
         if pending is not None:
             harvest(pending)
         pending = nxt
-        k += 1
     if pending is None:
         raise ValueError("no windows")
     harvest(pending)
-    harvest(send(st.tail, 0, st.tail_position(), INTERP_LEN))   # after the last window its tail is final too
-    compute.wait_stream(copy_stream)
+    harvest((ring.start(st.tail, INTERP_LEN), tail_position(st.k)))   # after the last window its tail is final too
+    ring.join()
     return out
 
 
@@ -184,7 +167,7 @@ class DeviceKeyOps:
         self._pieces_left()
         got = []
         if self.result_ranks is None:
-            _exchange_all(self.piece_recv[s], self.piece[s])
+            all_gather(self.piece_recv[s], self.piece[s])
             got = [(k, self.piece_recv[s][r]) for r, k in enumerate(ks) if k < self.n_windows]
         else:
             for dst in self.result_ranks:
@@ -201,9 +184,11 @@ class DeviceKeyOps:
         self.last_copy = event
 
 
-def _exchange_all(out, inp):
-    """out[r] = rank r's inp (RCCL all-gather; any other backend - the shared-GPU rehearsal over gloo - staged through the host).
-    The wait is bound to the current stream here: nothing downstream depends on which stream is current later."""
+def all_gather(out, inp):
+    """out[r] = rank r's inp (RCCL all-gather; any other backend - the shared-GPU rehearsal over gloo of tests/test_forward_gpu.py -
+    staged through the host). The wait for the collective is bound HERE, explicitly, to the current stream (Work.wait() on the
+    NCCL backend is a stream-side wait of whichever stream is current - it does not block the host): nothing downstream depends
+    on which stream is current later."""
     import torch.distributed as dist
     if dist.get_backend() == "nccl":
         dist.all_gather_into_tensor(out, inp, async_op=True).wait()
@@ -229,39 +214,29 @@ def collect_pieces(pieces, n_frames, H0, W0, device, on_copied=None):
     """(first output frame, count, device frames) pieces -> host float32 [n_frames, H0, W0]; each piece crosses to the host once,
     through a small ring of pinned buffers on a side stream."""
     out = np.empty((n_frames, H0, W0), dtype=np.float32)
-    compute = torch.cuda.current_stream(device)
-    copy_stream = torch.cuda.Stream(device=device)
     NB = 4
-    pinned = [torch.empty(FIRST, H0, W0, dtype=torch.float32, pin_memory=True) for _ in range(NB)]
-    done = [torch.cuda.Event() for _ in range(NB)]
-    inflight = [None] * NB
+    ring = HostCopyRing(NB, FIRST, H0, W0, device)
+    inflight = collections.deque()                  # (copy in flight, first output frame), oldest first
     seen = np.zeros(n_frames, dtype=np.int32)
 
-    def land(b):
-        if inflight[b] is not None:
-            done[b].synchronize()
-            lo, hi = inflight[b]
-            out[lo:hi] = pinned[b][:hi - lo].numpy()
-            seen[lo:hi] += 1
-            inflight[b] = None
+    def land():
+        token, lo = inflight.popleft()
+        view = ring.wait(token)
+        out[lo:lo + view.shape[0]] = view.numpy()
+        seen[lo:lo + view.shape[0]] += 1
 
-    i = 0
     for pos, cnt, frames in pieces:
         hi = min(pos + cnt, n_frames)
         if hi <= pos:
             continue
-        b = i % NB
-        land(b)
-        copy_stream.wait_stream(compute)
-        with torch.cuda.stream(copy_stream):
-            pinned[b][:hi - pos].copy_(frames[:hi - pos], non_blocking=True)
-            done[b].record(copy_stream)
-        inflight[b] = (pos, hi)
+        if len(inflight) == NB:
+            land()                                  # the buffer the next copy takes
+        token = ring.start(frames, hi - pos)
+        inflight.append((token, pos))
         if on_copied is not None:
-            on_copied(done[b])
-        i += 1
-    for b in range(NB):
-        land(b)
-    compute.wait_stream(copy_stream)
+            on_copied(token[0])
+    while inflight:
+        land()
+    ring.join()
     assert (seen == 1).all(), "every output frame exactly once"
     return out

@@ -2,7 +2,9 @@
 
 The same kernels on the same lanes in the same order as the single-rank path of infer_video_depth (two windows in flight, the
 next window's frames uploaded under the current one, the device stitcher, one device-to-host copy per finished chunk through a
-pinned ring), so every output frame is bit-identical. What differs is what is kept:
+pinned ring), so every output frame is bit-identical - by construction: both paths queue every window through lanes.WindowLanes.run,
+every upload through lanes.upload_runs, every chunk through stitch.DeviceStitcher and lanes.HostCopyRing, inside one
+lanes.video_session. This module holds only the schedule: decide, reserve, issue, stitch, harvest. What differs is what is kept:
 
   host    frames that were drawn from the source and are not uploaded yet (at most scheduler.READ_AHEAD beyond the last frame
           handed out, plus the rest of the block the source delivered them in); finished pieces belong to the caller
@@ -18,30 +20,10 @@ import numpy as np
 import torch
 
 from . import ops
-from .config import INFER_LEN, INTERP_LEN
-from .scheduler import STEP, FrameRing, WindowPlanner, network_size
+from .config import INTERP_LEN
+from .lanes import HostCopyRing, WindowLanes, as_u8_frames, check_frames, upload_runs, video_session
+from .scheduler import STEP, FrameRing, WindowPlanner, _as_block, network_size, piece_position, tail_position
 from .stitch import FIRST, DeviceStitcher
-
-
-def _as_u8_block(block, shape):
-    """One item drawn from the source as uint8 [m,H0,W0,3] (a single [H0,W0,3] frame is a block of one), under the rules
-    infer_video_depth applies to its array: [.., H, W, 3], one frame size, 8-bit values in whatever dtype."""
-    if not isinstance(block, np.ndarray):
-        block = np.asarray(block)
-    if block.ndim == 3:
-        block = block[None]
-    if block.ndim != 4 or block.shape[-1] != 3:
-        raise ValueError("infer_video_depth: frames must be [N, H, W, 3], got shape %r" % (tuple(block.shape),))
-    if shape is not None and tuple(block.shape[1:3]) != tuple(shape):
-        raise ValueError("infer_video_depth: every frame must have the first frame's size %r, got shape %r" % (tuple(shape), tuple(block.shape)))
-    if block.dtype != np.uint8:
-        ok = bool(block.size == 0 or (block.min() >= 0 and block.max() <= 255 and
-                                      (np.issubdtype(block.dtype, np.integer) or np.array_equal(block, np.rint(block)))))
-        if not ok:
-            raise TypeError("infer_video_depth: frames must hold 8-bit values (uint8, or any dtype whose values are integers "
-                            "within 0..255); got dtype %s with other values" % block.dtype)
-        block = block.astype(np.uint8)
-    return block
 
 
 class _FrameFeed:
@@ -51,8 +33,7 @@ class _FrameFeed:
         if isinstance(frames, np.ndarray):
             # an array (or memory map) of the whole video: the same checks as infer_video_depth up front, then views of STEP frames -
             # a memory map is paged in run by run as the uploads reach it
-            if frames.ndim != 4 or frames.shape[-1] != 3:
-                raise ValueError("infer_video_depth: frames must be [N, H, W, 3], got shape %r" % (tuple(frames.shape),))
+            check_frames(frames)
             self._it = (frames[i:i + STEP] for i in range(0, frames.shape[0], STEP))
         else:
             self._it = iter(frames)
@@ -67,7 +48,7 @@ class _FrameFeed:
                 block = next(self._it)
             except StopIteration:
                 return None
-            block = _as_u8_block(block, self.shape)
+            block = as_u8_frames(_as_block(block), self.shape)   # (a single [H0,W0,3] frame is a block of one)
             if block.shape[0] == 0:
                 continue
             if self.shape is None:
@@ -119,15 +100,11 @@ class DepthStream:
     # ------------------------------------------------------------------------------------------------------------
     def _run(self, eng, input_size, fp32, metric):
         dev = eng.device
-        keep = eng.options.get("enc_split", -1)           # as infer_video_depth: two windows in flight already fill the chip
-        eng.set_option("enc_split", 0)
-        streams = []                                      # everything that has to be joined on the way out
-        compute = None
-        try:
+        # one rank: no collective beside the GEMMs (dyn_sched 0). On every way out the lanes, the upload and the copy stream are
+        # joined and the consumer stream is synchronised: no kernel of the handle is in flight when control returns
+        with video_session(eng, 0, synchronize=True) as (compute, streams):
             with torch.cuda.device(dev):
-                compute = torch.cuda.current_stream(dev)
-                eng.set_option("dyn_sched", 0)            # one rank: no collective beside the GEMMs
-                core = _Core(eng, self._feed, input_size, fp32, metric, compute, streams)
+                core = _Core(eng, self._feed, input_size, fp32, metric, streams)
             while True:
                 with torch.cuda.device(dev), torch.cuda.stream(compute):
                     piece = core.step()
@@ -138,49 +115,33 @@ class DepthStream:
                 self.n_frames = core.planner.arrived
                 lo, hi = core.minmax.cpu().tolist()       # (waits for the consumer stream: every chunk's reduction is behind it)
                 self.depth_min, self.depth_max = np.float32(lo), np.float32(hi)
-        finally:
-            with torch.cuda.device(dev):
-                if compute is not None:
-                    for s in streams:
-                        compute.wait_stream(s)
-                    compute.synchronize()                 # no kernel of the handle is in flight when control returns
-                eng.set_option("enc_split", keep)
         eng.check()                                       # (only reached when the stream ran to its end)
 
 
 class _Core:
     """The single-rank schedule of infer_video_depth, one window per step()."""
-    NSLOT = 2
 
-    def __init__(self, eng, feed, input_size, fp32, metric, compute, streams):
-        self.eng, self.feed, self.fp32, self.compute = eng, feed, fp32, compute
+    def __init__(self, eng, feed, input_size, fp32, metric, streams):
+        self.eng, self.feed = eng, feed
         self.planner = WindowPlanner()
         self.windows = {}                                 # decided, not yet issued: k -> source frames
         self.reserved = set()
         self.k = 0                                        # next window to issue
-        self.pending = None                               # (pinned slot, first output frame, count) of the copy in flight
+        self.pending = None                               # (copy in flight, first output frame)
         self.state = "windows"
         if not self._decide(0):
             raise ValueError("empty video")               # (WindowPlanner.feed(end=True) raises it for a source without frames)
-        dev = self.dev = eng.device
-        H0, W0 = self.H0, self.W0 = feed.shape
-        H, W = self.H, self.W = network_size(H0, W0, input_size)
-        NSLOT = self.NSLOT
+        dev = eng.device
+        H0, W0 = feed.shape
+        self.px = H0 * W0
         self.ring = FrameRing()
         self.video = torch.empty((self.ring.capacity, H0, W0, 3), dtype=torch.uint8, device=dev)
         self.upload = torch.cuda.Stream(device=dev)
-        self.lanes = [torch.cuda.Stream(device=dev) for _ in range(NSLOT)]
-        self.copy_stream = torch.cuda.Stream(device=dev)
-        streams += self.lanes + [self.upload, self.copy_stream]
-        self.computed = [torch.cuda.Event() for _ in range(NSLOT)]     # slot's window is in send[s] (recorded on its lane)
-        self.freed = [torch.cuda.Event() for _ in range(NSLOT)]        # the stitcher is done with the slot (recorded on `compute`)
-        self.used = [False] * NSLOT
-        self.xin = [torch.empty(1, INFER_LEN, 3, H, W, dtype=torch.float32, device=dev) for _ in range(NSLOT)]
-        self.send = [torch.empty(INFER_LEN, H0, W0, dtype=torch.float32, device=dev) for _ in range(NSLOT)]
+        self.lanes = WindowLanes(eng, self.video, *network_size(H0, W0, input_size), fp32)
         self.st = DeviceStitcher(H0, W0, dev, metric)
         self.chunk = [torch.empty(FIRST, H0, W0, dtype=torch.float32, device=dev) for _ in range(2)]
-        self.pinned = [torch.empty(FIRST, H0, W0, dtype=torch.float32, pin_memory=True) for _ in range(2)]
-        self.done = [torch.cuda.Event() for _ in range(2)]
+        self.out = HostCopyRing(2, FIRST, H0, W0, dev)
+        streams += self.lanes.lanes + [self.upload, self.out.copy_stream]
         self.minmax = torch.tensor([float("inf"), float("-inf")], dtype=torch.float32, device=dev)
 
     # ---- source -> plan -> ring
@@ -206,67 +167,41 @@ class _Core:
             # consumer behind the stitch of window k - 3 - behind its forward, behind its gather. The upload stream waits for that
             # event: the `freed` events order the reuse, not stream order on the lanes (uploads have their own stream).
             assert s is not None and evicted_reader <= k - 3, (k, evicted_reader)
-            self.upload.wait_event(self.freed[s])
+            self.upload.wait_event(self.lanes.freed[s])
         with torch.cuda.stream(self.upload):
-            i = 0
-            while i < len(todo):
-                j = i
-                while j + 1 < len(todo) and todo[j + 1][0] == todo[j][0] + 1 and todo[j + 1][1] == todo[j][1] + 1:
-                    j += 1
-                f0, s0 = todo[i]
-                for lo, run in self.feed.runs(f0, todo[j][0] + 1):
-                    if not (run.flags.c_contiguous and run.flags.writeable):
-                        run = np.array(run)              # a memory-mapped or strided source: page this run in
-                    d0 = s0 + (lo - f0)
-                    self.video[d0:d0 + run.shape[0]].copy_(torch.from_numpy(run), non_blocking=True)
-                i = j + 1
+            upload_runs(self.video, todo, self.feed.runs)
         if todo:
             self.feed.uploaded_through(todo[-1][0])
 
-    # ---- one window on its lane (infer_video_depth.window_depth)
+    # ---- one window on its lane
     def _window_depth(self, k, s):
         self._ensure(k, None)
-        lane = self.lanes[s]
-        lane.wait_stream(self.upload)
-        if self.used[s]:
-            lane.wait_event(self.freed[s])
-        self.used[s] = True
         win = self.windows.pop(k)
-        H0, W0, H, W = self.H0, self.W0, self.H, self.W
-        with torch.cuda.stream(lane):
-            idx = torch.tensor(self.ring.slots(win), dtype=torch.int32, device=self.dev)
-            if (H0, W0) == (H, W):
-                ops.gather_normalize_u8(self.video, idx, self.xin[s], INFER_LEN, H0, W0)
-            else:
-                ops.gather_resize_normalize_u8(self.video, idx, self.xin[s], INFER_LEN, H0, W0, H, W)
-            self.ring.issued(k, win)                      # the slot-consuming kernel is queued
-            depth = self.eng.forward(self.xin[s], fp32=self.fp32, slot=s)
-            ops.bilinear_plane(depth.view(INFER_LEN, H, W), self.send[s], INFER_LEN, H, W, H0, W0)
-            self.computed[s].record(lane)
+        self.lanes.run(self.ring.slots(win), s, self.upload)
+        # The slot-consuming kernel (the gather) is queued. FrameRing is host bookkeeping that asserts host state, and between the
+        # gather inside run() and here no upload is queued and FrameRing is not asked anything (run() goes on to the forward, the
+        # resize and the event, all on the lane): telling it now is the same as telling it right behind the gather.
+        self.ring.issued(k, win)
         self.reserved.discard(k)
         self._ensure(k + 1, s)                            # overlaps this window's compute
 
     # ---- finished chunks
-    def _send(self, src, b, lo, cnt):
+    def _send(self, src, lo, cnt):
         """Trim to the video, fold the chunk into the running depth range, start its device-to-host copy."""
         if self.planner.ended:
             cnt = min(lo + cnt, self.planner.arrived) - lo
         if cnt <= 0:
             return None
-        ops.minmax_accum(src, self.minmax, cnt * self.H0 * self.W0)
-        self.copy_stream.wait_stream(self.compute)
-        with torch.cuda.stream(self.copy_stream):
-            self.pinned[b][:cnt].copy_(src[:cnt], non_blocking=True)
-            self.done[b].record(self.copy_stream)
-        return (b, lo, cnt)
+        ops.minmax_accum(src, self.minmax, cnt * self.px)
+        return self.out.start(src, cnt), lo
 
     def _harvest(self, p):
-        b, lo, cnt = p
-        self.done[b].synchronize()
+        token, lo = p
+        view = self.out.wait(token)
         # the chunk's window (and every earlier one) has finished: a window that left fp16's range is reported here, before its
         # frames - NaN by then - could be handed out
         self.eng.check(synchronize=False)
-        return lo, self.pinned[b][:cnt].numpy().copy()    # the caller's own array; the pinned buffer is reused two chunks on
+        return lo, view.numpy().copy()                    # the caller's own array; the pinned buffer is reused two chunks on
 
     def step(self):
         """Issue windows until a piece is ready; returns (first frame, depths) or None at the end."""
@@ -275,12 +210,12 @@ class _Core:
             if not self._decide(k):
                 self.state = "last"
                 break
-            s = k % self.NSLOT
+            s = k % 2
             self._window_depth(k, s)
-            self.compute.wait_event(self.computed[s])
-            cnt = self.st.push(self.send[s], self.chunk[k & 1])
-            nxt = self._send(self.chunk[k & 1], k & 1, self.st.first_frame_of(k), cnt)
-            self.freed[s].record(self.compute)
+            self.lanes.ready(s)
+            cnt = self.st.push(self.lanes.send[s], self.chunk[k & 1])
+            nxt = self._send(self.chunk[k & 1], piece_position(k)[0], cnt)
+            self.lanes.release(s)
             self.k += 1
             out, self.pending = self.pending, nxt
             if out is not None:
@@ -292,7 +227,7 @@ class _Core:
                 return self._harvest(out)
         if self.state == "tail":
             self.state = "end"
-            p = self._send(self.st.tail, 0, self.st.tail_position(), INTERP_LEN)   # after the last window its tail is final too
+            p = self._send(self.st.tail, tail_position(self.st.k), INTERP_LEN)   # after the last window its tail is final too
             if p is not None:
                 return self._harvest(p)
         return None

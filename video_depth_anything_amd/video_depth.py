@@ -19,18 +19,6 @@ from .config import INFER_LEN, get_config
 from .scheduler import network_size
 
 
-def _all_gather(out, inp):
-    """out[r] = rank r's `inp`. NCCL (= RCCL): asynchronous on the collective's own stream, returns the work handle.
-    Any other backend (gloo: the ranks-share-one-GPU rehearsal of tests/test_forward_gpu.py) is staged through the host."""
-    import torch.distributed as dist
-    if dist.get_backend() == "nccl":
-        return dist.all_gather_into_tensor(out, inp, async_op=True)
-    parts = [torch.empty(inp.shape, dtype=inp.dtype) for _ in range(dist.get_world_size())]
-    dist.all_gather(parts, inp.cpu())
-    out.copy_(torch.stack(parts))
-    return None
-
-
 class VideoDepthAnything:
     METRIC = False   # metric variant stitches with scale=1, shift=0 (metric_depth/.../video_depth.py:132)
 
@@ -114,16 +102,7 @@ class VideoDepthAnything:
     def infer_video_depth(self, frames, target_fps, input_size=518, device='cuda', fp32=False):
         if torch.device(device).type != 'cuda':
             raise RuntimeError("video_depth_anything_amd runs on an MI355X HIP device only (got device=%r)" % (device,))
-        eng = self._ensure_engine()
-        # two windows in flight on two lanes already fill each other's idle time: the encoder's frame-half split (vda_set_option
-        # "enc_split") measured -2 % on a 1024-frame video on top of them (profiles/r05), so it is off for the video and restored after
-        keep = eng.options.get("enc_split", -1)           # (-1: the library's default)
-        eng.set_option("enc_split", 0)
-        try:
-            with torch.cuda.device(eng.device):
-                return self._infer_video_depth(eng, frames, target_fps, input_size, bool(fp32))
-        finally:
-            eng.set_option("enc_split", keep)
+        return self._infer_video_depth(self._ensure_engine(), frames, target_fps, input_size, bool(fp32))
 
     def infer_video_depth_stream(self, frames, target_fps, input_size=518, device='cuda', fp32=False):
         """infer_video_depth for a video of unknown length, in bounded memory (stream.py):
@@ -150,40 +129,26 @@ class VideoDepthAnything:
 
     def _infer_video_depth(self, eng, frames, target_fps, input_size, fp32):
         import torch.distributed as dist
-        from . import ops
+        from .lanes import WindowLanes, as_u8_frames, check_frames, upload_runs, video_session
         from .scheduler import drive_windows, plan_windows, shard_windows
-        from .stitch import stitch_stream
+        from .stitch import all_gather, stitch_stream
         if not isinstance(frames, np.ndarray):
             frames = np.asarray(frames)
-        if frames.ndim != 4 or frames.shape[-1] != 3:
-            raise ValueError("infer_video_depth: frames must be [N, H, W, 3], got shape %r" % (tuple(frames.shape),))
+        check_frames(frames)
+        n = frames.shape[0]
         if frames.dtype != np.uint8:
-            # The reference computes frame.astype(float32) / 255 on whatever it is handed (video_depth.py:198). The device path
-            # keeps the video as uint8 in HBM, which is the same arithmetic exactly when the values ARE 0..255 integers: arrays of
-            # any dtype holding such values (wider integers, float32 frames out of a cv2 pipeline) are converted; values that are
-            # not 8-bit (fractions, negatives, > 255, NaN) are refused rather than silently truncated.
-            ok = True
-            for i in range(0, frames.shape[0], 64):              # chunked: a memory-mapped video is not paged in at once
-                c = np.asarray(frames[i:i + 64])
-                ok = bool(c.size == 0 or (c.min() >= 0 and c.max() <= 255 and
-                                          (np.issubdtype(c.dtype, np.integer) or np.array_equal(c, np.rint(c)))))
-                if not ok:
-                    break
-            if not ok:
-                raise TypeError("infer_video_depth: frames must hold 8-bit values (uint8, or any dtype whose values are integers "
-                                "within 0..255); got dtype %s with other values" % frames.dtype)
-            frames = frames.astype(np.uint8)
+            u8 = np.empty(frames.shape, dtype=np.uint8)
+            for i in range(0, n, 64):                            # chunked: a memory-mapped video is not paged in at once
+                u8[i:i + 64] = as_u8_frames(frames[i:i + 64])
+            frames = u8
         H0, W0 = frames.shape[1:3]
         H, W = network_size(H0, W0, input_size)
         dev = eng.device
-        n = frames.shape[0]
         plan = plan_windows(n)
         world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
         rank = dist.get_rank() if world > 1 else 0
         mine = list(shard_windows(len(plan), world, rank))
-        # multi-rank: the per-round all-gather runs beside the next windows' kernels - GEMMs that find CUs taken by it should lose
-        # those CUs, not a whole shift of tiles (dynamic tile draw)
-        eng.set_option("dyn_sched", 1 if world > 1 else 0)
+        wanted = self.result_ranks is None or rank in self.result_ranks
 
         # The uint8 frames THIS rank's windows read (frame 0, the previous window's key frame and its own 30 frames each -
         # SURVEY.md section 8e) live in HBM in a compact buffer, and each crosses PCIe once - not all up front: what the next
@@ -191,144 +156,60 @@ class VideoDepthAnything:
         # `frames` may be a memory map (utils/dc_utils.read_video_frames on a .npy): only the runs a window needs are touched
         need = sorted({f for k in mine for f in plan[k]})
         slot_of = {f: i for i, f in enumerate(need)}
-        video = torch.empty((max(len(need), 1), H0, W0, 3), dtype=torch.uint8, device=dev)
-        compute = torch.cuda.current_stream(dev)
-        upload = torch.cuda.Stream(device=dev)
         resident = set()
 
-        def ensure(k):
-            """Queue the upload of window k's not-yet-resident frames (runs of consecutive frames = one copy each)."""
-            if k is None:
-                return
-            todo = sorted(f for f in set(plan[k]) if f not in resident)
-            with torch.cuda.stream(upload):
-                i = 0
-                while i < len(todo):
-                    j = i
-                    while j + 1 < len(todo) and todo[j + 1] == todo[j] + 1:
-                        j += 1
-                    s0 = slot_of[todo[i]]
-                    run = frames[todo[i]:todo[j] + 1]
-                    if not (run.flags.c_contiguous and run.flags.writeable):
-                        run = np.array(run)                  # a memory-mapped or strided source: page this run in
-                    video[s0:s0 + (j - i + 1)].copy_(torch.from_numpy(run), non_blocking=True)
-                    i = j + 1
-            resident.update(todo)
+        with video_session(eng, 1 if world > 1 else 0) as (_, streams), torch.cuda.device(dev):
+            video = torch.empty((max(len(need), 1), H0, W0, 3), dtype=torch.uint8, device=dev)
+            upload = torch.cuda.Stream(device=dev)
+            lanes = WindowLanes(eng, video, H, W, fp32)
+            streams += lanes.lanes
+            send, acquire, ready, release = lanes.send, lanes.acquire, lanes.ready, lanes.release
 
-        # Windows are independent, so TWO are kept in flight on this GPU, each on its own HIP stream with its own input buffer,
-        # workspace slot and output slot: the tail rounds and launch gaps of one window's kernels are filled by the other's
-        # (measured: +6 % ViT-L, +17 % ViT-S frames/s over one window at a time, tools/two_stream.py).
-        NSLOT = 2
-        lanes = [torch.cuda.Stream(device=dev) for _ in range(NSLOT)]
-        computed = [torch.cuda.Event() for _ in range(NSLOT)]      # slot's window is in send[s] (recorded on its lane)
-        freed = [torch.cuda.Event() for _ in range(NSLOT)]         # the consumer is done with the slot (recorded on `compute`)
-        xin = [torch.empty(1, INFER_LEN, 3, H, W, dtype=torch.float32, device=dev) for _ in range(NSLOT)]
-        send = [torch.empty(INFER_LEN, H0, W0, dtype=torch.float32, device=dev) for _ in range(NSLOT)]
-        recv = [torch.empty(world, INFER_LEN, H0, W0, dtype=torch.float32, device=dev) for _ in range(NSLOT)] if world > 1 else None
-        used = [False] * NSLOT
+            def ensure(k):
+                """Queue the upload of window k's not-yet-resident frames (runs of consecutive frames = one copy each)."""
+                if k is None:
+                    return
+                todo = sorted(f for f in set(plan[k]) if f not in resident)
+                with torch.cuda.stream(upload):
+                    upload_runs(video, [(f, slot_of[f]) for f in todo], lambda f0, f1: [(f0, frames[f0:f1])])
+                resident.update(todo)
 
-        def acquire(s):
-            """Before anything of slot s (send[s], recv[s]) is overwritten: its lane waits until the consumer has finished with
-            what the slot held two rounds ago."""
-            if used[s]:
-                lanes[s].wait_event(freed[s])
-            used[s] = True
+            def window_depth(k, s, keys=None):
+                ensure(k)
+                lanes.run([slot_of[f] for f in plan[k]], s, upload, keys)
+                pos = mine.index(k)
+                ensure(mine[pos + 1] if pos + 1 < len(mine) else None)          # overlaps this window's compute
 
-        def window_depth(k, s, keys=None):
-            """Window k on lane s: gather (+ resize to the network size) + normalise (video_depth.py:197-201,
-            util/transform.py:109-147), forward, resize to the source size (video_depth.py:207-208) into send[s] [32,H0,W0]
-            (keys: the window's KEY_SLOTS frames are copied there too - three contiguous runs)."""
-            ensure(k)
-            lane = lanes[s]
-            lane.wait_stream(upload)
-            acquire(s)
-            with torch.cuda.stream(lane):
-                idx = torch.tensor([slot_of[f] for f in plan[k]], dtype=torch.int32, device=dev)
-                if (H0, W0) == (H, W):
-                    ops.gather_normalize_u8(video, idx, xin[s], INFER_LEN, H0, W0)
-                else:
-                    # cv2.resize(INTER_CUBIC) in the reference (util/transform.py:113); cv2 is absent offline, so this leg is
-                    # PARITY UNPINNED against cv2 itself: the kernel evaluates cv2's published definition (a = -0.75, half-pixel
-                    # centres, clamped taps) and is tested against that definition on the CPU.
-                    ops.gather_resize_normalize_u8(video, idx, xin[s], INFER_LEN, H0, W0, H, W)
-                depth = eng.forward(xin[s], fp32=fp32, slot=s)                   # [1,32,H,W] fp32
-                ops.bilinear_plane(depth.view(INFER_LEN, H, W), send[s], INFER_LEN, H, W, H0, W0)
-                if keys is not None:
-                    keys[0:2].copy_(send[s][0:2])
-                    keys[2].copy_(send[s][12])
-                    keys[3:].copy_(send[s][INFER_LEN - 8:])
-                computed[s].record(lane)
-            pos = mine.index(k)
-            ensure(mine[pos + 1] if pos + 1 < len(mine) else None)              # overlaps this window's compute
+            if self.exchange == "keys":
+                from .scheduler import KEY_SLOTS, drive_windows_keys
+                from .stitch import DeviceKeyOps, collect_pieces
+                assert tuple(KEY_SLOTS) == (0, 1, 12) + tuple(range(INFER_LEN - 8, INFER_LEN))
 
-        def exchange(s):
-            """The one exchange of the path (RCCL all-gather over xGMI), issued on the slot's lane behind its window. A rank with
-            no window in this round still takes part, so the slot is acquired here too.
-            The wait for the collective is bound HERE, explicitly, to the slot's lane (Work.wait() on the NCCL backend is a
-            stream-side wait of whichever stream is current - it does not block the host): computed[s] is recorded behind it, and
-            the consumer's stream waits for that event in ready(s). Nothing depends on which stream happens to be current when
-            drive_windows harvests the round. The lane's next window (two rounds on) queues behind the gather, which by then has
-            long finished under the other lane's compute."""
-            acquire(s)
-            with torch.cuda.stream(lanes[s]):
-                h = _all_gather(recv[s], send[s])
-                if h is not None:
-                    h.wait()
-                computed[s].record(lanes[s])
-            return None
+                def gather_keys(s, out, inp):
+                    lanes.behind(s, (lambda: all_gather(out, inp)) if world > 1 else (lambda: out[0].copy_(inp)))
 
-        def ready(s):
-            compute.wait_event(computed[s])
-
-        def release(s):
-            freed[s].record(compute)
-
-        if self.exchange == "keys":
-            from .scheduler import KEY_SLOTS, drive_windows_keys
-            from .stitch import DeviceKeyOps, collect_pieces
-            assert tuple(KEY_SLOTS) == (0, 1, 12) + tuple(range(INFER_LEN - 8, INFER_LEN))
-
-            def gather_keys(s, out, inp):
-                acquire(s)
-                with torch.cuda.stream(lanes[s]):
-                    if world > 1:
-                        h = _all_gather(out, inp)
-                        if h is not None:
-                            h.wait()
-                    else:
-                        out[0].copy_(inp)
-                    computed[s].record(lanes[s])
-                return None
-
-            kops = DeviceKeyOps(send, H0, W0, dev, self.METRIC, world, rank, len(plan), self.result_ranks, window_depth, ready, release,
-                                gather_keys, acquire)
-            pieces = drive_windows_keys(len(plan), world, rank, kops, self.result_ranks)
-            if self.result_ranks is not None and rank not in self.result_ranks:
-                for _ in pieces:
+                kops = DeviceKeyOps(send, H0, W0, dev, self.METRIC, world, rank, len(plan), self.result_ranks, window_depth, ready,
+                                    release, gather_keys, acquire)
+                pieces = drive_windows_keys(len(plan), world, rank, kops, self.result_ranks)
+                if wanted:
+                    depths = collect_pieces(pieces, n, H0, W0, dev, on_copied=kops.copied)
+            else:
+                # One process per GPU: rank r computes windows r, r + world, ... with no data-path collective; after each round
+                # the finished windows are all-gathered (the one exchange of the path: RCCL over xGMI, on the slot's lane behind
+                # its window, under the next round's compute - the lane's next window, two rounds on, queues behind a gather that
+                # has long finished under the other lane's compute) and handed to the stitcher in window order, so only a two-slot
+                # ring of gathered windows ever exists. Ranks without a window in the last round contribute an unused slot.
+                recv = [torch.empty(world, INFER_LEN, H0, W0, dtype=torch.float32, device=dev) for _ in send] if world > 1 else None
+                pieces = drive_windows(len(plan), world, rank, send, recv, window_depth,
+                                       lambda s: lanes.behind(s, lambda: all_gather(recv[s], send[s])), ready, release)
+                if wanted:
+                    depths = stitch_stream(pieces, n, H0, W0, dev, metric=self.METRIC)
+            if not wanted:
+                for _ in pieces:                                                 # compute and exchange; no stitch, no D2H
                     pass
-                eng.check()
-                return None, target_fps
-            depths = collect_pieces(pieces, n, H0, W0, dev, on_copied=kops.copied)
-            for lane in lanes:
-                compute.wait_stream(lane)
+                depths = None
             eng.check()                                   # a window whose residual stream left fp16's range is an error, not a NaN video
             return depths, target_fps
-
-        # One process per GPU: rank r computes windows r, r + world, ... with no data-path collective; after each round the
-        # finished windows are all-gathered (asynchronously, under the next round's compute) and handed to the stitcher in window
-        # order, so only a two-slot ring of gathered windows ever exists. Ranks without a window in the last round contribute an
-        # unused slot.
-        windows = drive_windows(len(plan), world, rank, send, recv, window_depth, exchange, ready, release)
-        if self.result_ranks is not None and rank not in self.result_ranks:
-            for _ in windows:                                                    # compute and exchange; no stitch, no D2H
-                pass
-            eng.check()
-            return None, target_fps
-        depths = stitch_stream(windows, n, H0, W0, dev, metric=self.METRIC)
-        for lane in lanes:
-            compute.wait_stream(lane)
-        eng.check()
-        return depths, target_fps
 
 
 class MetricVideoDepthAnything(VideoDepthAnything):
