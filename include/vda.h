@@ -96,8 +96,8 @@ typedef struct vda_gemm_args {
                                not by a whole shift of tiles. Other kernels ignore it. Results do not depend on it. */
     int32_t stats_ld;       /* VDA_EPI_SCALE_RES_SPLIT: rows per column block of the stats array (0 = M): lets a caller run a GEMM as
                                several row ranges (pointers advanced, M = rows of the range) into one [N/64, stats_ld, 2] array */
-    int32_t tile_rows;      /* 0 = the dispatcher's choice; 192 = 192-row tiles where the kernel family has them (the remainder
-                               launch of a row split, vda_gemm_plan_split). Results do not depend on it. */
+    int32_t tile_rows;      /* 0 = the planner's choice; 192 = 192-row tiles where the kernel family has them (the remainder
+                               launch of a row split); any other value: a part of a split made by hand. Results do not depend on it. */
 } vda_gemm_args;
 
 int vda_gemm_f16(const vda_gemm_args* args, vda_stream_t stream);
@@ -121,18 +121,55 @@ int vda_gemm_set_debug(int flags);
 /* Cap on the workgroups the persistent GEMM / conv kernels launch (0 = one per CU, the default; a multiple of 8): lets two
  * independent launch sequences on two streams take half the chip each instead of queueing behind each other's full grids. */
 int vda_set_max_wgs(int n);
-/* Row split of a large dense GEMM on the current device: returns M1 <= M. Rows [0, M1) fill whole rounds of 256 x 256 tiles on the
- * device's CUs; rows [M1, M) run as one more call with tile_rows = 192 (a 192-row round costs ~0.8 of a 256-row one). M1 == M: no
- * split pays (or the epilogue / shape has no 192-row kernel). vda_gemm_f16 applies the same plan by itself when sched == NULL and
- * tile_rows == 0; a caller that wants the two launches bracketed separately (or has per-launch sched counters) splits by hand:
- * advance A / out / res / res2 / out2 by M1 rows, stats (VDA_EPI_LN_*) and pos (VDA_EPI_SCALE_RES_SPLIT) by M1 rows of 2 floats,
- * stats (VDA_EPI_SCALE_RES_SPLIT) by M1 rows of 2 floats with stats_ld = M. A row's result is bit-identical either way. */
+/* What vda_gemm_f16 would run, as a value: vda_gemm_f16 = validate, vda_gemm_plan, launch each record. The planner launches nothing,
+ * follows no operand pointer (a shape with NULL operands plans) and needs no GPU when ncu is given. One record = one kernel launch. */
+enum vda_gemm_family {
+    VDA_GEMM_FAM_128 = 0,       /* gemm_kernel: 128-row tiles, any size, any epilogue */
+    VDA_GEMM_FAM_256 = 1,       /* gemm256_kernel: 256-row tiles, one barrier per K tile, 32x32x16 MFMA (variants 1 / 2 only) */
+    VDA_GEMM_FAM_256S = 2,      /* gemm256s_kernel: the same on 16x16x32 MFMA; also 192 x 128 and 192 x 384 tiles */
+    VDA_GEMM_FAM_8P = 3,        /* gemm8p_kernel: 8-phase two-group schedule, 256 x 256 / 256 x 128 / 192 x 256 tiles */
+    VDA_GEMM_FAM_CONV_LDS = 4   /* patch-in-LDS direct 3x3 convolution (bn = 32 or 64 output channels per pass) */
+};
+typedef struct vda_gemm_launch {
+    int32_t r0, rows;           /* the rows [r0, r0 + rows) of the GEMM this launch computes */
+    int32_t family;             /* vda_gemm_family */
+    int32_t bm, bn, per_cu;     /* tile and persistent workgroups per CU (bm = 0: VDA_GEMM_FAM_CONV_LDS) */
+    int32_t ksched;             /* K-loop schedule of the 8-phase kernel as its name reports it (1 = default) */
+    int32_t dyn;                /* the dynamic-draw instantiation (args.sched set, 8-phase kernel, default schedule) */
+    int32_t options;            /* vda_gemm_args.relu_in as the kernel sees it: bit 0 + the planner's option bits (vda_common.h) */
+    int32_t tile_rows;          /* vda_gemm_args.tile_rows of the launch */
+    int32_t a_mode, epilogue;   /* (of the call: with the above, everything a kernel's name is made of) */
+} vda_gemm_launch;
+typedef struct vda_gemm_plan_t {
+    int32_t n;                  /* 1, or 2 for a row split */
+    vda_gemm_launch rec[2];     /* in row order; together they cover [0, M) exactly once */
+} vda_gemm_plan_t;
+/* m_plan: the rows the shape decisions (tile family, 192-row tiles, the small-grid fallback, non-temporal stores) are taken for when
+ *   args is a row range of a larger GEMM whose other rows run beside it (0 or <= args->M: args->M). The forward's encoder runs each
+ *   GEMM as two frame halves on two streams: each half gets the kernel the whole-clip GEMM would get - same family, same per-row
+ *   arithmetic, same store policy - and is never row-split further.
+ * ncu: the CUs to plan for (0 = the current device's, capped by vda_set_max_wgs).
+ * sched_per_launch: != 0 when the caller gives every record its own args.sched counters (they belong to ONE launch, so a call that
+ *   brings one block of them - vda_gemm_f16 - is not split).
+ * Row split: a large dense GEMM on the 8-phase 256 x 256 tile runs rows [0, M1) as whole rounds of the chip and rows [M1, M) on
+ *   192 x 256 tiles (a 192-row round costs ~0.8 of a 256-row one) when the cost model of vda_gemm_plan_split predicts a gain; never
+ *   with tile_rows != 0 or lda == 0 (a broadcast row). A row's result is bit-identical either way. */
+int vda_gemm_plan(const vda_gemm_args* args, int m_plan, int ncu, int sched_per_launch, vda_gemm_plan_t* out);
+/* The kernel instantiation of a record exactly as a profiler prints it (without the namespace); returns the length, name cut to len. */
+int vda_gemm_launch_name(const vda_gemm_launch* rec, char* name, int len);
+/* 1 when the (family, tile, A mode, epilogue) instantiation exists in this build: the planner emits nothing else. */
+int vda_gemm_built(int family, int bm, int bn, int per_cu, int a_mode, int epilogue);
+/* Re-read the planner's environment switches (they are read once, at the first use): for tools and tests that compare settings. */
+int vda_gemm_reload_tuning(void);
+/* The two pieces of the row split on their own (tests and tools). vda_gemm_plan_split: M1 <= M of the cost model alone, for the
+ * current device (M1 == M: no split pays, or the epilogue / shape has no 192-row kernel). vda_gemm_row_range: *out = the arguments of
+ * rows [r0, r0 + rows) of *args, as the launch of a record builds them: A / out / res / res2 / out2 advanced by r0 rows, stats
+ * (VDA_EPI_LN_*) and pos (VDA_EPI_SCALE_RES_SPLIT) by r0 rows of 2 floats, stats (VDA_EPI_SCALE_RES_SPLIT) by r0 rows of 2 floats
+ * with stats_ld = M. lda / ldc of 0 are read as K / N HERE (a row range is of a real matrix); vda_gemm_f16 itself reads lda == 0 as
+ * "every row is A's row 0". Any kernel family honours stats_ld (the 8-phase, one-barrier and 128-row kernels alike). */
 int vda_gemm_plan_split(int M, int N, int K, int epilogue, int a_mode);
-/* *out = the arguments of rows [r0, r0 + rows) of *args by exactly those rules. lda / ldc of 0 are read as K / N HERE (a row range
- * is of a real matrix); vda_gemm_f16 itself reads lda == 0 as "every row is A's row 0" (broadcast) and never row-splits such a
- * call on its own. Any kernel family honours stats_ld (the 8-phase, one-barrier and 128-row kernels alike). */
 int vda_gemm_row_range(const vda_gemm_args* args, int r0, int rows, vda_gemm_args* out);
-/* Name of the kernel family the last vda_gemm_f16 call on this thread dispatched to (for profiling reports). */
+/* vda_gemm_launch_name of the last record vda_gemm_f16 launched on this thread ("" before the first). */
 const char* vda_gemm_last_kernel(void);
 
 /* ---------------------------------------------------------------- norms

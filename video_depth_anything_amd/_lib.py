@@ -36,6 +36,16 @@ class Config(C.Structure):
                 ("use_bn", C.c_int32), ("pe_rope", C.c_int32)]
 
 
+class GemmLaunch(C.Structure):
+    """vda_gemm_launch (include/vda.h): one kernel launch of a plan."""
+    _fields_ = [(n, C.c_int32) for n in ("r0", "rows", "family", "bm", "bn", "per_cu", "ksched", "dyn", "options", "tile_rows", "a_mode", "epilogue")]
+
+
+class GemmPlan(C.Structure):
+    _fields_ = [("n", C.c_int32), ("rec", GemmLaunch * 2)]
+
+
+FAM_128, FAM_256, FAM_256S, FAM_8P, FAM_CONV_LDS = range(5)
 PREC_F16, PREC_F32 = 0, 1
 DTYPE_F32 = 0
 
@@ -51,6 +61,10 @@ SIGNATURES = {
     "vda_gemm_plan_split": (_i, [_i, _i, _i, _i, _i]),
     "vda_gemm_row_range": (_i, [C.POINTER(GemmArgs), _i, _i, C.POINTER(GemmArgs)]),
     "vda_gemm_last_kernel": (C.c_char_p, []),
+    "vda_gemm_plan": (_i, [C.POINTER(GemmArgs), _i, _i, _i, C.POINTER(GemmPlan)]),
+    "vda_gemm_launch_name": (_i, [C.POINTER(GemmLaunch), C.c_char_p, _i]),
+    "vda_gemm_built": (_i, [_i, _i, _i, _i, _i, _i]),
+    "vda_gemm_reload_tuning": (_i, []),
     "vda_layernorm_f32_f16": (_i, [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     "vda_layernorm_residual_f32_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _vp]),
     "vda_layernorm_f32_f32": (_i, [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _vp, _i, _i, _vp]),
@@ -145,6 +159,12 @@ def _load():
 
 
 lib = _load()
+
+
+def launch_name(rec):
+    buf = C.create_string_buffer(64)
+    lib.vda_gemm_launch_name(C.byref(rec), buf, 64)
+    return buf.value.decode()
 
 
 def check(rc, what=""):

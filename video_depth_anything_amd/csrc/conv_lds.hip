@@ -444,13 +444,17 @@ extern "C" int vda_conv_lds_set_variant(int v) {      // 0 = default (the C = 64
     return 0;
 }
 
-// Called by vda_gemm_f16's dispatcher (gemm.hip) for VDA_A_CONV3X3 problems this kernel covers; returns -1 when it does not.
+// The VDA_A_CONV3X3 problems this file covers (asked by the planner in gemm.hip; reads shape fields only)
+bool vda_conv3x3_lds_covers(const vda_gemm_args& a) {
+    if (a.a_mode != VDA_A_CONV3X3 || a.cStride != 1 || a.N > 64 || a.N % 4 != 0 || a.cCin % CC != 0 || a.ldc % 4 != 0) return false;
+    if (a.epilogue != VDA_EPI_BIAS_F16 && a.epilogue != VDA_EPI_BIAS_RELU_F16 && a.epilogue != VDA_EPI_RES_F16) return false;
+    return (long long)((a.cW + TW - 1) / TW) * ((a.cH + TH - 1) / TH) * a.cB < (1ll << 30);
+}
+
 int vda_conv3x3_lds(const vda_gemm_args& a, hipStream_t s) {
-    if (a.a_mode != VDA_A_CONV3X3 || a.cStride != 1 || a.N > 64 || a.N % 4 != 0 || a.cCin % CC != 0 || a.ldc % 4 != 0) return -1;
-    if (a.epilogue != VDA_EPI_BIAS_F16 && a.epilogue != VDA_EPI_BIAS_RELU_F16 && a.epilogue != VDA_EPI_RES_F16) return -1;
+    if (!vda_conv3x3_lds_covers(a)) return -1;
     const int tiles_x = (a.cW + TW - 1) / TW, tiles_y = (a.cH + TH - 1) / TH;
     const long long ntiles = (long long)tiles_x * tiles_y * a.cB;
-    if (ntiles >= (1ll << 30)) return -1;
     const dim3 grid((unsigned)((ntiles + 7) / 8 * 8));
     const h16* res = a.epilogue == VDA_EPI_RES_F16 ? (const h16*)a.res : nullptr;
     const h16* res2 = a.epilogue == VDA_EPI_RES_F16 ? (const h16*)a.res2 : nullptr;
@@ -469,28 +473,28 @@ int vda_conv3x3_lds(const vda_gemm_args& a, hipStream_t s) {
         const int g64 = (int)(ntiles < ncu ? (ntiles + 7) / 8 * 8 : ncu);
         if (cb == 1)
             hipLaunchKernelGGL((c64::conv3x3_c64_kernel<1>), dim3(g64), dim3(c64::NT64), smem, s, (const h16*)a.A, (const h16*)a.W, a.bias, res, res2, (h16*)a.out,
-                               (const h16*)a.zero_page, a.cH, a.cW, a.N, a.ldc, a.relu_in & 1, relu_out, tiles_x, tiles_y, (int)ntiles);
+                               (const h16*)a.zero_page, a.cH, a.cW, a.N, a.ldc, a.relu_in & VDA_OPT_RELU_IN, relu_out, tiles_x, tiles_y, (int)ntiles);
         else if (g_conv_lds_variant == 2)
             hipLaunchKernelGGL((c64::conv3x3_c64_kernel<2, 1>), dim3(g64), dim3(c64::NT64), smem, s, (const h16*)a.A, (const h16*)a.W, a.bias, res, res2, (h16*)a.out,
-                               (const h16*)a.zero_page, a.cH, a.cW, a.N, a.ldc, a.relu_in & 1, relu_out, tiles_x, tiles_y, (int)ntiles);
+                               (const h16*)a.zero_page, a.cH, a.cW, a.N, a.ldc, a.relu_in & VDA_OPT_RELU_IN, relu_out, tiles_x, tiles_y, (int)ntiles);
         else if (g_conv_lds_variant == 4)
             hipLaunchKernelGGL((c64::conv3x3_c64_kernel<2, 3>), dim3(g64), dim3(c64::NT64), smem, s, (const h16*)a.A, (const h16*)a.W, a.bias, res, res2, (h16*)a.out,
-                               (const h16*)a.zero_page, a.cH, a.cW, a.N, a.ldc, a.relu_in & 1, relu_out, tiles_x, tiles_y, (int)ntiles);
+                               (const h16*)a.zero_page, a.cH, a.cW, a.N, a.ldc, a.relu_in & VDA_OPT_RELU_IN, relu_out, tiles_x, tiles_y, (int)ntiles);
         else if (g_conv_lds_variant == 3)
             hipLaunchKernelGGL((c64::conv3x3_c64_kernel<2, 2>), dim3(g64), dim3(c64::NT64), smem, s, (const h16*)a.A, (const h16*)a.W, a.bias, res, res2, (h16*)a.out,
-                               (const h16*)a.zero_page, a.cH, a.cW, a.N, a.ldc, a.relu_in & 1, relu_out, tiles_x, tiles_y, (int)ntiles);
+                               (const h16*)a.zero_page, a.cH, a.cW, a.N, a.ldc, a.relu_in & VDA_OPT_RELU_IN, relu_out, tiles_x, tiles_y, (int)ntiles);
         else
             hipLaunchKernelGGL((c64::conv3x3_c64_kernel<2>), dim3(g64), dim3(c64::NT64), smem, s, (const h16*)a.A, (const h16*)a.W, a.bias, res, res2, (h16*)a.out,
-                               (const h16*)a.zero_page, a.cH, a.cW, a.N, a.ldc, a.relu_in & 1, relu_out, tiles_x, tiles_y, (int)ntiles);
+                               (const h16*)a.zero_page, a.cH, a.cW, a.N, a.ldc, a.relu_in & VDA_OPT_RELU_IN, relu_out, tiles_x, tiles_y, (int)ntiles);
         VDA_LAUNCH_CHECK();
         return 0;
     }
     if (a.N <= 32)
         hipLaunchKernelGGL((conv3x3_lds_kernel<1>), grid, dim3(256), 0, s, (const h16*)a.A, (const h16*)a.W, a.bias, res, res2, (h16*)a.out,
-                           (const h16*)a.zero_page, a.cH, a.cW, a.cCin, a.N, a.ldc, a.relu_in & 1, relu_out, tiles_x, tiles_y, (int)ntiles);
+                           (const h16*)a.zero_page, a.cH, a.cW, a.cCin, a.N, a.ldc, a.relu_in & VDA_OPT_RELU_IN, relu_out, tiles_x, tiles_y, (int)ntiles);
     else
         hipLaunchKernelGGL((conv3x3_lds_kernel<2>), grid, dim3(256), 0, s, (const h16*)a.A, (const h16*)a.W, a.bias, res, res2, (h16*)a.out,
-                           (const h16*)a.zero_page, a.cH, a.cW, a.cCin, a.N, a.ldc, a.relu_in & 1, relu_out, tiles_x, tiles_y, (int)ntiles);
+                           (const h16*)a.zero_page, a.cH, a.cW, a.cCin, a.N, a.ldc, a.relu_in & VDA_OPT_RELU_IN, relu_out, tiles_x, tiles_y, (int)ntiles);
     VDA_LAUNCH_CHECK();
     return 0;
 }

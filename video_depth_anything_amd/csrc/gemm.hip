@@ -206,40 +206,27 @@ __global__ void __launch_bounds__(256) split_partials_kernel(const h16* __restri
 
 }  // namespace
 
-// gemm256_*.hip: return -1 when the (A mode, epilogue) pair is not instantiated for the large tile
-int vda_gemm256_dense_bn256(const vda_gemm_args& a, hipStream_t s);
+// The family launchers. Each returns -1 for an (A mode, epilogue) pair its family is not built for (gemm_epilogue.h); the planner
+// asks vda_gemm_built first, so -1 from a planned launch is an internal error.
+int vda_gemm256_dense_bn256(const vda_gemm_args& a, hipStream_t s);          // gemm256_*.hip: 32x32x16 MFMA
 int vda_gemm256_dense_bn128(const vda_gemm_args& a, hipStream_t s);
 int vda_gemm256_conv_bn256(const vda_gemm_args& a, hipStream_t s);
 int vda_gemm256_conv_bn128(const vda_gemm_args& a, hipStream_t s);
-// gemm256s_*.hip: the same tiles on v_mfma_f32_16x16x32_f16
-int vda_gemm256s_dense_bn256(const vda_gemm_args& a, hipStream_t s);
+int vda_gemm256s_dense_bn256(const vda_gemm_args& a, hipStream_t s);         // gemm256s_*.hip: the same tiles on 16x16x32 MFMA
 int vda_gemm256s_dense_bn128(const vda_gemm_args& a, hipStream_t s);
 int vda_gemm256s_conv_bn256(const vda_gemm_args& a, hipStream_t s);
 int vda_gemm256s_conv_bn128(const vda_gemm_args& a, hipStream_t s);
-int vda_gemm256s_dense_bn128_bm192(const vda_gemm_args& a, hipStream_t s);      // 192 x 128 tiles, six waves; -1 = epilogue not built
-int vda_gemm256s_dense_bn128_bm192_x2(const vda_gemm_args& a, hipStream_t s);   // the same tile, TWO workgroups per CU (variant 11); -1 = not built
-int vda_gemm256s_dense_bn384_bm192(const vda_gemm_args& a, hipStream_t s);      // 192 x 384 tiles, twelve waves; -1 = epilogue not built
-
-// gemm8p_*.hip: 256 x 256 tile, 8-phase two-group schedule
-int vda_gemm8p_dense_bn256(const vda_gemm_args& a, hipStream_t s);
+int vda_gemm256s_dense_bn128_bm192(const vda_gemm_args& a, hipStream_t s);      // 192 x 128 tiles, six waves
+int vda_gemm256s_dense_bn128_bm192_x2(const vda_gemm_args& a, hipStream_t s);   // the same tile, TWO workgroups per CU (variant 11)
+int vda_gemm256s_dense_bn384_bm192(const vda_gemm_args& a, hipStream_t s);      // 192 x 384 tiles, twelve waves
+int vda_gemm8p_dense_bn256(const vda_gemm_args& a, hipStream_t s);           // gemm8p_*.hip: 8-phase two-group schedule
 int vda_gemm8p_conv_bn256(const vda_gemm_args& a, hipStream_t s);
 int vda_gemm8p_dense_bn256_sched(const vda_gemm_args& a, hipStream_t s, int sched);
 int vda_gemm8p_dense_bn128(const vda_gemm_args& a, hipStream_t s);
-int vda_gemm8p_dense_bn256_bm192(const vda_gemm_args& a, hipStream_t s);         // 192 x 256 tiles; -1 = epilogue not built
+int vda_gemm8p_dense_bn256_bm192(const vda_gemm_args& a, hipStream_t s);     // 192 x 256 tiles
 int vda_gemm8p_conv_bn128(const vda_gemm_args& a, hipStream_t s);
-
-// conv_lds.hip: patch-in-LDS direct 3x3 convolution for narrow outputs; -1 when the problem is not one it covers
-int vda_conv3x3_lds(const vda_gemm_args& a, hipStream_t s);
-
-static int vda_gemm256s_launch(const vda_gemm_args& a, int bn, hipStream_t s) {
-    if (a.a_mode == VDA_A_DENSE) return bn == 256 ? vda_gemm256s_dense_bn256(a, s) : vda_gemm256s_dense_bn128(a, s);
-    return bn == 256 ? vda_gemm256s_conv_bn256(a, s) : vda_gemm256s_conv_bn128(a, s);
-}
-
-static int vda_gemm256_launch(const vda_gemm_args& a, int bn, hipStream_t s) {
-    if (a.a_mode == VDA_A_DENSE) return bn == 256 ? vda_gemm256_dense_bn256(a, s) : vda_gemm256_dense_bn128(a, s);
-    return bn == 256 ? vda_gemm256_conv_bn256(a, s) : vda_gemm256_conv_bn128(a, s);
-}
+int vda_conv3x3_lds(const vda_gemm_args& a, hipStream_t s);                  // conv_lds.hip: patch-in-LDS direct 3x3 convolution for
+bool vda_conv3x3_lds_covers(const vda_gemm_args& a);                         // narrow outputs, and the problems it covers
 
 // the 128-row kernel (any size, any epilogue)
 static int launch_small(const vda_gemm_args& a, hipStream_t s) {
@@ -258,23 +245,57 @@ static int launch_small(const vda_gemm_args& a, hipStream_t s) {
     return narrow ? launch<128, 64, VDA_A_CONV3X3>(a, s) : launch<128, 128, VDA_A_CONV3X3>(a, s);
 }
 
-static int g_gemm_variant = -1;   // tuning / A-B hook, see the dispatch in vda_gemm_f16
-
-static thread_local const char* g_last_kernel = "";
-
-extern "C" const char* vda_gemm_last_kernel(void) { return g_last_kernel; }
-
-extern "C" int vda_gemm_set_variant(int v) {
-    g_gemm_variant = v;
-    return 0;
+extern "C" int vda_gemm_built(int family, int bm, int bn, int per_cu, int a_mode, int epilogue) {
+    const bool dense = a_mode == VDA_A_DENSE, conv = a_mode == VDA_A_CONV3X3, wide = bn == 256 || bn == 128;
+    if (epilogue < 0 || epilogue > VDA_EPI_LN_GELU_F16 || !(dense || conv)) return 0;
+    switch (family) {
+        case VDA_GEMM_FAM_128: return bm == 128 && (bn == 64 || bn == 128) && per_cu == 1;
+        case VDA_GEMM_FAM_256: return bm == 256 && wide && per_cu == 1 && (dense ? VDA_EPI_BUILT(VDA_EPIS_DENSE_MFMA32, epilogue) : VDA_EPI_BUILT(VDA_EPIS_CONV, epilogue));
+        case VDA_GEMM_FAM_256S:
+            if (bm == 256) return wide && per_cu == 1 && (dense ? VDA_EPI_BUILT(VDA_EPIS_DENSE, epilogue) : VDA_EPI_BUILT(VDA_EPIS_CONV, epilogue));
+            if (bm != 192 || !dense) return 0;
+            if (bn == 384) return per_cu == 1 && VDA_EPI_BUILT(VDA_EPIS_256S_BN384, epilogue);
+            return bn == 128 && (per_cu == 2 ? VDA_EPI_BUILT(VDA_EPIS_256S_BM192_X2, epilogue) : per_cu == 1 && VDA_EPI_BUILT(VDA_EPIS_256S_BM192, epilogue));
+        case VDA_GEMM_FAM_8P:
+            if (per_cu != 1) return 0;
+            if (bm == 192) return bn == 256 && dense && VDA_EPI_BUILT(VDA_EPIS_8P_BM192, epilogue);
+            return bm == 256 && wide && (dense ? VDA_EPI_BUILT(VDA_EPIS_DENSE, epilogue) : VDA_EPI_BUILT(VDA_EPIS_CONV, epilogue));
+        case VDA_GEMM_FAM_CONV_LDS: return bm == 0 && (bn == 32 || bn == 64) && per_cu == 1 && conv && VDA_EPI_BUILT(VDA_EPIS_CONV, epilogue);
+        default: return 0;
+    }
 }
 
-static int g_gemm_debug = 0;      // diagnostic switches of the 8-phase kernel (bit 0 clock stamps into pos, bit 1 L2-blocked tile order)
-
-extern "C" int vda_gemm_set_debug(int flags) {
-    g_gemm_debug = flags & 0xff;
-    return 0;
+// Everything the planner reads besides the call's own arguments, in one place: the A/B integers of vda_gemm_set_variant /
+// vda_gemm_set_debug and the environment switches (read once, at the first use; vda_gemm_reload_tuning reads them again).
+struct GemmTuning {
+    int variant = -1;      // vda_gemm_set_variant: -1 auto; 0 = 128-row tiles; 1 / 2 = 256x256 / 256x128 on 32x32x16 MFMA; 3 / 4 = the same on
+                           // 16x16x32 MFMA; 5 (+ 16 * flags + 32 * sched) = 256x256 8-phase; 7 = patch-in-LDS conv; 8 = 192x128; 9 = 256x128
+                           // 8-phase; 10 = 192x384; 11 = 192x128 twice per CU
+    int debug = 0;         // vda_gemm_set_debug: diagnostic switches of the 8-phase kernel (VDA_DEBUG_*)
+    int split, r192;       // VDA_GEMM_SPLIT (1; 0 = never, 2 = whenever the round count says so, any K), VDA_GEMM_R192 (84: cost of a 192-row round, %)
+    int big_min_n;         // VDA_GEMM_BIG_MIN_N (192): narrower outputs stay on the 128-row kernel
+    int eight128;          // VDA_GEMM_8P128 (0): 256 x 128 on the 8-phase schedule too (ViT-S's N = 384 / 1152 / 1536 GEMMs, output_conv1: -4..+2 %)
+    int stagger;           // VDA_GEMM_STAGGER (0; 1 / 2 = start stagger, see gemm8p_kernel.h)
+    long long nt_mb;       // VDA_GEMM_NT_MB (192; 0 = never): outputs of that many megabytes and up get non-temporal stores
+    int bm192;             // VDA_GEMM_BM192 (1): 192 x 128 tiles when they quantise better
+    int small_grid;        // VDA_GEMM_SMALL_GRID (1): the 128-row kernel when 256-row tiles fill at most half of the CUs
+    int bn384;             // VDA_GEMM_BN384 (2): where 192 x 384 tiles apply, see plan_one
+    int conv_lds;          // VDA_CONV_LDS (1): narrow-output 3x3 convs as a patch-in-LDS direct convolution
+    void read_env() {
+        auto env = [](const char* k, long long d) { const char* v = getenv(k); return v ? atoll(v) : d; };
+        split = (int)env("VDA_GEMM_SPLIT", 1), r192 = (int)env("VDA_GEMM_R192", 84), big_min_n = (int)env("VDA_GEMM_BIG_MIN_N", 192);
+        eight128 = (int)env("VDA_GEMM_8P128", 0), stagger = (int)env("VDA_GEMM_STAGGER", 0), nt_mb = env("VDA_GEMM_NT_MB", 192);
+        bm192 = (int)env("VDA_GEMM_BM192", 1), small_grid = (int)env("VDA_GEMM_SMALL_GRID", 1), bn384 = (int)env("VDA_GEMM_BN384", 2);
+        conv_lds = (int)env("VDA_CONV_LDS", 1);
+    }
+};
+static GemmTuning& tuning() {
+    static GemmTuning t = [] { GemmTuning x; x.read_env(); return x; }();
+    return t;
 }
+extern "C" int vda_gemm_set_variant(int v) { return tuning().variant = v, 0; }
+extern "C" int vda_gemm_set_debug(int flags) { return tuning().debug = flags & VDA_OPT_BYTE, 0; }
+extern "C" int vda_gemm_reload_tuning(void) { return tuning().read_env(), 0; }
 
 static int device_cus() {
     static thread_local int ncu = 0;
@@ -288,10 +309,6 @@ static int device_cus() {
     return (cap >= 8 && cap < ncu) ? (cap & ~7) : ncu;
 }
 
-static bool bm192_epilogue(int epilogue) {
-    return epilogue == VDA_EPI_BIAS_F16 || epilogue == VDA_EPI_SCALE_RES_F32 || epilogue == VDA_EPI_SCALE_RES_SPLIT || epilogue == VDA_EPI_LN_BIAS_F16;
-}
-
 // Rows [0, M1) on 256 x 256 tiles in whole rounds of the chip, rows [M1, M) on 192 x 256 tiles. Cost model, calibrated on the MI355X
 // (tools/gemm_ab.py -1,5,1029, round 3): a round of 256-row tiles takes t = 1.6 us per K tile + 5 us; a round of 192-row tiles 0.84 t
 // (not 0.75: the load sections of the two-group schedule shrink less than its MFMA sections); the second launch costs ~10 us
@@ -299,21 +316,19 @@ static bool bm192_epilogue(int epilogue) {
 // plain epilogue, 357 -> 348 with the split-residual one) pays; K = 1024 (qkv 9 -> 6 + 3 x 0.84: 260 -> 272 us; proj) does not - a
 // partial last round already runs faster than a full one, which a round count cannot see: K < 2048 never splits. M1 == M unless
 // the model predicts at least 1.5 % (VDA_GEMM_SPLIT=0: never; 2: whenever the round count says so, any K - the A/B switch).
-extern "C" int vda_gemm_plan_split(int M, int N, int K, int epilogue, int a_mode) {
-    static const int allow = getenv("VDA_GEMM_SPLIT") ? atoi(getenv("VDA_GEMM_SPLIT")) : 1;
-    static const int r192 = getenv("VDA_GEMM_R192") ? atoi(getenv("VDA_GEMM_R192")) : 84;
-    if (!allow || a_mode != VDA_A_DENSE || !bm192_epilogue(epilogue) || M < 4096 || N < 256 || K < (allow == 2 ? 256 : 2048)) return M;
-    const long long ncu = device_cus(), nbn = (N + 255) / 256;
-    const long long rt = (M + 255) / 256;
+static int plan_split(const GemmTuning& t, long long ncu, int M, int N, int K, int epilogue, int a_mode) {
+    const int allow = t.split;
+    if (!allow || a_mode != VDA_A_DENSE || !VDA_EPI_BUILT(VDA_EPIS_8P_BM192, epilogue) || M < 4096 || N < 256 || K < (allow == 2 ? 256 : 2048)) return M;
+    const long long nbn = (N + 255) / 256, rt = (M + 255) / 256;
     auto rounds = [&](long long tiles) { return (tiles + ncu - 1) / ncu; };
-    const double t = 1.6 * (K / 64) + 5.0, launch = allow == 2 ? 0.0 : 10.0;         // us (VDA_GEMM_SPLIT=2: A/B, split whenever rounds say so)
-    const double single = (double)rounds(rt * nbn) * t;
+    const double tk = 1.6 * (K / 64) + 5.0, launch = allow == 2 ? 0.0 : 10.0;         // us (VDA_GEMM_SPLIT=2: A/B, split whenever rounds say so)
+    const double single = (double)rounds(rt * nbn) * tk;
     double best = single * 0.985;
     int best_m1 = M;
     for (long long r = 8; r * 256 < M; ++r) {               // (both parts stay on the 8-phase kernels: >= 2048 rows each, so a row's
         const long long m2 = M - r * 256;                   // arithmetic - K order, bias in the accumulators' start - is the same in either)
         if (m2 < 2048) break;
-        const double cost = (double)rounds(r * nbn) * t + 0.01 * r192 * (double)rounds(((m2 + 191) / 192) * nbn) * t + launch;
+        const double cost = (double)rounds(r * nbn) * tk + 0.01 * t.r192 * (double)rounds(((m2 + 191) / 192) * nbn) * tk + launch;
         if (cost < best) {
             best = cost;
             best_m1 = (int)(r * 256);
@@ -321,12 +336,13 @@ extern "C" int vda_gemm_plan_split(int M, int N, int K, int epilogue, int a_mode
     }
     return best_m1;
 }
+extern "C" int vda_gemm_plan_split(int M, int N, int K, int epilogue, int a_mode) { return plan_split(tuning(), device_cus(), M, N, K, epilogue, a_mode); }
 
-// args of the row range [r0, r0 + rows) of a dense GEMM (the layout rules of vda_gemm_plan_split's comment in vda.h)
+// args of the row range [r0, r0 + rows) of a dense GEMM (the layout rules of vda_gemm_row_range's comment in vda.h)
 static vda_gemm_args row_range(const vda_gemm_args& a0, int r0, int rows) {
     vda_gemm_args a = a0;
-    if (a.lda == 0) a.lda = a.K;       // vda.h: the public row-range helper reads 0 as "dense, K" (vda_gemm_f16 itself reads lda == 0 as a
-    if (a.ldc == 0) a.ldc = a.N;       // broadcast row and therefore never row-splits such a GEMM on its own: see the guard at its split)
+    if (a.lda == 0) a.lda = a.K;       // vda.h: a row range reads 0 as "dense, K" (vda_gemm_f16 itself reads lda == 0 as a broadcast
+    if (a.ldc == 0) a.ldc = a.N;       // row, and the planner never row-splits such a GEMM)
     vda_gemm_args p = a;
     auto adv = [&](const void* q, size_t bytes_per_row) -> const void* { return q ? (const char*)q + (size_t)r0 * bytes_per_row : nullptr; };
     const bool f32_out = a.epilogue == VDA_EPI_SCALE_RES_F32;
@@ -349,32 +365,26 @@ static vda_gemm_args row_range(const vda_gemm_args& a0, int r0, int rows) {
 
 extern "C" int vda_gemm_row_range(const vda_gemm_args* args, int r0, int rows, vda_gemm_args* out) {
     VDA_REQUIRE(args && out && r0 >= 0 && rows > 0 && r0 + rows <= args->M, "vda_gemm_row_range: bad range");
-    VDA_REQUIRE(args->a_mode == VDA_A_DENSE && bm192_epilogue(args->epilogue), "vda_gemm_row_range: dense A and a row-splittable epilogue only");
+    VDA_REQUIRE(args->a_mode == VDA_A_DENSE && VDA_EPI_BUILT(VDA_EPIS_8P_BM192, args->epilogue), "vda_gemm_row_range: dense A and a row-splittable epilogue only");
     *out = row_range(*args, r0, rows);
     return 0;
 }
 
-static int vda_gemm_f16_impl(const vda_gemm_args* args, vda_stream_t stream, bool may_split, int m_plan);
-
-extern "C" int vda_gemm_f16(const vda_gemm_args* args, vda_stream_t stream) { return vda_gemm_f16_impl(args, stream, true, 0); }
-
-int vda_gemm_f16_planned(const vda_gemm_args* args, vda_stream_t stream, int m_plan) { return vda_gemm_f16_impl(args, stream, true, m_plan); }
-
-static int vda_gemm_f16_impl(const vda_gemm_args* args, vda_stream_t stream, bool may_split, int m_plan) {
-    VDA_REQUIRE(args != nullptr, "vda_gemm_f16: null args");
-    vda_gemm_args a = *args;
-    VDA_REQUIRE(a.A && a.W && a.out, "vda_gemm_f16: null operand");
+// ---- 1. validate. operands = false (the planner): the shape and mode rules alone, no pointer is looked at.
+static int validate(vda_gemm_args& a, bool operands) {
+#define VDA_PTR(cond) (!operands || (cond))
+    VDA_REQUIRE(VDA_PTR(a.A && a.W && a.out), "vda_gemm_f16: null operand");
     VDA_REQUIRE(a.M > 0 && a.N > 0 && a.K > 0, "vda_gemm_f16: empty problem M=%d N=%d K=%d", a.M, a.N, a.K);
     VDA_REQUIRE(a.K % BK == 0, "vda_gemm_f16: K=%d must be a multiple of %d (pad at pack time)", a.K, BK);
     VDA_REQUIRE(a.N % 4 == 0 && a.ldc % 4 == 0, "vda_gemm_f16: N=%d and ldc=%d must be multiples of 4", a.N, a.ldc);
-    VDA_REQUIRE(((uintptr_t)a.A & 15) == 0 && ((uintptr_t)a.W & 15) == 0 && ((uintptr_t)a.out & 15) == 0,
+    VDA_REQUIRE(VDA_PTR(((uintptr_t)a.A & 15) == 0 && ((uintptr_t)a.W & 15) == 0 && ((uintptr_t)a.out & 15) == 0),
                 "vda_gemm_f16: operands must be 16-byte aligned");
     VDA_REQUIRE(a.epilogue >= 0 && a.epilogue <= VDA_EPI_LN_GELU_F16, "vda_gemm_f16: bad epilogue %d", a.epilogue);
     if (a.a_mode == VDA_A_DENSE) {
         VDA_REQUIRE(a.relu_in == 0, "vda_gemm_f16: relu_in is only built for the conv A operand");
         VDA_REQUIRE((a.lda >= a.K || a.lda == 0) && a.lda % 8 == 0, "vda_gemm_f16: lda=%d must be >= K (or 0 = broadcast row) and a multiple of 8", a.lda);
     } else if (a.a_mode == VDA_A_CONV3X3) {
-        VDA_REQUIRE(a.zero_page != nullptr, "vda_gemm_f16: conv needs zero_page");
+        VDA_REQUIRE(VDA_PTR(a.zero_page != nullptr), "vda_gemm_f16: conv needs zero_page");
         VDA_REQUIRE(a.cCin % BK == 0 && a.K == 9 * a.cCin, "vda_gemm_f16: conv needs Cin%%64==0 and K==9*Cin (Cin=%d K=%d)", a.cCin, a.K);
         VDA_REQUIRE(a.cStride == 1 || a.cStride == 2, "vda_gemm_f16: conv stride %d", a.cStride);
         VDA_REQUIRE(a.cHo == (a.cH + 2 - 3) / a.cStride + 1 && a.cWo == (a.cW + 2 - 3) / a.cStride + 1,
@@ -388,19 +398,20 @@ static int vda_gemm_f16_impl(const vda_gemm_args* args, vda_stream_t stream, boo
         case VDA_EPI_SCALE_RES_F32:
         case VDA_EPI_SCALE_RES_F32_H:
         case VDA_EPI_RES_F16:
-            VDA_REQUIRE(a.res != nullptr, "vda_gemm_f16: residual epilogue needs res");
+            VDA_REQUIRE(VDA_PTR(a.res != nullptr), "vda_gemm_f16: residual epilogue needs res");
             break;
         case VDA_EPI_GEGLU_F16:
             VDA_REQUIRE(a.N % 32 == 0, "vda_gemm_f16: GEGLU needs N%%32==0");
             break;
         case VDA_EPI_SCALE_RES_SPLIT:
-            VDA_REQUIRE(a.res != nullptr && a.res2 != nullptr && a.out2 != nullptr && a.stats != nullptr,
+            VDA_REQUIRE(VDA_PTR(a.res != nullptr && a.res2 != nullptr && a.out2 != nullptr && a.stats != nullptr),
                         "vda_gemm_f16: the split-residual epilogue needs res, res2 (hi / lo planes), out2 and stats");
             VDA_REQUIRE(a.N % 64 == 0 && a.ldc % 8 == 0 && a.a_mode == VDA_A_DENSE, "vda_gemm_f16: the split-residual epilogue needs a dense A operand, N%%64==0 and ldc%%8==0");
             VDA_REQUIRE(((uintptr_t)a.res & 15) == 0 && ((uintptr_t)a.res2 & 15) == 0 && ((uintptr_t)a.out2 & 15) == 0 && ((uintptr_t)a.stats & 7) == 0,
                         "vda_gemm_f16: split-residual planes must be 16-byte aligned");
+            if (!operands) break;
             // re-centring rows (pos = [M, 2] (mean, rstd), optional): the kernels load pos[m * P] unconditionally
-            // (pos == zero_page is this function's own "no re-centring" form coming back through the row split below: stride 0 stays)
+            // (pos == zero_page is this function's own "no re-centring" form coming back with a record of a split: stride 0 stays)
             if (a.pos != nullptr && (const void*)a.pos != a.zero_page) {
                 VDA_REQUIRE(((uintptr_t)a.pos & 7) == 0, "vda_gemm_f16: pos (re-centring statistics) must be 8-byte aligned");
                 a.P = 2;
@@ -412,12 +423,12 @@ static int vda_gemm_f16_impl(const vda_gemm_args* args, vda_stream_t stream, boo
             break;
         case VDA_EPI_LN_BIAS_F16:
         case VDA_EPI_LN_GELU_F16:
-            VDA_REQUIRE(a.stats != nullptr && a.gamma != nullptr && a.bias != nullptr && a.a_mode == VDA_A_DENSE,
+            VDA_REQUIRE(VDA_PTR(a.stats != nullptr && a.gamma != nullptr && a.bias != nullptr) && a.a_mode == VDA_A_DENSE,
                         "vda_gemm_f16: a LayerNorm-folded epilogue needs a dense A operand, stats (mean, rstd rows), gamma (= c1) and bias (= c2)");
             VDA_REQUIRE(((uintptr_t)a.stats & 7) == 0, "vda_gemm_f16: stats must be 8-byte aligned");
             break;
         case VDA_EPI_PATCH_F32:
-            VDA_REQUIRE(a.pos != nullptr && a.P > 0 && a.M % a.P == 0, "vda_gemm_f16: patch epilogue needs pos and M%%P==0");
+            VDA_REQUIRE(VDA_PTR(a.pos != nullptr) && a.P > 0 && a.M % a.P == 0, "vda_gemm_f16: patch epilogue needs pos and M%%P==0");
             break;
         case VDA_EPI_CONVT_F16:
             VDA_REQUIRE(a.tK > 0 && a.tCout > 0 && a.tCout % 4 == 0 && a.N == a.tK * a.tK * a.tCout && a.M % (a.tH * a.tW) == 0,
@@ -426,171 +437,190 @@ static int vda_gemm_f16_impl(const vda_gemm_args* args, vda_stream_t stream, boo
         default:
             break;
     }
-    hipStream_t s = (hipStream_t)stream;
-    const int Mp = m_plan > a.M ? m_plan : a.M;      // the rows the shape decisions below are taken for (vda_gemm_f16_planned)
+#undef VDA_PTR
+    return 0;
+}
+
+// ---- 2. plan. ONE launch of `a`, its shape decisions taken for Mp >= a.M rows (vda_gemm_plan's m_plan). Reads the shape and mode
+// fields, tile_rows and whether sched is set. *splittable: the automatic path reached the 8-phase 256 x 256 tile with dense A, where a
+// row split may apply; what the record then holds is the launch of the whole GEMM.
+static int plan_one(const GemmTuning& t, const vda_gemm_args& a, int Mp, int ncu, vda_gemm_launch* r, bool* splittable) {
+    const int v = t.variant;
+    const bool dense = a.a_mode == VDA_A_DENSE;
+    *splittable = false;
+    *r = vda_gemm_launch{0, a.M, VDA_GEMM_FAM_128, 128, a.N <= 64 ? 64 : 128, 1, 1, 0, a.relu_in, a.tile_rows, a.a_mode, a.epilogue};
+    auto pick = [&](int family, int bm, int bn, int per_cu, int options) {
+        if (!vda_gemm_built(family, bm, bn, per_cu, a.a_mode, a.epilogue)) return false;
+        r->family = family, r->bm = bm, r->bn = bn, r->per_cu = per_cu, r->options = options;
+        return true;
+    };
     // Narrow-output 3x3 convs (Cout <= 64: the ViT-S head) run as a patch-in-LDS direct convolution instead of an implicit GEMM
     // (variant 7 forces it, any other explicit variant or VDA_CONV_LDS=0 keeps the GEMM: A/B and cross-checks).
-    static const int conv_lds = getenv("VDA_CONV_LDS") ? atoi(getenv("VDA_CONV_LDS")) : 1;
-    if (a.a_mode == VDA_A_CONV3X3 && ((g_gemm_variant < 0 && conv_lds) || g_gemm_variant == 7)) {
-        const int rc = vda_conv3x3_lds(a, s);
-        if (rc >= 0) {
-            g_last_kernel = a.N <= 32 ? "conv3x3_lds_kernel<1>" : "conv3x3_lds_kernel<2>";
-            return rc;
-        }
-    }
-    const bool fits32 = (a.a_mode == VDA_A_DENSE ? (long long)a.M * a.lda : 0ll) + a.K < (1ll << 31) && (long long)a.N * a.K < (1ll << 31);
-    VDA_REQUIRE(fits32 || g_gemm_variant == 0 || g_gemm_variant < 0, "vda_gemm_f16: operand too large for the 256-row kernel's 32-bit offsets");
-    if (!fits32) return launch_small(a, s);
-    // variants: -1 auto; 0 = 128-row tiles; 1 / 2 = 256x256 / 256x128 on 32x32x16 MFMA; 3 / 4 = the same on 16x16x32 MFMA;
-    // 5 = 256x256 8-phase two-group schedule (16x16x32 MFMA)
-    int big = 0, small_mfma = 1;
-    bool eight = g_gemm_variant >= 5 && (g_gemm_variant & 15) == 5;      // upper bits: A/B switches of the 8-phase kernel
-    if (eight) big = 256;
-    if (g_gemm_variant == 1 || g_gemm_variant == 3) big = 256;
-    if (g_gemm_variant == 2 || g_gemm_variant == 4 || g_gemm_variant == 8 || g_gemm_variant == 10 || g_gemm_variant == 11) big = 128;
-    if (g_gemm_variant == 1 || g_gemm_variant == 2) small_mfma = 0;
-    if (g_gemm_variant == 9) {               // 9 = 256x128 8-phase two-group schedule
-        eight = true;
-        big = 128;
-    }
-    static const int big_min_n = getenv("VDA_GEMM_BIG_MIN_N") ? atoi(getenv("VDA_GEMM_BIG_MIN_N")) : 192;      // A/B hook
-    if (g_gemm_variant < 0 && a.N >= big_min_n && Mp >= 2048) {
-        // large-tile kernel; BN picked for the smaller padded width
+    if (!dense && ((v < 0 && t.conv_lds) || v == 7) && vda_conv3x3_lds_covers(a) && pick(VDA_GEMM_FAM_CONV_LDS, 0, a.N <= 32 ? 32 : 64, 1, a.relu_in)) return 0;
+    const bool fits32 = (dense ? (long long)a.M * a.lda : 0ll) + a.K < (1ll << 31) && (long long)a.N * a.K < (1ll << 31);
+    VDA_REQUIRE(fits32 || v <= 0, "vda_gemm_f16: operand too large for the 256-row kernel's 32-bit offsets");
+    if (!fits32) return 0;
+    // ---- the A/B integer: tile width, MFMA shape, 8-phase schedule and its switches
+    int big = (v == 1 || v == 3) ? 256 : (v == 2 || v == 4 || v == 8 || v == 9 || v == 10 || v == 11) ? 128 : 0;
+    const bool mfma32 = v == 1 || v == 2;
+    bool eight = v == 9 || (v >= 5 && (v & 15) == 5);                         // 5 + 16 * flags + 32 * sched (the two overlap, as they always did)
+    if (eight && v != 9) big = 256;
+    const int sched8 = eight ? ((v >> 5) & 3) : 0;
+    if (v < 0 && a.N >= t.big_min_n && Mp >= 2048) {
+        // large-tile kernel, BN picked for the smaller padded width. 256 x 256: the 8-phase two-group schedule (tools/gemm_ab.py,
+        // in-process A/B: -4..-15 % on every encoder shape and epilogue; the conv A operand too, gathered by bounds-checked buffer
+        // loads: +7..10 % over the one-barrier kernel on the head's 256-channel convs). 256 x 128 on that schedule is not the default.
         const int pad256 = (a.N + 255) / 256 * 256, pad128 = (a.N + 127) / 128 * 128;
         big = pad128 < pad256 ? 128 : 256;
-        // 256 x 256: the 8-phase two-group schedule (tools/gemm_ab.py, in-process A/B: -4..-15 % on every encoder shape and
-        // epilogue). The conv A operand too since it is gathered by bounds-checked buffer loads (one scalar tap offset per K tile,
-        // no pointer select): +7..10 % over the one-barrier kernel on the head's 256-channel convs (it had been 8-16 % SLOWER with
-        // per-stage address math in its load sections).
-        // 256 x 128 on the same schedule (variant 9 / VDA_GEMM_8P128=1) is built and tested but NOT the default: in-process A/B on
-        // ViT-S's N = 384 / 1152 / 1536 GEMMs (K = 384: six K tiles) and on output_conv1 it is -4..+2 % against the one-barrier kernel
-        static const int eight128 = getenv("VDA_GEMM_8P128") ? atoi(getenv("VDA_GEMM_8P128")) : 0;
-        if (big == 256 || eight128) eight = true;
+        eight = big == 256 || t.eight128;
     }
     if (big && (a.N % 8 != 0 || a.ldc % 8 != 0)) {
-        VDA_REQUIRE(g_gemm_variant < 0, "vda_gemm_f16: the 256-row kernel needs N and ldc to be multiples of 8");
+        VDA_REQUIRE(v < 0, "vda_gemm_f16: the 256-row kernel needs N and ldc to be multiples of 8");
         big = 0;                            // its epilogue owns 8-column (16-byte) row segments
     }
-    if (big) {
-        vda_gemm_args a8 = a;
-        static const int stagger = getenv("VDA_GEMM_STAGGER") ? atoi(getenv("VDA_GEMM_STAGGER")) : 0;      // 1 / 2 = start stagger (off: see gemm8p_kernel.h)
-        if (!stagger) a8.relu_in |= 16 << 8;
-        if (stagger == 2) a8.relu_in |= 32 << 8;             // A/B: panel-aligned phases
-        if (eight && g_gemm_variant > 0) a8.relu_in = (a.relu_in & 0xff) | (((g_gemm_variant >> 4) & 0xff) << 8);   // A/B switches
-        a8.relu_in |= g_gemm_debug << 16;                      // vda_gemm_set_debug (0 unless a diagnostic tool set it)
-        // Non-temporal output stores (8-phase kernel, fp16 row stores) for outputs that no cache will hand to the next kernel:
-        // VDA_GEMM_NT_MB (default 192; 0 = never) megabytes and up. ViT-L: qkv, hid, the GEGLU hidden, the 148^2 conv maps; ViT-S: none.
-        static const long long nt_mb = getenv("VDA_GEMM_NT_MB") ? atoll(getenv("VDA_GEMM_NT_MB")) : 192;
-        if (nt_mb > 0 && (long long)Mp * a.N * 2 >= nt_mb * 1000000ll) a8.relu_in |= 1 << 24;
-        const int sched8 = (eight && g_gemm_variant > 0) ? ((g_gemm_variant >> 5) & 3) : 0;   // A/B: variant 5 + 32 * sched
-        // 192-row tiles when they quantise better on this device: rounds of 256-row tiles against 3/4-size rounds of 192-row tiles
-        // (ViT-S proj / fc2: 3 against 2.25; variant 8 forces them). Only the one-barrier 256 x 128 family has the shape.
-        bool tall192 = g_gemm_variant == 8 && a.a_mode == VDA_A_DENSE;
-        const int ncu = device_cus();
-        if (g_gemm_variant < 0 && !eight && big == 128 && a.a_mode == VDA_A_DENSE) {
-            const long long nbn = (a.N + 127) / 128;
-            const long long r256 = (((Mp + 255) / 256) * nbn + ncu - 1) / ncu, r192 = (((Mp + 191) / 192) * nbn + ncu - 1) / ncu;
-            static const int allow192 = getenv("VDA_GEMM_BM192") ? atoi(getenv("VDA_GEMM_BM192")) : 1;
-            tall192 = allow192 && r192 * 3 * 100 < r256 * 4 * 85;                 // at least 15 % fewer tile-time units (a 192-row tile costs ~0.8, not 0.75, of a 256-row one)
-        }
-        // Few large tiles leave most of the chip idle for a whole K loop: when the 256-row tiling fills at most half of the CUs the
-        // 128-row kernel (four times the tiles, two workgroups per CU) is faster - the head's 19x19 maps: rn4 (46 tiles, K = 9216)
-        // 223 -> 133 us, the refinenet4 convs 62 -> 39 us (tools/gemm_ab.py, AB_SHAPES=small). VDA_GEMM_SMALL_GRID=0 switches it off.
-        static const int small_grid = getenv("VDA_GEMM_SMALL_GRID") ? atoi(getenv("VDA_GEMM_SMALL_GRID")) : 1;
-        if (g_gemm_variant < 0 && small_grid && ((long long)(Mp + 255) / 256) * ((a.N + big - 1) / big) * 2 <= ncu) {
-            g_last_kernel = a.a_mode == VDA_A_DENSE ? (a.N <= 64 ? "gemm_kernel<128, 64, 0>" : "gemm_kernel<128, 128, 0>")
-                                                    : (a.N <= 64 ? "gemm_kernel<128, 64, 1>" : "gemm_kernel<128, 128, 1>");
-            return launch_small(a, s);
-        }
-        // N a multiple of 384 (ViT-S's embedding width: proj / fc2 N = 384, qkv N = 1152): 192 x 384 tiles on twelve waves, one tile
-        // per row panel and column third - A and the residual rows are read once, 229 row panels are one round of the chip.
-        // Built, tested (variant 10) and NOT the default (VDA_GEMM_BN384=1 enables it): in-process A/B (tools/gemm_ab.py
-        // AB_SHAPES=vits -1,3,8,10, round 3) it wins with a plain epilogue (fc2's shape 70.7 -> 52.4 us) and not with the ones the
-        // model uses - split residual: fc2 80.0 -> 79.6, proj 38.2 -> 43.2 us; qkv + LayerNorm 61.5 -> 64.1 - and the ViT-S forward is
-        // 8.86 -> 9.15 ms with it: a single round puts every CU's residual epilogue (270 MB for fc2) on HBM at the same moment with no
-        // K loop anywhere to hide behind.
-        // [r4] The split-residual instantiation had been reloading two K-loop registers from scratch in every K tile (168 VGPRs; a
-        // scratch reload is a vector-memory load whose in-order wait drains the tile's LDS-DMA) and spilling 76 registers around its
-        // epilogue. With the epilogue's lane-derived addresses kept out of the K loop's live set and half-size row groups (gemm256s_kernel.h)
-        // fc2's shape is 86.9 -> 69.5 us with the split residual and 82.1 -> 63.0 with the fp32 one, proj's is a tie (41.6 / 41.4),
-        // and with the LayerNorm-folded epilogues it now wins on qkv (N = 1152: 60.4 -> 55.5 us) and fc1 (N = 1536, against the 8-phase
-        // 256 x 256 tile: 107.0 -> 91.1 us) (profiles/r04/vits_bn384_ab.txt). DEFAULT (VDA_GEMM_BN384 unset or 2): N = 384 with
-        // K >= 1024 (ViT-S's fc2, any built epilogue) and N <= 1536 with a LayerNorm-folded epilogue (ViT-S's qkv and fc1);
-        // 1 = every N % 384 == 0 up to 1152, 0 = never.
-        static const int wide384 = getenv("VDA_GEMM_BN384") ? atoi(getenv("VDA_GEMM_BN384")) : 2;
-        const bool ln_epi = a.epilogue == VDA_EPI_LN_BIAS_F16 || a.epilogue == VDA_EPI_LN_GELU_F16;
-        const bool auto384 = g_gemm_variant < 0 && a.tile_rows == 0 &&
-                             (wide384 == 1 ? (!eight && a.N <= 1152)
-                                            : wide384 == 2 ? ((a.N == 384 && a.K >= 1024) || (ln_epi && a.N <= 1536))
-                                            : wide384 == 3 ? (a.N == 384 && a.K >= 1024)                                     // (A/B: fc2 only)
-                                            : wide384 == 4 ? ((a.N == 384 && a.K >= 1024) || (ln_epi && a.N == 1536)) : false);   // (A/B: fc2 + fc1)
-        if (a.a_mode == VDA_A_DENSE && a.N % 384 == 0 && (auto384 || g_gemm_variant == 10)) {
-            const int rc384 = vda_gemm256s_dense_bn384_bm192(a8, s);
-            if (rc384 >= 0) {
-                static thread_local char name384[64];
-                snprintf(name384, sizeof(name384), "gemm256s_kernel<384, %d, %d, 192, 1>", a.a_mode, a.epilogue);
-                g_last_kernel = name384;
-                return rc384;
-            }
-        }
-        // Row split (vda_gemm_plan_split): whole rounds of 256-row tiles + one launch of 192-row tiles for the remainder. Applied here
-        // when the caller left it to the dispatcher (no per-launch sched counters: those belong to ONE launch).
-        // (Not for a row range planned as part of a larger GEMM, vda_gemm_f16_planned: its other rows run beside it.)
-        if (eight && big == 256 && a.a_mode == VDA_A_DENSE && g_gemm_variant < 0 && may_split && Mp == a.M && a.tile_rows == 0 && a.sched == nullptr &&
-            a.lda != 0) {
-            const int m1 = vda_gemm_plan_split(a.M, a.N, a.K, a.epilogue, a.a_mode);
-            if (m1 < a.M) {
-                vda_gemm_args p1 = row_range(a, 0, m1), p2 = row_range(a, m1, a.M - m1);
-                p2.tile_rows = 192;
-                const int rc1 = vda_gemm_f16_impl(&p1, stream, false, m_plan);
-                if (rc1 != 0) return rc1;
-                return vda_gemm_f16_impl(&p2, stream, false, m_plan);
-            }
-        }
-        if (eight && big == 256 && a.a_mode == VDA_A_DENSE && (a.tile_rows == 192 || g_gemm_variant == 5 + 16 * 64)) {
-            const int rc192 = vda_gemm8p_dense_bn256_bm192(a8, s);
-            if (rc192 >= 0) {
-                static thread_local char name192[64];
-                snprintf(name192, sizeof(name192), "gemm8p_kernel<256, %d, %d, 1, 192, %s>", a.a_mode, a.epilogue, a.sched ? "true" : "false");
-                g_last_kernel = name192;
-                return rc192;
-            }
-        }
-        if (g_gemm_variant == 11 && a.a_mode == VDA_A_DENSE) {        // 192 x 128, two workgroups per CU (A/B only, see gemm256s_kernel.h)
-            const int rcx2 = vda_gemm256s_dense_bn128_bm192_x2(a8, s);
-            if (rcx2 >= 0) {
-                static thread_local char namex2[64];
-                snprintf(namex2, sizeof(namex2), "gemm256s_kernel<128, %d, %d, 192, 2>", a.a_mode, a.epilogue);
-                g_last_kernel = namex2;
-                return rcx2;
-            }
-        }
-        if (tall192) {
-            const int rc192 = vda_gemm256s_dense_bn128_bm192(a8, s);
-            if (rc192 >= 0) {
-                static thread_local char name192[64];
-                snprintf(name192, sizeof(name192), "gemm256s_kernel<128, %d, %d, 192, 1>", a.a_mode, a.epilogue);
-                g_last_kernel = name192;
-                return rc192;
-            }
-        }
-        const int rc = !eight ? (small_mfma ? vda_gemm256s_launch(a8, big, s) : vda_gemm256_launch(a, big, s))
-                       : big == 128 ? (a.a_mode == VDA_A_DENSE ? vda_gemm8p_dense_bn128(a8, s) : vda_gemm8p_conv_bn128(a8, s))
-                       : a.a_mode == VDA_A_DENSE ? (sched8 ? vda_gemm8p_dense_bn256_sched(a8, s, sched8) : vda_gemm8p_dense_bn256(a8, s))
-                                                 : vda_gemm8p_conv_bn256(a8, s);
-        if (rc >= 0) {
-            // exact instantiation name as rocprofv3 prints it: gemm256[s]_kernel<BN, a_mode, epilogue> / gemm8p_kernel<...>
-            static thread_local char name[64];
-            // (every template argument, defaults included, as the profiler prints them)
-            const int sch = sched8 == 1 ? 0 : sched8 == 2 ? 2 : 1;
-            if (eight) snprintf(name, sizeof(name), "gemm8p_kernel<%d, %d, %d, %d, 256, %s>", big, a.a_mode, a.epilogue, sch, (a.sched && sch == 1) ? "true" : "false");
-            else if (small_mfma) snprintf(name, sizeof(name), "gemm256s_kernel<%d, %d, %d, 256, 1>", big, a.a_mode, a.epilogue);
-            else snprintf(name, sizeof(name), "gemm256_kernel<%d, %d, %d>", big, a.a_mode, a.epilogue);
-            g_last_kernel = name;
-            return rc;
-        }                                   // -1: pair not built for the large tile, use the 128-row kernel
+    if (!big) return 0;
+    // ---- the option word
+    int opt = a.relu_in;
+    if (!t.stagger) opt |= VDA_FLAG_NO_STAGGER << VDA_OPT_FLAGS_SHIFT;
+    if (t.stagger == 2) opt |= VDA_FLAG_STAGGER_PANEL << VDA_OPT_FLAGS_SHIFT;
+    if (eight && v > 0) opt = (a.relu_in & VDA_OPT_BYTE) | (((v >> 4) & VDA_OPT_BYTE) << VDA_OPT_FLAGS_SHIFT);      // A/B switches
+    opt |= t.debug << VDA_OPT_DEBUG_SHIFT;
+    // Non-temporal output stores (8-phase kernel, fp16 row stores) for outputs that no cache will hand to the next kernel.
+    // ViT-L: qkv, hid, the GEGLU hidden, the 148^2 conv maps; ViT-S: none.
+    if (t.nt_mb > 0 && (long long)Mp * a.N * 2 >= t.nt_mb * 1000000ll) opt |= VDA_OPT_NT_STORES;
+    // 192-row tiles when they quantise better on this device: rounds of 256-row tiles against 3/4-size rounds of 192-row tiles
+    // (ViT-S proj / fc2: 3 against 2.25; variant 8 forces them). Only the one-barrier 256 x 128 family has the shape.
+    bool tall192 = v == 8 && dense;
+    if (v < 0 && !eight && big == 128 && dense) {
+        const long long nbn = (a.N + 127) / 128;
+        const long long r256 = (((Mp + 255) / 256) * nbn + ncu - 1) / ncu, r192 = (((Mp + 191) / 192) * nbn + ncu - 1) / ncu;
+        tall192 = t.bm192 && r192 * 3 * 100 < r256 * 4 * 85;                 // at least 15 % fewer tile-time units (a 192-row tile costs ~0.8, not 0.75, of a 256-row one)
     }
-    g_last_kernel = a.a_mode == VDA_A_DENSE ? (a.N <= 64 ? "gemm_kernel<128, 64, 0>" : "gemm_kernel<128, 128, 0>")
-                                            : (a.N <= 64 ? "gemm_kernel<128, 64, 1>" : "gemm_kernel<128, 128, 1>");
-    return launch_small(a, s);
+    // Few large tiles leave most of the chip idle for a whole K loop: when the 256-row tiling fills at most half of the CUs the
+    // 128-row kernel (four times the tiles, two workgroups per CU) is faster - the head's 19x19 maps: rn4 (46 tiles, K = 9216)
+    // 223 -> 133 us, the refinenet4 convs 62 -> 39 us (tools/gemm_ab.py, AB_SHAPES=small).
+    if (v < 0 && t.small_grid && ((long long)(Mp + 255) / 256) * ((a.N + big - 1) / big) * 2 <= ncu) return 0;
+    // N a multiple of 384 (ViT-S's embedding width): 192 x 384 tiles on twelve waves, one tile per row panel and column third - A and
+    // the residual rows are read once, 229 row panels are one round of the chip. Since the epilogue's lane-derived addresses stay out of
+    // the K loop's live set (gemm256s_kernel.h, round 4) it wins on fc2's shape with any built epilogue (split residual 86.9 -> 69.5 us)
+    // and with the LayerNorm-folded epilogues on qkv (60.4 -> 55.5 us) and fc1 (against the 8-phase 256 x 256 tile: 107.0 -> 91.1 us);
+    // proj's shape is a tie (profiles/r04/vits_bn384_ab.txt). VDA_GEMM_BN384 = 2 (default): N = 384 with K >= 1024 and N <= 1536 with a
+    // LayerNorm-folded epilogue; 1 = every N % 384 == 0 up to 1152 off the 8-phase tile; 3 / 4 = A/B subsets; 0 = never. Variant 10 forces it.
+    const bool ln_epi = a.epilogue == VDA_EPI_LN_BIAS_F16 || a.epilogue == VDA_EPI_LN_GELU_F16, fc2_384 = a.N == 384 && a.K >= 1024;
+    const bool auto384 = v < 0 && a.tile_rows == 0 &&
+                         (t.bn384 == 1 ? (!eight && a.N <= 1152) : t.bn384 == 2 ? (fc2_384 || (ln_epi && a.N <= 1536))
+                          : t.bn384 == 3 ? fc2_384 : t.bn384 == 4 ? (fc2_384 || (ln_epi && a.N == 1536)) : false);
+    if (dense && a.N % 384 == 0 && (auto384 || v == 10) && pick(VDA_GEMM_FAM_256S, 192, 384, 1, opt)) return 0;
+    *splittable = eight && big == 256 && dense && v < 0;
+    if (eight && big == 256 && dense && (a.tile_rows == 192 || v == 5 + 16 * VDA_FLAG_BM192) && pick(VDA_GEMM_FAM_8P, 192, 256, 1, opt))
+        return r->dyn = a.sched != nullptr, 0;
+    if (v == 11 && dense && pick(VDA_GEMM_FAM_256S, 192, 128, 2, opt)) return 0;      // (A/B only, see gemm256s_kernel.h)
+    if (tall192 && pick(VDA_GEMM_FAM_256S, 192, 128, 1, opt)) return 0;
+    // (the 32x32x16 kernel reads no option bits: it gets the caller's word)
+    if (!pick(eight ? VDA_GEMM_FAM_8P : mfma32 ? VDA_GEMM_FAM_256 : VDA_GEMM_FAM_256S, 256, big, 1, mfma32 && !eight ? a.relu_in : opt)) return 0;   // not built: 128-row tiles
+    if (eight) {
+        // the name reports the schedule ASKED for (vda_gemm8p_dense_bn256_sched falls back to the default one for other epilogues)
+        r->ksched = sched8 == 1 ? 0 : sched8 == 2 ? 2 : 1;
+        r->dyn = a.sched != nullptr && r->ksched == 1;
+    }
+    return 0;
+}
+
+// the plan of a validated call
+static int plan_call(const vda_gemm_args& a, int m_plan, int ncu, int sched_per_launch, vda_gemm_plan_t* out) {
+    const GemmTuning& t = tuning();
+    if (ncu <= 0) ncu = device_cus();
+    bool splittable = false;
+    out->n = 1;
+    if (int rc = plan_one(t, a, m_plan > a.M ? m_plan : a.M, ncu, &out->rec[0], &splittable)) return rc;
+    // Row split: whole rounds of 256-row tiles + one launch of 192-row tiles for the remainder, each part planned as a GEMM of its own.
+    // Not for a row range of a larger GEMM (its other rows run beside it), a part of a split made by hand, or a broadcast row.
+    if (!splittable || m_plan > a.M || a.tile_rows != 0 || (a.sched != nullptr && !sched_per_launch) || a.lda == 0) return 0;
+    const int m1 = plan_split(t, ncu, a.M, a.N, a.K, a.epilogue, a.a_mode);
+    if (m1 >= a.M) return 0;
+    vda_gemm_args part = a;
+    for (int i = 0; i < 2; ++i) {
+        part.M = i == 0 ? m1 : a.M - m1;
+        part.tile_rows = i == 0 ? 0 : 192;
+        if (int rc = plan_one(t, part, m_plan > part.M ? m_plan : part.M, ncu, &out->rec[i], &splittable)) return rc;
+        out->rec[i].r0 = i == 0 ? 0 : m1;
+    }
+    out->n = 2;
+    return 0;
+}
+
+extern "C" int vda_gemm_plan(const vda_gemm_args* args, int m_plan, int ncu, int sched_per_launch, vda_gemm_plan_t* out) {
+    VDA_REQUIRE(args != nullptr && out != nullptr, "vda_gemm_plan: null args");
+    vda_gemm_args a = *args;
+    if (int rc = validate(a, false)) return rc;
+    return plan_call(a, m_plan, ncu, sched_per_launch, out);
+}
+
+extern "C" int vda_gemm_launch_name(const vda_gemm_launch* r, char* name, int len) {
+    switch (r->family) {
+        case VDA_GEMM_FAM_128: return snprintf(name, len, "gemm_kernel<%d, %d, %d>", r->bm, r->bn, r->a_mode);
+        case VDA_GEMM_FAM_256: return snprintf(name, len, "gemm256_kernel<%d, %d, %d>", r->bn, r->a_mode, r->epilogue);
+        case VDA_GEMM_FAM_256S: return snprintf(name, len, "gemm256s_kernel<%d, %d, %d, %d, %d>", r->bn, r->a_mode, r->epilogue, r->bm, r->per_cu);
+        case VDA_GEMM_FAM_8P:   // (every template argument, defaults included, as the profiler prints them)
+            return snprintf(name, len, "gemm8p_kernel<%d, %d, %d, %d, %d, %s>", r->bn, r->a_mode, r->epilogue, r->ksched, r->bm, r->dyn ? "true" : "false");
+        case VDA_GEMM_FAM_CONV_LDS: return snprintf(name, len, "conv3x3_lds_kernel<%d>", r->bn / 32);      // (also what the C = 64 persistent kernel reports as)
+        default: return snprintf(name, len, "%s", "");
+    }
+}
+
+static thread_local vda_gemm_launch g_last_launch = {0, 0, -1};
+
+extern "C" const char* vda_gemm_last_kernel(void) {
+    static thread_local char name[64];
+    vda_gemm_launch_name(&g_last_launch, name, sizeof(name));
+    return name;
+}
+
+// ---- 3. launch one record of a plan of a0 (validated): its row range, its option word, the one launcher of its family
+static int launch_record(const vda_gemm_launch& r, const vda_gemm_args& a0, hipStream_t s) {
+    vda_gemm_args a = (r.r0 == 0 && r.rows == a0.M) ? a0 : row_range(a0, r.r0, r.rows);
+    a.relu_in = r.options;
+    a.tile_rows = r.tile_rows;
+    const bool dense = a.a_mode == VDA_A_DENSE, wide = r.bn == 256;
+    int rc = -1;
+    switch (r.family) {
+        case VDA_GEMM_FAM_128: rc = launch_small(a, s); break;
+        case VDA_GEMM_FAM_CONV_LDS: rc = vda_conv3x3_lds(a, s); break;
+        case VDA_GEMM_FAM_256:
+            rc = dense ? (wide ? vda_gemm256_dense_bn256(a, s) : vda_gemm256_dense_bn128(a, s)) : (wide ? vda_gemm256_conv_bn256(a, s) : vda_gemm256_conv_bn128(a, s));
+            break;
+        case VDA_GEMM_FAM_256S:
+            if (r.bm == 192) rc = r.bn == 384 ? vda_gemm256s_dense_bn384_bm192(a, s) : r.per_cu == 2 ? vda_gemm256s_dense_bn128_bm192_x2(a, s) : vda_gemm256s_dense_bn128_bm192(a, s);
+            else rc = dense ? (wide ? vda_gemm256s_dense_bn256(a, s) : vda_gemm256s_dense_bn128(a, s)) : (wide ? vda_gemm256s_conv_bn256(a, s) : vda_gemm256s_conv_bn128(a, s));
+            break;
+        case VDA_GEMM_FAM_8P:
+            if (r.bm == 192) rc = vda_gemm8p_dense_bn256_bm192(a, s);
+            else if (!wide) rc = dense ? vda_gemm8p_dense_bn128(a, s) : vda_gemm8p_conv_bn128(a, s);
+            else if (!dense) rc = vda_gemm8p_conv_bn256(a, s);
+            else rc = r.ksched != 1 ? vda_gemm8p_dense_bn256_sched(a, s, r.ksched == 0 ? 1 : 2) : vda_gemm8p_dense_bn256(a, s);
+            break;
+        default: break;
+    }
+    VDA_REQUIRE(rc >= 0, "vda_gemm_f16: internal error, the plan chose a kernel that is not built (family %d, %d x %d tiles, A mode %d, epilogue %d)", r.family,
+                r.bm, r.bn, a.a_mode, a.epilogue);
+    g_last_launch = r;
+    return rc;
+}
+
+int vda_gemm_f16_record(const vda_gemm_args* args, const vda_gemm_launch* rec, vda_stream_t stream) {
+    VDA_REQUIRE(args != nullptr && rec != nullptr, "vda_gemm_f16: null args");
+    vda_gemm_args a = *args;
+    if (int rc = validate(a, true)) return rc;
+    return launch_record(*rec, a, (hipStream_t)stream);
+}
+
+extern "C" int vda_gemm_f16(const vda_gemm_args* args, vda_stream_t stream) {
+    VDA_REQUIRE(args != nullptr, "vda_gemm_f16: null args");
+    vda_gemm_args a = *args;
+    if (int rc = validate(a, true)) return rc;
+    vda_gemm_plan_t plan;
+    if (int rc = plan_call(a, 0, 0, 0, &plan)) return rc;
+    for (int i = 0; i < plan.n; ++i)
+        if (int rc = launch_record(plan.rec[i], a, (hipStream_t)stream)) return rc;
+    return 0;
 }

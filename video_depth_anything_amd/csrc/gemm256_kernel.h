@@ -111,7 +111,7 @@ __global__ void __launch_bounds__(NT) gemm256_kernel(const vda_gemm_args p) {
     const int frow = lane & 31, fh = lane >> 5, fsw = (lane >> 1) & 7;     // ((row >> 1) & 7) with row = subtile*32 + frow
     const int a_off = (wm * WTM + frow) * ROW_BYTES, w_off = A_BYTES + (wn * WTN + frow) * ROW_BYTES;
     // relu on the activation operand (conv only), branch-free: max(x, 0) or max(x, -inf)
-    const h16 relu_floor = (p.relu_in & 1) ? (h16)0.f : (h16)(-65504.f);
+    const h16 relu_floor = (p.relu_in & VDA_OPT_RELU_IN) ? (h16)0.f : (h16)(-65504.f);
     h16x8 relu_thr;
 #pragma unroll
     for (int e = 0; e < 8; ++e) relu_thr[e] = relu_floor;
@@ -310,34 +310,17 @@ int launch256(const vda_gemm_args& a, hipStream_t s) {
     return 0;
 }
 
-// Dense A: every epilogue. Conv A: the three the head uses.
+// One case per epilogue of the family's list (gemm_epilogue.h: the lists the planner plans with); -1 = not built, which the planner
+// never asks for. Dense A: every epilogue but the LayerNorm-fold ones. Conv A: the three the head uses.
+#define VDA_256_CASE(E, AMODE) case E: return launch256<BN, AMODE, E>(a, s);
 template <int BN>
 int launch_dense(const vda_gemm_args& a, hipStream_t s) {
-    switch (a.epilogue) {
-        case VDA_EPI_BIAS_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_BIAS_F16>(a, s);
-        case VDA_EPI_BIAS_GELU_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_BIAS_GELU_F16>(a, s);
-        case VDA_EPI_BIAS_RELU_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_BIAS_RELU_F16>(a, s);
-        case VDA_EPI_SCALE_RES_F32: return launch256<BN, VDA_A_DENSE, VDA_EPI_SCALE_RES_F32>(a, s);
-        case VDA_EPI_RES_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_RES_F16>(a, s);
-        case VDA_EPI_GEGLU_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_GEGLU_F16>(a, s);
-        case VDA_EPI_PATCH_F32: return launch256<BN, VDA_A_DENSE, VDA_EPI_PATCH_F32>(a, s);
-        case VDA_EPI_CONVT_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_CONVT_F16>(a, s);
-        case VDA_EPI_BIAS_F32: return launch256<BN, VDA_A_DENSE, VDA_EPI_BIAS_F32>(a, s);
-        case VDA_EPI_SCALE_RES_F32_H: return launch256<BN, VDA_A_DENSE, VDA_EPI_SCALE_RES_F32_H>(a, s);
-        default: break;
-    }
-    return -1;
+    switch (a.epilogue) { VDA_EPIS_DENSE_MFMA32(VDA_256_CASE, VDA_A_DENSE) default: return -1; }
 }
-
 template <int BN>
 int launch_conv(const vda_gemm_args& a, hipStream_t s) {
-    switch (a.epilogue) {
-        case VDA_EPI_BIAS_F16: return launch256<BN, VDA_A_CONV3X3, VDA_EPI_BIAS_F16>(a, s);
-        case VDA_EPI_BIAS_RELU_F16: return launch256<BN, VDA_A_CONV3X3, VDA_EPI_BIAS_RELU_F16>(a, s);
-        case VDA_EPI_RES_F16: return launch256<BN, VDA_A_CONV3X3, VDA_EPI_RES_F16>(a, s);
-        default: break;
-    }
-    return -1;                                  // caller falls back to the 128-row kernel
+    switch (a.epilogue) { VDA_EPIS_CONV(VDA_256_CASE, VDA_A_CONV3X3) default: return -1; }
 }
+#undef VDA_256_CASE
 
 }  // namespace vda_gemm256

@@ -156,7 +156,7 @@ __global__ void __launch_bounds__(BN == 384 ? 768 : BM / 32 * 64) gemm256s_kerne
     const int frow = lane & 15, fh = lane >> 4, fsw = (lane >> 1) & 7;     // ((row >> 1) & 7) with row = subtile*16 + frow
     const int a_off = (wm * WTM + frow) * ROW_BYTES, w_off = A_BYTES + (wn * WTN + frow) * ROW_BYTES;
     // relu on the activation operand (conv only), branch-free: max(x, 0) or max(x, -inf)
-    const h16 relu_floor = (p.relu_in & 1) ? (h16)0.f : (h16)(-65504.f);
+    const h16 relu_floor = (p.relu_in & VDA_OPT_RELU_IN) ? (h16)0.f : (h16)(-65504.f);
     h16x8 relu_thr;
 #pragma unroll
     for (int e = 0; e < 8; ++e) relu_thr[e] = relu_floor;
@@ -188,10 +188,10 @@ __global__ void __launch_bounds__(BN == 384 ? 768 : BM / 32 * 64) gemm256s_kerne
     int tile = tile_of(0);
     if (tile >= ntiles) return;                        // uniform per workgroup
     // stagger of the workgroups that sit out the last round (gemm8p_kernel.h): up to 3/4 of a tile time, four phases, free
-    if (!((p.relu_in >> 8) & 16) && rem > 0 && full_rounds > 0 && tile_of(full_rounds) >= ntiles) {       // VDA_GEMM_STAGGER=0 switches it off
+    if (!VDA_OPT_FLAG(p.relu_in, VDA_FLAG_NO_STAGGER) && rem > 0 && full_rounds > 0 && tile_of(full_rounds) >= ntiles) {       // VDA_GEMM_STAGGER=0 switches it off
         // phase by slot: the nbn workgroups of an XCD that share an A row panel land in DIFFERENT phases (keeping them in phase -
         // VDA_GEMM_STAGGER=2 - is slower than no stagger at all: it is those neighbours' epilogues that collide)
-        const int q = ((p.relu_in >> 8) & 32) ? ((bid >> 3) / (nbn <= 8 ? nbn : 8)) & 3 : (bid >> 3) & 3;
+        const int q = VDA_OPT_FLAG(p.relu_in, VDA_FLAG_STAGGER_PANEL) ? ((bid >> 3) / (nbn <= 8 ? nbn : 8)) & 3 : (bid >> 3) & 3;
         const int units = (nt * 60 + 260) * q / 4;
         for (int i = 0; i < units; i += 120) __builtin_amdgcn_s_sleep(120);
     }
@@ -401,79 +401,22 @@ int launch256(const vda_gemm_args& a, hipStream_t s) {
     return 0;
 }
 
-// Dense A: every epilogue. Conv A: the three the head uses.
-template <int BN>
-int launch_dense(const vda_gemm_args& a, hipStream_t s) {
-    switch (a.epilogue) {
-        case VDA_EPI_BIAS_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_BIAS_F16>(a, s);
-        case VDA_EPI_BIAS_GELU_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_BIAS_GELU_F16>(a, s);
-        case VDA_EPI_BIAS_RELU_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_BIAS_RELU_F16>(a, s);
-        case VDA_EPI_SCALE_RES_F32: return launch256<BN, VDA_A_DENSE, VDA_EPI_SCALE_RES_F32>(a, s);
-        case VDA_EPI_RES_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_RES_F16>(a, s);
-        case VDA_EPI_GEGLU_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_GEGLU_F16>(a, s);
-        case VDA_EPI_PATCH_F32: return launch256<BN, VDA_A_DENSE, VDA_EPI_PATCH_F32>(a, s);
-        case VDA_EPI_CONVT_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_CONVT_F16>(a, s);
-        case VDA_EPI_BIAS_F32: return launch256<BN, VDA_A_DENSE, VDA_EPI_BIAS_F32>(a, s);
-        case VDA_EPI_SCALE_RES_F32_H: return launch256<BN, VDA_A_DENSE, VDA_EPI_SCALE_RES_F32_H>(a, s);
-        case VDA_EPI_SCALE_RES_SPLIT: return launch256<BN, VDA_A_DENSE, VDA_EPI_SCALE_RES_SPLIT>(a, s);
-        case VDA_EPI_LN_BIAS_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_LN_BIAS_F16>(a, s);
-        case VDA_EPI_LN_GELU_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_LN_GELU_F16>(a, s);
-        default: break;
+// One case per epilogue of the family's list (gemm_epilogue.h: the lists the planner plans with); -1 = not built, which the planner
+// never asks for. Dense A: every epilogue. Conv A: the three the head uses. 192 x 128 on six waves: the epilogues the encoder uses;
+// two of those workgroups per CU: the epilogues whose kernels fit 168 VGPRs (three waves per SIMD); 192 x 384 on twelve waves: ViT-S's
+// embedding width in one tile (templates so that the kernels are instantiated in the one translation unit that calls them).
+#define VDA_256S_FAMILY(fn, LIST, AMODE, BM, PER_CU)                       \
+    template <int BN>                                                      \
+    int fn(const vda_gemm_args& a, hipStream_t s) {                        \
+        switch (a.epilogue) { LIST(VDA_256S_CASE, AMODE, BM, PER_CU) default: return -1; } \
     }
-    return -1;
-}
-
-// two 192 x 128 workgroups per CU: the epilogues whose kernels fit 168 VGPRs (three waves per SIMD)
-template <int BN>
-int launch_dense_bm192_x2(const vda_gemm_args& a, hipStream_t s) {
-    switch (a.epilogue) {
-        case VDA_EPI_BIAS_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_BIAS_F16, 192, 2>(a, s);
-        case VDA_EPI_BIAS_GELU_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_BIAS_GELU_F16, 192, 2>(a, s);
-        case VDA_EPI_LN_BIAS_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_LN_BIAS_F16, 192, 2>(a, s);
-        case VDA_EPI_LN_GELU_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_LN_GELU_F16, 192, 2>(a, s);
-        default: break;
-    }
-    return -1;
-}
-
-// 192-row tiles (BN = 128, dense A): the epilogues the encoder uses
-template <int BN>        // (a template only so that the kernels are instantiated in the one translation unit that calls it)
-int launch_dense_bm192(const vda_gemm_args& a, hipStream_t s) {
-    switch (a.epilogue) {
-        case VDA_EPI_BIAS_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_BIAS_F16, 192>(a, s);
-        case VDA_EPI_BIAS_GELU_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_BIAS_GELU_F16, 192>(a, s);
-        case VDA_EPI_SCALE_RES_F32: return launch256<BN, VDA_A_DENSE, VDA_EPI_SCALE_RES_F32, 192>(a, s);
-        case VDA_EPI_SCALE_RES_SPLIT: return launch256<BN, VDA_A_DENSE, VDA_EPI_SCALE_RES_SPLIT, 192>(a, s);
-        case VDA_EPI_LN_BIAS_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_LN_BIAS_F16, 192>(a, s);
-        case VDA_EPI_LN_GELU_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_LN_GELU_F16, 192>(a, s);
-        default: break;
-    }
-    return -1;
-}
-
-// 192 x 384 tiles on twelve waves (dense A): ViT-S's embedding width in one tile
-template <int BN>
-int launch_dense_bn384(const vda_gemm_args& a, hipStream_t s) {
-    switch (a.epilogue) {
-        case VDA_EPI_BIAS_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_BIAS_F16, 192>(a, s);
-        case VDA_EPI_SCALE_RES_F32: return launch256<BN, VDA_A_DENSE, VDA_EPI_SCALE_RES_F32, 192>(a, s);
-        case VDA_EPI_SCALE_RES_SPLIT: return launch256<BN, VDA_A_DENSE, VDA_EPI_SCALE_RES_SPLIT, 192>(a, s);
-        case VDA_EPI_LN_BIAS_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_LN_BIAS_F16, 192>(a, s);
-        case VDA_EPI_LN_GELU_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_LN_GELU_F16, 192>(a, s);
-        default: break;
-    }
-    return -1;
-}
-
-template <int BN>
-int launch_conv(const vda_gemm_args& a, hipStream_t s) {
-    switch (a.epilogue) {
-        case VDA_EPI_BIAS_F16: return launch256<BN, VDA_A_CONV3X3, VDA_EPI_BIAS_F16>(a, s);
-        case VDA_EPI_BIAS_RELU_F16: return launch256<BN, VDA_A_CONV3X3, VDA_EPI_BIAS_RELU_F16>(a, s);
-        case VDA_EPI_RES_F16: return launch256<BN, VDA_A_CONV3X3, VDA_EPI_RES_F16>(a, s);
-        default: break;
-    }
-    return -1;                                  // caller falls back to the 128-row kernel
-}
+#define VDA_256S_CASE(E, AMODE, BM, PER_CU) case E: return launch256<BN, AMODE, E, BM, PER_CU>(a, s);
+VDA_256S_FAMILY(launch_dense, VDA_EPIS_DENSE, VDA_A_DENSE, 256, 1)
+VDA_256S_FAMILY(launch_dense_bm192_x2, VDA_EPIS_256S_BM192_X2, VDA_A_DENSE, 192, 2)
+VDA_256S_FAMILY(launch_dense_bm192, VDA_EPIS_256S_BM192, VDA_A_DENSE, 192, 1)
+VDA_256S_FAMILY(launch_dense_bn384, VDA_EPIS_256S_BN384, VDA_A_DENSE, 192, 1)
+VDA_256S_FAMILY(launch_conv, VDA_EPIS_CONV, VDA_A_CONV3X3, 256, 1)
+#undef VDA_256S_CASE
+#undef VDA_256S_FAMILY
 
 }  // namespace vda_gemm256s

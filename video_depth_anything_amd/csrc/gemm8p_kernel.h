@@ -88,16 +88,16 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
     // per launch against 98 MB algorithmic, profiles/r03; 546 MB with it, profiles/r04). Needs 32 workgroups per XCD and at least one
     // full round; any other launch keeps the default walk. vda_gemm_set_debug: bit 0 = clock stamps (below), bit 1 = blocked also for
     // nbn = 4, bit 4 = never blocked.
-    const int dbg2 = __builtin_amdgcn_readfirstlane((p.relu_in >> 16) & 0xff);
+    const int dbg2 = __builtin_amdgcn_readfirstlane(VDA_OPT_DEBUG(p.relu_in));
     // Column group width CG (panels) and the number of groups G = nbn / CG (2, 4 or 8: 8 / G XCDs share a group and interleave its
     // row panels): nbn = 8, 16, 32 -> CG 4; on request (debug bit 1) also nbn = 12 (qkv), 24 -> CG 6 and nbn = 4 -> one group: qkv
     // measured 275.0 against 272.7 us with it on one box - no gain; the sign of the fc1 gain itself flips between boxes (-1.5 % / +0.7 %).
     // DEFAULT for those widths (fc1: the dominant kernel fetched 8.5 x its algorithmic bytes without it; -1.5 .. -3 % on that launch
     // alone, +0.3 % on the power-capped forward); nbn = 4 (proj / fc2: the default walk already shares all of W) only when debug bit 1
     // asks for it (measured +1 % slower there); debug bit 4 switches it off everywhere (A/B).
-    const int cgw = (nbn % 4 == 0 && (nbn == 8 || nbn == 16 || nbn == 32 || (nbn == 4 && (dbg2 & 2)))) ? 4 : (((nbn == 12 || nbn == 24) && (dbg2 & 2)) ? 6 : 0);
+    const int cgw = (nbn % 4 == 0 && (nbn == 8 || nbn == 16 || nbn == 32 || (nbn == 4 && (dbg2 & VDA_DEBUG_BLOCKED_MORE)))) ? 4 : (((nbn == 12 || nbn == 24) && (dbg2 & VDA_DEBUG_BLOCKED_MORE)) ? 6 : 0);
     const int cgroups = cgw ? nbn / cgw : 1;
-    const bool blocked = cgw != 0 && per_xcd == 32 && !DYN && !(dbg2 & 16) && full_rounds > 0;
+    const bool blocked = cgw != 0 && per_xcd == 32 && !DYN && !(dbg2 & VDA_DEBUG_NEVER_BLOCKED) && full_rounds > 0;
     auto tile_of = [&](int round) {
         if (blocked) {
             // the group's tiles in row-major order (CG wide), dealt 32 at a time to its XCDs: XCD i of the group takes chunk r * xpg + i
@@ -224,7 +224,7 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
     const int frow = lane & 15, fh = lane >> 4, fsw = (lane >> 1) & 7;     // ((row >> 1) & 7) with row = subtile*16 + frow
     const int a_off = (wm * WTM + frow) * ROW_BYTES, w_off = (wn * WTN + frow) * ROW_BYTES;
     // relu on the activation operand (conv only), branch-free: max(x, 0) or max(x, -inf)
-    const h16 relu_floor = (p.relu_in & 1) ? (h16)0.f : (h16)(-65504.f);
+    const h16 relu_floor = (p.relu_in & VDA_OPT_RELU_IN) ? (h16)0.f : (h16)(-65504.f);
     h16x8 relu_thr;
 #pragma unroll
     for (int e = 0; e < 8; ++e) relu_thr[e] = relu_floor;
@@ -306,10 +306,10 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
     // nothing on others, and it costs L2 sharing (PMC: +40 % fetched bytes, the workgroups of an XCD no longer read the same W
     // and A tiles at the same moment) and 2 % with two clips in flight (a sleeping workgroup holds a CU the other stream's
     // kernel could use). Tile time estimate: 1.6 us per K tile + 8 us, at ~2.1 GHz, in 64-cycle sleep units.
-    if (!dyn && !((p.relu_in >> 8) & 16) && rem > 0 && full_rounds > 0 && tile_of(full_rounds) >= ntiles) {       // switch off: variant 5 + 16 * 16
+    if (!dyn && !VDA_OPT_FLAG(p.relu_in, VDA_FLAG_NO_STAGGER) && rem > 0 && full_rounds > 0 && tile_of(full_rounds) >= ntiles) {       // switch off: variant 5 + 16 * 16
         // phase by slot: the nbn workgroups of an XCD that share an A row panel land in DIFFERENT phases (keeping them in phase -
         // VDA_GEMM_STAGGER=2 - is slower than no stagger at all: it is those neighbours' epilogues that collide)
-        const int q = ((p.relu_in >> 8) & 32) ? ((bid >> 3) / (nbn <= 8 ? nbn : 8)) & 3 : (bid >> 3) & 3;
+        const int q = VDA_OPT_FLAG(p.relu_in, VDA_FLAG_STAGGER_PANEL) ? ((bid >> 3) / (nbn <= 8 ? nbn : 8)) & 3 : (bid >> 3) & 3;
         const int units = (nt * 52 + 260) * q / 4;
         for (int i = 0; i < units; i += 120) __builtin_amdgcn_s_sleep(120);
     }
@@ -322,13 +322,13 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
     stage_w(0, smem + W_BASE);
     // In-kernel stamps (tools/gemm_stamps.py; vda_gemm_set_variant(5 + 16 * 2)): thread 0 of every workgroup writes the shader clock at
     // tile start / K-loop start / K-loop end / tile end into the (otherwise unused) pos operand.
-    const bool stamp = EPI != VDA_EPI_PATCH_F32 && ((p.relu_in >> 9) & 1) && p.pos != nullptr && tid == 0;
+    const bool stamp = EPI != VDA_EPI_PATCH_F32 && VDA_OPT_STAMPS(p.relu_in) && p.pos != nullptr && tid == 0;
     long long* stamps = (long long*)p.pos;
     // Clock stamps (vda_gemm_set_debug bit 0; MI355X_MICROARCH.md "DVFS give-back" item 6): thread 0 of every workgroup writes
     // (s_memtime = shader clock, s_memrealtime = 100 MHz) at tile start / K-loop start / K-loop end / tile end of its first 16 tiles
     // into pos, [workgroup][tile][4][2] int64. Diagnostic only: the buffer is read by nothing, no output depends on it, and a build
     // without the flag executes none of it (the flag is a wave-uniform scalar test).
-    const bool stamp2 = EPI != VDA_EPI_PATCH_F32 && EPI != VDA_EPI_SCALE_RES_SPLIT && (dbg2 & 1) && p.pos != nullptr && tid == 0;
+    const bool stamp2 = EPI != VDA_EPI_PATCH_F32 && EPI != VDA_EPI_SCALE_RES_SPLIT && (dbg2 & VDA_DEBUG_CLOCKS) && p.pos != nullptr && tid == 0;
     auto clk = [&](int round, int which) {
         if (stamp2 && round < 16) {
             long long* q = (long long*)p.pos + ((size_t)(bid * 16 + round) * 4 + which) * 2;
@@ -416,7 +416,7 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
         for (int kt = 0; kt < nt; ++kt) {
             // (diagnostic, vda_gemm_set_debug bit 2: the shader clock at the top of each of the first 32 K tiles of the workgroup's
             // SECOND tile, behind the tile stamps: where the K loop's ramp-up goes)
-            if (stamp2 && (dbg2 & 4) && round == 1 && kt < 32) ((long long*)p.pos)[(size_t)nwg * 16 * 4 * 2 + bid * 32 + kt] = (long long)__builtin_amdgcn_s_memtime();
+            if (stamp2 && (dbg2 & VDA_DEBUG_KTILE_CLOCKS) && round == 1 && kt < 32) ((long long*)p.pos)[(size_t)nwg * 16 * 4 * 2 + bid * 32 + kt] = (long long)__builtin_amdgcn_s_memtime();
             const char* ab = smem + sa * A_BYTES;
             const char* wb = smem + W_BASE + (kt & 1) * W_BYTES;
             const int sa2 = sa == 0 ? 2 : sa - 1;                   // (kt + 2) % 3
@@ -528,8 +528,8 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
             const int idx = __builtin_amdgcn_readfirstlane(*sched_slot);
             next = idx < xc ? xb + idx : ntiles;
         }
-        const int dbg = __builtin_amdgcn_readfirstlane((p.relu_in >> 8) & 0xff);      // A/B switches (vda_gemm_set_variant(5 + 16 * flags))
-        if ((dbg & 1) && next < ntiles) {
+        const int dbg = __builtin_amdgcn_readfirstlane(VDA_OPT_FLAGS(p.relu_in));      // A/B switches (vda_gemm_set_variant(5 + 16 * flags))
+        if ((dbg & VDA_FLAG_PREFETCH_FIRST) && next < ntiles) {
             load_bias(next);
             load_stats(next);
             set_sources(next);
@@ -546,7 +546,7 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
         // residual reads and the output stores become contiguous 16-byte accesses covering full 128-byte lines.
         const int bm0 = m0 + wm * WTM, bn0 = n0 + wn * WTN;
         const bool interior = bm0 + WTM <= p.M && bn0 + WTN <= p.N;       // wave-uniform
-        const bool nt_out = !RT_F32OUT && __builtin_amdgcn_readfirstlane((p.relu_in >> 24) & 1) != 0;      // set by vda_gemm_f16 for outputs past the caches
+        const bool nt_out = !RT_F32OUT && __builtin_amdgcn_readfirstlane(VDA_OPT_NT(p.relu_in)) != 0;      // set by vda_gemm_f16 for outputs past the caches
         if constexpr (LN_EPI) {
             *reinterpret_cast<float2*>(sst + lane * 8) = nstat[0];
             if constexpr (WTM > 64) *reinterpret_cast<float2*>(sst + (64 + lane) * 8) = nstat[1];
@@ -670,8 +670,8 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
                 // (the LayerNorm-folded epilogues' 8-byte row statistics do not count: measured -20 us on fc1 with the early prefetch)
                 constexpr bool ROW_AUX = EPI == VDA_EPI_SCALE_RES_F32 || EPI == VDA_EPI_SCALE_RES_F32_H || EPI == VDA_EPI_RES_F16 || EPI == VDA_EPI_PATCH_F32 ||
                                          EPI == VDA_EPI_SCALE_RES_SPLIT;
-                const int pf_block = ((ROW_AUX && !(dbg & 4)) || (dbg & 8)) ? MI / 2 - 1 : 0;          // dbg 8: A/B, late for every epilogue
-                if (i == pf_block && next < ntiles && !(dbg & 1)) {
+                const int pf_block = ((ROW_AUX && !(dbg & VDA_FLAG_PREFETCH_EARLY)) || (dbg & VDA_FLAG_PREFETCH_LATE)) ? MI / 2 - 1 : 0;          // dbg 8: A/B, late for every epilogue
+                if (i == pf_block && next < ntiles && !(dbg & VDA_FLAG_PREFETCH_FIRST)) {
                     load_bias(next);
                     load_stats(next);
                     set_sources(next);
@@ -726,50 +726,19 @@ int launch256(const vda_gemm_args& a, hipStream_t s) {
     return 0;
 }
 
-// Dense A: every epilogue. Conv A: the three the head uses.
-template <int BN>
-int launch_dense(const vda_gemm_args& a, hipStream_t s) {
-    switch (a.epilogue) {
-        case VDA_EPI_BIAS_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_BIAS_F16>(a, s);
-        case VDA_EPI_BIAS_GELU_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_BIAS_GELU_F16>(a, s);
-        case VDA_EPI_BIAS_RELU_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_BIAS_RELU_F16>(a, s);
-        case VDA_EPI_SCALE_RES_F32: return launch256<BN, VDA_A_DENSE, VDA_EPI_SCALE_RES_F32>(a, s);
-        case VDA_EPI_RES_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_RES_F16>(a, s);
-        case VDA_EPI_GEGLU_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_GEGLU_F16>(a, s);
-        case VDA_EPI_PATCH_F32: return launch256<BN, VDA_A_DENSE, VDA_EPI_PATCH_F32>(a, s);
-        case VDA_EPI_CONVT_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_CONVT_F16>(a, s);
-        case VDA_EPI_BIAS_F32: return launch256<BN, VDA_A_DENSE, VDA_EPI_BIAS_F32>(a, s);
-        case VDA_EPI_SCALE_RES_F32_H: return launch256<BN, VDA_A_DENSE, VDA_EPI_SCALE_RES_F32_H>(a, s);
-        case VDA_EPI_SCALE_RES_SPLIT: return launch256<BN, VDA_A_DENSE, VDA_EPI_SCALE_RES_SPLIT>(a, s);
-        case VDA_EPI_LN_BIAS_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_LN_BIAS_F16>(a, s);
-        case VDA_EPI_LN_GELU_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_LN_GELU_F16>(a, s);
-        default: break;
+// One case per epilogue of the family's list (gemm_epilogue.h: the lists the planner plans with); -1 = not built, which the planner
+// never asks for. Dense A: every epilogue. Conv A: the three the head uses. 192-row tiles (dense, 256 columns): the epilogues of the
+// encoder GEMMs a row split applies to (templates so that the kernels are instantiated in the one translation unit that calls them).
+#define VDA_8P_FAMILY(fn, LIST, AMODE, BM)                                 \
+    template <int BN>                                                      \
+    int fn(const vda_gemm_args& a, hipStream_t s) {                        \
+        switch (a.epilogue) { LIST(VDA_8P_CASE, AMODE, BM) default: return -1; } \
     }
-    return -1;
-}
-
-// 192-row tiles (dense, 256 columns): the epilogues of the encoder GEMMs a row split applies to
-template <int BN>        // (a template only so that the kernels are instantiated in the one translation unit that calls it)
-int launch_dense_bm192(const vda_gemm_args& a, hipStream_t s) {
-    switch (a.epilogue) {
-        case VDA_EPI_BIAS_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_BIAS_F16, 1, 192>(a, s);
-        case VDA_EPI_SCALE_RES_F32: return launch256<BN, VDA_A_DENSE, VDA_EPI_SCALE_RES_F32, 1, 192>(a, s);
-        case VDA_EPI_SCALE_RES_SPLIT: return launch256<BN, VDA_A_DENSE, VDA_EPI_SCALE_RES_SPLIT, 1, 192>(a, s);
-        case VDA_EPI_LN_BIAS_F16: return launch256<BN, VDA_A_DENSE, VDA_EPI_LN_BIAS_F16, 1, 192>(a, s);
-        default: break;
-    }
-    return -1;
-}
-
-template <int BN>
-int launch_conv(const vda_gemm_args& a, hipStream_t s) {
-    switch (a.epilogue) {
-        case VDA_EPI_BIAS_F16: return launch256<BN, VDA_A_CONV3X3, VDA_EPI_BIAS_F16>(a, s);
-        case VDA_EPI_BIAS_RELU_F16: return launch256<BN, VDA_A_CONV3X3, VDA_EPI_BIAS_RELU_F16>(a, s);
-        case VDA_EPI_RES_F16: return launch256<BN, VDA_A_CONV3X3, VDA_EPI_RES_F16>(a, s);
-        default: break;
-    }
-    return -1;                                  // caller falls back to the 128-row kernel
-}
+#define VDA_8P_CASE(E, AMODE, BM) case E: return launch256<BN, AMODE, E, 1, BM>(a, s);
+VDA_8P_FAMILY(launch_dense, VDA_EPIS_DENSE, VDA_A_DENSE, 256)
+VDA_8P_FAMILY(launch_dense_bm192, VDA_EPIS_8P_BM192, VDA_A_DENSE, 192)
+VDA_8P_FAMILY(launch_conv, VDA_EPIS_CONV, VDA_A_CONV3X3, 256)
+#undef VDA_8P_CASE
+#undef VDA_8P_FAMILY
 
 }  // namespace vda_gemm8p

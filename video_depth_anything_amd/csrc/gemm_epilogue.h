@@ -4,6 +4,29 @@
 #include "vda_common.h"
 #include <type_traits>
 
+// ---- The epilogues each large-tile kernel family is BUILT for, written once: a family's launch switch has one case per entry
+// (gemm8p_kernel.h, gemm256s_kernel.h, gemm256_kernel.h) and the planner asks vda_gemm_built (gemm.hip) before it picks the family.
+// The 128-row kernel (gemm.hip) takes every epilogue.
+#define VDA_EPIS_DENSE_MFMA32(X, ...)                                                                                          \
+    X(VDA_EPI_BIAS_F16, __VA_ARGS__) X(VDA_EPI_BIAS_GELU_F16, __VA_ARGS__) X(VDA_EPI_BIAS_RELU_F16, __VA_ARGS__)               \
+    X(VDA_EPI_SCALE_RES_F32, __VA_ARGS__) X(VDA_EPI_RES_F16, __VA_ARGS__) X(VDA_EPI_GEGLU_F16, __VA_ARGS__)                    \
+    X(VDA_EPI_PATCH_F32, __VA_ARGS__) X(VDA_EPI_CONVT_F16, __VA_ARGS__) X(VDA_EPI_BIAS_F32, __VA_ARGS__) X(VDA_EPI_SCALE_RES_F32_H, __VA_ARGS__)
+#define VDA_EPIS_DENSE(X, ...) \
+    VDA_EPIS_DENSE_MFMA32(X, __VA_ARGS__) X(VDA_EPI_SCALE_RES_SPLIT, __VA_ARGS__) X(VDA_EPI_LN_BIAS_F16, __VA_ARGS__) X(VDA_EPI_LN_GELU_F16, __VA_ARGS__)
+#define VDA_EPIS_CONV(X, ...) X(VDA_EPI_BIAS_F16, __VA_ARGS__) X(VDA_EPI_BIAS_RELU_F16, __VA_ARGS__) X(VDA_EPI_RES_F16, __VA_ARGS__)
+#define VDA_EPIS_8P_BM192(X, ...) \
+    X(VDA_EPI_BIAS_F16, __VA_ARGS__) X(VDA_EPI_SCALE_RES_F32, __VA_ARGS__) X(VDA_EPI_SCALE_RES_SPLIT, __VA_ARGS__) X(VDA_EPI_LN_BIAS_F16, __VA_ARGS__)
+#define VDA_EPIS_256S_BM192_X2(X, ...) \
+    X(VDA_EPI_BIAS_F16, __VA_ARGS__) X(VDA_EPI_BIAS_GELU_F16, __VA_ARGS__) X(VDA_EPI_LN_BIAS_F16, __VA_ARGS__) X(VDA_EPI_LN_GELU_F16, __VA_ARGS__)
+#define VDA_EPIS_256S_BM192(X, ...)                                                                             \
+    X(VDA_EPI_BIAS_F16, __VA_ARGS__) X(VDA_EPI_BIAS_GELU_F16, __VA_ARGS__) X(VDA_EPI_SCALE_RES_F32, __VA_ARGS__) \
+    X(VDA_EPI_SCALE_RES_SPLIT, __VA_ARGS__) X(VDA_EPI_LN_BIAS_F16, __VA_ARGS__) X(VDA_EPI_LN_GELU_F16, __VA_ARGS__)
+#define VDA_EPIS_256S_BN384(X, ...)                                                                                   \
+    X(VDA_EPI_BIAS_F16, __VA_ARGS__) X(VDA_EPI_SCALE_RES_F32, __VA_ARGS__) X(VDA_EPI_SCALE_RES_SPLIT, __VA_ARGS__) \
+    X(VDA_EPI_LN_BIAS_F16, __VA_ARGS__) X(VDA_EPI_LN_GELU_F16, __VA_ARGS__)
+#define VDA_EPI_IN_LIST(E, ...) case E:
+#define VDA_EPI_BUILT(LIST, epilogue) [](int e_) { switch (e_) { LIST(VDA_EPI_IN_LIST, 0) return true; default: return false; } }(epilogue)
+
 namespace vda_gemm {
 
 // fp32 -> fp16 of an epilogue result, always as "round to fp32, then round to fp16". Left alone, hipcc fuses the last fp32

@@ -145,7 +145,7 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_f32_kernel(const vda_gemm_a
             for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
     const int fr = lane & 31, fh = lane >> 5;
-    const bool relu = AMODE == VDA_A_CONV3X3 && (p.relu_in & 1);
+    const bool relu = AMODE == VDA_A_CONV3X3 && (p.relu_in & VDA_OPT_RELU_IN);
 
     auto compute = [&](const char* buf) {
         const char* At = buf + (wm * WTM + fr) * ROW_BYTES;

@@ -541,7 +541,6 @@ struct Run {
     size_t ab;                // bytes per activation element
     int32_t* sched = nullptr; // dynamic-schedule counters: 8 per GEMM launch of the forward, zeroed at its start
     int nsched = 0;           // launches so far (dry pass: the count that sizes the block)
-    int mplan = 0;            // != 0: the GEMMs are row ranges of an mplan-row GEMM, dispatched as it would be (vda_gemm_f16_planned)
 
     void* buf(const std::string& name, size_t elems, size_t esize) {
         const size_t bytes = (elems * esize + 255) & ~(size_t)255;
@@ -563,54 +562,45 @@ struct Run {
     const void* W(const std::string& k) const { return dry ? nullptr : h->mat[prec].at(k); }
     const float* V(const std::string& k) const { return dry ? nullptr : h->vec.at(k); }
 
-    // A large dense GEMM runs as two launches when that quantises better on this device (vda_gemm_plan_split: whole rounds of
-    // 256-row tiles + the remainder on 192-row tiles). Split HERE rather than inside vda_gemm_f16 so that each launch has its own
-    // dynamic-schedule counters and its own profile bracket (kernel name, FLOPs of its rows).
-    // A half of enc_split (mplan != 0) runs as ONE launch: the remainder launch pays only when the GEMM has the chip to itself, and
-    // beside the other half it lost (ViT-L fc2, in-process A/B: 50.52 -> 50.13 ms per clip without it, profiles/r05).
-    int gemm(vda_gemm_args a) {
-        if (prec == VDA_PREC_F16 && mplan == 0) {
-            const int m1 = vda_gemm_plan_split(a.M, a.N, a.K, a.epilogue, a.a_mode);
-            if (m1 < a.M) {
-                if (dry) {
-                    VDA_TRY(gemm_one(a));
-                    return gemm_one(a);
-                }
-                vda_gemm_args p1, p2;
-                a.zero_page = h->zero_page;
-                VDA_TRY(vda_gemm_row_range(&a, 0, m1, &p1));
-                VDA_TRY(vda_gemm_row_range(&a, m1, a.M - m1, &p2));
-                p1.tile_rows = 256;
-                p2.tile_rows = 192;
-                VDA_TRY(gemm_one(p1));
-                return gemm_one(p2);
-            }
-        }
-        return gemm_one(a);
-    }
-    int gemm_one(vda_gemm_args a) {
-        if (prec == VDA_PREC_F16 && h->dyn_sched) {
-            if (!dry && sched != nullptr) a.sched = sched + 8 * nsched;
-            ++nsched;
-        }
-        if (dry) return 0;
-        a.zero_page = h->zero_page;
+    // One GEMM = the records of its plan (vda_gemm_plan: a large dense GEMM runs as two launches when that quantises better on this
+    // device). Planned HERE rather than inside vda_gemm_f16 so that each launch has its own dynamic-schedule counters and its own
+    // profile bracket (kernel name, FLOPs of its rows). m_plan != 0: `a` is a frame half of enc_split, planned as the m_plan-row GEMM of
+    // the whole clip would be and run as ONE launch: the remainder launch pays only when the GEMM has the chip to itself, and beside
+    // the other half it lost (ViT-L fc2, in-process A/B: 50.52 -> 50.13 ms per clip without it, profiles/r05).
+    int gemm(vda_gemm_args a, int m_plan = 0) {
         if (a.lda == 0) a.lda = a.K;
         if (a.ldc == 0) a.ldc = a.N;
+        a.zero_page = h->zero_page;
+        if (prec == VDA_PREC_F32) return dry ? 0 : bracket(a, nullptr);
+        vda_gemm_plan_t plan;
+        if (h->dyn_sched) a.sched = sched;          // (planned as a dynamic-draw launch; each record gets its own counters below)
+        VDA_TRY(vda_gemm_plan(&a, m_plan, 0, 1, &plan));
+        for (int i = 0; i < plan.n; ++i) {
+            if (h->dyn_sched) a.sched = sched + 8 * nsched++;
+            if (!dry) VDA_TRY(bracket(a, &plan.rec[i]));
+        }
+        return 0;
+    }
+    // one launch (rec == nullptr: the fp32 kernel) inside its profile bracket
+    int bracket(const vda_gemm_args& a, const vda_gemm_launch* rec) {
+        auto run = [&] { return rec == nullptr ? vda_gemm_f32(&a, s) : vda_gemm_f16_record(&a, rec, s); };
         Profile& pf = h->prof;
-        if (pf.every <= 0) return prec == VDA_PREC_F32 ? vda_gemm_f32(&a, s) : vda_gemm_f16_planned(&a, s, mplan);
-        const std::array<int, 5> key = {a.M, a.N, a.K, a.epilogue, a.a_mode};
+        if (pf.every <= 0) return run();
+        const int rows = rec ? rec->rows : a.M;
+        const std::array<int, 5> key = {rows, a.N, a.K, a.epilogue, a.a_mode};
         const int n = pf.seen[key]++;
-        const bool timed = n % pf.every == 0 && 2.0 * a.M * a.N * a.K >= pf.min_flops;
+        const double flops = 2.0 * rows * a.N * a.K;
+        const bool timed = n % pf.every == 0 && flops >= pf.min_flops;
         ProfSample smp;
         if (timed) {
             VDA_HIP(hipEventCreate(&smp.e0));
             VDA_HIP(hipEventCreate(&smp.e1));
             VDA_HIP(hipEventRecord(smp.e0, s));
         }
-        VDA_TRY(prec == VDA_PREC_F32 ? vda_gemm_f32(&a, s) : vda_gemm_f16_planned(&a, s, mplan));
-        const std::string name = prec == VDA_PREC_F32 ? std::string("gemm_f32_kernel") : std::string(vda_gemm_last_kernel());
-        const double flops = 2.0 * a.M * a.N * a.K;
+        VDA_TRY(run());
+        char kname[64] = "gemm_f32_kernel";
+        if (rec) vda_gemm_launch_name(rec, kname, sizeof(kname));
+        const std::string name = kname;
         auto& tot = pf.launches[name];
         tot.first += 1;
         tot.second += flops;
@@ -623,11 +613,11 @@ struct Run {
         return 0;
     }
     int dense(const void* A, const void* Wm, void* out, int epi, int M, int N, int K, const float* bias = nullptr, const void* res = nullptr,
-              const float* gamma = nullptr, int ldc = 0) {
+              const float* gamma = nullptr, int ldc = 0, int m_plan = 0) {
         vda_gemm_args a = {};
         a.A = A, a.W = Wm, a.out = out, a.bias = bias, a.res = res, a.gamma = gamma;
         a.M = M, a.N = N, a.K = K, a.ldc = ldc, a.a_mode = VDA_A_DENSE, a.epilogue = epi;
-        return gemm(a);
+        return gemm(a, m_plan);
     }
     int conv3x3(const void* x, const std::string& wname, void* out, int B, int H, int Wd, int Cin, int Cout, int epi, int stride,
                 const float* bias, bool relu_in = false, const void* res = nullptr, const void* res2 = nullptr) {
@@ -800,7 +790,7 @@ struct Run {
         // frame only and every GEMM / LayerNorm row is independent. So frames [0, F) and [F, BT) run as two launch chains, half A on the
         // caller's stream and half B on the handle's lane stream, and each chain's kernels fill the tail rounds, launch boundaries and
         // small launches the other leaves idle. Every op is a row range of the same buffers, and each GEMM half is dispatched as the
-        // whole-clip GEMM would be (mplan): the result is bit-identical to one chain. The head (its motion modules mix frames) runs
+        // whole-clip GEMM would be (gemm's m_plan): the result is bit-identical to one chain. The head (its motion modules mix frames) runs
         // after the join at full T. A captured forward keeps one stream (a linear graph); the dry pass takes the uncaptured decision
         // (the larger launch count, which sizes the dynamic-schedule counters).
         struct Part {
@@ -857,10 +847,7 @@ struct Run {
             a.A = (const h16*)thi + r0 * D, a.W = W(wk + ".weight.ln"), a.out = (h16*)out + r0 * N, a.bias = V(wk + ".c2"), a.gamma = V(wk + ".c1");
             a.stats = lnstat + r0 * 2;
             a.M = p.nf * Nt, a.N = N, a.K = D, a.a_mode = VDA_A_DENSE, a.epilogue = epi;
-            mplan = nparts > 1 ? rows : 0;
-            const int rc = gemm(a);
-            mplan = 0;
-            return rc;
+            return gemm(a, nparts > 1 ? rows : 0);
         };
         auto res_gemm = [&](const void* A, const std::string& wk, const std::string& gk, int K, bool stats_next, const Part& p) -> int {   // x += gamma * (A @ W^T + b)
             const size_t r0 = (size_t)p.f0 * Nt;
@@ -871,10 +858,7 @@ struct Run {
             a.stats = lnpart + r0 * np * 2;      // the part's own [np, nr, 2] block of partial statistics
             a.pos = lnstat + r0 * 2;             // re-centre by the mean the LayerNorm before this branch saw
             a.M = nr, a.N = D, a.K = K, a.a_mode = VDA_A_DENSE, a.epilogue = VDA_EPI_SCALE_RES_SPLIT;
-            mplan = nparts > 1 ? rows : 0;
-            const int rc = gemm(a);
-            mplan = 0;
-            VDA_TRY(rc);
+            VDA_TRY(gemm(a, nparts > 1 ? rows : 0));
             // (after the last block nothing reads the statistics: that finalize runs for its overflow check alone, 5 us per clip)
             (void)stats_next;
             if (!dry) VDA_TRY(vda_ln_stats_finalize(lnpart + r0 * np * 2, lnstat + r0 * 2, ENC_LN_EPS, nr, np, ovf, s));
@@ -1006,11 +990,8 @@ struct Run {
                         if (!dry)
                             VDA_TRY(prec == VDA_PREC_F32 ? vda_readout_concat_f32((const float*)full + r0 * D, (float*)cat + q0 * 2 * D, p.nf, P, D, s)
                                                          : vda_readout_concat_f16((const h16*)full + r0 * D, (h16*)cat + q0 * 2 * D, p.nf, P, D, s));
-                        mplan = nparts > 1 ? BT * P : 0;
-                        const int rc = dense((const char*)cat + q0 * 2 * D * ab, W(kr + ".w"), (char*)tp + q0 * D * ab, VDA_EPI_BIAS_GELU_F16, p.nf * P, D, 2 * D,
-                                             V(kr + ".b"));
-                        mplan = 0;
-                        return rc;
+                        return dense((const char*)cat + q0 * 2 * D * ab, W(kr + ".w"), (char*)tp + q0 * D * ab, VDA_EPI_BIAS_GELU_F16, p.nf * P, D, 2 * D,
+                                     V(kr + ".b"), nullptr, nullptr, 0, nparts > 1 ? BT * P : 0);
                     }));
                 }
                 taps[ntap++] = tp;

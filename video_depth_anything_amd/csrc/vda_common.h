@@ -207,12 +207,34 @@ struct VdaKernelDeviceState {
 // take HALF the chip were measured against two full-grid sequences interleaving freely (tools/two_stream.py, round 4): the capped
 // form loses (ViT-L 2 x 16 frames: 619 against 630 frames/s; two clips: 636 against 652), so nothing in the product sets it.
 extern int g_vda_max_wgs;
-// vda_gemm_f16 with the dispatcher's shape decisions (tile family, 192-row tiles, the small-grid fallback, non-temporal stores) taken
-// for m_plan rows instead of args->M (0: args->M). The forward's encoder runs each GEMM as two frame halves on two streams: each half
-// launch picks the kernel the whole-clip launch would have picked - same family, same per-row arithmetic, same store policy for what
-// the two halves write together. A planned row range is never row-split further (its other rows fill the chip beside it).
-// Library-internal (not part of the C ABI).
-int vda_gemm_f16_planned(const vda_gemm_args* args, vda_stream_t stream, int m_plan);
+// vda_gemm_args::relu_in as a KERNEL sees it (the option word of a vda_gemm_launch): bit 0 is the caller's field, the rest is set by
+// the planner (gemm.hip). The field, its layout and every bit position are fixed (ctypes.sizeof(GemmArgs), the kernels' code).
+enum : int {
+    VDA_OPT_RELU_IN = 1,             // apply relu to A elements on load
+    VDA_OPT_FLAGS_SHIFT = 8,         // bits 8..15: the VDA_FLAG_* switches below
+    VDA_OPT_DEBUG_SHIFT = 16,        // bits 16..23: vda_gemm_set_debug
+    VDA_OPT_BYTE = 0xff,
+    VDA_OPT_NT_STORES = 1 << 24,     // non-temporal fp16 row stores (8-phase kernel): the output is too large for a cache to hand on
+    // A/B switches, vda_gemm_set_variant(5 + 16 * flags): 8-phase kernel unless noted
+    VDA_FLAG_PREFETCH_FIRST = 1,     // next tile's K tile 0 before the epilogue
+    VDA_FLAG_STAMPS = 2,             // shader-clock stamps into pos (tools/gemm_stamps.py)
+    VDA_FLAG_PREFETCH_EARLY = 4,     // row-dependent epilogues prefetch after their first block too
+    VDA_FLAG_PREFETCH_LATE = 8,      // every epilogue prefetches after its last block
+    VDA_FLAG_NO_STAGGER = 16,        // no start stagger (also the one-barrier 16x16x32 kernel; set unless VDA_GEMM_STAGGER)
+    VDA_FLAG_STAGGER_PANEL = 32,     // VDA_GEMM_STAGGER=2: panel-aligned phases
+    VDA_FLAG_BM192 = 64,             // host side only: 192 x 256 tiles where built
+    // vda_gemm_set_debug
+    VDA_DEBUG_CLOCKS = 1, VDA_DEBUG_BLOCKED_MORE = 2, VDA_DEBUG_KTILE_CLOCKS = 4, VDA_DEBUG_NEVER_BLOCKED = 16,
+};
+// (macros, not functions: a kernel that reads a bit through its name must compile to exactly the code the bare literals gave)
+#define VDA_OPT_FLAGS(word) (((word) >> 8) & 0xff)
+#define VDA_OPT_FLAG(word, flag) (((word) >> 8) & (flag))
+#define VDA_OPT_STAMPS(word) (((word) >> 9) & 1)          /* VDA_FLAG_STAMPS as 0 / 1 */
+#define VDA_OPT_DEBUG(word) (((word) >> 16) & 0xff)
+#define VDA_OPT_NT(word) (((word) >> 24) & 1)             /* VDA_OPT_NT_STORES as 0 / 1 */
+// One record of a vda_gemm_plan_t on `args` (validated here, operands included). The forward plans a GEMM itself so that each record
+// gets its own sched counters and profile bracket. Library-internal (not part of the C ABI).
+int vda_gemm_f16_record(const vda_gemm_args* args, const vda_gemm_launch* rec, vda_stream_t stream);
 inline int vda_prepare_kernel(const void* fn, int dyn_lds_bytes, VdaKernelDeviceState& st) {
     int dev = 0;
     (void)hipGetDevice(&dev);
