@@ -594,7 +594,10 @@ def attn_ref(qkv, B, N, H):
 
 
 @pytest.mark.parametrize("variant", [-1, 1, 2, 3, 0, 4, 5, 7, 8, 9, 10, 11])
-@pytest.mark.parametrize("B,N,H", [(2, 13, 2), (1, 64, 1), (2, 200, 3), (1, 1370, 2)])
+# (1, 1, 1): one query, three idle waves, every staged row clamped or out of range; (2, 65, 2): the second key tile holds one key;
+# (1, 128, 3): exactly one full query block, no tail mask; (3, 129, 1): a second query block with one live query, and six
+# workgroups - fewer than the 8 XCDs, so the block remap's remainder branch runs.
+@pytest.mark.parametrize("B,N,H", [(2, 13, 2), (1, 64, 1), (2, 200, 3), (1, 1370, 2), (1, 1, 1), (2, 65, 2), (1, 128, 3), (3, 129, 1)])
 def test_attention(ops, B, N, H, variant):
     from video_depth_anything_amd._lib import lib
     qkv = rnd(B, N, 3 * H * 64, seed=43, scale=1.5).to(F16)
@@ -605,6 +608,24 @@ def test_attention(ops, B, N, H, variant):
     finally:
         lib.vda_attention_set_variant(-1)
     close(out, attn_ref(qkv, B, N, H), rtol=3e-3, atol=3e-3, what=f"attention variant {variant}")
+
+
+def test_attention_rejects_unknown_variant(ops):
+    """A code the dispatch table does not list is refused - non-zero, vda_last_error() names it - and leaves the variant as it
+    was: the next call is bit for bit the default kernel's."""
+    from video_depth_anything_amd._lib import lib
+    B, N, H = 2, 13, 2
+    qkv = dev(rnd(B, N, 3 * H * 64, seed=43, scale=1.5).to(F16))
+    ref, out = (torch.full((B, N, H * 64), float("nan"), dtype=F16, device="cuda") for _ in range(2))
+    try:
+        assert lib.vda_attention_set_variant(-1) == 0
+        ops.attention(qkv, ref, B, N, H)
+        assert lib.vda_attention_set_variant(6) != 0
+        assert b"vda_attention_set_variant: unknown variant 6" in lib.vda_last_error()
+        ops.attention(qkv, out, B, N, H)
+    finally:
+        lib.vda_attention_set_variant(-1)
+    assert torch.equal(out, ref)
 
 
 @pytest.mark.parametrize("H", [16, 6], ids=["vitl", "vits"])

@@ -11,7 +11,8 @@ for scale in [float(v) for v in os.environ.get('ATTN_SCALES', '0.3,1.0').split('
     q = (qkv * scale).contiguous()
     for rep in range(int(os.environ.get('ATTN_REPS', '3'))):
         for variant in [int(v) for v in os.environ.get('ATTN_VARIANTS', '1,8,9').split(',')]:
-            _lib.lib.vda_attention_set_variant(variant)
+            if _lib.lib.vda_attention_set_variant(variant) != 0:
+                sys.exit(_lib.lib.vda_last_error().decode())
             for _ in range(2):
                 ops.attention(q, o, 32, 1370, H)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

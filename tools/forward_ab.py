@@ -17,7 +17,8 @@ x = torch.randn(1, 32, 3, 518, 518, generator=torch.Generator().manual_seed(0)).
 ts = {v: [] for v in variants}
 for rep in range(5):
     for v in variants:
-        _lib.lib.vda_attention_set_variant(v)
+        if _lib.lib.vda_attention_set_variant(v) != 0:
+            sys.exit(_lib.lib.vda_last_error().decode())
         m.forward(x, fp32=False)
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

@@ -2,6 +2,14 @@
 // fp16 in / fp16 out, fp32 scores, softmax and accumulation; the N x N score matrix never
 // leaves registers (online softmax over 64-key tiles).
 //
+// Four kernels, in this order; they share the work split, the LDS image and the fragment layout below and differ in how the
+// softmax reference point is kept and how the tile loop is scheduled (vda_attention_set_variant codes in brackets):
+//   attn_kernel<TR, PK, LSUM, MB, ABL>   [0 - 5, 20 + k]  running maximum on the VALU; the cross-checks, the round-2 experiments, the ablations
+//   attn_pipe_kernel                     [7]              attn_kernel<true, false> software-pipelined over two key tiles
+//   attn_cm_kernel<LAZY>                 [8, 9]           reference point through the score MFMAs' C operand, lazy rescale
+//   attn_cs_kernel<FLAGS>                [10, 11]         as 9, rescale decided from the row sums, K / V staged by buffer loads.
+//                                                         attn_cs_kernel<false> (10) IS THE KERNEL THAT SHIPS; 11 = LDS counters for the barrier
+//
 // Work split: one workgroup = 128 queries of one (frame, head); 4 waves x 32 queries.
 // Per 64-key tile and wave:
 //   S^T[key][query] = K_tile . Q^T    v_mfma_f32_32x32x16_f16, K rows from LDS (A operand),
@@ -14,8 +22,10 @@
 //                                     the row-major V tile with ds_read_b64_tr_b16 in the same k order.
 //     -> the output accumulator also has the query on the lane, so the online-softmax rescale is a
 //        plain per-lane multiply.
-// K and V tiles arrive by 16-byte global_load_lds into a double buffer; XOR swizzles are applied on
-// the source address (the DMA image is lane-linear) and again on the LDS read.
+// K and V tiles arrive by 16-byte LDS-DMA (global_load_lds; buffer_load ... lds in attn_cs_kernel) into a double buffer; XOR
+// swizzles are applied on the source address (the DMA image is lane-linear) and again on the LDS read.
+// The steps every kernel takes - locate, q_frag, stage_kv, qk_chain, mask_tail, tile_max, tr16 / v_frag_tr / pv_tile, store_out - are
+// written once, ahead of the kernels; a kernel is its own state and its own tile loop over them.
 #include "vda_common.h"
 
 namespace {
@@ -31,6 +41,167 @@ typedef __fp16 fp16x4_t __attribute__((__vector_size__(4 * sizeof(__fp16))));
 __device__ __forceinline__ int k_swz(int row) { return (row >> 1) & 7; }          // 16-row conflict-free for 32-row b128 fragments
 __device__ __forceinline__ int v_swz(int row) { return ((row >> 1) & 1) << 2; }   // separates the 4 rows of a tr16 block
 
+// ---- the shared steps. In every one: lane = threadIdx.x & 63, r = lane & 31 (the lane's query within the wave), h = lane >> 5.
+
+// What a workgroup and a lane of it work on.
+struct Where {
+    int b, head;                 // frame, head
+    size_t rs;                   // row stride of qkv in halves
+    unsigned rs32;               // the same in 32 bits: one frame's N * rs fits (checked by the launcher)
+    const h16 *Qb, *Kb, *Vb;     // row 0 of the frame's q / k / v for this head
+    int q_row;                   // the lane's query
+    bool wave_active;            // false: all 32 queries of the wave lie past N (the 4th wave of a frame's last query block:
+                                 // 1370 = 10 x 128 + 90); it only helps with the staging and the synchronisation
+};
+
+__device__ __forceinline__ Where locate(const h16* qkv, int bid, int total_blocks, int nqb, int H, int N, int wave, int r) {
+    Where w;
+    // XCD-aware remap: blocks sharing an XCD (bid % 8) get whole (frame, head) groups so K/V stay in that L2.
+    const int xcd = bid & 7, qd = total_blocks >> 3, rm = total_blocks & 7;
+    const int t = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + (bid >> 3);
+    const int bh = t / nqb, qb = t - bh * nqb;
+    w.b = bh / H;
+    w.head = bh - w.b * H;
+    w.rs = (size_t)3 * H * HD;
+    w.rs32 = (unsigned)w.rs;
+    w.Qb = qkv + (size_t)w.b * N * w.rs + w.head * HD;
+    w.Kb = w.Qb + (size_t)H * HD;
+    w.Vb = w.Kb + (size_t)H * HD;
+    w.q_row = qb * BQ + wave * 32 + r;
+    w.wave_active = __builtin_amdgcn_readfirstlane((int)(qb * BQ + wave * 32 < N)) != 0;
+    return w;
+}
+
+// Q fragment ks (B operand: lane holds Q[query r][16ks + 8h .. +7]), pre-scaled by 1/8 (exact) or, LOG2, by log2(e) / 8: the scores
+// then leave the MFMAs in the log2 domain. (By value: filling a caller's array through a reference changed attn_cs_kernel's ISA.)
+template <bool LOG2>
+__device__ __forceinline__ h16x8 q_frag(const Where& w, int N, int h, int ks) {
+    h16x8 q = *reinterpret_cast<const h16x8*>(w.Qb + (size_t)min(w.q_row, N - 1) * w.rs + h * 8 + ks * 16);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) q[e] = LOG2 ? (h16)((float)q[e] * (0.125f * 1.4426950408889634f)) : q[e] * (h16)0.125f;
+    return q;
+}
+
+// LDS-DMA of key tile kt, global_load_lds form: each wave moves 2 pieces (8 rows x 128 B each) of K and / or of V; rows past N
+// repeat row N - 1 (their scores are masked).
+template <bool K, bool V>
+__device__ __forceinline__ void stage_kv(const Where& w, int kt, int N, int wave, int lane, char* kbuf, char* vbuf) {
+    const int lrow = lane >> 3, lpos = lane & 7;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int piece = wave + 4 * j;
+        const int row = piece * 8 + lrow;
+        const unsigned key = (unsigned)min(kt * BKV + row, N - 1) * w.rs32;     // 32-bit: one multiply, no 64-bit carry chain
+        if constexpr (K) glds16(w.Kb + (key + ((lpos ^ k_swz(row)) << 3)), kbuf + piece * 1024);
+        if constexpr (V) glds16(w.Vb + (key + ((lpos ^ v_swz(row)) << 3)), vbuf + piece * 1024);
+    }
+}
+__device__ __forceinline__ void stage_k(const Where& w, int kt, int N, int wave, int lane, char* kbuf) { stage_kv<true, false>(w, kt, N, wave, lane, kbuf, nullptr); }
+__device__ __forceinline__ void stage_v(const Where& w, int kt, int N, int wave, int lane, char* vbuf) { stage_kv<false, true>(w, kt, N, wave, lane, nullptr, vbuf); }
+
+// S^T = K . Q^T + c0 for 32-key half `sub` of the K tile at Kt, STEPS (4) k-steps of 16 channels; c0: a zero block, or -m.
+template <int STEPS = 4>
+__device__ __forceinline__ f32x16 qk_chain(const char* Kt, int sub, int r, int h, const h16x8 (&qf)[4], f32x16 c0) {
+    const int row = sub * 32 + r;
+    const char* kp = Kt + row * 128;
+    const int sw = k_swz(row);
+#pragma unroll
+    for (int ks = 0; ks < STEPS; ++ks) {
+        const h16x8 kf = *reinterpret_cast<const h16x8*>(kp + (((2 * ks + h) ^ sw) << 4));
+        c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[ks], c0, 0, 0, 0);
+    }
+    return c0;
+}
+
+// The last key tile when it is partial (a scalar condition), and its mask: accumulator register e of half `sub` is key
+// kt*64 + sub*32 + (e&3) + 8*(e>>2) + 4h.
+__device__ __forceinline__ bool tail_tile(int kt, int nt, int N) {
+    return __builtin_amdgcn_readfirstlane((int)(kt == nt - 1 && (N % BKV) != 0)) != 0;
+}
+__device__ __forceinline__ void mask_tail(f32x16 (&s)[2], int kt, int h, int N) {
+    const int kbase = kt * BKV + 4 * h;
+#pragma unroll
+    for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+        for (int e = 0; e < 16; ++e)
+            if (kbase + sub * 32 + (e & 3) + 8 * (e >> 2) >= N) s[sub][e] = -1e30f;
+}
+// The same on a copy, for attn_pipe_kernel and attn_cm_kernel: with the reference the compiler stops peeling the special first
+// tile off their loops; attn_kernel and attn_cs_kernel mask in place from a lambda, which keeps their registers (profiles/r09).
+struct Scores {
+    f32x16 s[2];
+};
+__device__ __forceinline__ Scores masked(Scores t, int kt, int h, int N) {
+    mask_tail(t.s, kt, h, N);
+    return t;
+}
+__device__ __forceinline__ void mask_copy(f32x16 (&s)[2], int kt, int h, int N) {
+    const Scores t = masked(Scores{{s[0], s[1]}}, kt, h, N);
+    s[0] = t.s[0];
+    s[1] = t.s[1];
+}
+
+// The tile's maximum per query (lane pair {lane, lane ^ 32}).
+__device__ __forceinline__ float tile_max(const f32x16 (&s)[2]) {
+    float mx = s[0][0];
+#pragma unroll
+    for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) mx = fmaxf(mx, s[sub][e]);
+    return fmaxf(mx, __shfl_xor(mx, 32, 64));
+}
+
+// ds_read_b64_tr_b16: four halves of the transposed 4-key x 16-channel block the lane's 16-lane group addresses.
+__device__ __forceinline__ h16x4 tr16(const char* ap) {
+    const fp16x4_t v4 = __builtin_amdgcn_ds_read_tr16_b64_v4f16((VDA_LDS_AS fp16x4_t*)ap);
+    return h16x4{(h16)v4[0], (h16)v4[1], (h16)v4[2], (h16)v4[3]};
+}
+
+// V^T fragment (A operand) of 16-key step kstep, channel half c, by transposed reads of the row-major V tile: a 16-lane group
+// reads a 4-key x 16-channel block; lane 4q+p addresses key q, channels 4p..4p+3.
+__device__ __forceinline__ h16x8 v_frag_tr(const char* Vt, int kstep, int c, int lane, int h) {
+    h16x8 vf;
+    const int i = lane & 15, qq = i >> 2, pp = i & 3;
+    const int col = c * 32 + 16 * ((lane >> 4) & 1) + 4 * pp;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        const int key = kstep * 16 + half * 8 + 4 * h + qq;
+        const char* ap = Vt + key * 128 + ((((col >> 3) ^ v_swz(key))) << 4) + ((col & 7) << 1);
+        const h16x4 v4 = tr16(ap);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) vf[half * 4 + e] = v4[e];
+    }
+    return vf;
+}
+
+// O^T += V^T . P^T  (4 steps of 16 keys, 2 halves of 32 channels)
+__device__ __forceinline__ void pv_tile(const char* Vt, int lane, int h, const h16x8 (&pf)[4], f32x16 (&acc_o)[2]) {
+#pragma unroll
+    for (int kstep = 0; kstep < 4; ++kstep)
+#pragma unroll
+        for (int c = 0; c < 2; ++c) acc_o[c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(v_frag_tr(Vt, kstep, c, lane, h), pf[kstep], acc_o[c], 0, 0, 0);
+}
+
+// Normalise by the query's softmax denominator and store: lane holds query r, channels c*32 + (e&3) + 8*(e>>2) + 4h.
+__device__ __forceinline__ void store_out(h16* out, const Where& w, int N, int H, int h, const f32x16 (&acc_o)[2], float l_tot) {
+    const float inv = 1.0f / l_tot;
+    if (w.q_row < N) {
+        h16* op = out + ((size_t)w.b * N + w.q_row) * ((size_t)H * HD) + w.head * HD + 4 * h;
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                h16x4 o = {(h16)(acc_o[c][4 * g + 0] * inv), (h16)(acc_o[c][4 * g + 1] * inv),
+                           (h16)(acc_o[c][4 * g + 2] * inv), (h16)(acc_o[c][4 * g + 3] * inv)};
+                *reinterpret_cast<h16x4*>(op + c * 32 + 8 * g) = o;
+            }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Rounds 1 - 2 (variants 0 - 5, 20 + k): the running maximum kept on the VALU, p = exp2(s * log2e - m * log2e).
+// TR: V^T fragments by ds_read_b64_tr_b16 (false, variant 0: scalar LDS reads, the cross-check). PK: the softmax math on float
+// pairs (variant 2).
 // MB ("max through the matrix pipe"): Q is pre-scaled by log2(e)/8 and the running reference point m of the online softmax is fed
 // to the score MFMAs as a fifth k-step (K side: a constant [1, 1, 0, ...] row; Q side: [-m_hi, -m_lo, 0, ...], m = m_hi + m_lo in
 // fp16 pairs): the accumulators come out as log2-domain scores MINUS the reference, and p = exp2(acc) needs no per-score fma
@@ -44,52 +215,18 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, h = lane >> 5;
-
-    // XCD-aware remap: blocks sharing an XCD (bid % 8) get whole (frame, head) groups so K/V stay in that L2.
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, qd = total_blocks >> 3, rm = total_blocks & 7;
-    const int t = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + (bid >> 3);
-    const int bh = t / nqb, qb = t - bh * nqb;
-    const int b = bh / H, head = bh - b * H;
-
-    const size_t rs = (size_t)3 * H * HD;                       // row stride of qkv in halves
-    const unsigned rs32 = (unsigned)rs;                         // one frame's N * rs fits 32 bits (checked by the launcher)
-    const h16* Qb = qkv + (size_t)b * N * rs + head * HD;
-    const h16* Kb = Qb + (size_t)H * HD;
-    const h16* Vb = Kb + (size_t)H * HD;
-
-    // ---- Q fragments (B operand: lane holds Q[query r][16ks + 8h .. +7]), pre-scaled by 1/8 (exact)
-    const int q_row = qb * BQ + wave * 32 + r;
-    const bool wave_active = __builtin_amdgcn_readfirstlane((int)(qb * BQ + wave * 32 < N)) != 0;
+    const Where w = locate(qkv, blockIdx.x, total_blocks, nqb, H, N, wave, r);
     h16x8 qf[4];
-    {
-        const h16* qp = Qb + (size_t)min(q_row, N - 1) * rs + h * 8;
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            qf[ks] = *reinterpret_cast<const h16x8*>(qp + ks * 16);
+    for (int ks = 0; ks < 4; ++ks) qf[ks] = q_frag<MB>(w, N, h, ks);
+
+    f32x16 acc_o[2], zero;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) qf[ks][e] = MB ? (h16)((float)qf[ks][e] * (0.125f * 1.4426950408889634f)) : qf[ks][e] * (h16)0.125f;
-        }
+    for (int e = 0; e < 16; ++e) {
+        acc_o[0][e] = 0.f;
+        acc_o[1][e] = 0.f;
+        zero[e] = 0.f;
     }
-
-    // ---- DMA sources: each wave moves 2 K pieces and 2 V pieces (8 rows x 128 B each) per tile
-    const int lrow = lane >> 3, lpos = lane & 7;
-    auto stage = [&](int kt, char* buf) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int piece = wave + 4 * j;
-            const int row = piece * 8 + lrow;
-            const unsigned key = (unsigned)min(kt * BKV + row, N - 1) * rs32;     // 32-bit: one multiply, no 64-bit carry chain
-            glds16(Kb + (key + ((lpos ^ k_swz(row)) << 3)), buf + piece * 1024);
-            glds16(Vb + (key + ((lpos ^ v_swz(row)) << 3)), buf + TILE_BYTES + piece * 1024);
-        }
-    };
-
-    f32x16 acc_o[2];
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc_o[c][e] = 0.f;
     float m_run = MB ? 0.f : -1e30f, l_run = 0.f;
     // MB: the fifth k-step's operands. K side: k' = 0, 1 are one (lanes of half h = 0 hold k' = 0..7); Q side: -m as an fp16 pair.
     h16x8 kone, mneg;
@@ -111,17 +248,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
     constexpr float LOG2E = 1.4426950408889634f;
 
     const int nt = (N + BKV - 1) / BKV;
-    stage(0, smem);
+    stage_kv<true, true>(w, 0, N, wave, lane, smem, smem + TILE_BYTES);
     int cur = 0;
     for (int kt = 0; kt < nt; ++kt) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if (kt + 1 < nt) stage(kt + 1, smem + (cur ^ 1) * STAGE_BYTES);
+        char* const nxt = smem + (cur ^ 1) * STAGE_BYTES;
+        if (kt + 1 < nt) stage_kv<true, true>(w, kt + 1, N, wave, lane, nxt, nxt + TILE_BYTES);
         const char* Kt = smem + cur * STAGE_BYTES;
         const char* Vt = Kt + TILE_BYTES;
-        // A wave whose 32 queries all lie past N (the 4th wave of a frame's last query block: 1370 = 10 x 128 + 90) only helps
-        // with the staging and the barriers: its SIMD is left to the other workgroups' waves.
-        if (!wave_active) {
+        if (!w.wave_active) {                   // its SIMD is left to the other workgroups' waves
             cur ^= 1;
             continue;
         }
@@ -130,37 +266,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
         f32x16 s[2];
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e) s[sub][e] = 0.f;
-            const int row = sub * 32 + r;
-            const char* kp = Kt + row * 128;
-            const int sw = k_swz(row);
-#pragma unroll
-            for (int ks = 0; ks < (ABL == 5 ? 1 : 4); ++ks) {
-                const h16x8 kf = *reinterpret_cast<const h16x8*>(kp + (((2 * ks + h) ^ sw) << 4));
-                s[sub] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[ks], s[sub], 0, 0, 0);
-            }
+            s[sub] = qk_chain<(ABL == 5 ? 1 : 4)>(Kt, sub, r, h, qf, zero);
             if constexpr (MB) s[sub] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kone, mneg, s[sub], 0, 0, 0);
         }
-        // accumulator register e of half `sub` is key  kt*64 + sub*32 + (e&3) + 8*(e>>2) + 4h
-        if (__builtin_amdgcn_readfirstlane((int)(kt == nt - 1 && (N % BKV) != 0))) {      // scalar branch, last tile only
-            const int kbase = kt * BKV + 4 * h;
-#pragma unroll
-            for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                for (int e = 0; e < 16; ++e)
-                    if (kbase + sub * 32 + (e & 3) + 8 * (e >> 2) >= N) s[sub][e] = -1e30f;
+        if (tail_tile(kt, nt, N)) {     // in place, from a lambda as in attn_cs_kernel: through `masked` variant 4 needs 126 VGPRs, not 124
+            auto mask = [&] { mask_tail(s, kt, h, N); };
+            mask();
         }
 
         // ---- online softmax (per query = per lane pair {lane, lane^32})
         float mx = s[0][0];
-        if constexpr (ABL != 2) {
-#pragma unroll
-        for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) mx = fmaxf(mx, s[sub][e]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        }
+        if constexpr (ABL != 2) mx = tile_max(s);
         if constexpr (MB) {
             // the accumulators are scores minus the reference m_run (log2 domain): nothing to do while no score exceeds it
             if (__builtin_amdgcn_readfirstlane((int)(kt == 0 || __ballot(mx > 0.f) != 0ull))) {
@@ -248,17 +364,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
             for (int c = 0; c < 2; ++c) {
                 h16x8 vf;
                 if constexpr (TR) {
-                    // 16-lane group reads a 4-key x 16-channel block; lane 4q+p addresses key q, channels 4p..4p+3.
-                    const int i = lane & 15, qq = i >> 2, pp = i & 3;
-                    const int col = c * 32 + 16 * ((lane >> 4) & 1) + 4 * pp;
-#pragma unroll
-                    for (int half = 0; half < 2; ++half) {
-                        const int key = kstep * 16 + half * 8 + 4 * h + qq;
-                        const char* ap = Vt + key * 128 + ((((col >> 3) ^ v_swz(key))) << 4) + ((col & 7) << 1);
-                        const fp16x4_t v4 = __builtin_amdgcn_ds_read_tr16_b64_v4f16((VDA_LDS_AS fp16x4_t*)ap);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) vf[half * 4 + e] = (h16)v4[e];
-                    }
+                    vf = v_frag_tr(Vt, kstep, c, lane, h);
                 } else {
                     const int ch = c * 32 + r;
 #pragma unroll
@@ -274,20 +380,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
         cur ^= 1;
     }
 
-    // ---- normalise and store: lane holds query r, channels c*32 + (e&3) + 8*(e>>2) + 4h
-    const float l_tot = LSUM ? acc_l[0] : l_run + __shfl_xor(l_run, 32, 64);   // every row of acc_l holds the query's full sum
-    const float inv = 1.0f / l_tot;
-    if (q_row < N) {
-        h16* op = out + ((size_t)b * N + q_row) * ((size_t)H * HD) + head * HD + 4 * h;
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                h16x4 o = {(h16)(acc_o[c][4 * g + 0] * inv), (h16)(acc_o[c][4 * g + 1] * inv),
-                           (h16)(acc_o[c][4 * g + 2] * inv), (h16)(acc_o[c][4 * g + 3] * inv)};
-                *reinterpret_cast<h16x4*>(op + c * 32 + 8 * g) = o;
-            }
-    }
+    store_out(out, w, N, H, h, acc_o, LSUM ? acc_l[0] : l_run + __shfl_xor(l_run, 32, 64));   // every row of acc_l holds the query's full sum
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -302,84 +395,34 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, h = lane >> 5;
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, qd = total_blocks >> 3, rm = total_blocks & 7;
-    const int t = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + (bid >> 3);
-    const int bh = t / nqb, qb = t - bh * nqb;
-    const int b = bh / H, head = bh - b * H;
-    const size_t rs = (size_t)3 * H * HD;
-    const unsigned rs32 = (unsigned)rs;
-    const h16* Qb = qkv + (size_t)b * N * rs + head * HD;
-    const h16* Kb = Qb + (size_t)H * HD;
-    const h16* Vb = Kb + (size_t)H * HD;
-    const int q_row = qb * BQ + wave * 32 + r;
-    const bool wave_active = __builtin_amdgcn_readfirstlane((int)(qb * BQ + wave * 32 < N)) != 0;
+    const Where w = locate(qkv, blockIdx.x, total_blocks, nqb, H, N, wave, r);
     h16x8 qf[4];
-    {
-        const h16* qp = Qb + (size_t)min(q_row, N - 1) * rs + h * 8;
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            qf[ks] = *reinterpret_cast<const h16x8*>(qp + ks * 16);
+    for (int ks = 0; ks < 4; ++ks) qf[ks] = q_frag<false>(w, N, h, ks);
+
+    f32x16 acc_o[2], zero;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) qf[ks][e] = qf[ks][e] * (h16)0.125f;
-        }
+    for (int e = 0; e < 16; ++e) {
+        acc_o[0][e] = 0.f;
+        acc_o[1][e] = 0.f;
+        zero[e] = 0.f;
     }
-    const int lrow = lane >> 3, lpos = lane & 7;
-    auto stage_k = [&](int kt, char* buf) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int piece = wave + 4 * j, row = piece * 8 + lrow;
-            const unsigned key = (unsigned)min(kt * BKV + row, N - 1) * rs32;
-            glds16(Kb + (key + ((lpos ^ k_swz(row)) << 3)), buf + piece * 1024);
-        }
-    };
-    auto stage_v = [&](int kt, char* buf) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int piece = wave + 4 * j, row = piece * 8 + lrow;
-            const unsigned key = (unsigned)min(kt * BKV + row, N - 1) * rs32;
-            glds16(Vb + (key + ((lpos ^ v_swz(row)) << 3)), buf + piece * 1024);
-        }
-    };
     auto qk = [&](const char* Kt, f32x16 (&s)[2]) {
 #pragma unroll
-        for (int sub = 0; sub < 2; ++sub) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e) s[sub][e] = 0.f;
-            const int row = sub * 32 + r;
-            const char* kp = Kt + row * 128;
-            const int sw = k_swz(row);
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                const h16x8 kf = *reinterpret_cast<const h16x8*>(kp + (((2 * ks + h) ^ sw) << 4));
-                s[sub] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[ks], s[sub], 0, 0, 0);
-            }
-        }
+        for (int sub = 0; sub < 2; ++sub) s[sub] = qk_chain(Kt, sub, r, h, qf, zero);
     };
-
-    f32x16 acc_o[2];
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc_o[c][e] = 0.f;
     float m_run = -1e30f, l_run = 0.f;
     constexpr float LOG2E = 1.4426950408889634f;
     const int nt = (N + BKV - 1) / BKV;
     char* const Ks = smem;
     char* const Vs = smem + 3 * TILE_BYTES;
-    stage_k(0, Ks);
-    stage_v(0, Vs);
-    if (nt > 1) stage_k(1, Ks + TILE_BYTES);
+    stage_k(w, 0, N, wave, lane, Ks);
+    stage_v(w, 0, N, wave, lane, Vs);
+    if (nt > 1) stage_k(w, 1, N, wave, lane, Ks + TILE_BYTES);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    f32x16 sc[2];
-    if (wave_active) qk(Ks, sc);
-    else {
-#pragma unroll
-        for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) sc[sub][e] = 0.f;
-    }
+    f32x16 sc[2] = {zero, zero};
+    if (w.wave_active) qk(Ks, sc);
     int kn = 1;                                             // K slot of tile kt + 1
     for (int kt = 0; kt < nt; ++kt) {
         if (kt > 0) {
@@ -387,26 +430,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))
             __syncthreads();                                      // ... for every wave; and everyone is done with tile kt-1's slots
         }
         const int k2 = kn == 2 ? 0 : kn + 1;                       // slot of K(kt+2) = the one K(kt-1) had
-        if (kt + 2 < nt) stage_k(kt + 2, Ks + k2 * TILE_BYTES);
-        if (kt + 1 < nt) stage_v(kt + 1, Vs + ((kt + 1) & 1) * TILE_BYTES);
+        if (kt + 2 < nt) stage_k(w, kt + 2, N, wave, lane, Ks + k2 * TILE_BYTES);
+        if (kt + 1 < nt) stage_v(w, kt + 1, N, wave, lane, Vs + ((kt + 1) & 1) * TILE_BYTES);
         const char* Kn = Ks + kn * TILE_BYTES;
         const char* Vt = Vs + (kt & 1) * TILE_BYTES;
         kn = k2;
-        if (!wave_active) continue;
-        if (__builtin_amdgcn_readfirstlane((int)(kt == nt - 1 && (N % BKV) != 0))) {
-            const int kbase = kt * BKV + 4 * h;
-#pragma unroll
-            for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                for (int e = 0; e < 16; ++e)
-                    if (kbase + sub * 32 + (e & 3) + 8 * (e >> 2) >= N) sc[sub][e] = -1e30f;
-        }
-        float mx = sc[0][0];
-#pragma unroll
-        for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) mx = fmaxf(mx, sc[sub][e]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        if (!w.wave_active) continue;
+        if (tail_tile(kt, nt, N)) mask_copy(sc, kt, h, N);
+        const float mx = tile_max(sc);
         const float m_new = fmaxf(m_run, mx);
         if (__builtin_amdgcn_readfirstlane((int)(__ballot(m_new > m_run) != 0ull))) {
             const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * LOG2E);
@@ -433,6 +464,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))
                 pf[sub * 2 + (e >> 3)][e & 7] = (h16)pv;
             }
         l_run += (ps[0] + ps[1]) + (ps[2] + ps[3]);
+        // O^T += V^T . P^T with v_frag_tr's address arithmetic restated, as in attn_cs_kernel: through pv_tile this kernel needs 161
+        // VGPRs, not 160 (profiles/r09)
 #pragma unroll
         for (int kstep = 0; kstep < 4; ++kstep) {
 #pragma unroll
@@ -444,9 +477,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))
                 for (int half = 0; half < 2; ++half) {
                     const int key = kstep * 16 + half * 8 + 4 * h + qq;
                     const char* ap = Vt + key * 128 + ((((col >> 3) ^ v_swz(key))) << 4) + ((col & 7) << 1);
-                    const fp16x4_t v4 = __builtin_amdgcn_ds_read_tr16_b64_v4f16((VDA_LDS_AS fp16x4_t*)ap);
+                    const h16x4 v4 = tr16(ap);
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) vf[half * 4 + e] = (h16)v4[e];
+                    for (int e = 0; e < 4; ++e) vf[half * 4 + e] = v4[e];
                 }
                 acc_o[c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[kstep], acc_o[c], 0, 0, 0);
             }
@@ -463,24 +496,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) sc[sub] = sn[sub];
     }
-    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    const float inv = 1.0f / l_tot;
-    if (q_row < N) {
-        h16* op = out + ((size_t)b * N + q_row) * ((size_t)H * HD) + head * HD + 4 * h;
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                h16x4 o = {(h16)(acc_o[c][4 * g + 0] * inv), (h16)(acc_o[c][4 * g + 1] * inv),
-                           (h16)(acc_o[c][4 * g + 2] * inv), (h16)(acc_o[c][4 * g + 3] * inv)};
-                *reinterpret_cast<h16x4*>(op + c * 32 + 8 * g) = o;
-            }
-    }
+    store_out(out, w, N, H, h, acc_o, l_run + __shfl_xor(l_run, 32, 64));
 }
 
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// Round 3 (variants 8 / 9, the default): the online softmax with the reference point in the MATRIX pipe and a lazy rescale.
+// Round 3 (variants 8 / 9): the online softmax with the reference point in the MATRIX pipe and a lazy rescale.
 //
 // attn_kernel spends ~185 VALU issues per 64-key tile and wave (32 exp, 31 fma for "score * log2e - max * log2e", 37 adds,
 // 16 max3, 16 cvt_pk, and - on 85 % of the tiles, because SOME query of the wave's 32 sees a new maximum - 32 multiplies of the
@@ -501,41 +522,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, h = lane >> 5;
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, qd = total_blocks >> 3, rm = total_blocks & 7;
-    const int t = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + (bid >> 3);
-    const int bh = t / nqb, qb = t - bh * nqb;
-    const int b = bh / H, head = bh - b * H;
-    const size_t rs = (size_t)3 * H * HD;
-    const unsigned rs32 = (unsigned)rs;
-    const h16* Qb = qkv + (size_t)b * N * rs + head * HD;
-    const h16* Kb = Qb + (size_t)H * HD;
-    const h16* Vb = Kb + (size_t)H * HD;
-
-    // Q fragments, pre-scaled by log2(e) / 8: the scores leave the MFMAs in the log2 domain
-    const int q_row = qb * BQ + wave * 32 + r;
-    const bool wave_active = __builtin_amdgcn_readfirstlane((int)(qb * BQ + wave * 32 < N)) != 0;
+    const Where w = locate(qkv, blockIdx.x, total_blocks, nqb, H, N, wave, r);
     h16x8 qf[4];
-    {
-        const h16* qp = Qb + (size_t)min(q_row, N - 1) * rs + h * 8;
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            qf[ks] = *reinterpret_cast<const h16x8*>(qp + ks * 16);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) qf[ks][e] = (h16)((float)qf[ks][e] * (0.125f * 1.4426950408889634f));
-        }
-    }
-    const int lrow = lane >> 3, lpos = lane & 7;
-    auto stage = [&](int kt, char* buf) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int piece = wave + 4 * j;
-            const int row = piece * 8 + lrow;
-            const unsigned key = (unsigned)min(kt * BKV + row, N - 1) * rs32;
-            glds16(Kb + (key + ((lpos ^ k_swz(row)) << 3)), buf + piece * 1024);
-            glds16(Vb + (key + ((lpos ^ v_swz(row)) << 3)), buf + TILE_BYTES + piece * 1024);
-        }
-    };
+    for (int ks = 0; ks < 4; ++ks) qf[ks] = q_frag<true>(w, N, h, ks);
 
     f32x16 acc_o[2], cneg;                      // cneg: -m in every register = the C operand of each score chain's first MFMA
 #pragma unroll
@@ -546,45 +536,25 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
     }
     float l_run = 0.f;
     const int nt = (N + BKV - 1) / BKV;
-    stage(0, smem);
+    stage_kv<true, true>(w, 0, N, wave, lane, smem, smem + TILE_BYTES);
     int cur = 0;
     for (int kt = 0; kt < nt; ++kt) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if (kt + 1 < nt) stage(kt + 1, smem + (cur ^ 1) * STAGE_BYTES);
+        char* const nxt = smem + (cur ^ 1) * STAGE_BYTES;
+        if (kt + 1 < nt) stage_kv<true, true>(w, kt + 1, N, wave, lane, nxt, nxt + TILE_BYTES);
         const char* Kt = smem + cur * STAGE_BYTES;
         const char* Vt = Kt + TILE_BYTES;
         cur ^= 1;
-        if (!wave_active) continue;             // (a wave whose 32 queries lie past N only stages and synchronises)
+        if (!w.wave_active) continue;           // (a wave whose 32 queries lie past N only stages and synchronises)
 
         // ---- S^T - m = K . Q^T + (-m): two 32-key halves, four 16-channel k-steps each
         f32x16 s[2];
 #pragma unroll
-        for (int sub = 0; sub < 2; ++sub) {
-            const int row = sub * 32 + r;
-            const char* kp = Kt + row * 128;
-            const int sw = k_swz(row);
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                const h16x8 kf = *reinterpret_cast<const h16x8*>(kp + (((2 * ks + h) ^ sw) << 4));
-                s[sub] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[ks], ks == 0 ? cneg : s[sub], 0, 0, 0);
-            }
-        }
-        if (__builtin_amdgcn_readfirstlane((int)(kt == nt - 1 && (N % BKV) != 0))) {      // scalar branch, last tile only
-            const int kbase = kt * BKV + 4 * h;
-#pragma unroll
-            for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                for (int e = 0; e < 16; ++e)
-                    if (kbase + sub * 32 + (e & 3) + 8 * (e >> 2) >= N) s[sub][e] = -1e30f;
-        }
-        // ---- the tile's maximum per query (lane pair {lane, lane ^ 32}), relative to the reference point
-        float mx = s[0][0];
-#pragma unroll
-        for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) mx = fmaxf(mx, s[sub][e]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        for (int sub = 0; sub < 2; ++sub) s[sub] = qk_chain(Kt, sub, r, h, qf, cneg);
+        if (tail_tile(kt, nt, N)) mask_copy(s, kt, h, N);
+        // ---- the tile's maximum per query, relative to the reference point
+        const float mx = tile_max(s);
         const bool move = kt == 0 || mx > (float)LAZY;             // first tile: the reference point becomes the tile's maximum
         if (__builtin_amdgcn_readfirstlane((int)(__ballot(move) != 0ull))) {
             const float delta = move ? mx : 0.f;                    // lanes that stay: alpha = exp2(-0) = 1 exactly, all no-ops
@@ -614,45 +584,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
             }
         l_run += (ps[0] + ps[1]) + (ps[2] + ps[3]);
 
-        // ---- O^T += V^T . P^T  (4 steps of 16 keys, 2 halves of 32 channels)
-#pragma unroll
-        for (int kstep = 0; kstep < 4; ++kstep) {
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                h16x8 vf;
-                const int i = lane & 15, qq = i >> 2, pp = i & 3;
-                const int col = c * 32 + 16 * ((lane >> 4) & 1) + 4 * pp;
-#pragma unroll
-                for (int half = 0; half < 2; ++half) {
-                    const int key = kstep * 16 + half * 8 + 4 * h + qq;
-                    const char* ap = Vt + key * 128 + ((((col >> 3) ^ v_swz(key))) << 4) + ((col & 7) << 1);
-                    const fp16x4_t v4 = __builtin_amdgcn_ds_read_tr16_b64_v4f16((VDA_LDS_AS fp16x4_t*)ap);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) vf[half * 4 + e] = (h16)v4[e];
-                }
-                acc_o[c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[kstep], acc_o[c], 0, 0, 0);
-            }
-        }
+        pv_tile(Vt, lane, h, pf, acc_o);
     }
-
-    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    const float inv = 1.0f / l_tot;
-    if (q_row < N) {
-        h16* op = out + ((size_t)b * N + q_row) * ((size_t)H * HD) + head * HD + 4 * h;
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                h16x4 o = {(h16)(acc_o[c][4 * g + 0] * inv), (h16)(acc_o[c][4 * g + 1] * inv),
-                           (h16)(acc_o[c][4 * g + 2] * inv), (h16)(acc_o[c][4 * g + 3] * inv)};
-                *reinterpret_cast<h16x4*>(op + c * 32 + 8 * g) = o;
-            }
-    }
+    store_out(out, w, N, H, h, acc_o, l_run + __shfl_xor(l_run, 32, 64));
 }
 
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// Variant 10: attn_cm_kernel with two more groups of VALU instructions taken out of the tile loop (PMC on variant 9: VALU issue
+// Variants 10 (attn_cs_kernel<false>, THE KERNEL THAT SHIPS) and 11: the reference point in the C operand as in attn_cm_kernel, with
+// two more groups of VALU instructions taken out of the tile loop (PMC on variant 9: VALU issue
 // 82 % of SIMD time, MFMA busy 44 %, 10.8 VALU per MFMA - the loop is bound by VALU ISSUE, not by dependency stalls):
 //   * K / V staging by bounds-checked `buffer_load ... lds` with per-lane constant offsets and ONE scalar per tile (the tile's
 //     row offset in soffset) instead of four 64-bit global addresses per lane and tile (~25 VALU); rows past N are out of the
@@ -691,34 +631,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, h = lane >> 5;
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, qd = total_blocks >> 3, rm = total_blocks & 7;
-    const int t = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + (bid >> 3);
-    const int bh = t / nqb, qb = t - bh * nqb;
-    const int b = bh / H, head = bh - b * H;
-    const size_t rs = (size_t)3 * H * HD;
-    const unsigned rs32 = (unsigned)rs;
-    const h16* Qb = qkv + (size_t)b * N * rs + head * HD;
-    const h16* Kb = Qb + (size_t)H * HD;
-    const h16* Vb = Kb + (size_t)H * HD;
-
-    const int q_row = qb * BQ + wave * 32 + r;
-    const bool wave_active = __builtin_amdgcn_readfirstlane((int)(qb * BQ + wave * 32 < N)) != 0;
+    const Where w = locate(qkv, blockIdx.x, total_blocks, nqb, H, N, wave, r);
     h16x8 qf[4];
-    {
-        const h16* qp = Qb + (size_t)min(q_row, N - 1) * rs + h * 8;
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            qf[ks] = *reinterpret_cast<const h16x8*>(qp + ks * 16);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) qf[ks][e] = (h16)((float)qf[ks][e] * (0.125f * 1.4426950408889634f));
-        }
-    }
+    for (int ks = 0; ks < 4; ++ks) qf[ks] = q_frag<true>(w, N, h, ks);
     // staging: descriptor = the frame's K (V) rows of this head, N rows of 64 halves at stride rs; per-lane byte offsets of the
     // wave's two pieces (rows piece * 8 + lrow, swizzled 16-byte chunk), constant for the whole kernel
+    const unsigned rs32 = w.rs32;
     const unsigned frame_bytes = ((unsigned)(N - 1) * rs32 + HD) * 2u;            // first byte past row N - 1's 64 halves
-    const auto k_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<h16*>(Kb), 0, frame_bytes, 0x00020000);
-    const auto v_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<h16*>(Vb), 0, frame_bytes, 0x00020000);
+    const auto k_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<h16*>(w.Kb), 0, frame_bytes, 0x00020000);
+    const auto v_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<h16*>(w.Vb), 0, frame_bytes, 0x00020000);
     const int lrow = lane >> 3, lpos = lane & 7;
     unsigned koff[2], voff[2];
 #pragma unroll
@@ -768,33 +690,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
         const char* Vt = Kt + TILE_BYTES;
         const int done_idx = 2 + cur;
         cur ^= 1;
-        if (!wave_active) {
+        if (!w.wave_active) {
             count_in(done_idx);                                          // (reads nothing)
             continue;
         }
 
-        const bool last_partial = __builtin_amdgcn_readfirstlane((int)(kt == nt - 1 && (N % BKV) != 0)) != 0;
+        const bool last_partial = tail_tile(kt, nt, N);
         // scores relative to the reference point: S^T - m = K . Q^T + (-m); keys past N masked
         auto scores = [&](f32x16 (&s)[2]) {
 #pragma unroll
-            for (int sub = 0; sub < 2; ++sub) {
-                const int row = sub * 32 + r;
-                const char* kp = Kt + row * 128;
-                const int sw = k_swz(row);
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    const h16x8 kf = *reinterpret_cast<const h16x8*>(kp + (((2 * ks + h) ^ sw) << 4));
-                    s[sub] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[ks], ks == 0 ? cneg : s[sub], 0, 0, 0);
-                }
-            }
-            if (last_partial) {
-                const int kbase = kt * BKV + 4 * h;
-#pragma unroll
-                for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e)
-                        if (kbase + sub * 32 + (e & 3) + 8 * (e >> 2) >= N) s[sub][e] = -1e30f;
-            }
+            for (int sub = 0; sub < 2; ++sub) s[sub] = qk_chain(Kt, sub, r, h, qf, cneg);
+            if (last_partial) mask_tail(s, kt, h, N);
         };
         // p = exp2(s), fp16 fragments of P^T, the lane's sum over its 32 keys
         h16x8 pf[4];
@@ -823,12 +729,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
             // slow path: scores again (the K tile is still in LDS), their maximum moves the reference point of the lanes that asked
             f32x16 s[2];
             scores(s);
-            float mx = s[0][0];
-#pragma unroll
-            for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) mx = fmaxf(mx, s[sub][e]);
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+            const float mx = tile_max(s);
             const float delta = trig ? mx : 0.f;                          // lanes that stay: exp2(-0) = 1 exactly, all no-ops
             const float alpha = __builtin_amdgcn_exp2f(-delta);
             l_run *= alpha;
@@ -846,7 +747,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
         }
         l_run += tsum;
 
-        // ---- O^T += V^T . P^T  (4 steps of 16 keys, 2 halves of 32 channels)
+        // ---- O^T += V^T . P^T, v_frag_tr's address arithmetic restated: the compiler simplifies a helper before it inlines it, and
+        // through v_frag_tr this (the shipped) kernel's ISA changes (profiles/r09); through tr16 alone it does not
 #pragma unroll
         for (int kstep = 0; kstep < 4; ++kstep) {
 #pragma unroll
@@ -858,9 +760,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
                 for (int half = 0; half < 2; ++half) {
                     const int key = kstep * 16 + half * 8 + 4 * h + qq;
                     const char* ap = Vt + key * 128 + ((((col >> 3) ^ v_swz(key))) << 4) + ((col & 7) << 1);
-                    const fp16x4_t v4 = __builtin_amdgcn_ds_read_tr16_b64_v4f16((VDA_LDS_AS fp16x4_t*)ap);
+                    const h16x4 v4 = tr16(ap);
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) vf[half * 4 + e] = (h16)v4[e];
+                    for (int e = 0; e < 4; ++e) vf[half * 4 + e] = v4[e];
                 }
                 acc_o[c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[kstep], acc_o[c], 0, 0, 0);
             }
@@ -870,33 +772,53 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
             count_in(done_idx);
         }
     }
-
-    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    const float inv = 1.0f / l_tot;
-    if (q_row < N) {
-        h16* op = out + ((size_t)b * N + q_row) * ((size_t)H * HD) + head * HD + 4 * h;
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                h16x4 o = {(h16)(acc_o[c][4 * g + 0] * inv), (h16)(acc_o[c][4 * g + 1] * inv),
-                           (h16)(acc_o[c][4 * g + 2] * inv), (h16)(acc_o[c][4 * g + 3] * inv)};
-                *reinterpret_cast<h16x4*>(op + c * 32 + 8 * g) = o;
-            }
-    }
+    store_out(out, w, N, H, h, acc_o, l_run + __shfl_xor(l_run, 32, 64));
 }
+
+// ---- dispatch
+template <auto KERNEL>
+void launch(const h16* qkv, h16* out, int N, int H, int nqb, int total, hipStream_t s) {
+    hipLaunchKernelGGL(KERNEL, dim3((unsigned)total), dim3(256), 0, s, qkv, out, N, H, nqb, total);
+}
+
+// Every code of vda_attention_set_variant (include/vda.h says what each one is for).
+constexpr int VDA_ATTN_DEFAULT = 10;
+using launch_fn = void (*)(const h16*, h16*, int, int, int, int, hipStream_t);
+constexpr struct {
+    int code;
+    launch_fn launch;
+} VARIANTS[] = {
+    {0, launch<attn_kernel<false, true>>},
+    {1, launch<attn_kernel<true, false>>},
+    {2, launch<attn_kernel<true, true>>},
+    {3, launch<attn_kernel<true, false, true>>},
+    {4, launch<attn_kernel<true, false, false, true>>},
+    {5, launch<attn_kernel<true, false, true, true>>},
+    {7, launch<attn_pipe_kernel>},
+    {8, launch<attn_cm_kernel<0>>},
+    {9, launch<attn_cm_kernel<6>>},
+    {10, launch<attn_cs_kernel<false>>},
+    {11, launch<attn_cs_kernel<true>>},
+    {21, launch<attn_kernel<true, false, false, false, 1>>},
+    {22, launch<attn_kernel<true, false, false, false, 2>>},
+    {23, launch<attn_kernel<true, false, false, false, 3>>},
+    {24, launch<attn_kernel<true, false, false, false, 4>>},
+    {25, launch<attn_kernel<true, false, false, false, 5>>},
+};
+
+launch_fn find_launcher(int code) {       // nullptr: no such code
+    for (const auto& v : VARIANTS)
+        if (v.code == code) return v.launch;
+    return nullptr;
+}
+
+int g_attn_variant = VDA_ATTN_DEFAULT;
 
 }  // namespace
 
-// -1 (default): the kernel picked below. 10: attn_cs_kernel (as 9, staging by scalar-offset buffer loads, no maximum in the hot path);
-// 8 / 9: attn_cm_kernel (reference point through the MFMA C operand; 9 = lazy rescale, 2^6);
-// 1: attn_kernel with ds_read_b64_tr_b16 V fragments + scalar softmax math; 2: the same with v_pk_*_f32 softmax math; 0: scalar LDS
-// reads of V (debug cross-check); 3 / 4 / 5 / 7: the round-2 experiments (row sums / running max through the matrix pipe, the
-// software-pipelined form); 11..15: timing ablations of attn_kernel (wrong results).
-constexpr int VDA_ATTN_DEFAULT = 10;
-static int g_attn_variant = -1;
-
 extern "C" int vda_attention_set_variant(int v) {
+    if (v == -1) v = VDA_ATTN_DEFAULT;
+    VDA_REQUIRE(find_launcher(v), "vda_attention_set_variant: unknown variant %d", v);
     g_attn_variant = v;
     return 0;
 }
@@ -909,36 +831,7 @@ extern "C" int vda_attention_f16(const void* qkv, void* out, int B, int N, int h
     const long long total = (long long)nqb * B * heads;
     VDA_REQUIRE(total < (1ll << 31), "vda_attention_f16: grid too large");
     VDA_REQUIRE((long long)N * 3 * heads * HD < (1ll << 31), "vda_attention_f16: one frame's qkv exceeds 32-bit element offsets");
-    hipStream_t s = (hipStream_t)stream;
-    const int g_attn_variant = ::g_attn_variant < 0 ? VDA_ATTN_DEFAULT : ::g_attn_variant;      // (shadows the global inside this call)
-#define VDA_ATTN_ABL(K)                                                                                                                        \
-    if (g_attn_variant == 20 + K)                                                                                                              \
-        hipLaunchKernelGGL((attn_kernel<true, false, false, false, K>), dim3((unsigned)total), dim3(256), 0, s, (const h16*)qkv, (h16*)out, N, heads, nqb, (int)total); \
-    else
-    VDA_ATTN_ABL(1) VDA_ATTN_ABL(2) VDA_ATTN_ABL(3) VDA_ATTN_ABL(4) VDA_ATTN_ABL(5)
-#undef VDA_ATTN_ABL
-    if (g_attn_variant == 11)
-        hipLaunchKernelGGL((attn_cs_kernel<true>), dim3((unsigned)total), dim3(256), 0, s, (const h16*)qkv, (h16*)out, N, heads, nqb, (int)total);
-    else if (g_attn_variant == 10)
-        hipLaunchKernelGGL((attn_cs_kernel<false>), dim3((unsigned)total), dim3(256), 0, s, (const h16*)qkv, (h16*)out, N, heads, nqb, (int)total);
-    else if (g_attn_variant == 8)
-        hipLaunchKernelGGL((attn_cm_kernel<0>), dim3((unsigned)total), dim3(256), 0, s, (const h16*)qkv, (h16*)out, N, heads, nqb, (int)total);
-    else if (g_attn_variant == 9)
-        hipLaunchKernelGGL((attn_cm_kernel<6>), dim3((unsigned)total), dim3(256), 0, s, (const h16*)qkv, (h16*)out, N, heads, nqb, (int)total);
-    else if (g_attn_variant == 7)
-        hipLaunchKernelGGL(attn_pipe_kernel, dim3((unsigned)total), dim3(256), 0, s, (const h16*)qkv, (h16*)out, N, heads, nqb, (int)total);
-    else if (g_attn_variant == 4)
-        hipLaunchKernelGGL((attn_kernel<true, false, false, true>), dim3((unsigned)total), dim3(256), 0, s, (const h16*)qkv, (h16*)out, N, heads, nqb, (int)total);
-    else if (g_attn_variant == 5)
-        hipLaunchKernelGGL((attn_kernel<true, false, true, true>), dim3((unsigned)total), dim3(256), 0, s, (const h16*)qkv, (h16*)out, N, heads, nqb, (int)total);
-    else if (g_attn_variant == 3)
-        hipLaunchKernelGGL((attn_kernel<true, false, true>), dim3((unsigned)total), dim3(256), 0, s, (const h16*)qkv, (h16*)out, N, heads, nqb, (int)total);
-    else if (g_attn_variant == 1)
-        hipLaunchKernelGGL((attn_kernel<true, false>), dim3((unsigned)total), dim3(256), 0, s, (const h16*)qkv, (h16*)out, N, heads, nqb, (int)total);
-    else if (g_attn_variant)
-        hipLaunchKernelGGL((attn_kernel<true, true>), dim3((unsigned)total), dim3(256), 0, s, (const h16*)qkv, (h16*)out, N, heads, nqb, (int)total);
-    else
-        hipLaunchKernelGGL((attn_kernel<false, true>), dim3((unsigned)total), dim3(256), 0, s, (const h16*)qkv, (h16*)out, N, heads, nqb, (int)total);
+    find_launcher(g_attn_variant)(static_cast<const h16*>(qkv), static_cast<h16*>(out), N, heads, nqb, (int)total, (hipStream_t)stream);
     VDA_LAUNCH_CHECK();
     return 0;
 }
