@@ -1,8 +1,9 @@
 #!/usr/bin/env python
 """Scene-batch driver with the reference's interface (/root/reference/benchmark/infer/infer.py:12-64) over the MI355X
 engine: for every scene of every dataset in the JSON manifest, stack the scene's images, run
-`infer_video_depth(..., fp32=True)` and write one .npy of float32 depth per frame next to `--infer_path`, so the
-reference's own `benchmark/eval` scripts can score the output.
+`infer_video_depth(..., fp32=True)` and write one .npy of float32 depth per frame next to `--infer_path`, where
+`benchmark/eval/eval.py` of this repository scores it against ground truth on the device (the reference's own scorer needs cv2
+and does not run as written).
 
 Differences that cannot be avoided offline: images are decoded with cv2 when importable, else PIL; either way the
 array handed to the model is BGR like `cv2.imread`'s (the reference feeds BGR straight in, infer.py:54), `.npy` frames are

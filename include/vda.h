@@ -362,6 +362,33 @@ int vda_affine_clamp_f32(const float* in, const float* scale_shift, float* out, 
  * and no workspace; x needs 4-byte alignment only. A NaN in x is never taken. Calls that share `minmax` must be stream-ordered. */
 int vda_minmax_accum_f32(const float* x, long long n, float* minmax, vda_stream_t stream);
 
+/* ---- benchmark scorer on the device (the reference's benchmark/eval/eval.py:67-122 and metric.py) -------------------------
+ * Scores a depth video against ground truth in two streaming passes with one finisher each; all four calls queue on `stream`
+ * and nothing returns to the host in between. Deterministic: fp64 partial rows, a fixed combination order, no atomics. The result
+ * depends on the block counts and on how the video is cut into calls, never on timing.
+ *   pred : fp32 model output, gt : fp32 (gt_is_f64 = 0) or fp64 (gt_is_f64 = 1) ground truth of the same shape, both dense.
+ *   valid = (gt > 1e-3) & (gt < max_depth) in gt's own type; x = max(pred, 1e-3f).
+ * A video that does not fit the device at once is fed in chunks of frames: pass 1 over every chunk (row_offset = rows written so
+ * far), vda_eval_lsq_finish once, pass 2 over every chunk (frame_offset = frames scored so far), vda_eval_metric_finish once.
+ *
+ * Pass 1: nblk rows of 5 doubles {count, sum x, sum x^2, sum y, sum x*y}, y = 1 / (gt + 1e-8), over the valid pixels among n,
+ * written to partial[(row_offset + b) * 5 ...]. nblk <= 4096. */
+int vda_eval_lsq_partial(const float* pred, const void* gt, int gt_is_f64, long long n, double max_depth, double* partial, int row_offset,
+                         int nblk, vda_stream_t stream);
+/* Sums the nrows rows in index order and solves the 2x2 normal equations of  min || scale * x + shift - y ||^2  in fp64:
+ * fit[0..2] = {scale, shift, n_valid} as DOUBLES on the device; scale = shift = NaN when n_valid < 2 or the determinant is 0. */
+int vda_eval_lsq_finish(const double* partial, int nrows, double* fit, vda_stream_t stream);
+/* Pass 2 over nframes frames of px pixels: p = clip(1 / max(scale * x + shift, 1e-3), 1e-3, max_depth) in fp64 (the product and
+ * the sum round separately), and per frame and block 7 doubles {n, sum |p-g|/g, sum (p-g)^2/g, sum (p-g)^2, #r<1.25, #r<1.25^2,
+ * #r<1.25^3}, r = max(p/g, g/p), at partial[((frame_offset + f) * blocks_per_frame + b) * 7 ...]. blocks_per_frame <= 4096 and
+ * must be the same in every call of one video. */
+int vda_eval_metric_partial(const float* pred, const void* gt, int gt_is_f64, int nframes, long long px, double max_depth, const double* fit,
+                            double* partial, int frame_offset, int blocks_per_frame, vda_stream_t stream);
+/* result[0..6] = {abs_relative_difference, squared_relative_difference, rmse_linear, delta1_acc, delta2_acc, delta3_acc, frames
+ * used} as doubles on the device: per frame  sum / n  (rmse: sqrt of it; the deltas: float32 count / float32 n as metric.py has
+ * them), then the mean over the frames that have a valid pixel. No such frame: the six metrics are NaN, frames used = 0. */
+int vda_eval_metric_finish(const double* partial, int nframes, int blocks_per_frame, double* result, vda_stream_t stream);
+
 /* ================================================================ handle API: the model behind one pointer
  * What a C / C++ host binds in place of the reference's Python class (the seam of SURVEY.md section 8b):
  *   VideoDepthAnything(**model_configs[enc])          run.py:45, video_depth.py:38-63      vda_create

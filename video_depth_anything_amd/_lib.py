@@ -109,6 +109,10 @@ SIGNATURES = {
     "vda_stitch_window_f32": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_longlong, _vp, _vp]),
     "vda_affine_clamp_f32": (_i, [_vp, _vp, _vp, C.c_longlong, _vp]),
     "vda_minmax_accum_f32": (_i, [_vp, C.c_longlong, _vp, _vp]),
+    "vda_eval_lsq_partial": (_i, [_vp, _vp, _i, _ll, C.c_double, _vp, _i, _i, _vp]),
+    "vda_eval_lsq_finish": (_i, [_vp, _i, _vp, _vp]),
+    "vda_eval_metric_partial": (_i, [_vp, _vp, _i, _i, _ll, C.c_double, _vp, _vp, _i, _i, _vp]),
+    "vda_eval_metric_finish": (_i, [_vp, _i, _i, _vp, _vp]),
     # handle API
     "vda_create": (_i, [C.POINTER(Config), C.POINTER(_vp)]),
     "vda_destroy": (_i, [_vp]),

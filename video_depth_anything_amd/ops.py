@@ -345,6 +345,56 @@ def minmax_accum(x, minmax, n=None):
     check(lib.vda_minmax_accum_f32(_p(x), n, _p(minmax), _stream(x)), "vda_minmax_accum_f32")
 
 
+# ---- benchmark scorer (csrc/eval.hip; evaluate.py lays the partial rows out) ------------------------------------------------
+def _eval_pair(pred, gt, what):
+    _req(pred, F32, "pred")
+    if gt.dtype not in (F32, torch.float64):
+        raise ValueError(f"{what}: gt must be float32 or float64, got {gt.dtype}")
+    _req(gt, gt.dtype, "gt")
+    if pred.shape != gt.shape or pred.device != gt.device or pred.numel() == 0:
+        raise ValueError(f"{what}: pred {tuple(pred.shape)} on {pred.device} and gt {tuple(gt.shape)} on {gt.device} do not match")
+    return int(gt.dtype == torch.float64)
+
+
+def eval_lsq_partial(pred, gt, max_depth, workspace, row_offset, nblk):
+    """Pass 1 of the scorer over all elements of pred / gt: nblk rows of 5 doubles at workspace[5 * row_offset ...]."""
+    f64 = _eval_pair(pred, gt, "eval_lsq_partial")
+    _req(workspace, torch.float64, "workspace")
+    if row_offset < 0 or nblk <= 0 or workspace.numel() < 5 * (row_offset + nblk):
+        raise ValueError("eval_lsq_partial: workspace too small")
+    check(lib.vda_eval_lsq_partial(_p(pred), _p(gt), f64, pred.numel(), float(max_depth), _p(workspace), row_offset, nblk, _stream(pred)),
+          "vda_eval_lsq_partial")
+
+
+def eval_lsq_finish(workspace, nrows, fit):
+    """fit[0..2] (device fp64) = {scale, shift, n_valid} from the first nrows rows of pass 1."""
+    _req(workspace, torch.float64, "workspace"), _req(fit, torch.float64, "fit")
+    if nrows <= 0 or workspace.numel() < 5 * nrows or fit.numel() < 3:
+        raise ValueError("eval_lsq_finish: bad sizes")
+    check(lib.vda_eval_lsq_finish(_p(workspace), nrows, _p(fit), _stream(workspace)), "vda_eval_lsq_finish")
+
+
+def eval_metric_partial(pred, gt, max_depth, fit, workspace, frame_offset, blocks_per_frame):
+    """Pass 2 of the scorer over pred / gt [n,H,W]: 7 doubles per (frame, block) at workspace[7 * frame_offset * blocks_per_frame ...]."""
+    f64 = _eval_pair(pred, gt, "eval_metric_partial")
+    _req(workspace, torch.float64, "workspace"), _req(fit, torch.float64, "fit")
+    if pred.dim() != 3:
+        raise ValueError("eval_metric_partial: pred must be [n,H,W]")
+    n, px = pred.shape[0], pred.shape[1] * pred.shape[2]
+    if frame_offset < 0 or blocks_per_frame <= 0 or workspace.numel() < 7 * (frame_offset + n) * blocks_per_frame or fit.numel() < 3:
+        raise ValueError("eval_metric_partial: workspace too small")
+    check(lib.vda_eval_metric_partial(_p(pred), _p(gt), f64, n, px, float(max_depth), _p(fit), _p(workspace), frame_offset, blocks_per_frame,
+                                      _stream(pred)), "vda_eval_metric_partial")
+
+
+def eval_metric_finish(workspace, nframes, blocks_per_frame, result):
+    """result[0..6] (device fp64) = {abs_rel, sq_rel, rmse, delta1, delta2, delta3, frames used} from pass 2's rows."""
+    _req(workspace, torch.float64, "workspace"), _req(result, torch.float64, "result")
+    if nframes <= 0 or blocks_per_frame <= 0 or workspace.numel() < 7 * nframes * blocks_per_frame or result.numel() < 7:
+        raise ValueError("eval_metric_finish: bad sizes")
+    check(lib.vda_eval_metric_finish(_p(workspace), nframes, blocks_per_frame, _p(result), _stream(workspace)), "vda_eval_metric_finish")
+
+
 # ---------------------------------------------------------------------------
 # Weight layouts the kernels expect (done once at load time, on the host or device)
 # ---------------------------------------------------------------------------
