@@ -149,7 +149,7 @@ def test_conv3x3_f32(ops, stride, relu_in, Cin, Cout, H, W_):
 
 
 # ---------------------------------------------------------------- norms
-@pytest.mark.parametrize("D,rows", [(384, 50), (1024, 37), (128, 9), (64, 130)])
+@pytest.mark.parametrize("D,rows", [(384, 50), (1024, 37), (128, 9), (64, 130), (192, 21), (256, 10), (2048, 5), (72, 11), (1032, 3)])
 def test_layernorm_f32(ops, D, rows):
     x, w, b = rnd(rows, D, seed=32, scale=3.0) + 0.5, rnd(D, seed=33) + 1.0, rnd(D, seed=34)
     out = torch.empty(rows, D, dtype=F32, device="cuda")

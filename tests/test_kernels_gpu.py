@@ -231,7 +231,7 @@ def split_planes(x):
     return hi, (x - hi.float()).to(F16)
 
 
-@pytest.mark.parametrize("D,rows", [(1024, 37), (384, 50), (128, 9), (64, 130)])
+@pytest.mark.parametrize("D,rows", [(1024, 37), (384, 50), (128, 9), (64, 130), (192, 20), (256, 30), (2048, 10), (72, 10)])
 def test_split_stats_and_layernorm_split(ops, D, rows):
     """fp32 rows -> (hi, lo) planes + (mean, rstd); LayerNorm of the split stream (with the cls-drop compaction)."""
     x = rnd(rows, D, seed=140, scale=3.0) + 0.7
@@ -253,6 +253,13 @@ def test_split_stats_and_layernorm_split(ops, D, rows):
         out = torch.empty(rows - rows // G, D, dtype=F16, device="cuda")
         ops.layernorm_split(hi, lo, out, dev(w), dev(b), 1e-6, rows, D, group=G, skip=1)
         close(out, F.layer_norm(x, (D,), w, b, 1e-6).reshape(-1, G, D)[:, 1:].reshape(-1, D), what="layernorm of hi + lo, cls dropped")
+
+    # the centred entry (the model's): hi + lo = x - mean(x), stat = (0, rstd)
+    ops.split_stats(dev(x), hi, lo, stat, 1e-6, rows, D, center=True)
+    xc = (x.double() - mean[:, None]).float()
+    assert float(((hi.float() + lo.float()).cpu() - xc).abs().max()) <= 2.0 ** -21 * float(x.abs().max())      # 22 significant bits
+    assert torch.equal(stat[:, 0].cpu(), torch.zeros(rows))
+    close(stat[:, 1], (var + 1e-6).rsqrt(), rtol=1e-5, atol=0, what="rstd of the centred entry")
 
 
 @pytest.mark.parametrize("M,N,K", [(777, 384, 384), (4100, 1024, 256), (2500, 384, 1536), (300, 64, 128)])
@@ -531,7 +538,7 @@ def test_gemm_dynamic_tile_schedule_is_result_neutral(ops):
 
 
 # ---------------------------------------------------------------- norms
-@pytest.mark.parametrize("D,rows", [(384, 50), (1024, 37), (128, 9), (64, 130)])
+@pytest.mark.parametrize("D,rows", [(384, 50), (1024, 37), (128, 9), (64, 130), (192, 21), (256, 10), (2048, 5), (72, 11), (1032, 3)])
 def test_layernorm(ops, D, rows):
     x, w, b = rnd(rows, D, seed=32, scale=3.0) + 0.5, rnd(D, seed=33) + 1.0, rnd(D, seed=34)
     out = torch.empty(rows, D, dtype=F16, device="cuda")
@@ -555,7 +562,7 @@ def test_layernorm_drop_cls_and_pe(ops):
     close(out, ref.reshape(-1, D), what="layernorm + pe")
 
 
-@pytest.mark.parametrize("D,G,nb,gamma", [(1024, 13, 5, True), (384, 7, 9, True), (128, 5, 4, False)])
+@pytest.mark.parametrize("D,G,nb,gamma", [(1024, 13, 5, True), (384, 7, 9, True), (128, 5, 4, False), (256, 5, 3, True)])
 def test_layernorm_residual(ops, D, G, nb, gamma):
     """x += gamma * y in place, then LayerNorm(x) (optionally dropping the cls row of every group): both results checked."""
     rows = nb * G

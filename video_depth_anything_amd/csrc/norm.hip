@@ -1,8 +1,11 @@
-// LayerNorm (fp32 rows -> fp16) and per-frame GroupNorm (NHWC fp16 -> token-major fp16) for gfx950.
-// Both are HBM-bound streaming kernels: 16-byte accesses, statistics in fp32, one pass over the
-// data for LayerNorm (row kept in registers), two launches with a fixed-order (deterministic)
-// partial-sum tree for GroupNorm.
+// Row normalisation for gfx950: LayerNorm of fp32 rows (fp16 or fp32 out, optionally with the residual add in front), the split
+// residual stream's entry and tap LayerNorm (fp32 rows <-> two fp16 planes + row statistics), the pieces of LayerNorm folded into
+// the neighbouring GEMMs, and per-frame GroupNorm (NHWC -> token-major). All are HBM-bound streaming kernels: 16-byte accesses,
+// statistics in fp32, one pass over the data for LayerNorm (row kept in registers), two launches with a fixed-order
+// (deterministic) partial-sum tree for GroupNorm.
 #include "vda_common.h"
+#include <initializer_list>
+#include <type_traits>
 
 namespace {
 
@@ -38,6 +41,83 @@ __device__ __forceinline__ float segment_sum(float v, int lane) {
     return v;
 }
 
+// Where a lane stands: lane `sub` of the LPR that share row `row`; a wave holds 64 / LPR rows, a workgroup four waves.
+struct RowLanes {
+    int sub, row;
+    bool row_ok;
+};
+template <int LPR>
+__device__ __forceinline__ RowLanes row_lanes(int lane, int rows) {
+    const int row = (blockIdx.x * 4 + (threadIdx.x >> 6)) * (64 / LPR) + lane / LPR;
+    return {lane % LPR, row, row < rows};
+}
+
+// 8 consecutive elements of a row. The per-chunk steps take it BY VALUE: a step that takes the register image by reference
+// is optimised before it is inlined, with the image in memory, and comes out scheduled with more live registers
+// (profiles/r10: the D > 1024 kernels lost occupancy that way).
+struct Chunk {
+    float e[8];
+};
+__device__ __forceinline__ float chunk_sum(Chunk x) {                    // pairwise
+    return ((x.e[0] + x.e[1]) + (x.e[2] + x.e[3])) + ((x.e[4] + x.e[5]) + (x.e[6] + x.e[7]));
+}
+__device__ __forceinline__ float chunk_sq(float sq, Chunk x, float mean, bool ok) {    // sq + centred squares, element order
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float d = ok ? x.e[e] - mean : 0.f;
+        sq += d * d;
+    }
+    return sq;
+}
+
+// The row's register image and its (mean, rstd). v[c] is chunk sub + c * LPR, zeros where the row has no such chunk (they
+// add nothing to the sums); load(ch) fetches chunk ch - the one step in which the kernels differ on the way in. Two-pass fp32
+// statistics: chunk sums in chunk order, then the centred squares in (chunk, element) order, each across the row's lanes by
+// segment_sum. Every kernel of this file that normalises a row takes its statistics here, so paths through different kernels
+// agree to the bit (tests/test_forward_gpu.py relies on it).
+template <int LPR, int NCH, typename LOAD>
+__device__ __forceinline__ float2 load_row_stats(Chunk (&v)[NCH], const RowLanes p, int nchunk, int D, float eps, int lane, LOAD load) {
+    float sum = 0.f;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+        const int ch = p.sub + c * LPR;
+        v[c] = Chunk{};
+        if (p.row_ok && ch < nchunk) v[c] = load(ch);
+        sum += chunk_sum(v[c]);
+    }
+    const float mean = segment_sum<LPR>(sum, lane) / (float)D;
+    float sq = 0.f;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) sq = chunk_sq(sq, v[c], mean, p.sub + c * LPR < nchunk);
+    return float2{mean, rsqrtf(segment_sum<LPR>(sq, lane) / (float)D + eps)};
+}
+
+// Output row of input row `row` when the first `skip` rows of every `group` are dropped (the cls token); -1 for a dropped row.
+__device__ __forceinline__ int out_row(int row, int group, int skip) {
+    if (group <= 0) return row;
+    const int g = row / group, i = row - g * group;
+    return i < skip ? -1 : g * (group - skip) + (i - skip);
+}
+
+// dst[0..8) = (x - mean) * rstd * w + b, then + per (NULL = nothing) - in that order.
+template <typename OT>
+__device__ __forceinline__ void affine_store(Chunk x, float mean, float rstd, const float* __restrict__ w, const float* __restrict__ b,
+                                             const float* __restrict__ per, OT* __restrict__ dst) {
+    float o[8];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const f32x4 ww = *reinterpret_cast<const f32x4*>(w + h * 4);
+        const f32x4 bb = *reinterpret_cast<const f32x4*>(b + h * 4);
+        f32x4 y = {x.e[h * 4], x.e[h * 4 + 1], x.e[h * 4 + 2], x.e[h * 4 + 3]};
+        y = (y - mean) * rstd * ww + bb;
+        if (per) y += *reinterpret_cast<const f32x4*>(per + h * 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[h * 4 + e] = y[e];
+    }
+    store8(dst, o);
+}
+
+// fp32 rows -> LayerNorm -> OT (h16 or float), optionally dropping the cls rows (group / skip) and adding pe after the affine.
 // RES: the row is first updated in place, in[r,:] += gamma * y[r,:] (y fp16: the bias-added output of the preceding projection,
 // gamma = LayerScale or NULL = 1) - the encoder's residual add (block.py:105-106) rides on the LayerNorm that follows it, so the
 // projection GEMM stores 2 bytes per element instead of reading and writing the fp32 stream in its (fabric-bound) epilogue.
@@ -47,76 +127,35 @@ __global__ void __launch_bounds__(256) layernorm_kernel(float* __restrict__ in, 
                                                         float eps, int rows, int D, int group, int skip,
                                                         const float* __restrict__ pe, int pe_rows_per_step, int pe_steps,
                                                         const h16* __restrict__ y, const float* __restrict__ gamma) {
-    constexpr int RPW = 64 / LPR;                                  // rows per wave
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int sub = lane % LPR, rsel = lane / LPR;
-    const int row = (blockIdx.x * 4 + wave) * RPW + rsel;
-    const bool row_ok = row < rows;
-    const int nchunk = D >> 3;                                     // 8-element chunks per row
-    float* src = in + (size_t)(row_ok ? row : 0) * D;
-    f32x4 v[NCH][2];
-    float sum = 0.f;
+    const int lane = threadIdx.x & 63, nchunk = D >> 3;             // 8-element chunks per row
+    const RowLanes p = row_lanes<LPR>(lane, rows);
+    float* src = in + (size_t)(p.row_ok ? p.row : 0) * D;
+    Chunk v[NCH];
+    const float2 st = load_row_stats<LPR>(v, p, nchunk, D, eps, lane, [=](int ch) {
+        Chunk x;
+        load8(src + ch * 8, x.e);
+        if constexpr (RES) {
+            const h16x8 yy = *reinterpret_cast<const h16x8*>(y + (size_t)p.row * D + ch * 8);
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        const int ch = sub + c * LPR;
-        const bool ok = row_ok && ch < nchunk;
-        v[c][0] = v[c][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (ok) {
-            v[c][0] = *reinterpret_cast<const f32x4*>(src + ch * 8);
-            v[c][1] = *reinterpret_cast<const f32x4*>(src + ch * 8 + 4);
-            if constexpr (RES) {
-                const h16x8 yy = *reinterpret_cast<const h16x8*>(y + (size_t)row * D + ch * 8);
+            for (int h = 0; h < 2; ++h) {
+                f32x4 g = {1.f, 1.f, 1.f, 1.f};
+                if (gamma) g = *reinterpret_cast<const f32x4*>(gamma + ch * 8 + h * 4);
 #pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    f32x4 g = {1.f, 1.f, 1.f, 1.f};
-                    if (gamma) g = *reinterpret_cast<const f32x4*>(gamma + ch * 8 + h * 4);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[c][h][e] = fmaf(g[e], (float)yy[h * 4 + e], v[c][h][e]);
-                    *reinterpret_cast<f32x4*>(src + ch * 8 + h * 4) = v[c][h];
-                }
+                for (int e = 0; e < 4; ++e) x.e[h * 4 + e] = fmaf(g[e], (float)yy[h * 4 + e], x.e[h * 4 + e]);
             }
+            store8(src + ch * 8, x.e);
         }
-        sum += ((v[c][0][0] + v[c][0][1]) + (v[c][0][2] + v[c][0][3])) + ((v[c][1][0] + v[c][1][1]) + (v[c][1][2] + v[c][1][3]));
-    }
-    const float mean = segment_sum<LPR>(sum, lane) / (float)D;
-    float sq = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        const bool ok = sub + c * LPR < nchunk;
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float d = ok ? v[c][h][e] - mean : 0.f;
-                sq += d * d;
-            }
-    }
-    const float rstd = rsqrtf(segment_sum<LPR>(sq, lane) / (float)D + eps);
-    if (!row_ok) return;
-    int orow = row;
-    if (group > 0) {
-        const int g = row / group, i = row - g * group;
-        if (i < skip) return;                                       // dropped row (cls token)
-        orow = g * (group - skip) + (i - skip);
-    }
-    const float* per = pe ? pe + (size_t)((row / pe_rows_per_step) % pe_steps) * D : nullptr;
+        return x;
+    });
+    if (!p.row_ok) return;
+    const int orow = out_row(p.row, group, skip);
+    if (orow < 0) return;
+    const float* per = pe ? pe + (size_t)((p.row / pe_rows_per_step) % pe_steps) * D : nullptr;
     OT* dst = out + (size_t)orow * D;
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
-        const int ch = sub + c * LPR;
-        if (ch < nchunk) {
-            float o[8];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const f32x4 ww = *reinterpret_cast<const f32x4*>(w + ch * 8 + h * 4);
-                const f32x4 bb = *reinterpret_cast<const f32x4*>(b + ch * 8 + h * 4);
-                f32x4 y = (v[c][h] - mean) * rstd * ww + bb;
-                if (per) y += *reinterpret_cast<const f32x4*>(per + ch * 8 + h * 4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[h * 4 + e] = y[e];
-            }
-            store8(dst + ch * 8, o);
-        }
+        const int ch = p.sub + c * LPR;
+        if (ch < nchunk) affine_store(v[c], st.x, st.y, w + ch * 8, b + ch * 8, per ? per + ch * 8 : nullptr, dst + ch * 8);
     }
 }
 
@@ -226,100 +265,59 @@ __global__ void __launch_bounds__(256) groupnorm_apply_kernel(const T* __restric
 //   MODE 0 (vda_split_stats_f32): fp32 rows -> hi, lo planes + stat[row] = (mean, rstd): the entry into the split stream.
 //   MODE 1 (vda_layernorm_split_f16): LayerNorm(hi + lo) * w + b -> fp16, group / skip as layernorm_kernel (the taps).
 //   MODE 2 (vda_split_center_stats_f32): as MODE 0 with the row's mean taken out: hi + lo = x - mean(x), stat[row] = (0, rstd).
-// Same row-in-registers, two-pass fp32 statistics as layernorm_kernel.
+// The steps of layernorm_kernel around its own loader (fp32 or hi + lo) and, for MODE 0 / 2, its own writer (planes + stat).
 template <int LPR, int NCH, int MODE>
 __global__ void __launch_bounds__(256) ln_split_kernel(const float* __restrict__ xin, const h16* __restrict__ hin, const h16* __restrict__ lin,
                                                        h16* __restrict__ o0, h16* __restrict__ o1, float* __restrict__ stat,
                                                        const float* __restrict__ w, const float* __restrict__ b, float eps, int rows, int D,
                                                        int group, int skip) {
-    constexpr int RPW = 64 / LPR;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int sub = lane % LPR, rsel = lane / LPR;
-    const int row = (blockIdx.x * 4 + wave) * RPW + rsel;
-    const bool row_ok = row < rows;
-    const int nchunk = D >> 3;
-    const size_t base = (size_t)(row_ok ? row : 0) * D;
-    float v[NCH][8];
-    float sum = 0.f;
+    const int lane = threadIdx.x & 63, nchunk = D >> 3;
+    const RowLanes p = row_lanes<LPR>(lane, rows);
+    const size_t base = (size_t)(p.row_ok ? p.row : 0) * D;
+    Chunk v[NCH];
+    const float2 st = load_row_stats<LPR>(v, p, nchunk, D, eps, lane, [=](int ch) {
+        Chunk x;
+        if constexpr (MODE != 1) {
+            load8(xin + base + ch * 8, x.e);
+        } else {
+            const h16x8 a = *reinterpret_cast<const h16x8*>(hin + base + ch * 8), l = *reinterpret_cast<const h16x8*>(lin + base + ch * 8);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) x.e[e] = (float)a[e] + (float)l[e];
+        }
+        return x;
+    });
+    const float mean = st.x, rstd = st.y;
+    if (!p.row_ok) return;
+    const int orow = MODE == 1 ? out_row(p.row, group, skip) : p.row;
+    if (orow < 0) return;
+    // MODE 2: the planes hold x - mean (the mean of what they hold is 0 up to fp32 rounding: 1e-7 of the row's spread)
+    const float ctr = MODE == 2 ? mean : 0.f;
+    if (MODE != 1 && p.sub == 0) *reinterpret_cast<float2*>(stat + 2 * (size_t)p.row) = float2{mean - ctr, rstd};
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
-        const int ch = sub + c * LPR;
-        const bool ok = row_ok && ch < nchunk;
+        const int ch = p.sub + c * LPR;
+        if (ch >= nchunk) continue;
+        if constexpr (MODE == 1) {
+            affine_store(v[c], mean, rstd, w + ch * 8, b + ch * 8, nullptr, o0 + (size_t)orow * D + ch * 8);
+        } else {
+            h16x8 a, l;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v[c][e] = 0.f;
-        if (ok) {
-            if constexpr (MODE != 1) {
-                load8(xin + base + ch * 8, v[c]);
-            } else {
-                const h16x8 a = *reinterpret_cast<const h16x8*>(hin + base + ch * 8), l = *reinterpret_cast<const h16x8*>(lin + base + ch * 8);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[c][e] = (float)a[e] + (float)l[e];
+            for (int e = 0; e < 8; ++e) {
+                const float d = v[c].e[e] - ctr;
+                a[e] = (h16)d;
+                l[e] = (h16)(d - (float)a[e]);
             }
-        }
-        sum += ((v[c][0] + v[c][1]) + (v[c][2] + v[c][3])) + ((v[c][4] + v[c][5]) + (v[c][6] + v[c][7]));
-    }
-    const float mean = segment_sum<LPR>(sum, lane) / (float)D;
-    float sq = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        const bool ok = sub + c * LPR < nchunk;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float d = ok ? v[c][e] - mean : 0.f;
-            sq += d * d;
-        }
-    }
-    const float rstd = rsqrtf(segment_sum<LPR>(sq, lane) / (float)D + eps);
-    if (!row_ok) return;
-    if constexpr (MODE != 1) {
-        // MODE 2: the planes hold x - mean (the mean of what they hold is 0 up to fp32 rounding: 1e-7 of the row's spread)
-        const float ctr = MODE == 2 ? mean : 0.f;
-        if (sub == 0) *reinterpret_cast<float2*>(stat + 2 * (size_t)row) = float2{mean - ctr, rstd};
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            const int ch = sub + c * LPR;
-            if (ch < nchunk) {
-                h16x8 a, l;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float d = v[c][e] - ctr;
-                    a[e] = (h16)d;
-                    l[e] = (h16)(d - (float)a[e]);
-                }
-                *reinterpret_cast<h16x8*>(o0 + base + ch * 8) = a;
-                *reinterpret_cast<h16x8*>(o1 + base + ch * 8) = l;
-            }
-        }
-    } else {
-        int orow = row;
-        if (group > 0) {
-            const int g = row / group, i = row - g * group;
-            if (i < skip) return;
-            orow = g * (group - skip) + (i - skip);
-        }
-        h16* dst = o0 + (size_t)orow * D;
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            const int ch = sub + c * LPR;
-            if (ch < nchunk) {
-                float o[8];
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const f32x4 ww = *reinterpret_cast<const f32x4*>(w + ch * 8 + h * 4);
-                    const f32x4 bb = *reinterpret_cast<const f32x4*>(b + ch * 8 + h * 4);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[h * 4 + e] = (v[c][h * 4 + e] - mean) * rstd * ww[e] + bb[e];
-                }
-                store8(dst + ch * 8, o);
-            }
+            *reinterpret_cast<h16x8*>(o0 + base + ch * 8) = a;
+            *reinterpret_cast<h16x8*>(o1 + base + ch * 8) = l;
         }
     }
 }
 
 // partial[np, r, 2] = (sum, centred sum of squares) per 64 columns -> stat[r] = (mean, rstd); pairwise update in column order
 // (Chan, Golub, LeVeque): no E[x^2] - mean^2 cancellation, fixed order.
-// overflow (optional): set to 1 when a row's statistics are not finite - the fp16 planes of the split stream saturate at 65 504 from
-// the token's own mean, and a saturated hi plane shows here as an infinite / NaN sum (every element of it is under these sums).
+// overflow (optional): set to 1 when a row's mean or m2 is not finite. The partials come from the producing GEMM's fp32 values, not
+// from the fp16 planes it stores, so the step in which a plane first saturates (an element beyond 65 504 of the token's mean) still
+// has finite statistics; the flag rises one step later, when a GEMM has read hi + lo = inf - inf back into its partials.
 __global__ void __launch_bounds__(64) ln_stats_finalize_kernel(const float* __restrict__ partial, float* __restrict__ stat, float eps, int rows, int np,
                                                                int* __restrict__ overflow) {
     const int r = blockIdx.x * 64 + threadIdx.x;          // one wave per workgroup: 685 workgroups for a ViT-L clip, every CU gets some
@@ -372,30 +370,44 @@ __global__ void __launch_bounds__(64) fold_ln_weight_kernel(const float* __restr
 
 }  // namespace
 
+// The checks every row-normalisation entry shares, under the entry's own name: `must` may not be NULL, `must` and `may` (NULL
+// allowed) take 16-byte accesses.
+static int ln_check(const char* name, int rows, int D, int group, int skip, std::initializer_list<const void*> must,
+                    std::initializer_list<const void*> may = {}) {
+    for (const void* q : must) VDA_REQUIRE(q != nullptr, "%s: null pointer", name);
+    VDA_REQUIRE(rows > 0 && D > 0 && D % 8 == 0 && D <= 2048, "%s: D=%d must be a multiple of 8 and <= 2048", name, D);
+    VDA_REQUIRE(group == 0 || (group > 0 && skip >= 0 && skip < group && rows % group == 0), "%s: bad group/skip", name);
+    for (const auto& list : {must, may})
+        for (const void* q : list) VDA_REQUIRE(((uintptr_t)q & 15) == 0, "%s: 16-byte alignment required", name);
+    return 0;
+}
+
+// The ladder: D / 8 chunks per row -> <LPR lanes per row, NCH chunks per lane>, and the grid (4 waves of 64 / LPR rows per
+// workgroup). launch(LPR, NCH, grid) receives the pair as std::integral_constants.
+template <typename LAUNCH>
+static void ln_ladder(int rows, int D, LAUNCH launch) {
+    const int nchunk = D / 8;
+    auto rung = [&](auto lpr, auto nch) { launch(lpr, nch, dim3((rows + 4 * (64 / lpr()) - 1) / (4 * (64 / lpr())))); };
+    using std::integral_constant;
+    if (nchunk <= 8) rung(integral_constant<int, 8>{}, integral_constant<int, 1>{});
+    else if (nchunk <= 16) rung(integral_constant<int, 16>{}, integral_constant<int, 1>{});
+    else if (nchunk <= 32) rung(integral_constant<int, 32>{}, integral_constant<int, 1>{});
+    else if (nchunk <= 64) rung(integral_constant<int, 64>{}, integral_constant<int, 1>{});
+    else if (nchunk <= 128) rung(integral_constant<int, 64>{}, integral_constant<int, 2>{});
+    else rung(integral_constant<int, 64>{}, integral_constant<int, 4>{});
+}
+
 template <typename OT, bool RES = false>
 static int layernorm_launch(float* in, OT* out, const float* w, const float* b, float eps, int rows, int D, int group, int skip,
                             const float* pe, int pe_rows_per_step, int pe_steps, vda_stream_t stream, const h16* y = nullptr,
                             const float* gamma = nullptr) {
-    VDA_REQUIRE(!RES || (y != nullptr && ((uintptr_t)y & 15) == 0 && ((uintptr_t)gamma & 15) == 0), "vda_layernorm_residual: y must be a 16-byte aligned pointer");
-    VDA_REQUIRE(in && out && w && b, "vda_layernorm: null pointer");
-    VDA_REQUIRE(rows > 0 && D > 0 && D % 8 == 0 && D <= 2048, "vda_layernorm: D=%d must be a multiple of 8 and <= 2048", D);
-    VDA_REQUIRE(group == 0 || (group > 0 && skip >= 0 && skip < group && rows % group == 0), "vda_layernorm: bad group/skip");
+    if (RES && ln_check("vda_layernorm_residual", rows, D, group, skip, {y}, {gamma})) return 1;
+    if (ln_check("vda_layernorm", rows, D, group, skip, {in, out, w, b}, {pe})) return 1;
     VDA_REQUIRE(pe == nullptr || (pe_rows_per_step > 0 && pe_steps > 0), "vda_layernorm: bad pe geometry");
-    VDA_REQUIRE(((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 15) == 0 && ((uintptr_t)w & 15) == 0 && ((uintptr_t)b & 15) == 0 &&
-                    ((uintptr_t)pe & 15) == 0,
-                "vda_layernorm: 16-byte alignment required");
-    hipStream_t s = (hipStream_t)stream;
-    const int nchunk = D / 8;
-#define VDA_LN_LAUNCH(LPR, NCH)                                                                                                     \
-    hipLaunchKernelGGL((layernorm_kernel<LPR, NCH, OT, RES>), dim3((rows + 4 * (64 / LPR) - 1) / (4 * (64 / LPR))), dim3(256), 0, s, in, \
-                       out, w, b, eps, rows, D, group, skip, pe, pe_rows_per_step, pe_steps, y, gamma)
-    if (nchunk <= 8) VDA_LN_LAUNCH(8, 1);
-    else if (nchunk <= 16) VDA_LN_LAUNCH(16, 1);
-    else if (nchunk <= 32) VDA_LN_LAUNCH(32, 1);
-    else if (nchunk <= 64) VDA_LN_LAUNCH(64, 1);
-    else if (nchunk <= 128) VDA_LN_LAUNCH(64, 2);
-    else VDA_LN_LAUNCH(64, 4);
-#undef VDA_LN_LAUNCH
+    ln_ladder(rows, D, [&](auto lpr, auto nch, dim3 grid) {
+        hipLaunchKernelGGL((layernorm_kernel<lpr(), nch(), OT, RES>), grid, dim3(256), 0, (hipStream_t)stream, in, out, w, b, eps, rows, D,
+                           group, skip, pe, pe_rows_per_step, pe_steps, y, gamma);
+    });
     VDA_LAUNCH_CHECK();
     return 0;
 }
@@ -417,47 +429,32 @@ extern "C" int vda_layernorm_f32_f32(const float* in, float* out, const float* w
     return layernorm_launch<float>(const_cast<float*>(in), out, w, b, eps, rows, D, group, skip, pe, pe_rows_per_step, pe_steps, stream);
 }
 
+// The three entries of ln_split_kernel; each passes the operands its MODE reads and NULL for the rest.
 template <int MODE>
-static int ln_split_launch(const float* xin, const h16* hin, const h16* lin, h16* o0, h16* o1, float* stat, const float* w, const float* b, float eps,
-                           int rows, int D, int group, int skip, vda_stream_t stream) {
-    VDA_REQUIRE(rows > 0 && D > 0 && D % 8 == 0 && D <= 2048, "vda_layernorm_split / vda_split_stats: D=%d must be a multiple of 8 and <= 2048", D);
-    VDA_REQUIRE(group == 0 || (group > 0 && skip >= 0 && skip < group && rows % group == 0), "vda_layernorm_split: bad group/skip");
-    hipStream_t s = (hipStream_t)stream;
-    const int nchunk = D / 8;
-#define VDA_LNS_LAUNCH(LPR, NCH)                                                                                                          \
-    hipLaunchKernelGGL((ln_split_kernel<LPR, NCH, MODE>), dim3((rows + 4 * (64 / LPR) - 1) / (4 * (64 / LPR))), dim3(256), 0, s, xin, hin, lin, \
-                       o0, o1, stat, w, b, eps, rows, D, group, skip)
-    if (nchunk <= 8) VDA_LNS_LAUNCH(8, 1);
-    else if (nchunk <= 16) VDA_LNS_LAUNCH(16, 1);
-    else if (nchunk <= 32) VDA_LNS_LAUNCH(32, 1);
-    else if (nchunk <= 64) VDA_LNS_LAUNCH(64, 1);
-    else if (nchunk <= 128) VDA_LNS_LAUNCH(64, 2);
-    else VDA_LNS_LAUNCH(64, 4);
-#undef VDA_LNS_LAUNCH
+static int ln_split_launch(const char* name, const float* xin, const h16* hin, const h16* lin, h16* o0, h16* o1, float* stat, const float* w,
+                           const float* b, float eps, int rows, int D, int group, int skip, vda_stream_t stream) {
+    if (MODE == 1 ? ln_check(name, rows, D, group, skip, {hin, lin, o0, w, b}) : ln_check(name, rows, D, group, skip, {xin, o0, o1})) return 1;
+    VDA_REQUIRE(MODE == 1 || (stat != nullptr && ((uintptr_t)stat & 7) == 0), "%s: stat must be an 8-byte aligned pointer", name);
+    ln_ladder(rows, D, [&](auto lpr, auto nch, dim3 grid) {
+        hipLaunchKernelGGL((ln_split_kernel<lpr(), nch(), MODE>), grid, dim3(256), 0, (hipStream_t)stream, xin, hin, lin, o0, o1, stat, w, b,
+                           eps, rows, D, group, skip);
+    });
     VDA_LAUNCH_CHECK();
     return 0;
 }
 
 extern "C" int vda_split_stats_f32(const float* x, void* hi, void* lo, float* stat, float eps, int rows, int D, vda_stream_t stream) {
-    VDA_REQUIRE(x && hi && lo && stat, "vda_split_stats_f32: null pointer");
-    VDA_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)hi & 15) == 0 && ((uintptr_t)lo & 15) == 0 && ((uintptr_t)stat & 7) == 0,
-                "vda_split_stats_f32: 16-byte alignment required");
-    return ln_split_launch<0>(x, nullptr, nullptr, (h16*)hi, (h16*)lo, stat, nullptr, nullptr, eps, rows, D, 0, 0, stream);
+    return ln_split_launch<0>("vda_split_stats_f32", x, nullptr, nullptr, (h16*)hi, (h16*)lo, stat, nullptr, nullptr, eps, rows, D, 0, 0, stream);
 }
 
 extern "C" int vda_split_center_stats_f32(const float* x, void* hi, void* lo, float* stat, float eps, int rows, int D, vda_stream_t stream) {
-    VDA_REQUIRE(x && hi && lo && stat, "vda_split_center_stats_f32: null pointer");
-    VDA_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)hi & 15) == 0 && ((uintptr_t)lo & 15) == 0 && ((uintptr_t)stat & 7) == 0,
-                "vda_split_center_stats_f32: 16-byte alignment required");
-    return ln_split_launch<2>(x, nullptr, nullptr, (h16*)hi, (h16*)lo, stat, nullptr, nullptr, eps, rows, D, 0, 0, stream);
+    return ln_split_launch<2>("vda_split_center_stats_f32", x, nullptr, nullptr, (h16*)hi, (h16*)lo, stat, nullptr, nullptr, eps, rows, D, 0, 0, stream);
 }
 
 extern "C" int vda_layernorm_split_f16(const void* hi, const void* lo, void* out, const float* w, const float* b, float eps, int rows, int D,
                                        int group, int skip, vda_stream_t stream) {
-    VDA_REQUIRE(hi && lo && out && w && b, "vda_layernorm_split_f16: null pointer");
-    VDA_REQUIRE(((uintptr_t)hi & 15) == 0 && ((uintptr_t)lo & 15) == 0 && ((uintptr_t)out & 15) == 0 && ((uintptr_t)w & 15) == 0 && ((uintptr_t)b & 15) == 0,
-                "vda_layernorm_split_f16: 16-byte alignment required");
-    return ln_split_launch<1>(nullptr, (const h16*)hi, (const h16*)lo, (h16*)out, nullptr, nullptr, w, b, eps, rows, D, group, skip, stream);
+    return ln_split_launch<1>("vda_layernorm_split_f16", nullptr, (const h16*)hi, (const h16*)lo, (h16*)out, nullptr, nullptr, w, b, eps, rows, D,
+                              group, skip, stream);
 }
 
 extern "C" int vda_ln_stats_finalize(const float* partial, float* stat, float eps, int rows, int np, int32_t* overflow, vda_stream_t stream) {
