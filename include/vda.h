@@ -389,6 +389,35 @@ int vda_eval_metric_partial(const float* pred, const void* gt, int gt_is_f64, in
  * them), then the mean over the frames that have a valid pixel. No such frame: the six metrics are NaN, frames used = 0. */
 int vda_eval_metric_finish(const double* partial, int nframes, int blocks_per_frame, double* result, vda_stream_t stream);
 
+/* ---- temporal alignment error on the device (the reference's benchmark/eval/eval_tae.py: eval_TAE and tae_torch) ------------
+ * For every pair of neighbouring frames (i, i+1), in both directions: the aligned depth of one frame is unprojected with K[i],
+ * moved with the relative pose, splatted into the other frame's pixel grid, and compared with that frame's own aligned depth.
+ *   d    = clip(1 / max(scale * max(pred, 1e-3f) + shift, 1e-3), 1e-3, max_depth) in fp64 for EVERY pixel; `fit` = {scale, shift, ..}
+ *          is what vda_eval_lsq_finish left on the device (the fit is the scorer's, run first over the whole video).
+ *   cam  : fp64 device array, 28 doubles per pair: fx, fy, cx, cy, then rows 0..2 of the 4x4 T21 = inv(pose[i+1]) @ pose[i]
+ *          (R|t, row-major, 12 doubles), then rows 0..2 of T12 = inv(T21). The host computes them.
+ *   plane = 2 * pair + direction; direction 0 splats frame i into i+1 with T21, direction 1 frame i+1 into i with T12.
+ * The splat is LAST WINS, as the reference's index assignment is on the CPU: of the source pixels that round to one target, the
+ * one with the largest row-major index stays, whatever the sign of its depth. It is an integer atomic max of (source index + 1)
+ * into `winner`, so it is deterministic; the sums are fp64 block rows combined in a fixed order. The result depends on
+ * blocks_per_plane, never on timing or on how the pairs are cut into calls.
+ * A video is fed `npairs` pairs at a time (pred, mask: the npairs + 1 frames the pairs touch; winner: 2 * npairs planes, reused
+ * from call to call): vda_tae_splat then vda_tae_compare per chunk (pair_offset = pairs compared so far), vda_tae_finish once.
+ * Refused: null or misaligned pointers, H * W >= 2^31 - 1 (a source index + 1 is a 32-bit word), npairs > 32767.
+ *
+ * Clears the 2 * npairs planes of `winner` ([2 * npairs, H, W] 32-bit words) on `stream`, then splats. pred: [npairs + 1, H, W]. */
+int vda_tae_splat(const float* pred, int npairs, int H, int W, double max_depth, const double* fit, const double* cam, unsigned int* winner,
+                  vda_stream_t stream);
+/* Per plane and block 2 doubles {sum |dst - proj| / dst, count} over the target pixels with proj > 0, dst > 0 and mask != 0, at
+ * partial[(((pair_offset + pair) * 2 + direction) * blocks_per_plane + b) * 2 ...]; proj is the winner's moved depth, recomputed.
+ * mask: bytes [npairs + 1, H, W], 0 = excluded, or NULL for none. blocks_per_plane <= 4096, the same in every call of one video. */
+int vda_tae_compare(const float* pred, const unsigned char* mask, int npairs, int H, int W, double max_depth, const double* fit, const double* cam,
+                    const unsigned int* winner, double* partial, int pair_offset, int blocks_per_plane, vda_stream_t stream);
+/* result[0] = TAE = 100 * (sum over planes of e) / (2 * npairs), e = sum / count of a plane's rows in index order (0 when the
+ * count is 0), planes added in order; result[1 .. 2 npairs] = e per plane, result[1 + 2 npairs ..] = the counts. Doubles on the
+ * device, 1 + 4 * npairs of them; npairs is the whole video's N - 1. */
+int vda_tae_finish(const double* partial, int npairs, int blocks_per_plane, double* result, vda_stream_t stream);
+
 /* ================================================================ handle API: the model behind one pointer
  * What a C / C++ host binds in place of the reference's Python class (the seam of SURVEY.md section 8b):
  *   VideoDepthAnything(**model_configs[enc])          run.py:45, video_depth.py:38-63      vda_create

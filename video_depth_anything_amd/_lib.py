@@ -113,6 +113,9 @@ SIGNATURES = {
     "vda_eval_lsq_finish": (_i, [_vp, _i, _vp, _vp]),
     "vda_eval_metric_partial": (_i, [_vp, _vp, _i, _i, _ll, C.c_double, _vp, _vp, _i, _i, _vp]),
     "vda_eval_metric_finish": (_i, [_vp, _i, _i, _vp, _vp]),
+    "vda_tae_splat": (_i, [_vp, _i, _i, _i, C.c_double, _vp, _vp, _vp, _vp]),
+    "vda_tae_compare": (_i, [_vp, _vp, _i, _i, _i, C.c_double, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "vda_tae_finish": (_i, [_vp, _i, _i, _vp, _vp]),
     # handle API
     "vda_create": (_i, [C.POINTER(Config), C.POINTER(_vp)]),
     "vda_destroy": (_i, [_vp]),

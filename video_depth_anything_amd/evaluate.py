@@ -15,6 +15,11 @@ stitcher); `evaluate_depth` never calls it - there is no CPU path.
 dtype rules (they decide the last bits): a float32 ground truth stays float32 and is widened exactly; an integer ground truth
 divided by its factor is float64. So `gt` may be float32 or float64 and is never narrowed. The validity comparisons happen in
 gt's own type, as numpy compares an array with a python scalar. The delta ratios are float32 count / n, everything else fp64.
+
+`evaluate_tae` is the benchmark's third stage (benchmark/eval/eval_tae.py there), the temporal alignment error: the same fit, then
+for every pair of neighbouring frames and both directions the aligned depth of one frame is unprojected with K, moved with the
+relative pose, splatted LAST-WINS into the other frame's grid and compared with that frame's aligned depth (csrc/tae.hip,
+vda_tae_*; the contract is in DESIGN.md 6d). `evaluate_tae_numpy` is its host twin for the CPU tests.
 """
 import numpy as np
 
@@ -132,6 +137,161 @@ def evaluate_depth(pred, gt, max_depth, max_eval_len=None, device="cuda", chunk_
         ops.eval_metric_finish(work, N, bpf, res)
         host = out.cpu().numpy()                                        # the one device-to-host copy (synchronises)
     return _result(host[:3], host[3:])
+
+
+# ---------------------------------------------------------------------------------------------- temporal alignment error
+TAE_MAX_BLOCKS = 64          # compare pass: blocks per (pair, direction) plane
+TAE_PX_PER_BLOCK = 4 * EVAL_T
+TAE_FIT_FRAMES = 8           # frames per call of the fit's pass 1: fixed, so that scale / shift do not depend on chunk_pairs
+
+
+def _host64(a, name, tail):
+    """K / poses as float64 numpy, whatever they came as; K [3,3] is left for the caller to broadcast."""
+    if hasattr(a, "detach"):
+        a = a.detach().cpu().numpy()
+    a = np.asarray(a, dtype=np.float64)
+    if a.shape[-2:] != tail or a.ndim not in ((2, 3) if name == "K" else (3,)):
+        raise ValueError(f"evaluate_tae: {name} must be [N,{tail[0]},{tail[1]}]" + (" or [3,3]" if name == "K" else "") + f", got {a.shape}")
+    return a
+
+
+def _check_tae(pred, gt, K, poses, mask):
+    """Argument checks shared by evaluate_tae and its twin; returns the cameras of _tae_cameras."""
+    if pred.ndim != 3 or gt.ndim != 3 or tuple(pred.shape) != tuple(gt.shape):
+        raise ValueError(f"evaluate_tae: pred {tuple(pred.shape)} and gt {tuple(gt.shape)} must be equal [N,H,W]. The reference resizes a "
+                         "mismatched prediction with cv2.resize; resizing is not part of this scorer - write the prediction at the "
+                         "(cropped) ground-truth size")
+    N = pred.shape[0]
+    if N < 2 or pred.shape[1] * pred.shape[2] == 0:
+        raise ValueError(f"evaluate_tae: needs at least two non-empty frames, got {tuple(pred.shape)} (the reference divides by 2 (N - 1))")
+    if mask is not None and tuple(mask.shape) != tuple(pred.shape):
+        raise ValueError(f"evaluate_tae: mask {tuple(mask.shape)} and pred {tuple(pred.shape)} differ in shape")
+    K, poses = _host64(K, "K", (3, 3)), _host64(poses, "poses", (4, 4))
+    if K.ndim == 2:
+        K = np.broadcast_to(K, (N, 3, 3))
+    if K.shape[0] != N or poses.shape[0] != N:
+        raise ValueError(f"evaluate_tae: {N} frames but K {K.shape} and poses {poses.shape}")
+    return _tae_cameras(K, poses)
+
+
+def _tae_cameras(K, poses):
+    """fp64 [N-1, 28] as vda_tae_* take it: fx, fy, cx, cy of K[i] (the reference reads K[i] for both directions), rows 0..2 of
+    T21 = inv(pose[i+1]) @ pose[i], rows 0..2 of T12 = inv(T21) - on the host, in exactly these two steps (eval_tae.py:169,203)."""
+    cam = np.empty((poses.shape[0] - 1, 28), dtype=np.float64)
+    for i in range(cam.shape[0]):
+        T21 = np.linalg.inv(poses[i + 1]) @ poses[i]
+        T12 = np.linalg.inv(T21)
+        cam[i, :4] = K[i, 0, 0], K[i, 1, 1], K[i, 0, 2], K[i, 1, 2]
+        cam[i, 4:16], cam[i, 16:] = T21[:3].ravel(), T12[:3].ravel()
+    return cam
+
+
+def _tae_result(fit, res, npairs):
+    return {"tae": float(res[0]), "scale": float(fit[0]), "shift": float(fit[1]), "n_valid": int(fit[2]),
+            "pair_errors": np.array(res[1:1 + 2 * npairs], dtype=np.float64).reshape(npairs, 2),
+            "pair_counts": np.array(res[1 + 2 * npairs:1 + 4 * npairs]).astype(np.int64).reshape(npairs, 2)}
+
+
+def evaluate_tae_numpy(pred, gt, K, poses, max_depth, mask=None):
+    """Host twin of evaluate_tae: the same arithmetic in vectorised numpy (last-wins through np.maximum.at on source indices).
+    For tests; not a product path."""
+    pred, gt = np.asarray(pred), np.asarray(gt)
+    if pred.dtype != np.float32 or gt.dtype not in (np.float32, np.float64):
+        raise ValueError(f"evaluate_tae_numpy: pred must be float32 and gt float32 or float64, got {pred.dtype} and {gt.dtype}")
+    mask = None if mask is None else np.asarray(mask) != 0
+    cam = _check_tae(pred, gt, K, poses, mask)
+    fit = evaluate_depth_numpy(pred, gt, max_depth)
+    N, H, W = pred.shape
+    with np.errstate(all="ignore"):
+        x = np.clip(pred, np.float32(1e-3), None).astype(np.float64)
+        d = np.clip(1.0 / np.clip(fit["scale"] * x + fit["shift"], 1e-3, None), 1e-3, float(max_depth)).reshape(N, -1)
+    ys, xs = (a.ravel().astype(np.float64) for a in np.indices((H, W)))
+    src_index = np.arange(H * W, dtype=np.int64)
+    err, cnt = np.zeros((N - 1, 2)), np.zeros((N - 1, 2), dtype=np.int64)
+    for i in range(N - 1):
+        fx, fy, cx, cy = cam[i, :4]
+        for direction in (0, 1):
+            m = cam[i, 4 + 12 * direction:16 + 12 * direction]
+            src, dst = d[i + direction], d[i + 1 - direction]
+            with np.errstate(all="ignore"):
+                X, Y = (xs - cx) * src / fx, (ys - cy) * src / fy
+                Qx, Qy, Qz = (X * m[4 * r] + Y * m[4 * r + 1] + src * m[4 * r + 2] + m[4 * r + 3] for r in range(3))
+                u, v = np.rint(Qx * fx / Qz + cx), np.rint(Qy * fy / Qz + cy)
+                inside = (u >= 0) & (u < W) & (v >= 0) & (v < H)
+            winner = np.zeros(H * W, dtype=np.int64)
+            np.maximum.at(winner, (v[inside] * W + u[inside]).astype(np.int64), src_index[inside] + 1)
+            proj = np.where(winner > 0, Qz[np.maximum(winner, 1) - 1], 0.0)
+            use = (proj > 0) & (dst > 0)
+            if mask is not None:
+                use &= mask[i + 1 - direction].ravel()
+            cnt[i, direction] = use.sum()
+            if cnt[i, direction]:
+                err[i, direction] = (np.abs(dst[use] - proj[use]) / dst[use]).mean()
+    tae = err.sum() / (2 * (N - 1)) * 100.0
+    return {"tae": float(tae), "scale": fit["scale"], "shift": fit["shift"], "n_valid": fit["n_valid"], "pair_errors": err, "pair_counts": cnt}
+
+
+def evaluate_tae(pred, gt, K, poses, max_depth, mask=None, device="cuda", chunk_pairs=None):
+    """Temporal alignment error of `pred` (float32 [N,H,W]) on the device. gt (float32 or float64 [N,H,W]) only takes part in the
+    scale / shift fit, which is evaluate_depth's; K [N,3,3] or [3,3] and poses [N,4,4] (camera to world) go through the host; mask
+    (bool or uint8 [N,H,W], optional) excludes target pixels. pred, gt and mask may be numpy arrays or CUDA tensors: device-resident
+    tensors are used in place, host arrays are uploaded a few frames at a time. `chunk_pairs` bounds the winner planes (8 bytes per
+    pixel and pair; all pairs at once when None); the result does not depend on it. Returns a dict: tae, scale, shift, n_valid,
+    pair_errors and pair_counts [N-1, 2] (column 0: frame i into i+1). Runs on the current stream of the device."""
+    import torch
+    from . import ops
+
+    def as_tensor(a, name, dtypes):
+        if not isinstance(a, torch.Tensor):
+            a = torch.from_numpy(np.asarray(a))
+        if a.dtype not in dtypes:
+            raise ValueError(f"evaluate_tae: {name} must be {' or '.join(str(d) for d in dtypes)}, got {a.dtype}")
+        return a
+
+    pred = as_tensor(pred, "pred", (torch.float32,))
+    gt = as_tensor(gt, "gt", (torch.float32, torch.float64))
+    mask = None if mask is None else as_tensor(mask, "mask", (torch.bool, torch.uint8))
+    cam_host = _check_tae(pred, gt, K, poses, mask)
+    on_dev = [t.device for t in (pred, gt, mask) if t is not None and t.is_cuda]
+    dev = on_dev[0] if on_dev else torch.device(device)
+    if dev.type != "cuda" or any(d != dev for d in on_dev):
+        raise ValueError(f"evaluate_tae: needs one cuda device, got {device!r} / {[str(d) for d in on_dev]}")
+    N, H, W = pred.shape
+    px, P = H * W, N - 1
+    if px >= 2 ** 31 - 1:
+        raise ValueError(f"evaluate_tae: a frame of {H} x {W} is too large (a pixel index + 1 must fit 31 bits)")
+    step = P if chunk_pairs is None else int(chunk_pairs)
+    if step <= 0:
+        raise ValueError("evaluate_tae: chunk_pairs must be positive")
+    fit_chunks = [(lo, min(lo + TAE_FIT_FRAMES, N)) for lo in range(0, N, TAE_FIT_FRAMES)]
+    nblk = [min(LSQ_MAX_BLOCKS, -(-(hi - lo) * px // EVAL_T)) for lo, hi in fit_chunks]
+    bpp = min(TAE_MAX_BLOCKS, -(-px // TAE_PX_PER_BLOCK))
+    max_depth = float(max_depth)
+
+    with torch.cuda.device(dev):
+        work = torch.empty(max(5 * sum(nblk), 4 * P * bpp), dtype=torch.float64, device=dev)
+        out = torch.empty(3 + 1 + 4 * P, dtype=torch.float64, device=dev)       # fit {scale, shift, n_valid} | tae, errors, counts
+        fit, res = out[:3], out[3:]
+        cam = torch.from_numpy(cam_host).to(dev)
+        winner = torch.empty((2 * min(step, P), H, W), dtype=torch.int32, device=dev)
+
+        def on_device(t, lo, hi):
+            return t[lo:hi].to(dev, non_blocking=False).contiguous()
+
+        row = 0
+        for (lo, hi), nb in zip(fit_chunks, nblk):
+            ops.eval_lsq_partial(on_device(pred, lo, hi), on_device(gt, lo, hi), max_depth, work, row, nb)
+            row += nb
+        ops.eval_lsq_finish(work, row, fit)
+        for lo in range(0, P, step):
+            hi = min(lo + step, P)                                              # pairs lo .. hi-1 touch frames lo .. hi
+            p = on_device(pred, lo, hi + 1)
+            m = None if mask is None else on_device(mask, lo, hi + 1).to(torch.uint8)
+            ops.tae_splat(p, max_depth, fit, cam[lo:hi], winner)
+            ops.tae_compare(p, m, max_depth, fit, cam[lo:hi], winner, work, lo, bpp)
+        ops.tae_finish(work, P, bpp, res)
+        host = out.cpu().numpy()                                                # the one device-to-host copy (synchronises)
+    return _tae_result(host[:3], host[3:], P)
 
 
 def load_gt(path, factor):

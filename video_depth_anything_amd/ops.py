@@ -395,6 +395,46 @@ def eval_metric_finish(workspace, nframes, blocks_per_frame, result):
     check(lib.vda_eval_metric_finish(_p(workspace), nframes, blocks_per_frame, _p(result), _stream(workspace)), "vda_eval_metric_finish")
 
 
+# ---- temporal alignment error (csrc/tae.hip; evaluate.py cuts the pairs into chunks and lays the partial rows out) ------------
+def _tae_planes(pred, fit, cam, winner, what):
+    """Checks shared by the two passes; returns (pairs, H, W) of pred [pairs + 1, H, W]."""
+    _req(pred, F32, "pred"), _req(fit, torch.float64, "fit"), _req(cam, torch.float64, "cam"), _req(winner, torch.int32, "winner")
+    if pred.dim() != 3 or pred.shape[0] < 2 or pred.shape[1] * pred.shape[2] == 0:
+        raise ValueError(f"{what}: pred must be [pairs + 1, H, W], got {tuple(pred.shape)}")
+    n, H, W = pred.shape[0] - 1, pred.shape[1], pred.shape[2]
+    if fit.numel() < 2 or cam.numel() < 28 * n or winner.numel() < 2 * n * H * W:
+        raise ValueError(f"{what}: fit, cam or winner too small for {n} pairs of {H} x {W}")
+    return n, H, W
+
+
+def tae_splat(pred, max_depth, fit, cam, winner):
+    """Clears winner (int32 [2 * pairs, H, W]) and splats both directions of every neighbouring pair of pred [pairs + 1, H, W]
+    into it: winner[plane, v, u] = 1 + the largest source index that lands on (v, u). cam: fp64 [pairs, 28] (include/vda.h)."""
+    n, H, W = _tae_planes(pred, fit, cam, winner, "tae_splat")
+    check(lib.vda_tae_splat(_p(pred), n, H, W, float(max_depth), _p(fit), _p(cam), _p(winner), _stream(pred)), "vda_tae_splat")
+
+
+def tae_compare(pred, mask, max_depth, fit, cam, winner, workspace, pair_offset, blocks_per_plane):
+    """Compares each plane's splat with the target frame: 2 doubles per (plane, block) at workspace[4 * pair_offset *
+    blocks_per_plane ...]. mask: uint8 of pred's shape (0 = excluded) or None."""
+    n, H, W = _tae_planes(pred, fit, cam, winner, "tae_compare")
+    _req(workspace, torch.float64, "workspace"), _req(mask, torch.uint8, "mask")
+    if mask is not None and mask.shape != pred.shape:
+        raise ValueError(f"tae_compare: mask {tuple(mask.shape)} and pred {tuple(pred.shape)} differ in shape")
+    if pair_offset < 0 or blocks_per_plane <= 0 or workspace.numel() < 4 * (pair_offset + n) * blocks_per_plane:
+        raise ValueError("tae_compare: workspace too small")
+    check(lib.vda_tae_compare(_p(pred), _p(mask), n, H, W, float(max_depth), _p(fit), _p(cam), _p(winner), _p(workspace), pair_offset,
+                              blocks_per_plane, _stream(pred)), "vda_tae_compare")
+
+
+def tae_finish(workspace, npairs, blocks_per_plane, result):
+    """result (device fp64 [1 + 4 * npairs]) = {tae, error per plane, count per plane} from the compare pass's rows."""
+    _req(workspace, torch.float64, "workspace"), _req(result, torch.float64, "result")
+    if npairs <= 0 or blocks_per_plane <= 0 or workspace.numel() < 4 * npairs * blocks_per_plane or result.numel() < 1 + 4 * npairs:
+        raise ValueError("tae_finish: bad sizes")
+    check(lib.vda_tae_finish(_p(workspace), npairs, blocks_per_plane, _p(result), _stream(workspace)), "vda_tae_finish")
+
+
 # ---------------------------------------------------------------------------
 # Weight layouts the kernels expect (done once at load time, on the host or device)
 # ---------------------------------------------------------------------------
