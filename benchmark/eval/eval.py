@@ -4,12 +4,12 @@
 The second stage of the reference's benchmark with its flags (`--infer_path`, `--infer_type`, `--benchmark_path`, `--datasets`):
 for every scene of every dataset in the dataset's JSON manifest, stack the scene's ground truth (divided by each frame's `factor`,
 cropped to the dataset's window) and the predictions, score them with `evaluate_depth` (one scale / shift per scene, fitted in
-disparity over every valid pixel), and append the mean over scenes to `<infer_path>/results.txt` as `metric: value` lines between
-the dataset's start and finish rules.
+disparity over every valid pixel; a prediction that is not at the cropped ground truth's size is resized to it on the device as
+the reference resizes it, cv2.resize's INTER_LINEAR arithmetic - so infer.py's full-size output scores on scannet and nyuv2), and
+append the mean over scenes to `<infer_path>/results.txt` as `metric: value` lines between the dataset's start and finish rules.
 
-Differences from the reference's script: the arithmetic runs in HIP kernels (csrc/eval.hip) instead of host numpy; predictions
-must be .npy at the cropped ground-truth size (the reference resizes a mismatched one with cv2, which this project does not
-depend on); `--all_metrics` also writes squared_relative_difference, delta2_acc and delta3_acc.
+Differences from the reference's script: the arithmetic runs in HIP kernels (csrc/eval.hip, csrc/resize.hip) instead of host numpy
+and cv2; predictions must be .npy; `--all_metrics` also writes squared_relative_difference, delta2_acc and delta3_acc.
 """
 import argparse
 import json
@@ -40,8 +40,13 @@ def infer_file(infer_path, name, image):
     return os.path.join(infer_path, name, os.path.splitext(image)[0] + ".npy")
 
 
+def resized_note(resized):
+    return "" if resized is None else ", predictions resized from {}x{} to {}x{}".format(*resized[0], *resized[1])
+
+
 def score_scene(frames, infer_path, root, name, max_depth, max_eval_len, crop):
-    """frames: the manifest's list of {image, gt_depth, factor}. Frames whose prediction file is missing are left out."""
+    """frames: the manifest's list of {image, gt_depth, factor}. Frames whose prediction file is missing are left out. Returns
+    evaluate_depth's dict with "resized": (from size, to size) when the predictions were resized to the ground truth's, else None."""
     a, b, c, d = crop
     preds, gts = [], []
     for fr in frames[:max_eval_len]:
@@ -55,7 +60,10 @@ def score_scene(frames, infer_path, root, name, max_depth, max_eval_len, crop):
     gt = np.stack(gts, axis=0)
     if gt.dtype not in (np.float32, np.float64):
         gt = gt.astype(np.float64)
-    return evaluate_depth(np.stack(preds, axis=0), gt, max_depth, max_eval_len)
+    pred = np.stack(preds, axis=0)
+    r = evaluate_depth(pred, gt, max_depth, max_eval_len, resize=True)
+    r["resized"] = (pred.shape[1:], gt.shape[1:]) if pred.shape[1:] != gt.shape[1:] else None
+    return r
 
 
 def main():
@@ -86,7 +94,7 @@ def main():
                 for key, frames in scene.items():
                     r = score_scene(frames, args.infer_path, root, name, max_depth, max_eval_len, crop)
                     rows.append([r[m] for m in names])
-                    print(f"{name}/{key}: " + ", ".join(f"{m} {r[m]:.6f}" for m in names) + f" ({r['n_frames_used']} frames, {r['n_valid']} pixels)")
+                    print(f"{name}/{key}: " + ", ".join(f"{m} {r[m]:.6f}" for m in names) + f" ({r['n_frames_used']} frames, {r['n_valid']} pixels" + resized_note(r["resized"]) + ")")
             mean = np.mean(np.array(rows, dtype=np.float64), axis=0)
             for m, v in zip(names, mean):
                 print(f"{m}: {v:04f}")

@@ -10,9 +10,10 @@ every neighbouring pair reprojected in both directions), and append the mean ove
 
 Differences from the reference's script: the arithmetic runs in HIP kernels (csrc/tae.hip) instead of torch; only `scannet` is
 known, and it is the default - the reference's default also names `sintel`, for which its script has no settings and crashes;
-predictions must be .npy at the cropped ground-truth size, or at the full size with `--hard_crop` (the reference resizes a
-mismatched one with cv2, which this project does not depend on). Frames whose prediction file is missing are left out together
-with their K and pose, as in the reference.
+predictions must be .npy. As in the reference, `--hard_crop` cuts the dataset's window out of each prediction first, and a
+prediction that is then not at the cropped ground truth's size is resized to it (cv2.resize's INTER_LINEAR arithmetic, on the
+device: csrc/resize.hip) - so infer.py's full-size output scores with or without the flag. Frames whose prediction file is missing
+are left out together with their K and pose, as in the reference.
 """
 import argparse
 import json
@@ -33,7 +34,8 @@ def infer_file(infer_path, name, image):
 
 
 def score_scene(frames, infer_path, root, name, max_depth, crop, hard_crop):
-    """frames: the manifest's list of {image, gt_depth, factor, K, pose}. Frames whose prediction file is missing are left out."""
+    """frames: the manifest's list of {image, gt_depth, factor, K, pose}. Frames whose prediction file is missing are left out. Returns
+    evaluate_tae's dict with "resized": (from size, to size) when the predictions were resized to the ground truth's, else None."""
     a, b, c, d = crop
     preds, gts, Ks, poses = [], [], [], []
     for fr in frames:
@@ -50,7 +52,10 @@ def score_scene(frames, infer_path, root, name, max_depth, crop, hard_crop):
     gt = np.stack(gts, axis=0)
     if gt.dtype not in (np.float32, np.float64):
         gt = gt.astype(np.float64)
-    return evaluate_tae(np.stack(preds, axis=0), gt, np.stack(Ks, axis=0), np.stack(poses, axis=0), max_depth)
+    pred = np.stack(preds, axis=0)
+    r = evaluate_tae(pred, gt, np.stack(Ks, axis=0), np.stack(poses, axis=0), max_depth, resize=True)
+    r["resized"] = (pred.shape[1:], gt.shape[1:]) if pred.shape[1:] != gt.shape[1:] else None
+    return r
 
 
 def main():
@@ -61,7 +66,7 @@ def main():
     ap.add_argument("--start_idx", type=int, default=0)
     ap.add_argument("--end_idx", type=int, default=180)
     ap.add_argument("--eval_scenes_num", type=int, default=20)
-    ap.add_argument("--hard_crop", action="store_true", default=False, help="the predictions are at the uncropped size: cut the dataset's window out")
+    ap.add_argument("--hard_crop", action="store_true", default=False, help="cut the dataset's window out of the predictions (before any resize)")
     args = ap.parse_args()
     unknown = [d for d in args.datasets if d not in DATASETS]
     if unknown:
@@ -80,7 +85,8 @@ def main():
                 for key, frames in scene.items():
                     r = score_scene(frames[args.start_idx:args.end_idx], args.infer_path, root, name, max_depth, crop, args.hard_crop)
                     values.append(r["tae"])
-                    print(f"{name}/{key}: tae {r['tae']:.6f} ({r['pair_counts'].shape[0] + 1} frames, scale {r['scale']:.6g}, shift {r['shift']:.6g})")
+                    print(f"{name}/{key}: tae {r['tae']:.6f} ({r['pair_counts'].shape[0] + 1} frames, scale {r['scale']:.6g}, shift {r['shift']:.6g}"
+                          + ("" if r["resized"] is None else ", predictions resized from {}x{} to {}x{}".format(*r["resized"][0], *r["resized"][1])) + ")")
             mean = float(np.sum(np.array(values, dtype=np.float64)) / len(values))
             print(f"{name} :  tae  {mean}")
             out.write(f"{name}: {mean}\n")

@@ -418,6 +418,17 @@ int vda_tae_compare(const float* pred, const unsigned char* mask, int npairs, in
  * device, 1 + 4 * npairs of them; npairs is the whole video's N - 1. */
 int vda_tae_finish(const double* partial, int npairs, int blocks_per_plane, double* result, vda_stream_t stream);
 
+/* ---- a prediction resized to the ground truth's grid (the reference's scorers: cv2.resize(infer, (W, H)) on a size mismatch) ----
+ * n dense fp32 planes [h, w] -> n planes [H, W], cv2's INTER_LINEAR for CV_32F restated from its published algorithm. Per axis:
+ *   scale = 1.0 / ((double)n_dst / (double)n_src);  f = (float)((d + 0.5) * scale - 0.5);  s = floor(f);  f -= (float)s
+ * columns zero the weight at the border (s < 0: f = 0, s = 0;  s >= w - 1: f = 0, s = w - 1, and only tap s is read), rows keep f
+ * and clamp the indices s, s + 1 into [0, h - 1];
+ *   out = (S[y0][x0]*a0 + S[y0][x1]*a1) * b0 + (S[y1][x0]*a0 + S[y1][x1]*a1) * b1,  a0 = 1.f - fx, a1 = fx, b0 = 1.f - fy, b1 = fy
+ * with every operation rounded to fp32 (no fused multiply-add), so the result is deterministic and a host restatement reproduces
+ * it bit for bit. Non-finite inputs are outside the contract. Refused: null or misaligned (4-byte) pointers, a size < 1, in == out,
+ * a row of more than 2^30 pixels, n * H or n * h beyond 31 bits. One launch on `stream`, no allocation, no synchronisation. */
+int vda_resize_linear_f32(const float* in, float* out, int n, int h, int w, int H, int W, vda_stream_t stream);
+
 /* ================================================================ handle API: the model behind one pointer
  * What a C / C++ host binds in place of the reference's Python class (the seam of SURVEY.md section 8b):
  *   VideoDepthAnything(**model_configs[enc])          run.py:45, video_depth.py:38-63      vda_create

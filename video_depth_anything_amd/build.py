@@ -21,8 +21,10 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=f
 # v_pk_add_f32 (several times the issue cost of two v_add_f32 on gfx950) with the pairs misaligned against the
 # fp16 packing, which costs more shuffles than arithmetic - off for those files.
 # eval.hip restates numpy float64 arithmetic (scale * x + shift, two roundings) for the same reason; tae.hip shares that
-# expression and restates torch's fp64 elementwise arithmetic after it.
-PER_FILE = {"stitch.hip": ["-ffp-contract=off"], "eval.hip": ["-ffp-contract=off"], "tae.hip": ["-ffp-contract=off"]}
+# expression and restates torch's fp64 elementwise arithmetic after it. resize.hip restates cv2's float32 bilinear resize, whose
+# contract counts every rounding (a*b + c*d as three).
+PER_FILE = {"stitch.hip": ["-ffp-contract=off"], "eval.hip": ["-ffp-contract=off"], "tae.hip": ["-ffp-contract=off"],
+            "resize.hip": ["-ffp-contract=off"]}
 # attention: the softmax row sums are 32 scalar fp32 adds per tile; SLP packs 22 of them into v_pk_add_f32, which costs several
 # times two v_add_f32 next to MFMAs (MI355X_MICROARCH.md, "price of one filler") in a loop that is VALU-bound.
 PER_PREFIX = {"gemm": ["-fno-slp-vectorize"], "attention.hip": ["-fno-slp-vectorize"], "mlp_fused.hip": ["-fno-slp-vectorize"],

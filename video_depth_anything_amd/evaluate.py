@@ -16,6 +16,11 @@ dtype rules (they decide the last bits): a float32 ground truth stays float32 an
 divided by its factor is float64. So `gt` may be float32 or float64 and is never narrowed. The validity comparisons happen in
 gt's own type, as numpy compares an array with a python scalar. The delta ratios are float32 count / n, everything else fp64.
 
+`resize_prediction` is the reference's answer to a prediction that is not at the ground truth's size (eval.py: get_infer's
+cv2.resize(infer, (W, H)); eval_tae.py after its optional hard crop): cv2's INTER_LINEAR for float32 on the device (csrc/resize.hip,
+vda_resize_linear_f32; the contract is in DESIGN.md 6c). Both scorers apply it with `resize=True`, to the raw prediction before
+anything else, chunk by chunk. `resize_prediction_numpy` is its host twin for the CPU tests, bit for bit.
+
 `evaluate_tae` is the benchmark's third stage (benchmark/eval/eval_tae.py there), the temporal alignment error: the same fit, then
 for every pair of neighbouring frames and both directions the aligned depth of one frame is unprojected with K, moved with the
 relative pose, splatted LAST-WINS into the other frame's grid and compared with that frame's aligned depth (csrc/tae.hip,
@@ -30,17 +35,78 @@ METRIC_MAX_BLOCKS = 64       # pass 2: blocks per frame
 _D1, _D2, _D3 = 1.25, 1.25 ** 2, 1.25 ** 3
 
 
-def _check_pair(pred, gt, max_eval_len):
-    """Common argument checks; returns (pred[:L], gt[:L]) with pred.shape == gt.shape == [N,H,W]."""
+def _axis_taps(n_src, n_dst):
+    """One axis of cv2's INTER_LINEAR for float32: (floor of the source coordinate as int64, its fraction as float32), before any
+    border rule. The coordinate is fp64 and rounded once to float32."""
+    scale = 1.0 / (float(n_dst) / float(n_src))
+    c = ((np.arange(n_dst, dtype=np.float64) + 0.5) * scale - 0.5).astype(np.float32)
+    fl = np.floor(c)
+    return fl.astype(np.int64), c - fl
+
+
+def resize_prediction_numpy(pred, size):
+    """Host twin of resize_prediction: the same operations in numpy float32 (fp64 only for the coordinates), the same bits.
+    pred float32 [N,h,w], size (H, W) -> float32 [N,H,W]. For tests; not a product path."""
+    pred = np.asarray(pred)
+    H, W = (int(v) for v in size)
+    if pred.dtype != np.float32 or pred.ndim != 3 or pred.size == 0 or H < 1 or W < 1:
+        raise ValueError(f"resize_prediction_numpy: pred must be a non-empty float32 [N,h,w] and size positive, got {pred.dtype} {pred.shape} to {(H, W)}")
+    h, w = pred.shape[1:]
+    if (H, W) == (h, w):
+        return pred
+    one = np.float32(1.0)
+    x0, fx = _axis_taps(w, W)
+    fx = np.where((x0 < 0) | (x0 >= w - 1), np.float32(0.0), fx)           # columns: the weight is zeroed at the border ...
+    x0 = np.clip(x0, 0, w - 1)
+    x1 = np.minimum(x0 + 1, w - 1)                                          # ... and only tap x0 is read at the right one
+    sy, fy = _axis_taps(h, H)                                               # rows: the fraction stays, the indices are clamped
+    y0, y1 = np.clip(sy, 0, h - 1), np.clip(sy + 1, 0, h - 1)
+    a0, a1 = one - fx, fx
+    b0, b1 = (one - fy)[:, None], fy[:, None]
+    hor = pred[:, :, x0] * a0 + pred[:, :, x1] * a1                         # [N,h,W]: three float32 roundings
+    out = hor[:, y0] * b0 + hor[:, y1] * b1
+    assert out.dtype == np.float32
+    return out
+
+
+def resize_prediction(pred, size, device="cuda"):
+    """`pred` (float32 [N,h,w], a numpy array or a CUDA tensor) resized to size = (H, W) as the reference's scorers resize a
+    prediction, cv2.resize(infer, (W, H)): INTER_LINEAR on float32, in one kernel (csrc/resize.hip). Returns a CUDA tensor [N,H,W];
+    size == (h, w) returns the input unchanged apart from the upload, as the reference calls cv2 only on a mismatch. Runs on the
+    current stream of the device."""
+    import torch
+    from . import ops
+
+    if not isinstance(pred, torch.Tensor):
+        pred = torch.from_numpy(np.asarray(pred))
+    H, W = (int(v) for v in size)
+    if pred.dtype != torch.float32 or pred.ndim != 3 or pred.numel() == 0 or H < 1 or W < 1:
+        raise ValueError(f"resize_prediction: pred must be a non-empty float32 [N,h,w] and size positive, got {pred.dtype} {tuple(pred.shape)} to {(H, W)}")
+    dev = pred.device if pred.is_cuda else torch.device(device)
+    if dev.type != "cuda":
+        raise ValueError(f"resize_prediction: needs a cuda device, got {device!r}")
+    with torch.cuda.device(dev):
+        x = pred.to(dev).contiguous()
+        if (H, W) == tuple(x.shape[1:]):
+            return x
+        out = torch.empty((x.shape[0], H, W), dtype=torch.float32, device=dev)
+        ops.resize_linear(x, out)
+    return out
+
+
+def _check_pair(pred, gt, max_eval_len, resize=False):
+    """Common argument checks; returns (pred[:L], gt[:L]), both [N,H,W] - of one shape, or with `resize` of one N."""
     if pred.ndim != 3 or gt.ndim != 3:
         raise ValueError(f"evaluate_depth: pred and gt must be [N,H,W], got {tuple(pred.shape)} and {tuple(gt.shape)}")
     if max_eval_len is not None:
         pred, gt = pred[:max_eval_len], gt[:max_eval_len]
-    if tuple(pred.shape) != tuple(gt.shape):
+    if resize and pred.shape[0] != gt.shape[0]:
+        raise ValueError(f"evaluate_depth: pred {tuple(pred.shape)} and gt {tuple(gt.shape)} differ in the number of frames")
+    if tuple(pred.shape) != tuple(gt.shape) and not resize:
         raise ValueError(f"evaluate_depth: pred {tuple(pred.shape)} and gt {tuple(gt.shape)} differ in shape. The reference resizes a "
                          "mismatched prediction with cv2.resize; resizing is not part of this scorer - write the prediction at the "
                          "(cropped) ground-truth size")
-    if pred.shape[0] == 0 or pred.shape[1] * pred.shape[2] == 0:
+    if pred.shape[0] == 0 or pred.shape[1] * pred.shape[2] == 0 or gt.shape[1] * gt.shape[2] == 0:
         raise ValueError("evaluate_depth: empty video")
     return pred, gt
 
@@ -52,12 +118,13 @@ def _result(fit, res):
     return out
 
 
-def evaluate_depth_numpy(pred, gt, max_depth, max_eval_len=None):
+def evaluate_depth_numpy(pred, gt, max_depth, max_eval_len=None, resize=False):
     """Host twin of evaluate_depth: the same arithmetic in numpy, normal equations in fp64. For tests; not a product path."""
     pred, gt = np.asarray(pred), np.asarray(gt)
     if pred.dtype != np.float32 or gt.dtype not in (np.float32, np.float64):
         raise ValueError(f"evaluate_depth_numpy: pred must be float32 and gt float32 or float64, got {pred.dtype} and {gt.dtype}")
-    pred, gt = _check_pair(pred, gt, max_eval_len)
+    pred, gt = _check_pair(pred, gt, max_eval_len, resize)
+    pred = resize_prediction_numpy(pred, gt.shape[1:])                  # the identity unless `resize` let a mismatch through
     hi = gt.dtype.type(max_depth)
     valid = (gt > gt.dtype.type(1e-3)) & (gt < hi)
     xc = np.clip(pred, np.float32(1e-3), None)
@@ -88,10 +155,12 @@ def evaluate_depth_numpy(pred, gt, max_depth, max_eval_len=None):
     return _result((scale, shift, n), res + [int(used.sum())])
 
 
-def evaluate_depth(pred, gt, max_depth, max_eval_len=None, device="cuda", chunk_frames=None):
+def evaluate_depth(pred, gt, max_depth, max_eval_len=None, device="cuda", chunk_frames=None, resize=False):
     """Metrics of `pred` (float32 [N,H,W]) against `gt` (float32 or float64 [N,H,W]) on the device; numpy arrays or CUDA tensors.
     Device-resident tensors are used in place; host arrays are uploaded `chunk_frames` frames at a time (all at once when None), once
-    per pass. Returns a dict: the six METRICS, scale, shift, n_valid, n_frames_used. Runs on the current stream of the device."""
+    per pass. With `resize`, a prediction [N,h,w] at another size is resized to gt's grid first (resize_prediction), chunk by chunk
+    in both passes: the resized video is never resident as a whole and never returns to the host. Returns a dict: the six METRICS,
+    scale, shift, n_valid, n_frames_used. Runs on the current stream of the device."""
     import torch
     from . import ops
 
@@ -104,12 +173,12 @@ def evaluate_depth(pred, gt, max_depth, max_eval_len=None, device="cuda", chunk_
 
     pred = as_tensor(pred, "pred", (torch.float32,))
     gt = as_tensor(gt, "gt", (torch.float32, torch.float64))
-    pred, gt = _check_pair(pred, gt, max_eval_len)
+    pred, gt = _check_pair(pred, gt, max_eval_len, resize)
     on_dev = [t.device for t in (pred, gt) if t.is_cuda]
     dev = on_dev[0] if on_dev else torch.device(device)
     if dev.type != "cuda" or any(d != dev for d in on_dev):
         raise ValueError(f"evaluate_depth: needs one cuda device, got {device!r} / {[str(d) for d in on_dev]}")
-    N, H, W = pred.shape
+    N, H, W = gt.shape
     px = H * W
     step = N if chunk_frames is None else int(chunk_frames)
     if step <= 0:
@@ -127,13 +196,16 @@ def evaluate_depth(pred, gt, max_depth, max_eval_len=None, device="cuda", chunk_
         def on_device(t, lo, hi):
             return t[lo:hi].to(dev, non_blocking=False).contiguous()
 
+        def pred_chunk(lo, hi):                                         # at gt's size: deterministic, so both passes see the same bits
+            return resize_prediction(on_device(pred, lo, hi), (H, W))
+
         row = 0
         for (lo, hi), nb in zip(chunks, nblk):
-            ops.eval_lsq_partial(on_device(pred, lo, hi), on_device(gt, lo, hi), max_depth, work, row, nb)
+            ops.eval_lsq_partial(pred_chunk(lo, hi), on_device(gt, lo, hi), max_depth, work, row, nb)
             row += nb
         ops.eval_lsq_finish(work, row, fit)
         for lo, hi in chunks:
-            ops.eval_metric_partial(on_device(pred, lo, hi), on_device(gt, lo, hi), max_depth, fit, work, lo, bpf)
+            ops.eval_metric_partial(pred_chunk(lo, hi), on_device(gt, lo, hi), max_depth, fit, work, lo, bpf)
         ops.eval_metric_finish(work, N, bpf, res)
         host = out.cpu().numpy()                                        # the one device-to-host copy (synchronises)
     return _result(host[:3], host[3:])
@@ -155,17 +227,20 @@ def _host64(a, name, tail):
     return a
 
 
-def _check_tae(pred, gt, K, poses, mask):
-    """Argument checks shared by evaluate_tae and its twin; returns the cameras of _tae_cameras."""
-    if pred.ndim != 3 or gt.ndim != 3 or tuple(pred.shape) != tuple(gt.shape):
+def _check_tae(pred, gt, K, poses, mask, resize=False):
+    """Argument checks shared by evaluate_tae and its twin; returns the cameras of _tae_cameras. The mask is at gt's size."""
+    if resize and pred.ndim == 3 and gt.ndim == 3 and pred.shape[0] != gt.shape[0]:
+        raise ValueError(f"evaluate_tae: pred {tuple(pred.shape)} and gt {tuple(gt.shape)} differ in the number of frames")
+    mismatch = tuple(pred.shape) != tuple(gt.shape) and not (resize and pred.ndim == 3 and gt.ndim == 3)
+    if pred.ndim != 3 or gt.ndim != 3 or mismatch:
         raise ValueError(f"evaluate_tae: pred {tuple(pred.shape)} and gt {tuple(gt.shape)} must be equal [N,H,W]. The reference resizes a "
                          "mismatched prediction with cv2.resize; resizing is not part of this scorer - write the prediction at the "
                          "(cropped) ground-truth size")
     N = pred.shape[0]
-    if N < 2 or pred.shape[1] * pred.shape[2] == 0:
+    if N < 2 or pred.shape[1] * pred.shape[2] == 0 or gt.shape[1] * gt.shape[2] == 0:
         raise ValueError(f"evaluate_tae: needs at least two non-empty frames, got {tuple(pred.shape)} (the reference divides by 2 (N - 1))")
-    if mask is not None and tuple(mask.shape) != tuple(pred.shape):
-        raise ValueError(f"evaluate_tae: mask {tuple(mask.shape)} and pred {tuple(pred.shape)} differ in shape")
+    if mask is not None and tuple(mask.shape) != tuple(gt.shape):
+        raise ValueError(f"evaluate_tae: mask {tuple(mask.shape)} and gt {tuple(gt.shape)} differ in shape")
     K, poses = _host64(K, "K", (3, 3)), _host64(poses, "poses", (4, 4))
     if K.ndim == 2:
         K = np.broadcast_to(K, (N, 3, 3))
@@ -192,14 +267,15 @@ def _tae_result(fit, res, npairs):
             "pair_counts": np.array(res[1 + 2 * npairs:1 + 4 * npairs]).astype(np.int64).reshape(npairs, 2)}
 
 
-def evaluate_tae_numpy(pred, gt, K, poses, max_depth, mask=None):
+def evaluate_tae_numpy(pred, gt, K, poses, max_depth, mask=None, resize=False):
     """Host twin of evaluate_tae: the same arithmetic in vectorised numpy (last-wins through np.maximum.at on source indices).
     For tests; not a product path."""
     pred, gt = np.asarray(pred), np.asarray(gt)
     if pred.dtype != np.float32 or gt.dtype not in (np.float32, np.float64):
         raise ValueError(f"evaluate_tae_numpy: pred must be float32 and gt float32 or float64, got {pred.dtype} and {gt.dtype}")
     mask = None if mask is None else np.asarray(mask) != 0
-    cam = _check_tae(pred, gt, K, poses, mask)
+    cam = _check_tae(pred, gt, K, poses, mask, resize)
+    pred = resize_prediction_numpy(pred, gt.shape[1:])                  # the identity unless `resize` let a mismatch through
     fit = evaluate_depth_numpy(pred, gt, max_depth)
     N, H, W = pred.shape
     with np.errstate(all="ignore"):
@@ -231,13 +307,14 @@ def evaluate_tae_numpy(pred, gt, K, poses, max_depth, mask=None):
     return {"tae": float(tae), "scale": fit["scale"], "shift": fit["shift"], "n_valid": fit["n_valid"], "pair_errors": err, "pair_counts": cnt}
 
 
-def evaluate_tae(pred, gt, K, poses, max_depth, mask=None, device="cuda", chunk_pairs=None):
+def evaluate_tae(pred, gt, K, poses, max_depth, mask=None, device="cuda", chunk_pairs=None, resize=False):
     """Temporal alignment error of `pred` (float32 [N,H,W]) on the device. gt (float32 or float64 [N,H,W]) only takes part in the
     scale / shift fit, which is evaluate_depth's; K [N,3,3] or [3,3] and poses [N,4,4] (camera to world) go through the host; mask
     (bool or uint8 [N,H,W], optional) excludes target pixels. pred, gt and mask may be numpy arrays or CUDA tensors: device-resident
     tensors are used in place, host arrays are uploaded a few frames at a time. `chunk_pairs` bounds the winner planes (8 bytes per
-    pixel and pair; all pairs at once when None); the result does not depend on it. Returns a dict: tae, scale, shift, n_valid,
-    pair_errors and pair_counts [N-1, 2] (column 0: frame i into i+1). Runs on the current stream of the device."""
+    pixel and pair; all pairs at once when None); the result does not depend on it. With `resize`, a prediction [N,h,w] at another
+    size is resized to gt's grid first (resize_prediction), a few frames at a time wherever frames are fed. Returns a dict: tae, scale,
+    shift, n_valid, pair_errors and pair_counts [N-1, 2] (column 0: frame i into i+1). Runs on the current stream of the device."""
     import torch
     from . import ops
 
@@ -251,12 +328,12 @@ def evaluate_tae(pred, gt, K, poses, max_depth, mask=None, device="cuda", chunk_
     pred = as_tensor(pred, "pred", (torch.float32,))
     gt = as_tensor(gt, "gt", (torch.float32, torch.float64))
     mask = None if mask is None else as_tensor(mask, "mask", (torch.bool, torch.uint8))
-    cam_host = _check_tae(pred, gt, K, poses, mask)
+    cam_host = _check_tae(pred, gt, K, poses, mask, resize)
     on_dev = [t.device for t in (pred, gt, mask) if t is not None and t.is_cuda]
     dev = on_dev[0] if on_dev else torch.device(device)
     if dev.type != "cuda" or any(d != dev for d in on_dev):
         raise ValueError(f"evaluate_tae: needs one cuda device, got {device!r} / {[str(d) for d in on_dev]}")
-    N, H, W = pred.shape
+    N, H, W = gt.shape
     px, P = H * W, N - 1
     if px >= 2 ** 31 - 1:
         raise ValueError(f"evaluate_tae: a frame of {H} x {W} is too large (a pixel index + 1 must fit 31 bits)")
@@ -278,14 +355,17 @@ def evaluate_tae(pred, gt, K, poses, max_depth, mask=None, device="cuda", chunk_
         def on_device(t, lo, hi):
             return t[lo:hi].to(dev, non_blocking=False).contiguous()
 
+        def pred_chunk(lo, hi):                                                 # at gt's size: deterministic, the same bits every time
+            return resize_prediction(on_device(pred, lo, hi), (H, W))
+
         row = 0
         for (lo, hi), nb in zip(fit_chunks, nblk):
-            ops.eval_lsq_partial(on_device(pred, lo, hi), on_device(gt, lo, hi), max_depth, work, row, nb)
+            ops.eval_lsq_partial(pred_chunk(lo, hi), on_device(gt, lo, hi), max_depth, work, row, nb)
             row += nb
         ops.eval_lsq_finish(work, row, fit)
         for lo in range(0, P, step):
             hi = min(lo + step, P)                                              # pairs lo .. hi-1 touch frames lo .. hi
-            p = on_device(pred, lo, hi + 1)
+            p = pred_chunk(lo, hi + 1)
             m = None if mask is None else on_device(mask, lo, hi + 1).to(torch.uint8)
             ops.tae_splat(p, max_depth, fit, cam[lo:hi], winner)
             ops.tae_compare(p, m, max_depth, fit, cam[lo:hi], winner, work, lo, bpp)

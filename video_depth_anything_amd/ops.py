@@ -435,6 +435,16 @@ def tae_finish(workspace, npairs, blocks_per_plane, result):
     check(lib.vda_tae_finish(_p(workspace), npairs, blocks_per_plane, _p(result), _stream(workspace)), "vda_tae_finish")
 
 
+# ---- a prediction resized to the ground truth's grid (csrc/resize.hip) ---------------------------------------------------------
+def resize_linear(x, out):
+    """out [n,H,W] = x [n,h,w] resized with cv2's INTER_LINEAR arithmetic for float32 (include/vda.h); both device fp32, distinct."""
+    _req(x, F32, "x"), _req(out, F32, "out")
+    if x.dim() != 3 or out.dim() != 3 or x.shape[0] != out.shape[0] or x.numel() == 0 or out.numel() == 0 or x.device != out.device:
+        raise ValueError(f"resize_linear: x {tuple(x.shape)} on {x.device} and out {tuple(out.shape)} on {out.device} must be [n,h,w] and [n,H,W]")
+    (n, h, w), (H, W) = x.shape, out.shape[1:]
+    check(lib.vda_resize_linear_f32(_p(x), _p(out), n, h, w, H, W, _stream(x)), "vda_resize_linear_f32")
+
+
 # ---------------------------------------------------------------------------
 # Weight layouts the kernels expect (done once at load time, on the host or device)
 # ---------------------------------------------------------------------------
