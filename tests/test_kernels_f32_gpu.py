@@ -9,6 +9,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _exact import BILINEAR_EDGE_CASES, bilinear_id, check_sentinel, sentinel_out
+
 pytestmark = pytest.mark.gpu
 
 F16, F32 = torch.float16, torch.float32
@@ -233,6 +235,67 @@ def test_head_out_f32(ops):
     out = torch.empty(rows, dtype=F32, device="cuda")
     ops.head_out(dev(x), dev(w), 0.3, out, rows, Cp)
     close(out, F.relu(x @ w + 0.3), rtol=1e-5, atol=1e-5, what="head out f32")
+
+
+@pytest.mark.parametrize("h,w_,H,W_,B,Cc,with_add", BILINEAR_EDGE_CASES, ids=[bilinear_id(c) for c in BILINEAR_EDGE_CASES])
+def test_bilinear_nhwc_f32_edges(ops, h, w_, H, W_, B, Cc, with_add):
+    """Mild downsampling (the shared-rows path's third source row), single-row / single-column sources and outputs, channel counts
+    whose vectors per pixel do and do not divide the block (C = 192), with and without the `add` operand."""
+    x = rnd(B, Cc, h, w_, seed=146)
+    add = rnd(B, H, W_, Cc, seed=147) if with_add else None
+    out = sentinel_out(B * H * W_, Cc, Cc)
+    ops.bilinear_nhwc(dev(x.permute(0, 2, 3, 1).contiguous()), out, B, h, w_, H, W_, Cc, add=None if add is None else dev(add))
+    check_sentinel(out, B * H * W_, Cc, "bilinear f32")
+    ref = F.interpolate(x, size=(H, W_), mode="bilinear", align_corners=True).permute(0, 2, 3, 1)
+    close(out[:B * H * W_].reshape(B, H, W_, Cc), ref + add if with_add else ref, rtol=1e-5, atol=1e-5, what="bilinear f32 edges")
+
+
+@pytest.mark.parametrize("Cc", [32, 192])
+def test_bilinear_nhwc_f32_same_size_without_add_is_a_copy(ops, Cc):
+    B, h, w_ = 2, 8, 6
+    x = rnd(B, h, w_, Cc, seed=148)
+    out = sentinel_out(B * h * w_, Cc, Cc)
+    ops.bilinear_nhwc(dev(x), out, B, h, w_, h, w_, Cc)
+    check_sentinel(out, B * h * w_, Cc, "bilinear f32 same size")
+    assert torch.equal(out[:B * h * w_].reshape(B, h, w_, Cc).cpu(), x), "a same-size resize without add must be exact"
+
+
+@pytest.mark.parametrize("rows", [1, 63, 1000])
+@pytest.mark.parametrize("Cp", [32, 64])
+def test_head_out_f32_ignores_pad_channels(ops, Cp, rows):
+    """Channels [32, Cpad) hold NaN: only the 32 live ones may reach the result. rows = 1, 63: a partial block of 4-lane groups."""
+    x, w = rnd(rows, Cp, seed=149), rnd(32, seed=150)
+    x[:, 32:] = float("nan")
+    out = sentinel_out(rows, 1, 1)
+    ops.head_out(dev(x), dev(w), 0.3, out, rows, Cp)
+    check_sentinel(out, rows, 1, "head out f32")
+    assert bool(torch.isfinite(out[:rows]).all()), "a pad channel reached the result"
+    close(out[:rows, 0], F.relu(x[:, :32] @ w + 0.3), rtol=1e-5, atol=1e-5, what="head out f32")
+
+
+def test_depth_tail_chain_f32(ops):
+    """The fp32 forward's tail as it composes it: bilinear_nhwc_f32 (C = 32, no add) -> conv3x3 fp32 BIAS_RELU (32 -> 32, the 256x32
+    tile) -> head_out_f32 (Cpad 32), against the fp64 chain F.interpolate -> conv2d -> relu -> 1x1 -> relu."""
+    from video_depth_anything_amd import _lib
+    B, Cc, h, w_, H, W_ = 2, 32, 6, 7, 14, 14
+    x = rnd(B, Cc, h, w_, seed=151)
+    w2, b2 = rnd(32, Cc, 3, 3, seed=152, scale=(9 * Cc) ** -0.5), rnd(32, seed=153)
+    w3, b3 = rnd(32, seed=154, scale=32 ** -0.5), 0.2
+    M = B * H * W_
+    up, c2, depth = sentinel_out(M, Cc, Cc), sentinel_out(M, 32, 32), sentinel_out(M, 1, 1)
+    ops.bilinear_nhwc(dev(x.permute(0, 2, 3, 1).contiguous()), up, B, h, w_, H, W_, Cc)
+    ops.gemm(up, dev(ops.pack_conv3x3(w2, dtype=F32)), c2, _lib.EPI_BIAS_RELU_F16, M=M, N=32, K=9 * Cc, bias=dev(b2),
+             conv=(B, H, W_, Cc, H, W_, 1))
+    ops.head_out(c2, dev(w3), b3, depth, M, 32)
+    for buf, n, what in ((up, Cc, "upsample"), (c2, 32, "conv"), (depth, 1, "head out")):
+        check_sentinel(buf, M, n, f"tail chain: {what}")
+    r = F.interpolate(x.double(), size=(H, W_), mode="bilinear", align_corners=True)
+    r = F.relu(F.conv2d(r, w2.double(), b2.double(), padding=1)).permute(0, 2, 3, 1)
+    ref = F.relu(r @ w3.double() + b3).reshape(M)
+    y = depth[:M, 0].cpu()
+    assert bool(torch.isfinite(y).all()) and bool((ref > 0).any())
+    err = (y.double() - ref).abs()
+    assert bool((err <= 2e-5 + 2e-5 * ref.abs()).all()), f"tail chain: max err {float(err.max()):.4g} (ref absmax {float(ref.abs().max()):.4g})"
 
 
 # ---------------------------------------------------------------- bicubic kernels (shared by both precisions)

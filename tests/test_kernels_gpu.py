@@ -11,6 +11,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _exact import BILINEAR_EDGE_CASES, bilinear_id, check_sentinel, sentinel_out
+
 pytestmark = pytest.mark.gpu
 
 F16, F32 = torch.float16, torch.float32
@@ -740,6 +742,30 @@ def test_bilinear_nhwc(ops, h, w_, H, W_):
     close(out, ref, what="bilinear nhwc")
 
 
+@pytest.mark.parametrize("h,w_,H,W_,B,Cc,with_add", BILINEAR_EDGE_CASES, ids=[bilinear_id(c) for c in BILINEAR_EDGE_CASES])
+def test_bilinear_nhwc_edges(ops, h, w_, H, W_, B, Cc, with_add):
+    """Mild downsampling (the shared-rows path's third source row), single-row / single-column sources and outputs, channel counts
+    whose vectors per pixel do and do not divide the block (C = 192), with and without the `add` operand. One margin pixel behind
+    the output must keep its NaN."""
+    x = rnd(B, Cc, h, w_, seed=146).to(F16)
+    add = rnd(B, H, W_, Cc, seed=147).to(F16) if with_add else None
+    out = torch.full((B * H * W_ + 1, Cc), float("nan"), dtype=F16, device="cuda")
+    ops.bilinear_nhwc(dev(x.permute(0, 2, 3, 1).contiguous()), out, B, h, w_, H, W_, Cc, add=None if add is None else dev(add))
+    assert bool(out[-1].isnan().all()), "wrote past the last output pixel"
+    assert bool(torch.isfinite(out[:-1]).all()), "output pixels left unwritten"
+    ref = F.interpolate(x.float(), size=(H, W_), mode="bilinear", align_corners=True).permute(0, 2, 3, 1)
+    close(out[:-1].reshape(B, H, W_, Cc), ref + add.float() if with_add else ref, what="bilinear nhwc edges")
+
+
+@pytest.mark.parametrize("Cc", [32, 192])
+def test_bilinear_nhwc_same_size_without_add_is_a_copy(ops, Cc):
+    B, h, w_ = 2, 8, 6
+    x = rnd(B, h, w_, Cc, seed=148).to(F16)
+    out = torch.full((B, h, w_, Cc), float("nan"), dtype=F16, device="cuda")
+    ops.bilinear_nhwc(dev(x), out, B, h, w_, h, w_, Cc)
+    assert torch.equal(out.cpu(), x), "a same-size resize without add must be exact"
+
+
 def test_bilinear_plane_and_identity(ops):
     x = rnd(3, 20, 30, seed=48)
     out = torch.empty(3, 45, 50, dtype=F32, device="cuda")
@@ -775,6 +801,19 @@ def test_head_out_and_normalize(ops):
     ops.normalize_u8(torch.from_numpy(fr).cuda(), o, 3, 14, 28)
     ref = ((fr.astype(np.float32) / 255.0 - [0.485, 0.456, 0.406]) / [0.229, 0.224, 0.225]).astype(np.float32).transpose(0, 3, 1, 2)
     np.testing.assert_array_equal(o.cpu().numpy(), ref)
+
+
+@pytest.mark.parametrize("rows", [1, 63, 1000])
+@pytest.mark.parametrize("Cp", [32, 64])
+def test_head_out_ignores_pad_channels(ops, Cp, rows):
+    """Channels [32, Cpad) hold NaN: only the 32 live ones may reach the result. rows = 1, 63: a partial block of 4-lane groups."""
+    x, w = rnd(rows, Cp, seed=149).to(F16), rnd(32, seed=150)
+    x[:, 32:] = float("nan")
+    out = sentinel_out(rows, 1, 1)
+    ops.head_out(dev(x), dev(w), 0.3, out, rows, Cp)
+    check_sentinel(out, rows, 1, "head out")
+    assert bool(torch.isfinite(out[:rows]).all()), "a pad channel reached the result"
+    close(out[:rows, 0], F.relu(x[:, :32].float() @ w + 0.3), rtol=1e-4, atol=1e-4, what="head out")
 
 
 @pytest.mark.parametrize("Cc,h,w_,H,W_", [(64, 20, 37, 20, 37), (128, 9, 33, 9, 33), (64, 12, 12, 21, 21), (128, 17, 19, 29, 45)])
