@@ -21,6 +21,7 @@
  */
 #ifndef VDA_H
 #define VDA_H
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -428,6 +429,28 @@ int vda_tae_finish(const double* partial, int npairs, int blocks_per_plane, doub
  * it bit for bit. Non-finite inputs are outside the contract. Refused: null or misaligned (4-byte) pointers, a size < 1, in == out,
  * a row of more than 2^30 pixels, n * H or n * h beyond 31 bits. One launch on `stream`, no allocation, no synchronisation. */
 int vda_resize_linear_f32(const float* in, float* out, int n, int h, int w, int H, int W, vda_stream_t stream);
+
+/* ---- metric depth unprojected to coloured points, as the bytes of a PLY vertex list (metric_depth/depth_to_pointcloud.py) ----
+ * For frame i, pixel (row r, column c), z = depth[i, r, c], every operation in fp64 and rounded once (no fused multiply-add):
+ *   X = (((double)c - cx) / fx) * (double)z      Y = (((double)r - cy) / fy) * (double)z      Z = (double)z
+ * the IEEE division first, the product second (the reference's cx = W / 2.0, cy = H / 2.0 are the caller's to pass). A NaN X or Y
+ * (z NaN, or 0 * Inf) is stored as the quiet NaN 0x7ff8000000000000: IEEE leaves the sign of a generated NaN to the machine.
+ * One packed little-endian record per kept pixel, in row-major order:
+ *   record_f32 = 0: 27 bytes, doubles X, Y, Z at 0 / 8 / 16, r, g, b at 24 / 25 / 26 (what Open3D writes)
+ *   record_f32 = 1: 15 bytes, floats at 0 / 4 / 8 (X and Y the fp64 results rounded once, Z the depth's own bits), r, g, b at 12 / 13 / 14
+ * max_depth = 0 keeps every pixel, values untouched (zeros, negatives, NaN, Inf included); max_depth = m > 0 keeps a pixel iff
+ * 0 < z <= m (NaN is dropped). depth: fp32 [n,h,w]; rgb: uint8 [n,h,w,3]; records: n slots of vda_pointcloud_frame_stride bytes
+ * (h * w records rounded up to 16 bytes), slot i holds counts[i] records from its first byte, the rest of it is not written;
+ * counts: int32 [n]. All on the device. workspace: vda_pointcloud_workspace_bytes(n, h, w) device bytes, contents irrelevant.
+ * Deterministic: a count pass, an integer scan and a write pass, no atomics. Refused: null pointers, a size < 1, fx or fy zero or
+ * not finite, cx or cy not finite, max_depth negative or NaN, record_f32 outside {0, 1}, a workspace too small, depth, counts or
+ * workspace not 4-byte aligned, records not 16-byte aligned, h * w > 2^30 or n * ceil(h * w / 256) > 2^31 - 1 (a pixel index and
+ * a grid index are ints). Four launches on `stream` (two with max_depth = 0), no allocation, no synchronisation. */
+size_t vda_pointcloud_frame_stride(int h, int w, int record_f32);       /* 0 for a size < 1 or record_f32 outside {0, 1} */
+size_t vda_pointcloud_workspace_bytes(int n, int h, int w);             /* 0 for a size < 1 */
+int vda_pointcloud_f32(const float* depth, const uint8_t* rgb, void* records, int* counts, void* workspace, size_t workspace_bytes,
+                       int n, int h, int w, double fx, double fy, double cx, double cy, float max_depth, int record_f32,
+                       vda_stream_t stream);
 
 /* ================================================================ handle API: the model behind one pointer
  * What a C / C++ host binds in place of the reference's Python class (the seam of SURVEY.md section 8b):

@@ -445,6 +445,33 @@ def resize_linear(x, out):
     check(lib.vda_resize_linear_f32(_p(x), _p(out), n, h, w, H, W, _stream(x)), "vda_resize_linear_f32")
 
 
+# ---- metric depth unprojected to PLY vertex records (csrc/pointcloud.hip) -------------------------------------------------------
+def pointcloud_frame_stride(h, w, record_f32):
+    """Bytes of one frame's slot in the record buffer: h * w records of 15 (record_f32) or 27 bytes, rounded up to 16."""
+    return int(lib.vda_pointcloud_frame_stride(h, w, int(bool(record_f32))))
+
+
+def pointcloud_workspace_bytes(n, h, w):
+    return int(lib.vda_pointcloud_workspace_bytes(n, h, w))
+
+
+def pointcloud(depth, rgb, records, counts, workspace, fx, fy, cx, cy, max_depth=None, record_f32=False):
+    """records (device uint8, n slots of pointcloud_frame_stride bytes) and counts (device int32 [n]) = the PLY vertex records of
+    depth [n,h,w] (device fp32) coloured by rgb [n,h,w,3] (device uint8): include/vda.h. max_depth None keeps every pixel."""
+    _req(depth, F32, "depth"), _req(rgb, torch.uint8, "rgb"), _req(records, torch.uint8, "records"), _req(counts, torch.int32, "counts")
+    _req(workspace, torch.uint8, "workspace")
+    if depth.dim() != 3 or depth.numel() == 0 or tuple(rgb.shape) != tuple(depth.shape) + (3,):
+        raise ValueError(f"pointcloud: depth {tuple(depth.shape)} and rgb {tuple(rgb.shape)} must be [n,h,w] and [n,h,w,3]")
+    if len({t.device for t in (depth, rgb, records, counts, workspace)}) != 1:
+        raise ValueError("pointcloud: the operands live on different devices")
+    n, h, w = depth.shape
+    if counts.numel() < n or records.numel() < n * pointcloud_frame_stride(h, w, record_f32):
+        raise ValueError(f"pointcloud: counts ({counts.numel()}) or records ({records.numel()} bytes) too small for {n} frames of {h} x {w}")
+    check(lib.vda_pointcloud_f32(_p(depth), _p(rgb), _p(records), _p(counts), _p(workspace), workspace.numel(), n, h, w, float(fx), float(fy),
+                                 float(cx), float(cy), 0.0 if max_depth is None else float(max_depth), int(bool(record_f32)), _stream(depth)),
+          "vda_pointcloud_f32")
+
+
 # ---------------------------------------------------------------------------
 # Weight layouts the kernels expect (done once at load time, on the host or device)
 # ---------------------------------------------------------------------------
