@@ -1,4 +1,4 @@
-"""Exact-integer inputs and references for the fp32 GEMM's linear surface (dense, conv3x3, ConvTranspose, patch embed).
+"""Exact-integer inputs and references for the linear surface of the fp32 and fp16 GEMMs (dense, conv3x3, ConvTranspose, patch embed).
 
 With small integer operands every product and every partial sum of a contraction is an integer; while all of them stay below
 2**24 they are exactly representable in fp32, so an fp32 fmaf / MFMA chain reproduces the fp64 result BIT FOR BIT in any
@@ -7,13 +7,19 @@ The condition is checked, not assumed: `assert_exact_safe` takes the reference e
 bounds every partial sum of every ordering.
 
 The case lists and input builders live here so that tests/test_exact_inputs.py (CPU: the inputs meet the condition and the
-equalities can fail) and tests/test_kernels_f32_edges_gpu.py (GPU: the kernels meet them) use the same tensors."""
+equalities can fail) and tests/test_kernels_f32_edges_gpu.py (GPU: the kernels meet them) use the same tensors.
+
+The second half does the same for the fp16 GEMM (fp16 operands, fp32 accumulation, fp16 stores: a second condition, see there)
+and tests/test_kernels_f16_edges_gpu.py, and lists that file's launches as shapes (f16_launches) for the planner coverage test
+in tests/test_gemm_plan.py."""
 import torch
 import torch.nn.functional as F
 
-F32, F64 = torch.float32, torch.float64
+F16, F32, F64 = torch.float16, torch.float32, torch.float64
 EXACT_LIMIT = float(2 ** 24)
+FP16_EXACT_LIMIT = 2048.0             # every integer up to 2**11 is an fp16 value (every multiple of 2**-j up to 2**(11 - j))
 SENTINEL_BITS = 0x7FC5A5A5            # one fixed quiet-NaN bit pattern: never the result of arithmetic on finite inputs
+SENTINEL16_BITS = 0x7E5A              # the same for fp16 buffers
 NAN = float("nan")
 
 
@@ -40,11 +46,18 @@ def sentinel_out(M, N, ldc, extra_rows=8):
     return torch.full((M + extra_rows, ldc), SENTINEL_BITS, dtype=torch.int32, device="cuda").view(F32)
 
 
+def sentinel_out_f16(M, N, ldc, extra_rows=8):
+    """The fp16 twin: device fp16 [M + extra_rows, ldc] holding SENTINEL16_BITS everywhere."""
+    assert 0 < N <= ldc and M > 0 and extra_rows >= 0
+    return torch.full((M + extra_rows, ldc), SENTINEL16_BITS, dtype=torch.int16, device="cuda").view(F16)
+
+
 def check_sentinel(buf, M, N, what=""):
-    bits = buf.view(torch.int32).cpu()
-    assert bool((bits[M:] == SENTINEL_BITS).all()), f"{what}: wrote past the last row ({int((bits[M:] != SENTINEL_BITS).sum())} elements)"
-    assert bool((bits[:M, N:] == SENTINEL_BITS).all()), f"{what}: wrote into the columns [N, ldc) ({int((bits[:M, N:] != SENTINEL_BITS).sum())} elements)"
-    left = bits[:M, :N] == SENTINEL_BITS
+    """fp32 or fp16 buffer of sentinel_out / sentinel_out_f16: the pattern is that of the buffer's dtype."""
+    bits, pat = (buf.view(torch.int16).cpu(), SENTINEL16_BITS) if buf.dtype == F16 else (buf.view(torch.int32).cpu(), SENTINEL_BITS)
+    assert bool((bits[M:] == pat).all()), f"{what}: wrote past the last row ({int((bits[M:] != pat).sum())} elements)"
+    assert bool((bits[:M, N:] == pat).all()), f"{what}: wrote into the columns [N, ldc) ({int((bits[:M, N:] != pat).sum())} elements)"
+    left = bits[:M, :N] == pat
     assert not bool(left.any()), f"{what}: {int(left.sum())} elements of the output left unwritten"
 
 
@@ -204,3 +217,326 @@ BILINEAR_EDGE_CASES = [
 
 def bilinear_id(c):
     return "%dx%d-%dx%d-B%d-C%d-%s" % (c[:6] + ("add" if c[6] else "noadd",))
+
+
+# ================================================================================================ the fp16 GEMM (gemm.hip and its tile families)
+# fp16 operands, fp32 accumulation, most outputs fp16. Two conditions make the fp64 reference the only admissible result:
+#   1. every partial sum of every ordering stays below 2**24 (as above: the |operand| reference bounds them), and
+#   2. every value a kernel STORES as fp16 or reads back as fp16 (outputs, fp16 residuals, the hi plane of the split epilogue) is a
+#      multiple of `step` with |v| <= 2048 * step in the real reference: an fp16 value, so the one final rounding is exact too (and
+#      the lo plane of the split epilogue, fp16(x - hi), is exactly 0).
+# Operands are small integers (exact in fp16); the LayerNorm-folded epilogue multiplies by rstd in {0.5, 1, 2}: step = 0.5 there.
+EPI = dict(BIAS_F16=0, BIAS_GELU_F16=1, BIAS_RELU_F16=2, SCALE_RES_F32=3, RES_F16=4, GEGLU_F16=5, PATCH_F32=6, CONVT_F16=7, BIAS_F32=8,
+           SCALE_RES_F32_H=9, SCALE_RES_SPLIT=10, LN_BIAS_F16=11, LN_GELU_F16=12)          # include/vda.h (test_exact_inputs.py holds them to _lib)
+# vda_gemm_set_variant values: the parameters of test_kernels_gpu.py's gemm_variant fixture
+VARIANTS16 = [-1, 0, 1, 2, 3, 4, 5, 7, 9, 8, 5 + 16 * 64, 10, 11]
+NO_LARGE_TILE = (-1, 0, 7)       # variants that force no large tile (7 forces the LDS conv; dense A stays on the 128-row kernel under it)
+
+
+def assert_exact_safe_f16(bounds, outputs_f16, step=1.0):
+    """bounds: |operand| references (fp64) as for assert_exact_safe, in units of `step`; outputs_f16: the REAL references (fp64) of
+    everything stored or re-read as fp16: multiples of step, at most 2048 steps from zero."""
+    assert_exact_safe(*[b / step for b in bounds])
+    assert outputs_f16, "nothing stored as fp16 to check"
+    for v in outputs_f16:
+        assert v.dtype == F64
+        u = v / step
+        assert bool((u == u.round()).all()), f"not a multiple of {step}"
+        top = float(u.abs().max())
+        assert top <= FP16_EXACT_LIMIT, f"|value| reaches {top:.0f} steps of {step} > 2048: its fp16 rounding is not exact"
+        assert torch.equal(v.to(F16).double(), v)
+
+
+def guarded(t, rows_after=8, pad_elems=0):
+    """A host tensor as a device view of a larger allocation that holds NaN everywhere else: rows_after rows (elements, for a
+    vector) behind it, and at least pad_elems elements on EITHER side (a conv input: (W + 2) * Cin, one padded image row). The
+    view starts 16-byte aligned. A clamp or a bound that is off by one then reads a NaN, not a harmless zero or a neighbour."""
+    assert t.is_floating_point() and not t.is_cuda
+    unit = 16 // t.element_size()
+    front = -(-pad_elems // unit) * unit
+    back = max(rows_after * (t.shape[-1] if t.dim() >= 2 else 1), pad_elems)
+    n = t.numel()
+    buf = torch.full((front + n + back,), NAN, dtype=t.dtype, device="cuda")
+    buf[front:front + n] = t.reshape(-1).cuda()
+    v = buf[front:front + n].view(t.shape)
+    assert v.data_ptr() % 16 == 0 and v.is_contiguous()
+    return v
+
+
+def pad_cols(t, ld, dtype):
+    """[rows, n] -> host [rows, ld] of dtype with NaN in the columns [n, ld)."""
+    rows, n = t.shape
+    o = torch.full((rows, ld), NAN, dtype=dtype)
+    o[:, :n] = t.to(dtype)
+    return o
+
+
+# ------------------------------------------------------------------------------------------------ dense A
+# (M, N, K, lda, ldc): K % 64 == 0, lda % 8 == 0; N % 8 == 0 and ldc % 8 == 0 except in the last case
+DENSE16_CASES = [
+    (1, 8, 64, 64, 8),               # M == 1 (every staged row but one is the clamp), N below every tile width, one K step: no steady state in any pipeline
+    (129, 72, 128, 136, 80),         # M one past a 128-row tile, N one 8-column segment past 64, lda > K, ldc > N
+    (191, 128, 192, 192, 128),       # one short of a 192-row tile, three K steps
+    (193, 136, 192, 200, 136),       # one past it, N one segment past 128
+    (255, 256, 64, 64, 256),         # one short of a 256-row tile
+    (257, 264, 320, 320, 272),       # one past it, N one segment past 256, five K steps: the 8-phase kernel's A slots (3) and W slots (2) out of phase
+    (385, 384, 448, 448, 384),       # the 192 x 384 tile exactly (variant 10), seven K steps
+    (383, 392, 64, 72, 392),         # one segment past it: N % 384 != 0, variant 10 falls through to 256 x 128
+    (513, 768, 1536, 1536, 768),     # the model's longest K (24 steps), two column tiles of 384, three of 256
+    (130, 36, 64, 64, 36),           # N % 8 != 0: the 128-row kernel's 4-column stores; every forced large tile must refuse it
+]
+
+
+def dense16_inputs(case):
+    """Integer operands as fp32 host tensors (each is its own fp16 rounding). A [M, K] in [-3, 3] ({-1, 0, 1} where K >= 448), W in
+    [-2, 2]; bias, res, res2 in [-4, 4]; gamma, ln_w, ln_b, mean in [-2, 2]; rstd in {0.5, 1, 2}. (K >= 448: ln_w in {-1, 0, 1} too - with [-2, 2] the LayerNorm-folded
+    reference of the K = 1536 case reaches 1475 = 2950 half-steps, past what fp16 holds at a step of 0.5.)"""
+    M, N, K, lda, ldc = case
+    s = 5000 + 17 * DENSE16_CASES.index(case)
+    a = 1 if K >= 448 else 3
+    rstd = torch.tensor([0.5, 1.0, 2.0])[ints((M,), 0, 2, s + 9).long()]
+    return dict(A=ints((M, K), -a, a, s), W=ints((N, K), -2, 2, s + 1), bias=ints((N,), -4, 4, s + 2), gamma=ints((N,), -2, 2, s + 3),
+                res=ints((M, N), -4, 4, s + 4), res2=ints((M, N), -4, 4, s + 5), ln_w=ints((K,), -a if a == 1 else -2, a if a == 1 else 2, s + 6), ln_b=ints((K,), -2, 2, s + 7),
+                mean=ints((M,), -2, 2, s + 8), rstd=rstd)
+
+
+def fold_ln(d):
+    """vda_fold_ln_weight in the dtype of d: Wf = W * ln_w, c1 = row sums of Wf, c2 = bias + W ln_b."""
+    Wf = d["W"] * d["ln_w"]
+    return Wf, Wf.sum(1), d["bias"] + d["W"] @ d["ln_b"]
+
+
+def dense16_refs(d):
+    """Every exact dense epilogue's reference in the dtype of d (fp64 from the tests; fp32 to show the two agree)."""
+    lin = d["A"] @ d["W"].t() + d["bias"]
+    Wf, c1, c2 = fold_ln(d)
+    stream = d["res"] + d["res2"] + d["gamma"] * lin            # the split epilogue: (hi + lo) + gamma * (A W^T + b)
+    r = dict(bias_f16=lin, bias_f16_no_bias=lin - d["bias"], bias_f32=lin, bias_relu=F.relu(lin), scale_res_in_place_gamma=d["res"] + d["gamma"] * lin,
+             scale_res_h_separate_out=d["res"] + lin, res=lin + d["res"], res_res2=lin + d["res"] + d["res2"],
+             ln_bias=d["rstd"][:, None] * (d["A"] @ Wf.t() - d["mean"][:, None] * c1) + c2)
+    if d["W"].shape[0] % 64 == 0:
+        r.update(split=stream, split_pos=stream - d["mean"][:, None])
+    return r
+
+
+DENSE16_F32_OUT = ("bias_f32", "scale_res_in_place_gamma")       # every other exact dense epilogue stores fp16
+
+
+def dense16_check(inp):
+    """Both conditions for every exact epilogue of one case; returns the fp64 references."""
+    d = {k: v.double() for k, v in inp.items()}
+    a = {k: v.abs() for k, v in d.items()}
+    ra, r = dense16_refs(a), dense16_refs(d)
+    ln_a, ln = ra.pop("ln_bias"), r["ln_bias"]
+    stored = [v for k, v in r.items() if k not in DENSE16_F32_OUT and k != "ln_bias"]
+    assert_exact_safe_f16(list(ra.values()), stored + [d["res"], d["res2"]])
+    assert_exact_safe_f16([ln_a], [ln], step=0.5)
+    return r
+
+
+# lda == 0, the broadcast row of vda.h: every output row is row 0's result. (M, N, K)
+BROADCAST16_CASES = [(300, 136, 128)]
+
+
+# The persistent kernels' tile order (K = 64: a few milliseconds each). M from the CU count so that 256-row tiles number ncu plus a few:
+# one full round and a short last one.  N = 2048: nbn = 8, the L2-blocked walk (it needs a full round); N = 1024: nbn = 4, the last
+# partial round dealt by row panel (per_xcd % nbn == 0); N = 768: nbn = 3, the plain mapping with a partial last round.
+WALK16_N = [2048, 1024, 768]
+WALK16_VARIANTS = [-1, 3, 4, 5, 9, 5 + 16 * 64]
+
+
+def walk16_case(ncu, N):
+    rt = -(-(ncu + 5) // (N // 256))
+    return (256 * rt - 37, N, 64)
+
+
+def split16_case(ncu):
+    """The smallest kind of shape the automatic path row-splits (plan_split in gemm.hip): K = 4096, one round of 256-row tiles over
+    nbn = 8 column tiles + 2049 rows on 192-row tiles."""
+    return (256 * (ncu // 8) + 2049, 2048, 4096)
+
+
+def walk16_inputs(case, seed=5900):
+    M, N, K = case
+    a = 1 if K >= 448 else 3
+    return dict(A=ints((M, K), -a, a, seed + N), W=ints((N, K), -2, 2, seed + N + 1), bias=ints((N,), -4, 4, seed + N + 2))
+
+
+# ------------------------------------------------------------------------------------------------ patch embed / ConvTranspose epilogues (dense A)
+# (frames, P, N, K, ldc): M = frames * P rows scatter to frames * (P + 1) token rows, row 0 of each frame left to vda_cls_rows
+PATCH16_CASES = [(130, 1, 72, 128, 72), (130, 1, 136, 128, 144), (43, 6, 72, 128, 80), (43, 6, 136, 128, 136)]
+
+
+def patch16_inputs(case):
+    fr, P, N, K, ldc = case
+    s = 6000 + 17 * PATCH16_CASES.index(case)
+    return dict(A=ints((fr * P, K), -3, 3, s), W=ints((N, K), -2, 2, s + 1), bias=ints((N,), -4, 4, s + 2), pos=ints((P + 1, N), -4, 4, s + 3))
+
+
+def patch16_ref(d, P):
+    """[frames, P, N]: the rows 1.. of each frame's tokens."""
+    N = d["W"].shape[0]
+    return (d["A"] @ d["W"].t() + d["bias"]).reshape(-1, P, N) + d["pos"][1:]
+
+
+# (B, h, w, C, Cp), each with k in CONVT_K: K = Cp must be a multiple of 64 here; channels C..Cp-1 are the pad channels
+CONVT16_CASES = [
+    (1, 1, 1, 48, 64),       # M == 1
+    (3, 3, 2, 40, 64),       # three frames: the scatter's frame / row / column decomposition
+]
+
+
+def convt16_inputs(case, k):
+    B, h, w, C, Cp = case
+    s = 6501 + 17 * CONVT16_CASES.index(case) + k          # (seed 6500 has a zero in the last input channel of the 1 x 1 case, k = 4: a dropped k = C - 1 went unseen)
+    return dict(x=ints((B, C, h, w), -3, 3, s), w=ints((C, C, k, k), -2, 2, s + 1), bias=ints((C,), -4, 4, s + 2))
+
+
+# ------------------------------------------------------------------------------------------------ conv3x3
+# (B, H, W, Cin, Cout, stride, relu_in, ldc)
+CONV16_CASES = [
+    (1, 1, 1, 64, 8, 1, False, 8),          # M == 1: eight of the nine taps are padding
+    (1, 2, 3, 64, 32, 2, False, 32),        # even H at stride 2: the last window row is one real row + pad
+    (2, 8, 10, 64, 72, 2, True, 80),        # even H and W at stride 2, relu_in, N one segment past 64, ldc > N
+    (3, 9, 11, 64, 64, 1, True, 64),        # windows cross frame borders inside a tile; the C = 64 persistent LDS kernel's shape
+    (1, 5, 5, 128, 136, 1, False, 136),     # N one segment past 128, two K steps per tap
+    (1, 17, 33, 64, 24, 1, False, 32),      # the per-pass LDS kernel, Cout no multiple of 32; H = 2 TH + 1, W = TW + 1 (conv_lds.hip: TH = 8, TW = 32)
+    (2, 20, 37, 192, 256, 1, True, 256),    # three K steps per tap, a full 256-wide tile
+]
+CONV16_EPIS = ["bias_f16", "no_bias", "bias_relu", "res", "res_res2"]      # BIAS_F16, BIAS_RELU_F16, RES_F16: what the conv families are built for
+
+
+def conv16_id(c):
+    return "B%d-%dx%d-Cin%d-Cout%d-s%d-relu%d-ldc%d" % (c[:6] + (int(c[6]), c[7]))
+
+
+def conv16_inputs(case):
+    B, H, W, Cin, Cout, stride, _, _ = case
+    s = 7000 + 17 * CONV16_CASES.index(case)
+    Ho, Wo = conv_out_size(H, W, stride)
+    return dict(x=ints((B, Cin, H, W), -3, 3, s), w=ints((Cout, Cin, 3, 3), -2, 2, s + 1), bias=ints((Cout,), -4, 4, s + 2),
+                res=ints((B, Ho, Wo, Cout), -4, 4, s + 3), res2=ints((B, Ho, Wo, Cout), -4, 4, s + 4))
+
+
+def conv16_refs(d, stride, relu_in):
+    lin = conv_ref(d["x"], d["w"], None, stride, relu_in)
+    b = d["bias"]
+    return dict(bias_f16=lin + b, no_bias=lin, bias_relu=F.relu(lin + b), res=lin + b + d["res"], res_res2=lin + b + d["res"] + d["res2"])
+
+
+def conv16_check(case, inp):
+    d = {k: v.double() for k, v in inp.items()}
+    a = {k: v.abs() for k, v in d.items()}
+    r = conv16_refs(d, case[5], case[6])
+    assert_exact_safe_f16([conv16_refs(a, case[5], False)["res_res2"]], list(r.values()) + [d["res"], d["res2"]])
+    return r
+
+
+# ------------------------------------------------------------------------------------------------ depth tail, identity resize (h == H, w == W)
+# (B, H, W) x C: conv3x3(C -> 32) + ReLU + conv1x1(32 -> 1) + ReLU; fp32 between the two convolutions and out (tail.hip), so only 2**24 applies
+TAIL16_CASES = [(1, 1, 1), (2, 5, 7), (1, 33, 65)]
+TAIL16_C = [64, 128]
+
+
+def tail16_inputs(case, Cc):
+    B, H, W = case
+    s = 8002 + 17 * TAIL16_CASES.index(case) + Cc          # (seeds 8000 and 8001 leave the 1 x 1 image's only output at 0 after the last ReLU: nothing to see)
+    return dict(x=ints((B, Cc, H, W), -3, 3, s), w2=ints((32, Cc, 3, 3), -2, 2, s + 1), b2=ints((32,), -4, 4, s + 2), w3=ints((32,), -2, 2, s + 3),
+                b3=float(ints((1,), -4, 4, s + 4)))
+
+
+def tail16_ref(d, b3):
+    y = F.relu(F.conv2d(d["x"], d["w2"], d["b2"], padding=1))
+    return F.relu((y * d["w3"].view(1, 32, 1, 1)).sum(1) + b3)
+
+
+# ------------------------------------------------------------------------------------------------ what the GPU file launches, as shapes
+def gemm16_fields(M, N, K, epi, lda=None, ldc=None, conv=None, convt=None, P=0, relu_in=False, tile_rows=0):
+    """The shape fields ops.gemm gives vda_gemm_args for these keywords: what vda_gemm_plan reads."""
+    f = dict(M=M, N=N, K=K, lda=K if lda is None else lda, ldc=N if ldc is None else ldc, a_mode=0 if conv is None else 1, epilogue=epi,
+             relu_in=int(relu_in), P=P, tile_rows=tile_rows)
+    if conv is not None:
+        f.update(zip(("cB", "cH", "cW", "cCin", "cHo", "cWo", "cStride"), conv))
+    if convt is not None:
+        f.update(zip(("tK", "tH", "tW", "tCout"), convt))
+    return f
+
+
+def plan16(L, fields, ncu=0, sched=False):
+    """(rc, records) of vda_gemm_plan as vda_gemm_f16 itself plans the call (ncu = 0: the current device's)."""
+    import ctypes as C
+    a = L.GemmArgs(**fields)
+    if sched:
+        a.sched = 64                 # "set": the planner never follows it
+    p = L.GemmPlan()
+    rc = L.lib.vda_gemm_plan(C.byref(a), 0, ncu, 0, C.byref(p))
+    return rc, ([p.rec[i] for i in range(p.n)] if rc == 0 else [])
+
+
+DENSE16_EXACT = ["bias_f16", "bias_f16_no_bias", "bias_f32", "bias_relu", "scale_res_in_place_gamma", "scale_res_h_separate_out", "res", "res_res2",
+                 "ln_bias", "split", "split_pos"]
+DENSE16_REAL = ["gelu", "geglu", "ln_gelu"]
+EPI_OF = dict(bias_f16="BIAS_F16", bias_f16_no_bias="BIAS_F16", bias_f32="BIAS_F32", bias_relu="BIAS_RELU_F16", scale_res_in_place_gamma="SCALE_RES_F32",
+              scale_res_h_separate_out="SCALE_RES_F32_H", res="RES_F16", res_res2="RES_F16", ln_bias="LN_BIAS_F16", split="SCALE_RES_SPLIT",
+              split_pos="SCALE_RES_SPLIT", gelu="BIAS_GELU_F16", geglu="GEGLU_F16", ln_gelu="LN_GELU_F16", no_bias="BIAS_F16")
+
+
+def dense16_epis(case):
+    """The epilogues the GPU file runs on a dense case: split needs N % 64 == 0, GEGLU N % 32 == 0 (its output is N / 2 wide, ldc = N / 2)."""
+    N = case[1]
+    return [e for e in DENSE16_EXACT + DENSE16_REAL if not (e.startswith("split") and N % 64) and not (e == "geglu" and N % 32)]
+
+
+def dense16_kw(case, epi):
+    M, N, K, lda, ldc = case
+    return dict(M=M, N=N, K=K, lda=lda, ldc=N // 2 if epi == "geglu" else ldc)
+
+
+def conv16_kw(case):
+    B, H, W, Cin, Cout, stride, relu_in, ldc = case
+    Ho, Wo = conv_out_size(H, W, stride)
+    return dict(M=B * Ho * Wo, N=Cout, K=9 * Cin, ldc=ldc, relu_in=relu_in, conv=(B, H, W, Cin, Ho, Wo, stride))
+
+
+def patch16_kw(case):
+    fr, P, N, K, ldc = case
+    return dict(M=fr * P, N=N, K=K, ldc=ldc, P=P)
+
+
+def convt16_kw(case, k):
+    B, h, w, C, Cp = case
+    return dict(M=B * h * w, N=k * k * Cp, K=Cp, ldc=Cp, convt=(k, h, w, Cp))
+
+
+ROWPOS16 = dict(M=257, N=264, K=192)        # row position independence: rows 0, 127, 128, 191, 192, 255, 256 of 257 hold the same A row
+ROWPOS16_ROWS = [0, 127, 128, 191, 192, 255, 256]
+
+
+def f16_launches(ncu):
+    """Every (variant, sched, fields) that tests/test_kernels_f16_edges_gpu.py hands to vda_gemm_f16, in no particular order: the planner
+    coverage test (CPU) walks this list, the GPU file asserts after every launch that the kernel that ran is the one planned."""
+    for v in VARIANTS16:
+        for case in DENSE16_CASES:
+            for e in dense16_epis(case):
+                yield v, False, gemm16_fields(epi=EPI[EPI_OF[e]], **dense16_kw(case, e))
+        for M, N, K in BROADCAST16_CASES:
+            for e in ("BIAS_F16", "SCALE_RES_F32"):
+                yield v, False, gemm16_fields(M, N, K, EPI[e], lda=0)
+        for case in PATCH16_CASES:
+            yield v, False, gemm16_fields(epi=EPI["PATCH_F32"], **patch16_kw(case))
+        for case in CONVT16_CASES:
+            for k in CONVT_K:
+                yield v, False, gemm16_fields(epi=EPI["CONVT_F16"], **convt16_kw(case, k))
+        for e in ("BIAS_F16", "BIAS_GELU_F16"):
+            yield v, False, gemm16_fields(epi=EPI[e], **ROWPOS16)
+        for case in CONV16_CASES:
+            for e in CONV16_EPIS:
+                yield v, False, gemm16_fields(epi=EPI[EPI_OF[e]], **conv16_kw(case))
+    for v in WALK16_VARIANTS:
+        for N in WALK16_N:
+            M, N, K = walk16_case(ncu, N)
+            yield v, False, gemm16_fields(M, N, K, EPI["BIAS_F16"])
+            if v in (-1, 5 + 16 * 64):
+                yield v, True, gemm16_fields(M, N, K, EPI["BIAS_F16"])
+    M, N, K = split16_case(ncu)
+    yield -1, False, gemm16_fields(M, N, K, EPI["BIAS_F16"])

@@ -6,9 +6,12 @@ For every dense, conv3x3, ConvTranspose and patch-embed case of tests/_exact.py:
   3. four indexing mistakes a kernel could make, restated in plain torch, each break the equality on the case's inputs:
      one k index dropped, one conv tap shifted by a pixel, zero padding replaced by edge clamping, two adjacent output columns
      swapped. (Tap shift: conv3x3 and the patch embed's 14x14 window; padding: conv3x3, the only op that pads.)
-A case whose inputs let a mistake through would make its GPU test vacuous for that mistake: the inputs are changed, not the check."""
+A case whose inputs let a mistake through would make its GPU test vacuous for that mistake: the inputs are changed, not the check.
+
+The second half of the file does the same for the fp16 GEMM's cases (tests/test_kernels_f16_edges_gpu.py), see there."""
 import pytest
 import torch
+import torch.nn.functional as F
 
 import _exact as E
 
@@ -143,3 +146,179 @@ def test_helpers_refuse_what_they_should():
     x = E.ints((1000,), -3, 3, 5)
     assert x.dtype == torch.float32 and float(x.min()) == -3 and float(x.max()) == 3 and torch.equal(x, E.ints((1000,), -3, 3, 5))
     assert bool(torch.tensor([E.SENTINEL_BITS], dtype=torch.int32).view(torch.float32).isnan().all()), "the sentinel is a NaN"
+
+
+# ================================================================================================ the fp16 GEMM's cases
+# The same three steps for tests/test_kernels_f16_edges_gpu.py, with the second condition (what is stored as fp16 is an fp16 value) and the
+# mistakes the fp16 kernels could make: a dropped 64-wide K step, a staged row taken from min(m + 1, M - 1), the last 8-column row
+# segment swapped with the one before it, a shifted tap, clamped padding.
+F16 = torch.float16
+
+
+def is_f16(t):
+    return torch.equal(t.to(F16).to(t.dtype), t)
+
+
+def next_row(t):
+    """Row m of the result from row min(m + 1, M - 1) of the operand."""
+    return t[torch.arange(1, t.shape[0] + 1).clamp_max(t.shape[0] - 1)]
+
+
+def last_segments_swapped(t):
+    N = t.shape[-1]
+    return torch.cat((t[..., :N - 16], t[..., N - 8:], t[..., N - 16:N - 8]), dim=-1)
+
+
+@pytest.mark.parametrize("case", E.DENSE16_CASES, ids=E.dense_id)
+def test_dense16_case_is_exact_and_sensitive(case):
+    M, N, K, lda, ldc = case
+    assert lda >= K and ldc >= N and K % 64 == 0 and lda % 8 == 0 and N % 4 == 0 and ldc % 4 == 0
+    assert (N % 8 == 0 and ldc % 8 == 0) or case == E.DENSE16_CASES[-1]
+    inp = E.dense16_inputs(case)
+    assert all(is_f16(v) for v in inp.values()), "every operand is its own fp16 rounding"
+    ref = E.dense16_check(inp)                                  # both conditions, every exact epilogue
+    f32 = E.dense16_refs(inp)                                   # torch's own fp32 evaluation, whatever its order
+    assert set(ref) == set(e for e in E.dense16_epis(case) if e in E.DENSE16_EXACT)
+    for k, r in ref.items():
+        assert torch.equal(f32[k].double(), r), k
+        if k not in E.DENSE16_F32_OUT:
+            assert is_f16(r), f"{k}: stored as fp16"
+    d = dbl(inp)
+    Wf, c1, c2 = E.fold_ln(d)
+    assert is_f16(Wf) and all(torch.equal(a.double(), b) for a, b in zip(E.fold_ln(inp), (Wf, c1, c2)))
+    assert bool((ref["bias_f16"] < 0).any()) and bool((ref["bias_f16"] > 0).any()), "ReLU has something to do"
+    assert len(set(inp["rstd"].tolist())) == (3 if M > 8 else 1) and (M == 1 or bool((inp["mean"] != 0).any()))
+
+    for name in ("bias_f16", "ln_bias"):
+        for kt in sorted({0, K // 128, K // 64 - 1}):           # a whole K step: what a pipeline that starts late or ends early loses
+            d2 = dict(d, A=d["A"].clone())
+            d2["A"][:, 64 * kt:64 * kt + 64] = 0
+            differs(E.dense16_refs(d2)[name], ref[name], f"{name}: dropping K step {kt}")
+        if M > 1:                                               # (M == 1 has no other row to take)
+            differs(E.dense16_refs(dict(d, A=next_row(d["A"])))[name], ref[name], f"{name}: rows staged from min(m + 1, M - 1)")
+    for name, r in ref.items():
+        if N >= 16:                                             # (N == 8 has one segment)
+            differs(last_segments_swapped(r), r, f"{name}: the last 8-column segment swapped with the one before")
+    if "split" in ref:
+        differs(ref["split_pos"], ref["split"], "ignoring the re-centring rows")
+        sums = ref["split"].reshape(M, N // 64, 64).sum(-1)
+        assert M == 1 or N == 64 or len(set(sums.flatten().tolist())) > 1, "the partial sums tell column blocks and rows apart"
+
+
+@pytest.mark.parametrize("case", E.BROADCAST16_CASES + [E.walk16_case(256, N) for N in E.WALK16_N] + [E.split16_case(256)], ids=lambda c: "M%d-N%d-K%d" % c)
+def test_walk16_and_broadcast_cases_are_exact_and_sensitive(case):
+    """(The broadcast case uses row 0 of the same inputs; the row-split case is checked on sampled rows, as on the GPU.)"""
+    M, N, K = case
+    inp = E.walk16_inputs(case)
+    rows = torch.arange(0, M, 61)
+    A = inp["A"][rows]
+    d = dict(A=A.double(), W=inp["W"].double(), bias=inp["bias"].double())
+    lin = d["A"] @ d["W"].t() + d["bias"]
+    E.assert_exact_safe_f16([d["A"].abs() @ d["W"].abs().t() + d["bias"].abs()], [lin])
+    assert torch.equal((A @ inp["W"].t() + inp["bias"]).double(), lin)
+    A2 = d["A"].clone()
+    A2[:, K - 64:] = 0
+    differs(A2 @ d["W"].t() + d["bias"], lin, "dropping the last K step")
+    differs(next_row(inp["A"].double())[rows] @ d["W"].t() + d["bias"], lin, "rows staged from min(m + 1, M - 1)")
+    differs(last_segments_swapped(lin), lin, "the last two 8-column segments swapped")
+    # a tile computed for the wrong place: tile (i, j) of 256 x 256 holds other values than its neighbours
+    assert not torch.equal(lin[:, :256], lin[:, 256:512]) if N >= 512 else True
+
+
+@pytest.mark.parametrize("case", E.PATCH16_CASES, ids=lambda c: "fr%d-P%d-N%d-K%d-ldc%d" % c)
+def test_patch16_case_is_exact_and_sensitive(case):
+    fr, P, N, K, ldc = case
+    inp = E.patch16_inputs(case)
+    d, a = dbl(inp), {k: v.double().abs() for k, v in inp.items()}
+    E.assert_exact_safe(E.patch16_ref(a, P))                    # fp32 out: the first condition alone
+    ref = E.patch16_ref(d, P)
+    assert all(is_f16(inp[k]) for k in ("A", "W")) and torch.equal(E.patch16_ref(inp, P).double(), ref)
+    differs(E.patch16_ref(dict(d, A=next_row(d["A"])), P), ref, "rows staged from min(m + 1, M - 1)")
+    differs(last_segments_swapped(ref), ref, "the last two 8-column segments swapped")
+    if P > 1:
+        differs(swapped(ref, 0, dim=1), ref, "two patch rows of a frame swapped")
+    differs(ref.flip(0), ref, "frames in the wrong order")
+
+
+@pytest.mark.parametrize("k", E.CONVT_K)
+@pytest.mark.parametrize("case", E.CONVT16_CASES, ids=lambda c: "B%d-%dx%d-C%d-Cp%d" % c)
+def test_convt16_case_is_exact_and_sensitive(case, k):
+    B, h, w, C, Cp = case
+    inp = E.convt16_inputs(case, k)
+    d, a = dbl(inp), {n: v.double().abs() for n, v in inp.items()}
+    ref = E.convt_ref(d["x"], d["w"], d["bias"], k)
+    E.assert_exact_safe_f16([E.convt_ref(a["x"], a["w"], a["bias"], k)], [ref])
+    assert Cp % 64 == 0 and all(is_f16(v) for v in inp.values())
+    assert torch.equal(E.convt_ref(inp["x"], inp["w"], inp["bias"], k).double(), ref)
+    w2 = d["w"].clone()
+    w2[C - 1] = 0
+    differs(E.convt_ref(d["x"], w2, d["bias"], k), ref, "dropping the last input channel")
+    differs(swapped(ref, 0, dim=2), ref, "two adjacent columns of the scatter swapped")
+    differs(swapped(ref, 0, dim=1), ref, "two adjacent rows of the scatter swapped")
+    differs(last_segments_swapped(ref), ref, "the last two 8-channel segments swapped")
+
+
+@pytest.mark.parametrize("case", E.CONV16_CASES, ids=E.conv16_id)
+def test_conv16_case_is_exact_and_sensitive(case):
+    B, H, W, Cin, Cout, stride, relu_in, ldc = case
+    assert Cin % 64 == 0 and Cout % 8 == 0 and ldc % 8 == 0 and ldc >= Cout
+    inp = E.conv16_inputs(case)
+    assert all(is_f16(v) for v in inp.values())
+    ref = E.conv16_check(case, inp)
+    f32 = E.conv16_refs(inp, stride, relu_in)
+    for k, r in ref.items():
+        assert torch.equal(f32[k].double(), r) and is_f16(r), k
+    d = dbl(inp)
+    lin = ref["bias_f16"]
+    assert lin.shape == inp["res"].shape
+    assert torch.equal(E.conv_by_taps(d["x"], d["w"], d["bias"], stride, relu_in), lin), "the tap-by-tap restatement is the convolution"
+    if relu_in:
+        differs(E.conv_ref(d["x"], d["w"], d["bias"], stride, False), lin, "ignoring relu_in")
+    for kt in sorted({0, Cin // 64 - 1}):                       # a K step = 64 input channels of one tap; the centre tap is inside the image for every pixel
+        w2 = d["w"].clone()
+        w2[:, 64 * kt:64 * kt + 64, 1, 1] = 0
+        differs(E.conv_ref(d["x"], w2, d["bias"], stride, relu_in), lin, f"dropping the K step (tap 4, channels {64 * kt}..)")
+    differs(E.conv_by_taps(d["x"], d["w"], d["bias"], stride, relu_in, shift_tap=(1, 1)), lin, "shifting the centre tap by a pixel")
+    differs(E.conv_by_taps(d["x"], d["w"], d["bias"], stride, relu_in, clamp_pad=True), lin, "edge clamping in place of zero padding")
+    flat = lin.reshape(-1, Cout)
+    if flat.shape[0] > 1:
+        differs(next_row(flat), flat, "output pixel m computed from the window of min(m + 1, M - 1)")
+    if Cout >= 16:
+        differs(last_segments_swapped(lin), lin, "the last two 8-channel segments swapped")
+
+
+@pytest.mark.parametrize("Cc", E.TAIL16_C)
+@pytest.mark.parametrize("case", E.TAIL16_CASES, ids=lambda c: "B%d-%dx%d" % c)
+def test_tail16_case_is_exact_and_sensitive(case, Cc):
+    inp = E.tail16_inputs(case, Cc)
+    b3 = inp.pop("b3")
+    assert all(is_f16(inp[k]) for k in ("x", "w2"))
+    d, a = dbl(inp), {k: v.double().abs() for k, v in inp.items()}
+    E.assert_exact_safe(E.tail16_ref(a, abs(b3)), F.conv2d(a["x"], a["w2"], a["b2"], padding=1))
+    ref = E.tail16_ref(d, b3)
+    assert torch.equal(E.tail16_ref(inp, b3).double(), ref) and bool((ref > 0).any())
+    w2 = d["w2"].clone()
+    w2[:, Cc - 64:, 1, 1] = 0
+    differs(E.tail16_ref(dict(d, w2=w2), b3), ref, "dropping the centre tap's last K step")
+    y = F.conv2d(d["x"], d["w2"], d["b2"], padding=1)
+    differs(F.relu((y * d["w3"].view(1, 32, 1, 1)).sum(1) + b3), ref, "no ReLU between the two convolutions")
+    xc = F.pad(d["x"], (1, 1, 1, 1), mode="replicate")
+    differs(F.relu((F.relu(F.conv2d(xc, d["w2"], d["b2"])) * d["w3"].view(1, 32, 1, 1)).sum(1) + b3), ref, "edge clamping in place of zero padding")
+
+
+def test_f16_helpers_refuse_what_they_should():
+    ok = torch.tensor([2048.0, -3.0], dtype=F64)
+    E.assert_exact_safe_f16([ok], [ok])
+    with pytest.raises(AssertionError, match="> 2048"):
+        E.assert_exact_safe_f16([ok], [torch.tensor([2049.0], dtype=F64)])
+    with pytest.raises(AssertionError, match="multiple"):
+        E.assert_exact_safe_f16([ok], [torch.tensor([0.5], dtype=F64)])
+    E.assert_exact_safe_f16([ok], [torch.tensor([1023.5], dtype=F64)], step=0.5)
+    with pytest.raises(AssertionError, match="> 2048"):
+        E.assert_exact_safe_f16([ok], [torch.tensor([1024.5], dtype=F64)], step=0.5)
+    with pytest.raises(AssertionError, match="2\\*\\*24"):
+        E.assert_exact_safe_f16([torch.tensor([2.0 ** 24], dtype=F64)], [ok])
+    assert E.FP16_EXACT_LIMIT == 2048.0
+    assert bool(torch.tensor([E.SENTINEL16_BITS], dtype=torch.int16).view(F16).isnan().all()), "the fp16 sentinel is a NaN"
+    from video_depth_anything_amd import _lib
+    assert all(getattr(_lib, "EPI_" + k) == v for k, v in E.EPI.items()) and len(E.EPI) == 13

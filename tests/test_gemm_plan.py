@@ -168,6 +168,64 @@ def test_planner_needs_no_operands_and_no_gpu(L):
     assert L.lib.vda_gemm_f16(C.byref(a), None) != 0 and b"null operand" in L.lib.vda_last_error()
 
 
+# ---------------------------------------------------------------- what the exact-integer fp16 edge tests run
+# A forced variant whose family has no instantiation for the epilogue (pick fails in plan_one) plans the 128-row kernel instead, silently.
+# With dense A: the 32x32x16-MFMA family (variants 1, 2) and the split-residual / LayerNorm-folded epilogues. With conv A: none - every
+# large-tile family is built for the three conv epilogues (BIAS_F16, BIAS_RELU_F16, RES_F16), the only ones the edge tests run on conv A.
+FALLBACK_128 = {(v, 0, e) for v in (1, 2) for e in (10, 11, 12)}        # (variant, A mode, epilogue)
+# Pairs a forced tile shape is not built for, which plan_one moves to ANOTHER large tile (never to the 128-row kernel): variant 8
+# (192 x 128) / 10 (192 x 384) / 11 (192 x 128 twice per CU) -> 256 x 128 of the same family, 5 + 16 * 64 (192 x 256) -> 256 x 256 8-phase.
+BUILT_192 = {8: (2, 192, 128, 1), 10: (2, 192, 384, 1), 11: (2, 192, 128, 2), 5 + 16 * 64: (3, 192, 256, 1)}
+
+
+def test_edge_tests_reach_every_built_kernel(L):
+    """tests/test_kernels_f16_edges_gpu.py asserts after every launch that the kernel that ran is the one vda_gemm_plan names; this is
+    the other half: over the launches of that file (tests/_exact.py: f16_launches, planned for 256 CUs) the planned kernels contain
+    EVERY (family, tile, workgroups per CU) that vda_gemm_built lists, for dense and for conv A - no built instantiation is beyond
+    vda_gemm_set_variant's reach. Refusals and fall-backs are the tabulated ones and no others."""
+    import _exact as E
+    lib = L.lib
+    lib.vda_gemm_set_debug(0)
+    built = {(fam, bm, bn, pc, mode) for fam in range(5) for bm in (0, 128, 192, 256) for bn in (32, 64, 128, 256, 384) for pc in (1, 2) for mode in (0, 1)
+             if any(lib.vda_gemm_built(fam, bm, bn, pc, mode, e) for e in range(13))}
+    assert len(built) == 22, sorted(built)
+    reached, fell_back, n, splits = set(), set(), 0, 0
+    for v, sched, f in E.f16_launches(256):
+        lib.vda_gemm_set_variant(v)
+        rc, recs = E.plan16(L, f, ncu=256, sched=sched)
+        n += 1
+        odd = f["N"] % 8 != 0 or f["ldc"] % 8 != 0
+        if odd and v not in E.NO_LARGE_TILE:                 # a refusal plan_one documents: the large tiles own 8-column row segments
+            assert rc != 0 and b"multiples of 8" in lib.vda_last_error(), (v, f)
+            continue
+        assert rc == 0, (v, f, lib.vda_last_error())
+        assert sum(r.rows for r in recs) == f["M"]
+        splits += len(recs) == 2
+        for r in recs:
+            key = (r.family, r.bm, r.bn, r.per_cu, r.a_mode)
+            assert lib.vda_gemm_built(*key, r.epilogue) == 1, (v, f)
+            reached.add(key)
+            if v in (0, 7) and not (v == 7 and r.family == L.FAM_CONV_LDS):
+                assert r.family == L.FAM_128
+            elif v > 0:
+                fb = (v, r.a_mode, r.epilogue) in FALLBACK_128
+                assert (r.family == L.FAM_128) == fb, (v, f, L.launch_name(r))
+                fell_back.add((v, r.a_mode, r.epilogue)) if fb else None
+                if v in BUILT_192 and r.a_mode == 0 and not fb:
+                    want = BUILT_192[v]
+                    is192 = lib.vda_gemm_built(*want, 0, r.epilogue) == 1 and (v != 10 or f["N"] % 384 == 0)
+                    assert (key[:4] == want) == is192, (v, f, L.launch_name(r))
+            if r.dyn:
+                assert sched and r.family == L.FAM_8P
+    lib.vda_gemm_set_variant(-1)
+    assert n > 2000 and splits == 1, "the row-split case splits, nothing else does"
+    assert fell_back == FALLBACK_128, "every tabulated fall-back is exercised"
+    assert reached == built, f"built but never planned: {sorted(built - reached)}; planned but not built: {sorted(reached - built)}"
+    for e in range(13):                                       # conv A: the three epilogues of E.CONV16_EPIS are what every conv family is built for
+        for fam, bm, bn in ((1, 256, 256), (2, 256, 128), (3, 256, 256), (3, 256, 128), (4, 0, 32), (4, 0, 64)):
+            assert lib.vda_gemm_built(fam, bm, bn, 1, 1, e) == (e in {E.EPI[E.EPI_OF[x]] for x in E.CONV16_EPIS})
+
+
 # ---------------------------------------------------------------- launch obeys plan (GPU)
 # (family, bm, bn, A mode, forced variant that names the family, tile_rows)
 TARGETS = [(0, 128, 64, 0, 0, 0), (0, 128, 128, 0, 0, 0), (0, 128, 128, 1, 0, 0), (2, 256, 128, 0, 4, 0), (2, 192, 128, 0, 8, 0), (2, 192, 384, 0, 10, 0),
