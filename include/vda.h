@@ -467,8 +467,8 @@ int vda_pointcloud_f32(const float* depth, const uint8_t* rgb, void* records, in
  * Allocation / synchronisation: vda_load_weight copies synchronously (host or device source); vda_finalize_weights packs
  * the fp16 layouts on the device and synchronises; the FIRST vda_forward of a new (shape, precision) - or vda_prepare -
  * may allocate (the fp32 weight pack, the positional embedding at that grid, the handle's own workspace when the caller
- * gave none). After that vda_forward only enqueues kernels on `stream` - and, with option "enc_split" (default on; fp16, not while
- * `stream` is capturing), on one stream the handle owns per caller stream, forked from `stream` and joined back into it before
+ * gave none). After that vda_forward only enqueues kernels on `stream` - and, with options "enc_split" and "head_lanes" (both default on;
+ * fp16, not while `stream` is capturing), on one stream the handle owns per caller stream, forked from `stream` and joined back into it before
  * anything later on `stream` runs: completion of `stream`'s work still means the forward is done. */
 typedef struct vda_model vda_model;
 
@@ -530,7 +530,12 @@ int vda_debug_occupy(int wgs, int lds_bytes, long long cycles, vda_stream_t stre
  * "mlp_fused" (default 0; fp16 path with ln_fold, widths vda_mlp_fused_supported reports): 1 = a block's fc1 + GELU + fc2 + residual
  * run as vda_mlp_fused_f16 instead of the two GEMM launches (measured slower on the MI355X: kept as a tested option).
  * "head_overlap" (default 0): 1 = the part of the head that needs taps 0..2 only (dpt_temporal.py:55-69 for i < 3, :75, :78-80) runs
- * on a side stream of the handle as soon as tap 2 exists, under the remaining encoder blocks; bit-identical results. */
+ * on a side stream of the handle as soon as tap 2 exists, under the remaining encoder blocks; bit-identical results.
+ * "head_lanes" (default 1, or the environment's VDA_HEAD_LANES; fp16 path; < 0 restores that default): after the encoder the head's
+ * branches that do not depend on tap 3 (the tap 0..2 work above and the first conv of resConfUnit1 in refinenets 3, 2, 1) run on the
+ * stream "enc_split" uses, beside proj3 .. motion module 2 on `stream`, joined back before refinenet 3 and refinenet 2
+ * read what it made. Bit-identical results, the same workspace layout. Like "enc_split" it does not apply while `stream`
+ * is capturing or another forward of the handle is in flight on a different stream, and not together with "head_overlap". */
 int vda_set_option(vda_model* h, const char* name, int value);
 /* Measurement hook (bench.py): from vda_profile_start until vda_profile_stop every `every`-th GEMM / conv launch of each
  * (shape, epilogue) inside vda_forward is bracketed by two events on the launch stream. vda_profile_stop waits for them and

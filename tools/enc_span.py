@@ -48,17 +48,18 @@ def union(iv):
     return tot + (cur_e - cur_s if cur_e is not None else 0)
 
 
-for path in sys.argv[1:]:
-    spans, sums, unions, counts = [], [], [], []
-    for t0, t1, enc in forwards(path):
-        spans.append((t1 - t0) / 1e6)
-        sums.append(sum(e - s for s, e, _ in enc) / 1e6)
-        unions.append(union([(s, e) for s, e, _ in enc]) / 1e6)
-        counts.append(len(enc))
-    if not spans:
-        print(f"{path}: no encoder found")
-        continue
-    med = statistics.median
-    print(f"{path}: {len(spans)} forwards, {med(counts):.0f} encoder kernels each; median ms per clip: span {med(spans):.3f}, "
-          f"kernel sum {med(sums):.3f}, busy (union) {med(unions):.3f}, idle (span - union) {med(spans) - med(unions):.3f}; "
-          f"spans {[round(v, 3) for v in spans]}")
+if __name__ == "__main__":
+    for path in sys.argv[1:]:
+        spans, sums, unions, counts = [], [], [], []
+        for t0, t1, enc in forwards(path):
+            spans.append((t1 - t0) / 1e6)
+            sums.append(sum(e - s for s, e, _ in enc) / 1e6)
+            unions.append(union([(s, e) for s, e, _ in enc]) / 1e6)
+            counts.append(len(enc))
+        if not spans:
+            print(f"{path}: no encoder found")
+            continue
+        med = statistics.median
+        print(f"{path}: {len(spans)} forwards, {med(counts):.0f} encoder kernels each; median ms per clip: span {med(spans):.3f}, "
+              f"kernel sum {med(sums):.3f}, busy (union) {med(unions):.3f}, idle (span - union) {med(spans) - med(unions):.3f}; "
+              f"spans {[round(v, 3) for v in spans]}")

@@ -174,7 +174,7 @@ struct vda_model {
                                               // -0.3 .. -0.5 % on a 50.0 ms box; two clips in flight -0.4 %), profiles/r04/head_overlap_ab.txt
     struct Side {
         hipStream_t stream = nullptr;
-        hipEvent_t fork = nullptr, join = nullptr;
+        hipEvent_t fork = nullptr, join = nullptr, join2 = nullptr;      // (join2: the lane's second join under head_lanes)
     };
     std::map<hipStream_t, Side> sides;        // one side stream + event pair per caller stream (two forwards may be in flight on two)
     // vda_set_option("enc_split") (environment default VDA_ENC_SPLIT): the fp16 ln_fold encoder runs as two frame halves, half B on a
@@ -184,6 +184,12 @@ struct vda_model {
     int enc_split = 1;
     std::map<hipStream_t, Side> lanes;
     std::map<hipStream_t, hipEvent_t> tails;
+    // vda_set_option("head_lanes") (environment default VDA_HEAD_LANES): after the encoder's join the head's branches that do not
+    // depend on tap 3 (head_early and conv1 of resConfUnit1 in refinenets 3, 2, 1) run on the LANE stream beside the chain
+    // proj3 .. motion module 2 on the caller's stream - see Run::forward. Same exclusions as enc_split, and not together with
+    // head_overlap. ON: in-process A/B, both orders, ViT-L 51.32 -> 50.36 and 51.41 -> 50.47 ms per clip (A/A spread 0.16 ms), ViT-S
+    // 8.23 -> 7.83 and 8.20 -> 7.89 ms (A/A spread 0.14 ms); profiles/r10/head_lanes/.
+    int head_lanes = 1;
     int mlp_fused = 0;                        // vda_set_option("mlp_fused"): fc1 + GELU + fc2 + residual in one kernel where built (D = 384; needs ln_fold).
                                               // OFF: measured slower than the two GEMM launches (ViT-S clip 8.69 -> 9.00 ms, mlp_fused.hip's header)
     // Split-stream overflow report (ln_fold): one sticky word in pinned host memory, set by the device at the end of a forward whose
@@ -531,6 +537,16 @@ int pack_all(vda_model* h, int prec) {
     return 0;
 }
 
+// a side / lane stream and its events, created at first use
+int open_side(vda_model::Side& sd) {
+    if (sd.stream != nullptr) return 0;
+    VDA_HIP(hipStreamCreateWithFlags(&sd.stream, hipStreamNonBlocking));
+    VDA_HIP(hipEventCreateWithFlags(&sd.fork, hipEventDisableTiming));
+    VDA_HIP(hipEventCreateWithFlags(&sd.join, hipEventDisableTiming));
+    VDA_HIP(hipEventCreateWithFlags(&sd.join2, hipEventDisableTiming));
+    return 0;
+}
+
 // ------------------------------------------------------------------ one forward pass
 struct Run {
     vda_model* h;
@@ -541,6 +557,9 @@ struct Run {
     size_t ab;                // bytes per activation element
     int32_t* sched = nullptr; // dynamic-schedule counters: 8 per GEMM launch of the forward, zeroed at its start
     int nsched = 0;           // launches so far (dry pass: the count that sizes the block)
+    std::string sp;           // prefix of the helpers' scratch names below. head_early sets "e." in every configuration (one layout,
+                              // whichever stream it runs on) and option head_lanes sets it for everything it issues to the lane
+                              // stream, so that work there never shares a block with the caller's stream's
 
     void* buf(const std::string& name, size_t elems, size_t esize) {
         const size_t bytes = (elems * esize + 255) & ~(size_t)255;
@@ -646,16 +665,16 @@ struct Run {
         const int BT = B * T, rows = BT * hw;
         int chunks = (hw + 31) / 32;
         chunks = chunks < 1 ? 1 : (chunks > 16 ? 16 : chunks);
-        float* part = f32("gn_partial", (size_t)BT * chunks * GN_GROUPS * 2);
-        void* g = act("tm_g", (size_t)rows * Cc);
+        float* part = f32(sp + "gn_partial", (size_t)BT * chunks * GN_GROUPS * 2);
+        void* g = act(sp + "tm_g", (size_t)rows * Cc);
         if (!dry)
             VDA_TRY(prec == VDA_PREC_F32 ? vda_groupnorm_nhwc_f32((const float*)x, (float*)g, V(k + "gn.w"), V(k + "gn.b"), GN_EPS, BT, hw, Cc, GN_GROUPS, part, chunks, s)
                                          : vda_groupnorm_nhwc_f16(x, g, V(k + "gn.w"), V(k + "gn.b"), GN_EPS, BT, hw, Cc, GN_GROUPS, part, chunks, s));
-        float* hs = f32("tm_hs", (size_t)rows * Cc);
+        float* hs = f32(sp + "tm_hs", (size_t)rows * Cc);
         VDA_TRY(dense(g, W(k + "in.w"), hs, VDA_EPI_BIAS_F32, rows, Cc, Cc, V(k + "in.b")));
-        void* n = act("tm_n", (size_t)rows * Cc);
-        void* qkv = act("tm_qkv", (size_t)rows * 3 * Cc);
-        void* ao = act("tm_ao", (size_t)rows * Cc);
+        void* n = act(sp + "tm_n", (size_t)rows * Cc);
+        void* qkv = act(sp + "tm_qkv", (size_t)rows * 3 * Cc);
+        void* ao = act(sp + "tm_ao", (size_t)rows * Cc);
         for (int a = 0; a < 2; ++a) {
             const std::string ka = k + "a" + std::to_string(a) + ".";
             const bool rope = h->cfg.pe_rope != 0;                   // motion_module.py:221-224: no additive encoding, q and k rotated instead
@@ -672,9 +691,9 @@ struct Run {
             VDA_TRY(dense(ao, W(ka + "out.w"), hs, VDA_EPI_SCALE_RES_F32, rows, Cc, Cc, V(ka + "out.b"), hs));
         }
         VDA_TRY(layernorm(hs, n, V(k + "ffln.w"), V(k + "ffln.b"), TMP_LN_EPS, rows, Cc));
-        void* gg = act("tm_gg", (size_t)rows * 4 * Cc);
+        void* gg = act(sp + "tm_gg", (size_t)rows * 4 * Cc);
         VDA_TRY(dense(n, W(k + "ff1.w"), gg, VDA_EPI_GEGLU_F16, rows, 8 * Cc, Cc, V(k + "ff1.b"), nullptr, nullptr, 4 * Cc));
-        void* hh = act("tm_hh", (size_t)rows * Cc);
+        void* hh = act(sp + "tm_hh", (size_t)rows * Cc);
         VDA_TRY(dense(gg, W(k + "ff2.w"), hh, VDA_EPI_SCALE_RES_F32_H, rows, Cc, 4 * Cc, V(k + "ff2.b"), hs));
         void* out = act(tag, (size_t)rows * Cc);
         VDA_TRY(dense(hh, W(k + "out.w"), out, VDA_EPI_RES_F16, rows, Cc, Cc, V(k + "out.b"), x));
@@ -683,27 +702,38 @@ struct Run {
     }
 
     // util/blocks.py:68-91: conv2(relu(conv1(relu(x)))) + x (+ res2: the fusion block's skip add)
-    int rcu(int i, int u, const void* x, void* out, int B, int H, int Wd, int Fe, const void* res2 = nullptr) {
+    // rcu_conv1 is y = relu(conv1(relu(x))) alone. It reads x only, so option head_lanes runs it ahead on the lane stream for
+    // resConfUnit1 of refinenets 3, 2, 1 and hands the result to rcu as y1 (!= nullptr: conv1 already done, here is y)
+    int rcu_conv1(int i, int u, const void* x, void* y, int B, int H, int Wd, int Fe) {
         const std::string k = "ref" + std::to_string(i) + ".rcu" + std::to_string(u) + ".";
-        void* y = act("rcu_y", (size_t)B * H * Wd * Fe);
-        VDA_TRY(conv3x3(x, k + "c1.w", y, B, H, Wd, Fe, Fe, VDA_EPI_BIAS_RELU_F16, 1, V(k + "c1.b"), true));
+        return conv3x3(x, k + "c1.w", y, B, H, Wd, Fe, Fe, VDA_EPI_BIAS_RELU_F16, 1, V(k + "c1.b"), true);
+    }
+    int rcu(int i, int u, const void* x, void* out, int B, int H, int Wd, int Fe, const void* res2 = nullptr, const void* y1 = nullptr) {
+        const std::string k = "ref" + std::to_string(i) + ".rcu" + std::to_string(u) + ".";
+        const void* y = y1;
+        if (y1 == nullptr) {
+            void* t = act(sp + "rcu_y", (size_t)B * H * Wd * Fe);
+            VDA_TRY(rcu_conv1(i, u, x, t, B, H, Wd, Fe));
+            y = t;
+        }
         VDA_TRY(conv3x3(y, k + "c2.w", out, B, H, Wd, Fe, Fe, VDA_EPI_RES_F16, 1, V(k + "c2.b"), false, x, res2));
         return 0;
     }
     // util/blocks.py:135-162 with out_conv moved in front of the (commuting) bilinear resize
     // upsample = false: the caller's next conv does the resize itself (vda_conv3x3_up2_f16); *result is the out_conv output at H x Wd
+    // y1: see rcu
     int fusion(int i, const void* x0, const void* x1, int B, int H, int Wd, int Ho, int Wo, int Fe, const std::string& tag, void** result,
-               bool upsample = true) {
+               bool upsample = true, const void* y1 = nullptr) {
         const size_t rows = (size_t)B * H * Wd;
         const void* sm = x0;
         if (x1 != nullptr) {
-            void* t = act("fus_s", rows * Fe);
-            VDA_TRY(rcu(i, 1, x1, t, B, H, Wd, Fe, x0));
+            void* t = act(sp + "fus_s", rows * Fe);
+            VDA_TRY(rcu(i, 1, x1, t, B, H, Wd, Fe, x0, y1));
             sm = t;
         }
-        void* r = act("fus_r", rows * Fe);
+        void* r = act(sp + "fus_r", rows * Fe);
         VDA_TRY(rcu(i, 2, sm, r, B, H, Wd, Fe));
-        void* c = act(upsample ? "fus_c" : tag, rows * Fe);
+        void* c = act(upsample ? sp + "fus_c" : tag, rows * Fe);
         const std::string k = "ref" + std::to_string(i) + ".out.";
         VDA_TRY(dense(r, W(k + "w"), c, VDA_EPI_BIAS_F16, (int)rows, Fe, Fe, V(k + "b")));
         if (!upsample) {
@@ -801,28 +831,29 @@ struct Run {
         int nparts = 1;
         vda_model::Side* lane = nullptr;
         bool split = fold && !mlp1 && h->enc_split != 0 && BT >= 2;
-        if (split && !dry) {
-            split = !capturing;
+        // Option head_lanes (fp16 path; below, after the encoder's join) puts two branches of the head on the same two streams.
+        // Neither option applies (`alone` is false) on a capturing stream or while a forward of this handle on another caller stream
+        // is in flight; head_lanes and head_overlap exclude each other.
+        const bool want_lanes = !dry && prec == VDA_PREC_F16 && h->head_lanes != 0 && !h->head_overlap;
+        bool alone = !capturing;
+        if (!dry && (split || want_lanes))
             for (auto& kv : h->tails) {
-                if (!split) break;
+                if (!alone) break;
                 if (kv.first == s || kv.second == nullptr) continue;
                 if (hipEventQuery(kv.second) != hipSuccess) {
                     (void)hipGetLastError();      // (hipErrorNotReady: that forward is still running)
-                    split = false;
+                    alone = false;
                 }
             }
-        }
+        if (!dry) split = split && alone;
+        const bool hlanes = want_lanes && alone;
         if (split) {
             parts[0] = {0, BT / 2, s};
             parts[1] = {BT / 2, BT - BT / 2, s};
             nparts = 2;
             if (!dry) {
                 vda_model::Side& ln = h->lanes[s];
-                if (ln.stream == nullptr) {
-                    VDA_HIP(hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking));
-                    VDA_HIP(hipEventCreateWithFlags(&ln.fork, hipEventDisableTiming));
-                    VDA_HIP(hipEventCreateWithFlags(&ln.join, hipEventDisableTiming));
-                }
+                VDA_TRY(open_side(ln));
                 lane = &ln;
                 parts[1].st = ln.stream;
                 VDA_HIP(hipEventRecord(ln.fork, s));                   // the centred token planes and their statistics exist
@@ -887,37 +918,50 @@ struct Run {
         const int Fe = c.features, Fhp = h->Fhp;
         const int h1 = 4 * ph, w1 = 4 * pw, h2 = 2 * ph, w2 = 2 * pw, h4 = (ph - 1) / 2 + 1, w4 = (pw - 1) / 2 + 1;
         void *l1r = nullptr, *l2r = nullptr, *l3r = nullptr;
-        auto head_early = [&]() -> int {
-            void* t0 = act("t0", (size_t)BT * P * ocp[0]);
-            VDA_TRY(dense(taps[0], W("proj0.w"), t0, VDA_EPI_BIAS_F16, BT * P, ocp[0], D, V("proj0.b")));
+        // part: 1 = the tap 0 / tap 1 chains (-> l1r, l2r), 2 = the tap 2 chain (-> l3r), 3 = both, in the order of one chain. Its
+        // motion module takes scratch blocks of its own ("e."): with option head_lanes motion module 1 runs beside it.
+        auto head_early = [&](int part = 3) -> int {
+            const std::string keep_sp = sp;
+            sp = "e.";
             void* l1 = act("l1", (size_t)BT * h1 * w1 * ocp[0]);
-            {
-                vda_gemm_args a = {};
-                a.A = t0, a.W = W("resize0.w"), a.out = l1, a.bias = V("resize0.b");
-                a.M = BT * P, a.N = 16 * ocp[0], a.K = ocp[0], a.ldc = ocp[0], a.a_mode = VDA_A_DENSE, a.epilogue = VDA_EPI_CONVT_F16;
-                a.tK = 4, a.tH = ph, a.tW = pw, a.tCout = ocp[0];
-                VDA_TRY(gemm(a));
-            }
-            void* t1 = act("t1", (size_t)BT * P * ocp[1]);
-            VDA_TRY(dense(taps[1], W("proj1.w"), t1, VDA_EPI_BIAS_F16, BT * P, ocp[1], D, V("proj1.b")));
             void* l2 = act("l2", (size_t)BT * h2 * w2 * ocp[1]);
-            {
-                vda_gemm_args a = {};
-                a.A = t1, a.W = W("resize1.w"), a.out = l2, a.bias = V("resize1.b");
-                a.M = BT * P, a.N = 4 * ocp[1], a.K = ocp[1], a.ldc = ocp[1], a.a_mode = VDA_A_DENSE, a.epilogue = VDA_EPI_CONVT_F16;
-                a.tK = 2, a.tH = ph, a.tW = pw, a.tCout = ocp[1];
-                VDA_TRY(gemm(a));
-            }
-            void* l3 = act("l3", (size_t)BT * P * ocp[2]);
-            VDA_TRY(dense(taps[2], W("proj2.w"), l3, VDA_EPI_BIAS_F16, BT * P, ocp[2], D, V("proj2.b")));
             void* l3t = nullptr;
-            VDA_TRY(temporal(0, l3, B, T, P, ocp[2], "l3t", &l3t));                  // dpt_temporal.py:75
-            l1r = act("l1r", (size_t)BT * h1 * w1 * Fe);
-            VDA_TRY(conv3x3(l1, "rn1.w", l1r, BT, h1, w1, ocp[0], Fe, VDA_EPI_BIAS_F16, 1, nullptr));
-            l2r = act("l2r", (size_t)BT * h2 * w2 * Fe);
-            VDA_TRY(conv3x3(l2, "rn2.w", l2r, BT, h2, w2, ocp[1], Fe, VDA_EPI_BIAS_F16, 1, nullptr));
-            l3r = act("l3r", (size_t)BT * P * Fe);
-            VDA_TRY(conv3x3(l3t, "rn3.w", l3r, BT, ph, pw, ocp[2], Fe, VDA_EPI_BIAS_F16, 1, nullptr));
+            if (part & 1) {
+                void* t0 = act("t0", (size_t)BT * P * ocp[0]);
+                VDA_TRY(dense(taps[0], W("proj0.w"), t0, VDA_EPI_BIAS_F16, BT * P, ocp[0], D, V("proj0.b")));
+                {
+                    vda_gemm_args a = {};
+                    a.A = t0, a.W = W("resize0.w"), a.out = l1, a.bias = V("resize0.b");
+                    a.M = BT * P, a.N = 16 * ocp[0], a.K = ocp[0], a.ldc = ocp[0], a.a_mode = VDA_A_DENSE, a.epilogue = VDA_EPI_CONVT_F16;
+                    a.tK = 4, a.tH = ph, a.tW = pw, a.tCout = ocp[0];
+                    VDA_TRY(gemm(a));
+                }
+                void* t1 = act("t1", (size_t)BT * P * ocp[1]);
+                VDA_TRY(dense(taps[1], W("proj1.w"), t1, VDA_EPI_BIAS_F16, BT * P, ocp[1], D, V("proj1.b")));
+                {
+                    vda_gemm_args a = {};
+                    a.A = t1, a.W = W("resize1.w"), a.out = l2, a.bias = V("resize1.b");
+                    a.M = BT * P, a.N = 4 * ocp[1], a.K = ocp[1], a.ldc = ocp[1], a.a_mode = VDA_A_DENSE, a.epilogue = VDA_EPI_CONVT_F16;
+                    a.tK = 2, a.tH = ph, a.tW = pw, a.tCout = ocp[1];
+                    VDA_TRY(gemm(a));
+                }
+            }
+            if (part & 2) {
+                void* l3 = act("l3", (size_t)BT * P * ocp[2]);
+                VDA_TRY(dense(taps[2], W("proj2.w"), l3, VDA_EPI_BIAS_F16, BT * P, ocp[2], D, V("proj2.b")));
+                VDA_TRY(temporal(0, l3, B, T, P, ocp[2], "l3t", &l3t));              // dpt_temporal.py:75
+            }
+            if (part & 1) {
+                l1r = act("l1r", (size_t)BT * h1 * w1 * Fe);
+                VDA_TRY(conv3x3(l1, "rn1.w", l1r, BT, h1, w1, ocp[0], Fe, VDA_EPI_BIAS_F16, 1, nullptr));
+                l2r = act("l2r", (size_t)BT * h2 * w2 * Fe);
+                VDA_TRY(conv3x3(l2, "rn2.w", l2r, BT, h2, w2, ocp[1], Fe, VDA_EPI_BIAS_F16, 1, nullptr));
+            }
+            if (part & 2) {
+                l3r = act("l3r", (size_t)BT * P * Fe);
+                VDA_TRY(conv3x3(l3t, "rn3.w", l3r, BT, ph, pw, ocp[2], Fe, VDA_EPI_BIAS_F16, 1, nullptr));
+            }
+            sp = keep_sp;
             return 0;
         };
         bool early_done = false;
@@ -1004,11 +1048,7 @@ struct Run {
                         }
                     } else {
                         vda_model::Side& sd = h->sides[s];
-                        if (sd.stream == nullptr) {
-                            VDA_HIP(hipStreamCreateWithFlags(&sd.stream, hipStreamNonBlocking));
-                            VDA_HIP(hipEventCreateWithFlags(&sd.fork, hipEventDisableTiming));
-                            VDA_HIP(hipEventCreateWithFlags(&sd.join, hipEventDisableTiming));
-                        }
+                        VDA_TRY(open_side(sd));
                         side = &sd;
                         VDA_HIP(hipEventRecord(sd.fork, s));               // taps 0..2 are behind this point of the caller's stream
                         VDA_HIP(hipStreamWaitEvent(sd.stream, sd.fork, 0));
@@ -1036,7 +1076,39 @@ struct Run {
             return 1;
         }
         // ---- head: reassemble (dpt_temporal.py:55-69), temporal modules on layer_3 / layer_4 (:75-76), layer_rn (:78-81)
-        if (!early_done) VDA_TRY(head_early());
+        // ---- option head_lanes: a TASK split of the head's DAG over the caller's stream and the lane stream (idle after the join).
+        // The chain through tap 3 (proj3 -> resize3 -> motion module 1 -> rn4 -> refinenet 4 -> motion module 2) holds the head's
+        // poorly filled launches: 19 x 19 maps, 18 .. 72 % of one round of 256 x 256 tiles, and the bandwidth-bound LayerNorm /
+        // GroupNorm / temporal attention passes between them. Beside it the lane runs what does not depend on it and fills the
+        // grid: head_early, and conv1 of resConfUnit1 of refinenets 3, 2, 1 (it reads l3r / l2r / l1r only; the other input of the
+        // unit enters in conv2's epilogue). Every kernel keeps its rows, its tile plan and its arguments, and the two sides share no
+        // scratch block (Run::sp, and y1[] for the hoisted convs): bit-identical to one chain. The lane's order puts what
+        // refinenet 3 needs first: refinenet 3 waits for that alone (join) and refinenet 2 for the rest (join2). One join before
+        // refinenet 3 for all of it measured 0.18 - 0.20 ms per ViT-L clip slower (profiles/r10/head_lanes/) and is not kept.
+        // The dry pass requests y1[] in every configuration, so the layout does not depend on the option.
+        void* y1[4] = {nullptr, act("ref1.y1", (size_t)BT * h1 * w1 * Fe), act("ref2.y1", (size_t)BT * h2 * w2 * Fe), act("ref3.y1", (size_t)BT * P * Fe)};
+        if (hlanes) {
+            vda_model::Side& ln = h->lanes[s];
+            VDA_TRY(open_side(ln));
+            lane = &ln;
+            VDA_HIP(hipEventRecord(ln.fork, s));                       // behind the encoder's join: every tap row exists
+            VDA_HIP(hipStreamWaitEvent(ln.stream, ln.fork, 0));
+            auto on_lane = [&]() -> int {
+                VDA_TRY(head_early(2));
+                VDA_TRY(rcu_conv1(3, 1, l3r, y1[3], BT, ph, pw, Fe));
+                VDA_HIP(hipEventRecord(ln.join, ln.stream));
+                VDA_TRY(head_early(1));
+                VDA_TRY(rcu_conv1(2, 1, l2r, y1[2], BT, h2, w2, Fe));
+                VDA_TRY(rcu_conv1(1, 1, l1r, y1[1], BT, h1, w1, Fe));
+                VDA_HIP(hipEventRecord(ln.join2, ln.stream));
+                return 0;
+            };
+            const hipStream_t keep = s;
+            s = ln.stream, sp = "e.";
+            const int rc = on_lane();
+            s = keep, sp = "";
+            if (rc != 0) return rc;
+        } else if (!early_done) VDA_TRY(head_early());
         else if (side != nullptr) VDA_HIP(hipStreamWaitEvent(s, side->join, 0));     // the side stream's part is done before anything reads it
         void* t3 = act("t3", (size_t)BT * P * ocp[3]);
         VDA_TRY(dense(taps[3], W("proj3.w"), t3, VDA_EPI_BIAS_F16, BT * P, ocp[3], D, V("proj3.b")));
@@ -1049,13 +1121,15 @@ struct Run {
         void *p4 = nullptr, *p4t = nullptr, *p3 = nullptr, *p3t = nullptr, *p2 = nullptr, *p1 = nullptr;
         VDA_TRY(fusion(4, l4r, nullptr, BT, h4, w4, ph, pw, Fe, "p4", &p4));
         VDA_TRY(temporal(2, p4, B, T, P, Fe, "p4t", &p4t));
-        VDA_TRY(fusion(3, p4t, l3r, BT, ph, pw, h2, w2, Fe, "p3", &p3));
+        if (hlanes) VDA_HIP(hipStreamWaitEvent(s, lane->join, 0));                   // l3r and y1[3]
+        VDA_TRY(fusion(3, p4t, l3r, BT, ph, pw, h2, w2, Fe, "p3", &p3, true, hlanes ? y1[3] : nullptr));
         VDA_TRY(temporal(3, p3, B, T, h2 * w2, Fe, "p3t", &p3t));
-        VDA_TRY(fusion(2, p3t, l2r, BT, h2, w2, h1, w1, Fe, "p2", &p2));
+        if (hlanes) VDA_HIP(hipStreamWaitEvent(s, lane->join2, 0));                    // l2r, l1r, y1[2], y1[1]
+        VDA_TRY(fusion(2, p3t, l2r, BT, h2, w2, h1, w1, Fe, "p2", &p2, true, hlanes ? y1[2] : nullptr));
         // refinenet1's 2x upsample (util/blocks.py:156-160) is folded into output_conv1 on the fp16 path: path_1 at 8 ph x 8 pw (1.4 GB
         // per ViT-L clip) never exists; "p1c" is refinenet1's out_conv output at 4 ph x 4 pw (bilinear and the 1x1 conv commute)
         const bool up_fused = prec == VDA_PREC_F16 && h->oc1_fused != 0 && Fhp <= 128 && Fe % 16 == 0;
-        VDA_TRY(fusion(1, p2, l1r, BT, h1, w1, 2 * h1, 2 * w1, Fe, up_fused ? "p1c" : "p1", &p1, !up_fused));
+        VDA_TRY(fusion(1, p2, l1r, BT, h1, w1, 2 * h1, 2 * w1, Fe, up_fused ? "p1c" : "p1", &p1, !up_fused, hlanes ? y1[1] : nullptr));
         // ---- output convs (dpt.py:117-124, dpt_temporal.py:93-100)
         const int hh = 2 * h1, ww = 2 * w1;
         void* o1 = act("o1", (size_t)BT * hh * ww * Fhp);
@@ -1118,6 +1192,11 @@ int check_shape(const vda_model* h, int B, int T, int H, int W, int prec) {
     return 0;
 }
 
+int head_lanes_default() {
+    static const int v = getenv("VDA_HEAD_LANES") ? atoi(getenv("VDA_HEAD_LANES")) : 1;      // (A/B through an unmodified caller)
+    return v != 0;
+}
+
 int enc_split_default() {
     static const int v = getenv("VDA_ENC_SPLIT") ? atoi(getenv("VDA_ENC_SPLIT")) : 1;      // (A/B through an unmodified caller)
     return v != 0;
@@ -1164,6 +1243,7 @@ extern "C" int vda_create(const vda_config* cfg, vda_model** out) {
     memset(ring, 0, 64);
     h->ovf_host = (volatile int32_t*)ring;
     h->enc_split = enc_split_default();
+    h->head_lanes = head_lanes_default();
     *out = h;
     return 0;
 }
@@ -1177,6 +1257,7 @@ extern "C" int vda_destroy(vda_model* h) {
         for (auto& kv : *m) {
             if (kv.second.fork) (void)hipEventDestroy(kv.second.fork);
             if (kv.second.join) (void)hipEventDestroy(kv.second.join);
+            if (kv.second.join2) (void)hipEventDestroy(kv.second.join2);
             if (kv.second.stream) (void)hipStreamDestroy(kv.second.stream);
         }
     for (void* p : h->owned) (void)hipFree(p);
@@ -1348,7 +1429,8 @@ static int vda_debug_copy_impl(vda_model* h, const char* name, void* dst, int64_
 }
 
 // Tuning / A-B switches of the launch sequence: "residual_in_ln" (default 0), "ln_fold" (default 1), "dyn_sched" (default 0), "oc1_fused"
-// (default 1), "mlp_fused" (default 0), "head_overlap" (default 0), "enc_split" (default 1, or VDA_ENC_SPLIT): see Run::forward.
+// (default 1), "mlp_fused" (default 0), "head_overlap" (default 0), "enc_split" (default 1, or VDA_ENC_SPLIT), "head_lanes" (default 1,
+// or VDA_HEAD_LANES): see Run::forward.
 extern "C" int vda_set_option(vda_model* h, const char* name, int value) {
     VDA_REQUIRE(h && name, "vda_set_option: null argument");
     if (strcmp(name, "residual_in_ln") == 0) {
@@ -1377,6 +1459,10 @@ extern "C" int vda_set_option(vda_model* h, const char* name, int value) {
     if (strcmp(name, "enc_split") == 0) {                // (< 0: the default, VDA_ENC_SPLIT or 1)
         h->enc_split = value < 0 ? enc_split_default() : value != 0;
         h->layouts.clear();                  // the GEMM launch count (dynamic-schedule counters) depends on it
+        return 0;
+    }
+    if (strcmp(name, "head_lanes") == 0) {               // (< 0: the default, VDA_HEAD_LANES or 1). The layout does not depend on it.
+        h->head_lanes = value < 0 ? head_lanes_default() : value != 0;
         return 0;
     }
     if (strcmp(name, "mlp_fused") == 0) {

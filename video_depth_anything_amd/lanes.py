@@ -172,13 +172,15 @@ def video_session(eng, dyn_sched, synchronize=False):
     creates to `streams`, and the consumer stream waits for them on the way out (synchronize: the host then waits for it too).
     enc_split: two windows in flight on two lanes already fill each other's idle time; the encoder's frame-half split measured
     -2 % on a 1024-frame video on top of them (profiles/r05), so it is off for the video.
+    head_lanes: the same lane stream and the same reasoning, off for the video as well.
     dyn_sched: multi-rank, the per-round all-gather runs beside the next windows' kernels - GEMMs that find CUs taken by it should
     lose those CUs, not a whole shift of tiles (dynamic tile draw).
     The device is current while this is entered and left, not in between: a generator holds a session across its yields, and its
     consumer's current device is not ours to change - the body enters torch.cuda.device itself wherever it queues work."""
     dev = eng.device
-    keep = eng.options.get("enc_split", -1)               # (-1: the library's default)
-    eng.set_option("enc_split", 0)
+    keep = {k: eng.options.get(k, -1) for k in ("enc_split", "head_lanes")}      # (-1: the library's default)
+    for k in keep:
+        eng.set_option(k, 0)
     try:
         eng.set_option("dyn_sched", dyn_sched)
         with torch.cuda.device(dev):
@@ -193,4 +195,5 @@ def video_session(eng, dyn_sched, synchronize=False):
                 if synchronize:
                     consumer.synchronize()
     finally:
-        eng.set_option("enc_split", keep)
+        for k, v in keep.items():
+            eng.set_option(k, v)
