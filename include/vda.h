@@ -452,6 +452,22 @@ int vda_pointcloud_f32(const float* depth, const uint8_t* rgb, void* records, in
                        int n, int h, int w, double fx, double fy, double cx, double cy, float max_depth, int record_f32,
                        vda_stream_t stream);
 
+/* ---- depth mapped to the bytes of a visualisation video (utils/dc_utils.py save_video: global range to uint8, then a colour table) ----
+ * For each of n dense fp32 pixels, every operation rounded to fp32 once (no fused multiply-add, no reciprocal):
+ *   span = minmax[1] - minmax[0];  if (!(span > 0)) span = 1e-12f        (a constant video maps to 0)
+ *   v    = ((depth[i] - minmax[0]) / span) * 255.f                       (the IEEE division, correctly rounded)
+ *   k    = 0 if v is NaN or v < 0,  255 if v >= 255,  else v truncated
+ * For finite depth inside [min, max] this is the reference's ((d - d_min) / (d_max - d_min) * 255).astype(np.uint8); the clamp
+ * only defines what numpy leaves undefined. minmax: device fp32 [2] = {min, max}, exactly what vda_minmax_accum_f32 leaves, so
+ * range and mapping chain on one stream without a host round trip. lut: device uint8 [256, 3], out[3 i .. 3 i + 2] = lut[k]
+ * (3 n bytes, packed RGB), or NULL: out[i] = k (n bytes, grayscale). All pointers are device pointers. depth needs 4-byte
+ * alignment only and out may sit at any byte address: a head of at most 3 pixels is peeled so that the body stores whole dwords
+ * (four pixels are one dword of gray or three of RGB), and a tail of at most 3 pixels follows as single bytes. Nothing outside
+ * out[0 .. n) / out[0 .. 3 n) is written. Deterministic. Refused: a null depth, minmax or out, n < 1, depth or minmax not
+ * 4-byte aligned. Indices are long long (sizes past 2^31 pixels are untested). One launch on `stream`, no allocation, no
+ * synchronisation, no atomics. */
+int vda_depth_vis_u8(const float* depth, long long n, const float* minmax, const uint8_t* lut, uint8_t* out, vda_stream_t stream);
+
 /* ================================================================ handle API: the model behind one pointer
  * What a C / C++ host binds in place of the reference's Python class (the seam of SURVEY.md section 8b):
  *   VideoDepthAnything(**model_configs[enc])          run.py:45, video_depth.py:38-63      vda_create

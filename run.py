@@ -4,6 +4,9 @@
 Frame I/O is utils/dc_utils.py (same two helpers as the reference's): `--input_video` may be an .npy / .npz (key `frames`)
 of uint8 [N,H,W,3] RGB frames, a directory of images, a GIF, or a video file when decord or cv2 is importable; the
 visualisations are mp4 through imageio when present and animated GIFs otherwise; `--save_npz` adds <name>_depths.npz.
+<name>_vis carries the reference's colours: depth is mapped through matplotlib's 256-entry inferno table, which ships in
+video_depth_anything_amd/visualize.py (not through the polynomial fit utils/dc_utils.py keeps as save_video's default), and on a
+GPU the mapping itself runs on the device (csrc/visualize.hip) - the same bytes as on the host.
 `--metric` selects the metric-depth variant (metric_depth/run.py: ViT-L, no scale/shift alignment).
 `--stream` runs infer_video_depth_stream instead: the frames (a memory map for .npy) are fed to the stream, the depths go piece by
 piece into <name>_depths.npy on disk and the visualisation is made from that file block by block, so neither the video nor its
@@ -17,6 +20,7 @@ import numpy as np
 import torch
 
 from utils.dc_utils import read_video_frames, save_video
+from video_depth_anything_amd.visualize import inferno_table
 from video_depth_anything_amd.video_depth import MetricVideoDepthAnything, VideoDepthAnything
 
 
@@ -116,7 +120,8 @@ if __name__ == '__main__':
 
     # run.py:57-62: <name>_src.mp4 and <name>_vis.mp4 (GIFs when no H.264 encoder is importable)
     src_path = save_video(frames, stem + '_src.mp4', fps=fps)
-    vis_path = save_video(depths, stem + '_vis.mp4', fps=fps, is_depths=True, grayscale=args.grayscale, **d_range)
+    vis_path = save_video(depths, stem + '_vis.mp4', fps=fps, is_depths=True, grayscale=args.grayscale, palette=inferno_table(),
+                          device=DEVICE if DEVICE == 'cuda' else None, **d_range)
     if args.save_npz:
         np.savez_compressed(stem + '_depths.npz', depths=depths)
     if args.save_exr:

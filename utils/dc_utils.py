@@ -96,9 +96,11 @@ def read_video_frames(video_path, process_length, target_fps=-1, max_res=-1):
 
 
 def _inferno(u8):
-    """uint8 [..] -> uint8 [..,3]: degree-6 polynomial fit of matplotlib's 'inferno' (the reference indexes the 256-entry table,
-    dc_utils.py:75-83; matplotlib is not installed here). VISUALISATION ONLY and unpinned: no fixture of the reference holds a
-    colour-mapped frame; the depth values themselves (npz / exr / the returned array) never pass through this."""
+    """uint8 [..] -> uint8 [..,3]: degree-6 polynomial fit of matplotlib's 'inferno', written when matplotlib could not be imported.
+    It is NOT the reference's colour map: the reference indexes the 256-entry table (dc_utils.py:75-83), and this fit differs from
+    (table * 255).astype(uint8) in every one of the 256 rows, by up to 9 levels. It stays as save_video's default palette, byte for
+    byte (tests/test_io.py, tests/test_io_stream.py); the reference's own colours are `palette=visualize.inferno_table()`, which is
+    what run.py passes. The depth values themselves (npz / exr / the returned array) never pass through either."""
     t = u8.astype(np.float32) / 255.0
     c = np.array([[0.0002189403691192265, 0.001651004631001012, -0.01948089843709184],
                   [0.1065134194856116, 0.5639564367884091, 3.932712388889277],
@@ -116,17 +118,23 @@ def _inferno(u8):
 SAVE_BLOCK = 32                                        # frames mapped to uint8 / colour at a time by save_video
 
 
-def save_video(frames, output_video_path, fps=10, is_depths=False, grayscale=False, d_min=None, d_max=None):
-    """dc_utils.py:73-88. Depth is mapped through its GLOBAL min / max to uint8 (then inferno unless `grayscale`).
+def save_video(frames, output_video_path, fps=10, is_depths=False, grayscale=False, d_min=None, d_max=None, palette=None, device=None):
+    """dc_utils.py:73-88. Depth is mapped through its GLOBAL min / max to uint8 (then a colour map unless `grayscale`).
     Returns the path written (the reference returns None): the .mp4 asked for, or a .gif when there is no encoder.
     Works SAVE_BLOCK frames at a time and hands each frame to the writer as it is mapped, so `frames` may be a memory map of a video
     that does not fit in RAM (run.py --stream); d_min / d_max: the global range when the caller knows it already
     (infer_video_depth_stream's depth_min / depth_max) - otherwise one block-wise pass finds it. Element by element the same
-    arithmetic as mapping the whole array at once: the bytes written do not depend on the block size."""
+    arithmetic as mapping the whole array at once: the bytes written do not depend on the block size.
+    palette / device (depth only, float32): with both None the colours are the polynomial `_inferno`, as they always were here.
+    palette = uint8 [256,3] indexes that table instead - video_depth_anything_amd.visualize.inferno_table() is the reference's own
+    (the contract of visualize.colorize_numpy, which adds a clamp for NaN / out-of-range pixels and treats a range
+    narrower than 1e-12 as it is rather than as 1e-12). device = a cuda device maps each block on the GPU (visualize.colorize,
+    csrc/visualize.hip): the same bytes as the host path for the same palette (None = inferno_table() then)."""
     if not isinstance(frames, np.ndarray):
         frames = np.asarray(frames)
     n = frames.shape[0]
     blocks = [slice(i, min(i + SAVE_BLOCK, n)) for i in range(0, n, SAVE_BLOCK)]
+    table_path = is_depths and (palette is not None or device is not None)
     if is_depths:
         if d_min is None:
             d_min = min(frames[b].min() for b in blocks)
@@ -134,10 +142,15 @@ def save_video(frames, output_video_path, fps=10, is_depths=False, grayscale=Fal
             d_max = max(frames[b].max() for b in blocks)
         d_min, d_max = frames.dtype.type(d_min), frames.dtype.type(d_max)
         span = max(float(d_max - d_min), 1e-12)
+    if table_path:
+        from video_depth_anything_amd import visualize
+        to_bytes = visualize.colorize_numpy if device is None else visualize.colorize
 
     def mapped():
         for b in blocks:
-            if is_depths:
+            if table_path:
+                vis = to_bytes(frames[b], d_min, d_max, grayscale, palette, device)
+            elif is_depths:
                 norm = ((frames[b] - d_min) / span * 255).astype(np.uint8)
                 vis = norm if grayscale else _inferno(norm)
             else:

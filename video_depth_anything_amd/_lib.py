@@ -120,6 +120,7 @@ SIGNATURES = {
     "vda_pointcloud_frame_stride": (C.c_size_t, [_i, _i, _i]),
     "vda_pointcloud_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
     "vda_pointcloud_f32": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_size_t, _i, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, _f, _i, _vp]),
+    "vda_depth_vis_u8": (_i, [_vp, _ll, _vp, _vp, _vp, _vp]),
     # handle API
     "vda_create": (_i, [C.POINTER(Config), C.POINTER(_vp)]),
     "vda_destroy": (_i, [_vp]),

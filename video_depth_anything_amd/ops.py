@@ -472,6 +472,22 @@ def pointcloud(depth, rgb, records, counts, workspace, fx, fy, cx, cy, max_depth
           "vda_pointcloud_f32")
 
 
+# ---- depth mapped to visualisation bytes (csrc/visualize.hip) -------------------------------------------------------------------
+def depth_vis(depth, minmax, lut, out, n=None):
+    """out (device uint8) = the first n pixels of depth (device fp32; all of them when n is None) mapped through minmax (device fp32
+    [2], as minmax_accum leaves it) to levels 0..255, n bytes - or, with lut (device uint8 [256,3]), to lut rows, 3 n bytes packed
+    RGB: include/vda.h. depth and out may be views at any element / byte offset of a larger buffer."""
+    _req(depth, F32, "depth"), _req(minmax, F32, "minmax"), _req(lut, torch.uint8, "lut"), _req(out, torch.uint8, "out")
+    n = depth.numel() if n is None else int(n)
+    if n <= 0 or n > depth.numel() or minmax.numel() < 2 or out.numel() < n * (1 if lut is None else 3):
+        raise ValueError(f"depth_vis: bad sizes (n={n} of {depth.numel()} pixels, minmax {minmax.numel()}, out {out.numel()} bytes)")
+    if lut is not None and tuple(lut.shape) != (256, 3):
+        raise ValueError(f"depth_vis: lut must be [256,3], got {tuple(lut.shape)}")
+    if len({t.device for t in (depth, minmax, out) + (() if lut is None else (lut,))}) != 1:
+        raise ValueError("depth_vis: the operands live on different devices")
+    check(lib.vda_depth_vis_u8(_p(depth), n, _p(minmax), _p(lut), _p(out), _stream(depth)), "vda_depth_vis_u8")
+
+
 # ---------------------------------------------------------------------------
 # Weight layouts the kernels expect (done once at load time, on the host or device)
 # ---------------------------------------------------------------------------
