@@ -11,7 +11,10 @@ equalities can fail) and tests/test_kernels_f32_edges_gpu.py (GPU: the kernels m
 
 The second half does the same for the fp16 GEMM (fp16 operands, fp32 accumulation, fp16 stores: a second condition, see there)
 and tests/test_kernels_f16_edges_gpu.py, and lists that file's launches as shapes (f16_launches) for the planner coverage test
-in tests/test_gemm_plan.py."""
+in tests/test_gemm_plan.py.
+
+The last part builds inputs whose SOFTMAX is exact - one key that wins by 52 bits, or every weight 1 - for the fp16 attention
+kernels and tests/test_attention_edges_gpu.py, with their preconditions (assert_selector_safe, assert_tattn_selector_safe)."""
 import torch
 import torch.nn.functional as F
 
@@ -540,3 +543,314 @@ def f16_launches(ncu):
                 yield v, True, gemm16_fields(M, N, K, EPI["BIAS_F16"])
     M, N, K = split16_case(ncu)
     yield -1, False, gemm16_fields(M, N, K, EPI["BIAS_F16"])
+
+
+# ================================================================================================ the fp16 attention kernels (attention.hip, temporal.hip)
+# Softmax is not linear, but three families of inputs make its real-arithmetic result an fp16 value that no rounding of a correct
+# kernel can move (tests/test_attention_edges_gpu.py; shown sound, and the equalities shown able to fail, in tests/test_exact_inputs.py):
+#   selector   every query has ONE key whose score beats every other by >= 51.9 (log2): the result is that key's V row, bit for bit;
+#   counting   q = 0: every weight is 1, the result is a count of keys over N;
+#   straddle   (real-valued) a whole key tile whose row sum sits below the shipped kernel's fast / slow limit for even queries and
+#              above it for odd ones.
+ATTN_VARIANTS = [-1, 0, 1, 2, 3, 4, 5, 7, 8, 9, 10, 11]           # vda_attention_set_variant; the ablation codes 21 - 25 compute wrong results by design
+ATTN_EDGE_N = [1, 31, 32, 33, 63, 64, 65, 127, 128, 129, 191, 192, 193, 321, 449]      # wave, key-tile and query-block edges; 4, 6, 8 tiles
+# (B, N, H): after the (1, N, 1) edges, 6 workgroups twice (the XCD remap's remainder arm only), 8 (the quotient arm only), 18 (both)
+ATTN_CASES = [(1, n, 1) for n in ATTN_EDGE_N] + [(3, 129, 1), (1, 129, 3), (2, 65, 4), (3, 193, 3)]
+ATTN_BIG_CASE = (1, 1370, 2)            # the workload's N: 22 tiles, 90 live queries in the last block
+ATTN_BIG_VARIANTS = [-1, 1]
+ATTN_STRADDLE_N = [129, 160, 192, 449]  # 160: a half-full last tile
+ATTN_TOL = 3e-3                         # tests/test_kernels_gpu.py's attention bound, rtol = atol
+ATTN_SUM_LIMIT = 2048.0                 # SUM_LIMIT of attn_cs_kernel
+LOG2E = 1.4426950408889634
+
+
+def attn_case_id(c):
+    return "B%d-N%d-H%d" % c
+
+
+def attn_seed(case):
+    B, N, H = case
+    return 9000 + 97 * N + 7 * B + H
+
+
+def key_codes(j):
+    """[len(j), 64]: key j's four base-16 digits (the fourth is the others' sum mod 16, so two keys below 4096 agree in at most
+    two), 12.0 at channel 16 s + d_s: each digit fills one 16-channel MFMA k-step."""
+    d0, d1, d2 = j % 16, (j // 16) % 16, (j // 256) % 16
+    code = torch.zeros(j.numel(), 64)
+    for s, d in enumerate((d0, d1, d2, (d0 + d1 + d2) % 16)):
+        code[torch.arange(j.numel()), 16 * s + d] = 12.0
+    return code
+
+
+def attn_value_code(B, N, H):
+    """V [B, N, H, 64]: integers with |v| <= 1019 that differ between keys, heads and frames."""
+    b, j, h, c = torch.meshgrid(torch.arange(B), torch.arange(N), torch.arange(H), torch.arange(64), indexing="ij")
+    return ((31 * j + 7 * c + 13 * (b * H + h)) % 2039 - 1019).to(F32)
+
+
+def attn_selector_inputs(B, N, H, seed):
+    """(qkv fp32 [B, N, 3 * H * 64] of fp16 values, pi [B, H, N]): query i of (frame b, head h) carries the code of key pi[b][h][i]."""
+    assert 0 < N <= 4096
+    g = torch.Generator().manual_seed(seed)
+    pi = torch.stack([torch.stack([torch.randperm(N, generator=g) for _ in range(H)]) for _ in range(B)])
+    qkv = torch.zeros(B, N, 3, H, 64)
+    qkv[:, :, 1] = key_codes(torch.arange(N))[None, :, None, :]
+    for b in range(B):
+        for h in range(H):
+            qkv[b, :, 0, h] = key_codes(pi[b][h])
+    qkv[:, :, 2] = attn_value_code(B, N, H)
+    return qkv.reshape(B, N, 3 * H * 64), pi
+
+
+def attn_split(qkv, B, N, H, log2_q=False):
+    """q, k, v as fp64 [B, H, N, 64] and the factor that turns q . k into natural-log scores. log2_q: q as q_frag<true> rounds it,
+    fp16(fp32(q) * fp32(log2(e) / 8)), the scores then in log2 units."""
+    q, k, v = qkv.reshape(B, N, 3, H, 64).permute(2, 0, 3, 1, 4)
+    if log2_q:
+        c = torch.tensor(LOG2E, dtype=F32) * 0.125
+        return (q.float() * c).to(F16).double(), k.double(), v.double(), 1.0 / LOG2E
+    return q.double() * 0.125, k.double(), v.double(), 1.0
+
+
+def attn_ref64(qkv, B, N, H, log2_q=False):
+    """fp64 softmax(q k^T / 8) v -> [B, N, H * 64]."""
+    q, k, v, nat = attn_split(qkv, B, N, H, log2_q)
+    a = (q @ k.transpose(-1, -2) * nat).softmax(dim=-1)
+    return (a @ v).transpose(1, 2).reshape(B, N, H * 64)
+
+
+def selector_expected(qkv, pi, B, N, H):
+    """V[pi] as fp64 [B, N, H * 64]."""
+    v = qkv.reshape(B, N, 3, H, 64)[:, :, 2].double()
+    out = torch.empty(B, N, H, 64, dtype=F64)
+    for b in range(B):
+        for h in range(H):
+            out[b, :, h] = v[b, pi[b][h], h]
+    return out.reshape(B, N, H * 64)
+
+
+def assert_selector_safe(qkv, pi, B, N, H):
+    """The preconditions under which every fp16 attention kernel must return V[pi] bit for bit, in fp64 and under both q scalings
+    (q / 8, exact; q * log2(e) / 8 rounded to fp16 as the LOG2 kernels do). A condition on the inputs, not a measurement of a kernel:
+      * every winner weight >= 1 - 2**-40: every other weight is <= 2**-40, so against a reference point at the winner's score each
+        other p rounds to 0 in fp16 (below 2**-25) and vanishes against 1 in the fp32 row sum; what was accumulated before the winner
+        arrived is scaled by as little;
+      * sum over the other keys of weight * |v| <= 2**-26: half of half the smallest fp16 subnormal. V holds zeros, and the output next
+        to a zero must round to zero (this is tighter than 2**-20, which would do next to |v| >= 1 only);
+      * every |v| <= 1019 and integral: an fp16 value, and a relative error of 2e-5 in p (codes 4 and 5 keep the reference point as
+        an fp16 pair) moves it by 0.02, far from the quarter unit that could change the final rounding;
+      * the largest log2-domain score < 128: exp2 of it is finite in fp32 (the first tile's reference point is 0)."""
+    v = qkv.reshape(B, N, 3, H, 64)[:, :, 2].double()
+    assert bool((v == v.round()).all()) and float(v.abs().max()) <= 1019, "V: integers up to 1019"
+    assert torch.equal(qkv.to(F16).float(), qkv), "every operand is its own fp16 rounding"
+    win = pi[:, :, :, None]
+    for log2_q in (False, True):
+        q, k, vv, nat = attn_split(qkv, B, N, H, log2_q)
+        s = q @ k.transpose(-1, -2) * nat                       # natural-log scores [B, H, N, N]
+        top = float(s.max()) * LOG2E
+        assert top < 128, f"log2 score {top:.1f}: exp2 overflows"
+        assert torch.equal(s.argmax(dim=-1), pi), "the winner is not the coded key"
+        w = s.softmax(dim=-1)
+        others = w.scatter(-1, win, 0.0)
+        lose = float(others.sum(-1).max())
+        assert lose <= 2.0 ** -40, f"log2_q={log2_q}: a winner's weight is 1 - {lose:.3g} < 1 - 2**-40"
+        leak = float((others @ vv.abs()).max())
+        assert leak <= 2.0 ** -26, f"log2_q={log2_q}: the other keys contribute up to {leak:.3g} > 2**-26"
+
+
+def selector_mismatch(y, expect, v_rows=None):
+    """None if y [B, N, H * 64] equals expect bit for bit; otherwise a message: how many (row, head) blocks differ and, for the first,
+    which key's V row it equals, if any (v_rows: V as [B, N, H, 64])."""
+    y = y.double()
+    if y.shape == expect.shape and torch.equal(y, expect):
+        return None
+    B, N, W = expect.shape
+    H = W // 64
+    bad = ((y != expect) | y.isnan()).reshape(B, N, H, 64).any(-1)
+    b, i, h = bad.nonzero()[0].tolist()
+    msg = f"{int(bad.sum())}/{bad.numel()} (query, head) rows differ from V[pi] ({int(y.isnan().sum())} NaN); first: frame {b} query {i} head {h}"
+    if v_rows is not None:
+        row = y.reshape(B, N, H, 64)[b, i, h]
+        hit = [(bb, jj) for bb in range(B) for jj in (v_rows[bb, :, h].double() == row).all(-1).nonzero().flatten().tolist()]
+        msg += f", which is V of (frame, key) {hit[:3]}" if hit else ", which is no key's V row of that head"
+    return msg
+
+
+def attn_counting_inputs(B, N, H, seed):
+    """q = 0, k small integers that must not matter, V[b, j, h, c] = (1 + (b H + h) % 3) * (j % 64 == c): every score 0, every p 1."""
+    qkv = torch.zeros(B, N, 3, H, 64)
+    qkv[:, :, 1] = ints((B, N, H, 64), -3, 3, seed)
+    b, j, h, c = torch.meshgrid(torch.arange(B), torch.arange(N), torch.arange(H), torch.arange(64), indexing="ij")
+    qkv[:, :, 2] = ((1 + (b * H + h) % 3) * (j % 64 == c)).to(F32)
+    return qkv.reshape(B, N, 3 * H * 64)
+
+
+def counting_expected(B, N, H):
+    """count_c * (1 + (b H + h) % 3) / N as fp64 [B, N, H * 64]: the same row for every query of a (frame, head)."""
+    count = torch.bincount(torch.arange(N) % 64, minlength=64).double()
+    scale = (1 + torch.arange(B * H) % 3).double().reshape(B, 1, H, 1)
+    return (count * scale / N).expand(B, N, H, 64).reshape(B, N, H * 64)
+
+
+def ulp16(x):
+    """Spacing of fp16 at |x| (fp64 in, fp64 out)."""
+    e = torch.floor(torch.log2(x.abs().clamp_min(2.0 ** -14)))
+    return torch.exp2(e - 10)
+
+
+def counting_check(y, B, N, H):
+    """(ok, worst error in fp16 ulp). The numerator is an integer count times 1, 2 or 3 (exact in fp32), the row sum is N (exact).
+    N a power of two: 1/N, the product and the fp16 rounding are all exact - equality. Any other N: two fp32 roundings (1/N, the
+    product; 2**-23 relative together, a few times that where 1/N is the hardware's approximate reciprocal) put the fp32 value next
+    to the real one, so its fp16 rounding is the real value's fp16 rounding or a neighbour of it: within one fp16 ulp."""
+    e = counting_expected(B, N, H)
+    r = e.to(F16).double()
+    err = (y.double() - r).abs()
+    worst = float(torch.nan_to_num(err / ulp16(r), nan=float("inf")).max())
+    if N & (N - 1) == 0:
+        assert torch.equal(r, e)
+        return torch.equal(y.double(), e), worst
+    return bool((err <= ulp16(r)).all()), worst
+
+
+def attn_straddle_inputs(N, seed):
+    """B = H = 1. q: channel 0 only, 4.0 (even queries) / 4.5 (odd); k: tile 0 all zero, every later key 6.5 in channel 0; V: positive
+    integers. A full later tile's row sum against the reference point 0 the first tile leaves: 64 e^3.25 = 1650 (even) and
+    64 e^3.656 = 2478 (odd), either side of attn_cs_kernel's SUM_LIMIT = 2048, interleaved lane by lane in every wave."""
+    assert N >= 129
+    qkv = torch.zeros(1, N, 3, 64)
+    qkv[0, 0::2, 0, 0] = 4.0
+    qkv[0, 1::2, 0, 0] = 4.5
+    qkv[0, 64:, 1, 0] = 6.5
+    qkv[0, :, 2] = ints((N, 64), 1, 1019, seed)
+    return qkv.reshape(1, N, 192)
+
+
+def straddle_tile_sums(qkv, log2_q):
+    """(even, odd): row sum of a full later key tile, p relative to the reference point 0."""
+    N = qkv.shape[1]
+    q, k, _, nat = attn_split(qkv, 1, N, 1, log2_q)
+    s = q[0, 0, :2] @ k[0, 0, 64:128].t() * nat
+    return tuple(s.exp().sum(-1).tolist())
+
+
+def tiled_attention(qkv, B, N, H, mutation=None):
+    """Plain fp64 restatement of the kernels' tile loop - 64-key tiles, rows past N staged as row N - 1 and masked, running maximum,
+    rescale - with one mistake a kernel could make:
+      drop_last     the loop runs over N - 1 keys;
+      dup_last      the first clamped copy of key N - 1 is left unmasked (needs a partial last tile);
+      mask_moved    the last tile's mask boundary sits one key early (the other tiles' code is right);
+      stale_v       the last tile multiplies by the V tile before it (a double buffer not yet refilled; needs two tiles);
+      heads / frames / queries   results stored to the neighbouring head / frame / query row (needs two of them)."""
+    q, k, v, nat = attn_split(qkv, B, N, H)
+    Nk = N - 1 if mutation == "drop_last" else N
+    nt = -(-Nk // 64)
+    m = torch.full((B, H, N, 1), -1e30, dtype=F64)
+    l = torch.zeros(B, H, N, 1, dtype=F64)
+    acc = torch.zeros(B, H, N, 64, dtype=F64)
+    for kt in range(nt):
+        rows = torch.arange(kt * 64, kt * 64 + 64)
+        staged = rows.clamp_max(N - 1)
+        bound = Nk
+        if kt == nt - 1:
+            bound += {"dup_last": 1 if N % 64 else 0, "mask_moved": -1}.get(mutation, 0)
+        s = q @ k[:, :, staged].transpose(-1, -2) * nat
+        s[..., rows >= bound] = -1e30
+        m_new = torch.maximum(m, s.max(-1, keepdim=True).values)
+        alpha = (m - m_new).exp()
+        p = (s - m_new).exp()
+        vt = v[:, :, (staged - 64) if (mutation == "stale_v" and kt == nt - 1 and kt > 0) else staged]
+        acc = acc * alpha + p @ vt
+        l = l * alpha + p.sum(-1, keepdim=True)
+        m = m_new
+    out = acc / l
+    if mutation == "heads" and H > 1:
+        out = out[:, [1, 0] + list(range(2, H))]
+    if mutation == "frames" and B > 1:
+        out = out[[1, 0] + list(range(2, B))]
+    if mutation == "queries" and N > 1:
+        out = out[:, :, [1, 0] + list(range(2, N))]
+    return out.transpose(1, 2).reshape(B, N, H * 64)
+
+
+ATTN_MUTATIONS = ["drop_last", "dup_last", "mask_moved", "stale_v", "heads", "frames", "queries"]
+
+
+def attn_mutation_applies(mutation, B, N, H):
+    """(N == 1: any number of copies of the only key gives the same softmax - only dropping it can show.)"""
+    return dict(dup_last=N % 64 != 0 and N > 1, mask_moved=N > 1, stale_v=N > 64, heads=H > 1, frames=B > 1, queries=N > 1).get(mutation, True)
+
+
+# ------------------------------------------------------------------------------------------------ temporal attention
+TATTN_T = [1, 2, 15, 16, 17, 31, 32]                 # 16 / 17: the edge of the VALU kernel's two 16-query halves
+TATTN_HW = [1, 3]
+TATTN_SELECTOR_GEOM = [(256, 8), (512, 8), (1024, 8), (32, 1), (128, 2), (512, 4)]      # (C, heads): d = 32, 64, 128, 32, 64, 128
+TATTN_SMALL_GEOM = [(64, 8), (192, 8), (384, 8)]     # ViT-S: d = 8, 24, 48, which the MFMA kernel does not serve
+
+
+def tattn_seed(T, hw, C, heads):
+    return 9500 + 131 * T + 17 * hw + C + heads
+
+
+def tattn_selector_inputs(T, hw, C, heads, seed):
+    """(qkv fp32 [T * hw, 3 C], rows ordered (frame, pixel), pi [hw, heads, T]). k of frame t: 16.0 at channel t of its head; q of
+    frame t: the same code of frame pi[p][h][t]; the winner's score leads by 256 / sqrt(d) >= 22.6.
+    V: the spatial integer coding over (frame, pixel, head, channel) with the zero left out - values -1019..-1 and 1..1019. At d = 128
+    the other frames' weights (e^-22.6 each) times |v| reach 5e-6: nothing next to |v| >= 1, but next to v = 0 it is a nonzero fp16
+    subnormal (the VALU kernel multiplies V by fp32 weights), so with a zero in V the real result would not be V[pi]."""
+    d = C // heads
+    assert C % heads == 0 and T <= 32 <= d
+    g = torch.Generator().manual_seed(seed)
+    pi = torch.stack([torch.stack([torch.randperm(T, generator=g) for _ in range(heads)]) for _ in range(hw)])
+    qkv = torch.zeros(T, hw, 3, heads, d)
+    t = torch.arange(T)
+    qkv[t, :, 1, :, t] = 16.0
+    for p in range(hw):
+        for h in range(heads):
+            qkv[t, p, 0, h, pi[p][h]] = 16.0
+    f, px, h, c = torch.meshgrid(t, torch.arange(hw), torch.arange(heads), torch.arange(d), indexing="ij")
+    m = (31 * f + 7 * c + 13 * (px * heads + h)) % 2038
+    qkv[:, :, 2] = torch.where(m < 1019, m - 1019, m - 1018).to(F32)
+    return qkv.reshape(T * hw, 3 * C), pi
+
+
+def tattn_ref64(qkv, T, hw, C, heads):
+    """fp64 softmax(q k^T / sqrt(d)) v over the frames of each (pixel, head) -> [T * hw, C]."""
+    d = C // heads
+    x = qkv.double().reshape(T, hw, 3, heads, d).permute(2, 1, 3, 0, 4)          # [3, hw, heads, T, d]
+    a = (x[0] @ x[1].transpose(-1, -2) * d ** -0.5).softmax(dim=-1)
+    return (a @ x[2]).permute(2, 0, 1, 3).reshape(T * hw, C)
+
+
+def tattn_selector_expected(qkv, pi, T, hw, C, heads):
+    d = C // heads
+    v = qkv.double().reshape(T, hw, 3, heads, d)[:, :, 2]
+    out = torch.empty(T, hw, heads, d, dtype=F64)
+    for p in range(hw):
+        for h in range(heads):
+            out[:, p, h] = v[pi[p][h], p, h]
+    return out.reshape(T * hw, C)
+
+
+def assert_tattn_selector_safe(qkv, pi, T, hw, C, heads):
+    """The preconditions under which both temporal kernels must return V[pi] bit for bit (fp64; neither kernel rounds q or the scale
+    to fp16, so there is one scaling):
+      * every v is a nonzero integer with |v| <= 1019: the smallest gap from an output value to a neighbouring fp16 value is 2**-11;
+      * every other frame's weight <= 2**-26: the MFMA kernel's fp16 p is exactly 0 (below half the smallest subnormal, 2**-25);
+      * the other frames' weights sum to <= 2**-26: the fp32 row sum is 1 in any order (half an ulp of 1 is 2**-24), 1 / sum is 1 and
+        the winner's normalised weight is 1;
+      * sum over the other frames of weight * |v| <= 2**-13: a quarter of that smallest gap, with room for the VALU kernel's fp32
+        accumulation (2**-23 relative per step)."""
+    d = C // heads
+    x = qkv.double().reshape(T, hw, 3, heads, d).permute(2, 1, 3, 0, 4)
+    assert torch.equal(qkv.to(F16).float(), qkv)
+    v = x[2]
+    assert bool((v == v.round()).all()) and float(v.abs().max()) <= 1019 and float(v.abs().min()) >= 1, "V: nonzero integers up to 1019"
+    s = x[0] @ x[1].transpose(-1, -2) * d ** -0.5
+    assert torch.equal(s.argmax(dim=-1), pi), "the winner is not the coded frame"
+    w = s.softmax(dim=-1)
+    others = w.scatter(-1, pi[..., None], 0.0)
+    assert float(others.max()) <= 2.0 ** -26 and float(others.sum(-1).max()) <= 2.0 ** -26, f"the other frames weigh up to {float(others.sum(-1).max()):.3g} > 2**-26"
+    leak = float((others @ v.abs()).max())
+    assert leak <= 2.0 ** -13, f"the other frames contribute up to {leak:.3g} > 2**-13"

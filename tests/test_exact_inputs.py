@@ -8,7 +8,10 @@ For every dense, conv3x3, ConvTranspose and patch-embed case of tests/_exact.py:
      swapped. (Tap shift: conv3x3 and the patch embed's 14x14 window; padding: conv3x3, the only op that pads.)
 A case whose inputs let a mistake through would make its GPU test vacuous for that mistake: the inputs are changed, not the check.
 
-The second half of the file does the same for the fp16 GEMM's cases (tests/test_kernels_f16_edges_gpu.py), see there."""
+The second half of the file does the same for the fp16 GEMM's cases (tests/test_kernels_f16_edges_gpu.py), the last part for the fp16
+attention kernels' exact-softmax inputs (tests/test_attention_edges_gpu.py), see there."""
+import functools
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -322,3 +325,170 @@ def test_f16_helpers_refuse_what_they_should():
     assert bool(torch.tensor([E.SENTINEL16_BITS], dtype=torch.int16).view(F16).isnan().all()), "the fp16 sentinel is a NaN"
     from video_depth_anything_amd import _lib
     assert all(getattr(_lib, "EPI_" + k) == v for k, v in E.EPI.items()) and len(E.EPI) == 13
+
+
+# ================================================================================================ the fp16 attention kernels' cases
+# tests/test_attention_edges_gpu.py: the selector and counting inputs meet their preconditions on every case, their fp64 reference IS
+# the closed form, and a tiled restatement of attention with one mistake built in fails the GPU test's own assertion.
+
+ATTN_ALL_CASES = E.ATTN_CASES + [E.ATTN_BIG_CASE]
+
+
+@functools.lru_cache(maxsize=None)
+def selector_case(case):
+    B, N, H = case
+    qkv, pi = E.attn_selector_inputs(B, N, H, E.attn_seed(case))
+    return qkv, pi, E.selector_expected(qkv, pi, B, N, H)
+
+
+def test_attention_case_list_is_the_one_stated():
+    assert [c[1] for c in E.ATTN_CASES[:15]] == [1, 31, 32, 33, 63, 64, 65, 127, 128, 129, 191, 192, 193, 321, 449]
+    assert all(c[0] == 1 and c[2] == 1 for c in E.ATTN_CASES[:15])
+    assert E.ATTN_CASES[15:] == [(3, 129, 1), (1, 129, 3), (2, 65, 4), (3, 193, 3)] and E.ATTN_BIG_CASE == (1, 1370, 2)
+    assert [-(-n // 128) * b * h for b, n, h in E.ATTN_CASES[15:]] == [6, 6, 8, 18], "workgroups: remainder arm twice, quotient arm, both"
+    assert sorted(E.ATTN_VARIANTS) == [-1, 0, 1, 2, 3, 4, 5, 7, 8, 9, 10, 11] and E.ATTN_STRADDLE_N == [129, 160, 192, 449]
+
+
+@pytest.mark.parametrize("case", ATTN_ALL_CASES, ids=E.attn_case_id)
+def test_attention_selector_case_is_exact(case):
+    B, N, H = case
+    qkv, pi, expect = selector_case(case)
+    assert qkv.shape == (B, N, 3 * H * 64) and pi.shape == (B, H, N)
+    assert all(sorted(pi[b][h].tolist()) == list(range(N)) for b in range(B) for h in range(H)), "pi is a permutation per (frame, head)"
+    assert B * H == 1 or N == 1 or len({tuple(pi[b][h].tolist()) for b in range(B) for h in range(H)}) == B * H, "drawn separately"
+    E.assert_selector_safe(qkv, pi, B, N, H)
+    for log2_q in (False, True):
+        ref = E.attn_ref64(qkv, B, N, H, log2_q)
+        assert float((ref - expect).abs().max()) <= 2.0 ** -26
+        assert E.selector_mismatch(ref.to(F16), expect) is None, "the fp64 reference, rounded to fp16, is V[pi]"
+    assert E.selector_mismatch(E.tiled_attention(qkv, B, N, H).to(F16), expect) is None, "the tiled restatement is attention"
+    k = qkv.reshape(B, N, 3, H, 64)[0, :, 1, 0]
+    agree = (k @ k.t() / 144).fill_diagonal_(0)
+    assert float(agree.max()) <= 2, "two keys agree in at most two digits"
+    tiles = {int(j) // 64 for j in pi[0][0].tolist()}
+    assert tiles == set(range(-(-N // 64))), "winners fall in every tile, the last partial one included"
+    v = qkv.reshape(B, N, 3, H, 64)[:, :, 2]
+    rows = v.permute(0, 2, 1, 3).reshape(B * H, N, 64)          # (31 is a unit mod the prime 2039 > N: no two keys of a head share a row)
+    assert all(len({tuple(r.tolist()) for r in rows[g]}) == N for g in range(B * H)), "every key of a (frame, head) has a V row of its own"
+    assert all(not bool((rows[g] == rows[g2]).all(-1).any()) for g in range(B * H) for g2 in range(g)), "the same key differs between heads and frames"
+
+
+@pytest.mark.parametrize("case", ATTN_ALL_CASES, ids=E.attn_case_id)
+def test_attention_counting_case_is_exact(case):
+    B, N, H = case
+    qkv = E.attn_counting_inputs(B, N, H, E.attn_seed(case))
+    assert is_f16(qkv)
+    q, k, v = qkv.reshape(B, N, 3, H, 64).unbind(2)
+    assert not bool(q.any()) and (N < 4 or bool(k.any())) and float(v.sum(1).max()) < E.EXACT_LIMIT
+    expect = E.counting_expected(B, N, H)
+    ref = E.attn_ref64(qkv, B, N, H)
+    assert float((ref - expect).abs().max()) <= 1e-15, "the fp64 reference is the counts over N"
+    for y in (ref.to(F16), E.tiled_attention(qkv, B, N, H).to(F16), expect.float().to(F16)):
+        ok, worst = E.counting_check(y, B, N, H)
+        assert ok and worst <= 1
+    if B * H > 1:
+        rows = expect.reshape(B, N, H, 64)[:, 0].reshape(B * H, 64)
+        assert all(not torch.equal(rows[g], rows[g + 1]) for g in range(B * H - 1)), "neighbouring heads / frames differ in scale"
+
+
+# which family's own assertion must fail for which mistake. The selector is blind to a key counted twice (softmax normalises the
+# winner's doubled weight away) and the counting inputs to anything that permutes keys 64 apart or queries (every row is the same;
+# heads and frames differ by their scale 1 + (b H + h) % 3 only, which is not relied on);
+# between them every mistake is seen wherever it can occur.
+SEEN_BY_SELECTOR = {"drop_last", "mask_moved", "stale_v", "heads", "frames", "queries"}
+SEEN_BY_COUNTING = {"drop_last", "dup_last", "mask_moved"}
+
+
+@pytest.mark.parametrize("mutation", E.ATTN_MUTATIONS)
+@pytest.mark.parametrize("case", ATTN_ALL_CASES, ids=E.attn_case_id)
+def test_attention_equalities_can_fail(case, mutation):
+    B, N, H = case
+    if not E.attn_mutation_applies(mutation, B, N, H):
+        for fam in ("selector", "counting"):                     # the mistake cannot occur at this shape: the restatement is unchanged
+            qkv = selector_case(case)[0] if fam == "selector" else E.attn_counting_inputs(B, N, H, E.attn_seed(case))
+            assert torch.equal(E.tiled_attention(qkv, B, N, H, mutation), E.tiled_attention(qkv, B, N, H))
+        return
+    seen = set()
+    qkv, pi, expect = selector_case(case)
+    if E.selector_mismatch(E.tiled_attention(qkv, B, N, H, mutation).to(F16), expect) is not None:
+        seen.add("selector")
+    ok, _ = E.counting_check(E.tiled_attention(E.attn_counting_inputs(B, N, H, E.attn_seed(case)), B, N, H, mutation).to(F16), B, N, H)
+    if not ok:
+        seen.add("counting")
+    want = ({"selector"} if mutation in SEEN_BY_SELECTOR else set()) | ({"counting"} if mutation in SEEN_BY_COUNTING else set())
+    assert want and want <= seen, f"{mutation} goes unnoticed by {sorted(want - seen)} on these inputs"
+
+
+def test_selector_mismatch_names_the_key():
+    case = (1, 65, 1)
+    qkv, pi, expect = selector_case(case)
+    y = E.tiled_attention(qkv, 1, 65, 1, "stale_v").to(F16)
+    msg = E.selector_mismatch(y, expect, qkv.reshape(1, 65, 3, 1, 64)[:, :, 2])
+    i = pi[0][0].tolist().index(64)
+    assert msg is not None and msg.startswith("1/65 ") and f"query {i} head 0" in msg and "(0, 0)" in msg, msg
+
+
+@pytest.mark.parametrize("N", E.ATTN_STRADDLE_N)
+def test_attention_straddle_margins(N):
+    """Both row sums at least 8 % from SUM_LIMIT under either q scaling; the fp16 rounding of q * log2(e) / 8 moves the fp64 result by
+    less than a third of the GPU test's bound."""
+    qkv = E.attn_straddle_inputs(N, 9900 + N)
+    assert is_f16(qkv) and float(qkv[..., 128:].min()) >= 1
+    for log2_q in (False, True):
+        even, odd = E.straddle_tile_sums(qkv, log2_q)
+        assert even <= E.ATTN_SUM_LIMIT * 0.92 and odd >= E.ATTN_SUM_LIMIT * 1.08, (even, odd)
+        assert abs(even - 64 * 2.718281828459045 ** 3.25) < 5 and abs(odd - 64 * 2.718281828459045 ** 3.65625) < 8
+    ref, ref2 = E.attn_ref64(qkv, 1, N, 1), E.attn_ref64(qkv, 1, N, 1, log2_q=True)
+    err = (ref2 - ref).abs() / (1 + ref.abs())
+    assert float(err.max()) <= E.ATTN_TOL / 3, float(err.max())
+    assert float((E.tiled_attention(qkv, 1, N, 1) - ref).abs().max()) < 1e-9
+
+
+@pytest.mark.parametrize("C,heads", E.TATTN_SELECTOR_GEOM)
+def test_temporal_selector_cases_are_exact(C, heads):
+    for T in E.TATTN_T:
+        for hw in E.TATTN_HW:
+            qkv, pi = E.tattn_selector_inputs(T, hw, C, heads, E.tattn_seed(T, hw, C, heads))
+            assert qkv.shape == (T * hw, 3 * C) and pi.shape == (hw, heads, T)
+            E.assert_tattn_selector_safe(qkv, pi, T, hw, C, heads)
+            expect = E.tattn_selector_expected(qkv, pi, T, hw, C, heads)
+            ref = E.tattn_ref64(qkv, T, hw, C, heads)
+            assert torch.equal(ref.to(F16).double(), expect), "the fp64 reference, rounded to fp16, is V[pi]"
+            if T > 1:
+                differs(expect.reshape(T, hw * C).flip(0), expect.reshape(T, hw * C), "frames in the wrong order")
+            if hw > 1:
+                differs(expect.reshape(T, hw, C).flip(1), expect.reshape(T, hw, C), "pixels in the wrong order")
+            if heads > 1:
+                differs(expect.reshape(T * hw, heads, C // heads).flip(1), expect.reshape(T * hw, heads, C // heads), "heads in the wrong order")
+
+
+def test_temporal_selector_needs_nonzero_values():
+    """With a zero in V the d = 128 case's real result next to it is a nonzero fp16 subnormal: the precondition refuses it."""
+    T, hw, C, heads = 32, 1, 1024, 8
+    qkv, pi = E.tattn_selector_inputs(T, hw, C, heads, 1)
+    bad = qkv.clone()
+    bad[int(pi[0][0][0]), 2 * C] = 0.0                          # V of query 0's winner, head 0, channel 0
+    with pytest.raises(AssertionError, match="nonzero"):
+        E.assert_tattn_selector_safe(bad, pi, T, hw, C, heads)
+    assert float(E.tattn_ref64(bad, T, hw, C, heads)[0, 0].to(F16)) != 0.0
+
+
+def test_attention_helpers_refuse_what_they_should():
+    B, N, H = 1, 65, 1
+    qkv, pi = E.attn_selector_inputs(B, N, H, 3)
+    weak = qkv.clone().reshape(B, N, 3, H, 64)
+    weak[:, :, 0] *= 0.5                                         # a lead of 18 natural units: weights of e^-18 are not nothing
+    with pytest.raises(AssertionError, match="2\\*\\*-40"):
+        E.assert_selector_safe(weak.reshape(B, N, 192), pi, B, N, H)
+    big = qkv.clone()
+    big[0, 0, 128] = 1020.0
+    with pytest.raises(AssertionError, match="1019"):
+        E.assert_selector_safe(big, pi, B, N, H)
+    wrong = pi.clone()
+    wrong[0, 0, :2] = pi[0, 0, :2].flip(0)
+    with pytest.raises(AssertionError, match="winner"):
+        E.assert_selector_safe(qkv, wrong, B, N, H)
+    assert E.counting_check(E.counting_expected(1, 64, 1).to(F16), 1, 64, 1) == (True, 0.0)
+    off = E.counting_expected(1, 65, 1).to(F16)
+    nudged = (off.view(torch.int16) + 2).view(F16)              # two fp16 steps: refused; one: allowed
+    assert not E.counting_check(nudged, 1, 65, 1)[0] and E.counting_check((off.view(torch.int16) + 1).view(F16), 1, 65, 1)[0]
