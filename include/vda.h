@@ -68,7 +68,15 @@ enum vda_epilogue {
                                     token's spread, not its offset), 0 when pos == NULL (zero_page must then be set) */
     VDA_EPI_LN_BIAS_F16 = 11,    /* A = hi plane, W = W*diag(ln_w) (vda_fold_ln_weight): out_h = rstd[m]*(acc - mean[m]*gamma[n]) + bias[n]
                                     with (mean, rstd) = stats[m, 0:2], gamma = c1 = row sums of the folded W, bias = c2 = b + W.ln_b */
-    VDA_EPI_LN_GELU_F16 = 12     /* the same followed by gelu_erf (mlp.fc1) */
+    VDA_EPI_LN_GELU_F16 = 12,    /* the same followed by gelu_erf (mlp.fc1) */
+    /* ---- ConvTranspose2d(k == stride) folded into the bias-free 3x3 conv behind it (dpt.py:71-82 + dpt_temporal.py:78-79), fp16 path,
+     * VDA_A_CONV3X3 only. A = the ConvTranspose's INPUT (NHWC, the "tap grid": cH x cW = tH x tW, stride 1), W = vda_fold_convt_weight's
+     * Wf: row n = (py*k + px)*tCout + co is output phase (py, px) = the k x k sub-pixel of an input pixel, K = (dy, dx, ci) over the 3x3
+     * neighbourhood of the tap grid; the blocks of taps a phase does not reach are zero and the kernels skip them (a phase reaches at
+     * most 2 x 2 taps). bias = vda_fold_convt_weight's Bc [k*k][9][tCout] (REQUIRED): the ConvTranspose's bias seen through the conv's
+     * zero padding, by the pixel's border class 3*cy + cx (0 = first row / column, 1 = interior, 2 = last).
+     * out_h[((b*tH + y)*k + py) * tW*k + x*k + px, co] = acc + Bc[py*k + px][class(y, x)][co]; the accumulators start at zero. */
+    VDA_EPI_CONVT_FOLD_F16 = 13
 };
 
 typedef struct vda_gemm_args {
@@ -87,7 +95,7 @@ typedef struct vda_gemm_args {
     int32_t relu_in;        /* apply relu to A elements on load (blocks.py:78) */
     /* VDA_A_CONV3X3 */
     int32_t cB, cH, cW, cCin, cHo, cWo, cStride;
-    /* VDA_EPI_PATCH_F32: P patches per frame. VDA_EPI_CONVT_F16: k, input h, w, Cout */
+    /* VDA_EPI_PATCH_F32: P patches per frame. VDA_EPI_CONVT_F16 / VDA_EPI_CONVT_FOLD_F16: k, input h, w, Cout */
     int32_t P, tK, tH, tW, tCout;
     void* out2;             /* VDA_EPI_SCALE_RES_SPLIT: lo plane of the result */
     float* stats;           /* VDA_EPI_SCALE_RES_SPLIT: out, [N/64, M, 2] partial row statistics;
@@ -216,6 +224,17 @@ int vda_layernorm_split_f16(const void* hi, const void* lo, void* out, const flo
                             int rows, int D, int group, int skip, vda_stream_t stream);
 int vda_fold_ln_weight(const float* W, const float* bias, const float* ln_w, const float* ln_b, void* Wf, float* c1, float* c2,
                        int N, int K, vda_stream_t stream);
+
+/* ---- Pack-time fold of ConvTranspose2d(k == stride, weight Wt [Ci, Cm, k, k], bias bt [Cm]) into the bias-free 3x3 / pad 1 conv
+ * behind it (Wr [Co, Cm, 3, 3]): the operands of VDA_EPI_CONVT_FOLD_F16. For output phase (py, px) and conv tap (ky, kx):
+ * qy = py + ky - 1, dy = floor(qy / k) in {-1, 0, 1}, ConvTranspose row phase ry = qy - k*dy (the same in x), and
+ *   Wf[(py*k + px)*Co + co][((dy+1)*3 + dx+1)*Cip + ci] = fp16( sum over (ky, kx) -> (dy, dx), cm of Wr[co,cm,ky,kx] * Wt[ci,cm,ry,rx] )
+ *   Bc[py*k + px][3*cy + cx][co] = sum over the (ky, kx) whose (dy, dx) lies inside the image for border class (cy, cx), cm of
+ *                                  Wr[co,cm,ky,kx] * bt[cm]        (class 0: d = -1 is outside; 2: d = +1 is outside; 1: neither)
+ * composed in fp32 (fmaf, (ky, kx, cm) order) and rounded once. Cip >= Ci: the padded channel count of the GEMM's K (columns
+ * ci >= Ci are zero). Wf fp16 [k*k*Co, 9*Cip], Bc fp32 [k*k, 9, Co]. */
+int vda_fold_convt_weight(const float* Wt, const float* bt, const float* Wr, void* Wf, float* Bc, int k, int Ci, int Cm, int Co, int Cip,
+                          vda_stream_t stream);
 
 /* ---- One block's MLP branch on the split residual stream in ONE kernel (dinov2_layers/mlp.py:35-41, block.py:105-106,
  * layer_scale.py:27-28; fp16 path with the LayerNorm fold): hi + lo += gamma * (fc2(GELU(fc1(LayerNorm(hi + lo)))) + b2), hid never
@@ -533,7 +552,9 @@ int vda_forward(vda_model* h, const float* in, float* out, int B, int T, int H, 
  * a report nobody collected fails the NEXT vda_forward instead. Reports are cleared once returned. */
 int vda_forward_status(vda_model* h);
 /* Parity hook: copy `bytes` of a named intermediate of the last forward ("tap0".."tap3", "l1", "l2", "l3t", "l4t", "p4t",
- * "p3t", "p2", "p1"; activation dtype of that forward's precision, channels padded to multiples of 64) to device `dst`. */
+ * "p3t", "p2", "p1"; activation dtype of that forward's precision, channels padded to multiples of 64) to device `dst`.
+ * "l1" / "l2" of a forward that ran that level folded (option "convt_fold") were never written: they are rebuilt first, on `stream`,
+ * from the level's projection ("t0" / "t1") with the unfused ConvTranspose GEMM - what the unfused forward holds there, bit for bit. */
 int vda_debug_copy(vda_model* h, const char* name, void* dst, int64_t bytes, vda_stream_t stream);
 /* Test utility: occupy `wgs` workgroups (256 threads, lds_bytes of LDS each) for about `cycles` shader clocks on `stream` - a
  * stand-in for a communication kernel running beside the forward (tools/contention.py). Bounded: every wave leaves by itself. */
@@ -551,7 +572,12 @@ int vda_debug_occupy(int wgs, int lds_bytes, long long cycles, vda_stream_t stre
  * branches that do not depend on tap 3 (the tap 0..2 work above and the first conv of resConfUnit1 in refinenets 3, 2, 1) run on the
  * stream "enc_split" uses, beside proj3 .. motion module 2 on `stream`, joined back before refinenet 3 and refinenet 2
  * read what it made. Bit-identical results, the same workspace layout. Like "enc_split" it does not apply while `stream`
- * is capturing or another forward of the handle is in flight on a different stream, and not together with "head_overlap". */
+ * is capturing or another forward of the handle is in flight on a different stream, and not together with "head_overlap".
+ * "convt_fold" (default 1, or the environment's VDA_CONVT_FOLD; fp16 path; < 0 restores that default): resize_layers[i] (ConvTranspose2d,
+ * k == stride) and layer{i+1}_rn (3x3, no bias) for i = 0, 1 run as ONE implicit GEMM on the projection's grid (VDA_EPI_CONVT_FOLD_F16,
+ * weights composed at pack time by vda_fold_convt_weight) wherever the unfused 3x3 conv would run on the 256 x 256 8-phase or the
+ * 128-row GEMM kernel (ViT-L; not the 64-channel convs of ViT-S): "l1" / "l2" are then never written. Same workspace layout. Not
+ * bit-identical to 0: one fp16 rounding of l1 / l2 less, one rounding of the composed weights more. */
 int vda_set_option(vda_model* h, const char* name, int value);
 /* Measurement hook (bench.py): from vda_profile_start until vda_profile_stop every `every`-th GEMM / conv launch of each
  * (shape, epilogue) inside vda_forward is bracketed by two events on the launch stream. vda_profile_stop waits for them and

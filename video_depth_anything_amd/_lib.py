@@ -10,7 +10,8 @@ LIB_PATH = os.environ.get("VDA_LIB_PATH") or os.path.join(_HERE, "libvda_hip.so"
 
 A_DENSE, A_CONV3X3 = 0, 1
 (EPI_BIAS_F16, EPI_BIAS_GELU_F16, EPI_BIAS_RELU_F16, EPI_SCALE_RES_F32, EPI_RES_F16, EPI_GEGLU_F16,
- EPI_PATCH_F32, EPI_CONVT_F16, EPI_BIAS_F32, EPI_SCALE_RES_F32_H, EPI_SCALE_RES_SPLIT, EPI_LN_BIAS_F16, EPI_LN_GELU_F16) = range(13)
+ EPI_PATCH_F32, EPI_CONVT_F16, EPI_BIAS_F32, EPI_SCALE_RES_F32_H, EPI_SCALE_RES_SPLIT, EPI_LN_BIAS_F16, EPI_LN_GELU_F16,
+ EPI_CONVT_FOLD_F16) = range(14)
 
 
 class GemmArgs(C.Structure):
@@ -73,6 +74,7 @@ SIGNATURES = {
     "vda_ln_stats_finalize": (_i, [_vp, _vp, _f, _i, _i, _vp, _vp]),
     "vda_layernorm_split_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _vp]),
     "vda_fold_ln_weight": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "vda_fold_convt_weight": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "vda_mlp_fused_supported": (_i, [_i, _i]),
     "vda_mlp_permute_w2_f16": (_i, [_vp, _vp, _i, _i, _vp]),
     "vda_mlp_fused_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),

@@ -27,8 +27,11 @@ constexpr int ROW_BYTES = BK * 2;      // 128 B per tile row
 constexpr int NWAVES = 4;
 constexpr int NTHREADS = NWAVES * 64;
 
-template <int BM, int BN, int AMODE>
-__global__ void __launch_bounds__(NTHREADS) gemm_kernel(const vda_gemm_args p) {
+// FOLD (VDA_EPI_CONVT_FOLD_F16, vda.h; conv A): the K loop visits only the taps the tile's output phases reach, and the epilogue is
+// that one. A kernel of its own (gemm_fold_kernel), so that the other kernels' code and names do not change.
+template <int BM, int BN, int AMODE, bool FOLD>
+__device__ __forceinline__ void gemm_tile(const vda_gemm_args& p) {
+    static_assert(!FOLD || AMODE == VDA_A_CONV3X3, "the folded mode is a conv A mode");
     constexpr int WTM = BM / 2, WTN = BN / 2;     // wave tile
     constexpr int MI = WTM / 16, NI = WTN / 16;   // 16x16 subtiles per wave
     constexpr int AJ = BM / 8 / NWAVES;           // 1-KiB DMA pieces per wave, A tile
@@ -81,13 +84,17 @@ __global__ void __launch_bounds__(NTHREADS) gemm_kernel(const vda_gemm_args p) {
         w_src[j] = (const h16*)p.W + (size_t)n * p.K + lchk;
     }
 
+    [[maybe_unused]] const int tap_mask = FOLD ? vda_gemm::fold_tap_mask(n0, min(n0 + BN, p.N), p.tK, p.tCout) : 0x1FF;
     auto stage = [&](int kt, char* buf) {
         const int k0 = kt * BK;
+        [[maybe_unused]] int kw = k0;             // W's K offset (FOLD: it follows the tap)
         if constexpr (AMODE == VDA_A_DENSE) {
 #pragma unroll
             for (int j = 0; j < AJ; ++j) glds16(a_src[j] + k0, buf + (wave + NWAVES * j) * 1024);
         } else {
-            const int tap = k0 / p.cCin, ci0 = k0 - tap * p.cCin;
+            const int tap0 = k0 / p.cCin, ci0 = k0 - tap0 * p.cCin;
+            const int tap = FOLD ? vda_gemm::fold_nth_tap(tap_mask, tap0) : tap0;      // FOLD: the tap0-th SET tap of the mask
+            if constexpr (FOLD) kw = tap * p.cCin + ci0;
             const int ky = tap / 3, kx = tap - ky * 3;
 #pragma unroll
             for (int j = 0; j < AJ; ++j) {
@@ -99,7 +106,7 @@ __global__ void __launch_bounds__(NTHREADS) gemm_kernel(const vda_gemm_args p) {
             }
         }
 #pragma unroll
-        for (int j = 0; j < WJ; ++j) glds16(w_src[j] + k0, buf + A_BYTES + (wave + NWAVES * j) * 1024);
+        for (int j = 0; j < WJ; ++j) glds16(w_src[j] + (FOLD ? kw : k0), buf + A_BYTES + (wave + NWAVES * j) * 1024);
     };
 
     f32x4 acc[MI][NI];
@@ -138,7 +145,7 @@ __global__ void __launch_bounds__(NTHREADS) gemm_kernel(const vda_gemm_args p) {
         }
     };
 
-    const int nt = p.K / BK;
+    const int nt = FOLD ? __builtin_popcount(tap_mask) * (p.cCin / BK) : p.K / BK;
     stage(0, smem);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -168,16 +175,30 @@ __global__ void __launch_bounds__(NTHREADS) gemm_kernel(const vda_gemm_args p) {
                 for (int j = 0; j < NI; ++j) store_one<EPI>(p, em + i * 16, en + j * 16, acc[i][j], acc[i][j]);
         }
     };
-    vda_gemm::dispatch_epilogue(p.epilogue, run);
+    if constexpr (FOLD) run(std::integral_constant<int, VDA_EPI_CONVT_FOLD_F16>{});
+    else vda_gemm::dispatch_epilogue(p.epilogue, run);
 }
 
 template <int BM, int BN, int AMODE>
+__global__ void __launch_bounds__(NTHREADS) gemm_kernel(const vda_gemm_args p) {
+    gemm_tile<BM, BN, AMODE, false>(p);
+}
+template <int BM, int BN>
+__global__ void __launch_bounds__(NTHREADS) gemm_fold_kernel(const vda_gemm_args p) {
+    gemm_tile<BM, BN, VDA_A_CONV3X3, true>(p);
+}
+
+template <int BM, int BN, int AMODE, bool FOLD = false>
 int launch(const vda_gemm_args& a, hipStream_t s) {
     constexpr int smem = 2 * (BM + BN) * ROW_BYTES;
     static VdaKernelDeviceState dev_state;
-    if (vda_prepare_kernel(reinterpret_cast<const void*>(&gemm_kernel<BM, BN, AMODE>), smem, dev_state) < 0) return 2;
+    void (*const kern)(const vda_gemm_args) = [] {
+        if constexpr (FOLD) return &gemm_fold_kernel<BM, BN>;
+        else return &gemm_kernel<BM, BN, AMODE>;
+    }();
+    if (vda_prepare_kernel(reinterpret_cast<const void*>(kern), smem, dev_state) < 0) return 2;
     const int nbm = (a.M + BM - 1) / BM, nbn = (a.N + BN - 1) / BN;
-    hipLaunchKernelGGL((gemm_kernel<BM, BN, AMODE>), dim3(nbm * nbn), dim3(NTHREADS), smem, s, a);
+    hipLaunchKernelGGL(kern, dim3(nbm * nbn), dim3(NTHREADS), smem, s, a);
     VDA_LAUNCH_CHECK();
     return 0;
 }
@@ -225,6 +246,7 @@ int vda_gemm8p_dense_bn256_sched(const vda_gemm_args& a, hipStream_t s, int sche
 int vda_gemm8p_dense_bn128(const vda_gemm_args& a, hipStream_t s);
 int vda_gemm8p_dense_bn256_bm192(const vda_gemm_args& a, hipStream_t s);     // 192 x 256 tiles
 int vda_gemm8p_conv_bn128(const vda_gemm_args& a, hipStream_t s);
+int vda_gemm8p_conv_fold_bn256(const vda_gemm_args& a, hipStream_t s);       // VDA_EPI_CONVT_FOLD_F16
 int vda_conv3x3_lds(const vda_gemm_args& a, hipStream_t s);                  // conv_lds.hip: patch-in-LDS direct 3x3 convolution for
 bool vda_conv3x3_lds_covers(const vda_gemm_args& a);                         // narrow outputs, and the problems it covers
 
@@ -242,12 +264,16 @@ static int launch_small(const vda_gemm_args& a, hipStream_t s) {
         }
         return rc;
     }
+    if (a.epilogue == VDA_EPI_CONVT_FOLD_F16) return launch<128, 128, VDA_A_CONV3X3, true>(a, s);      // (N = k * k * Cout: never narrow)
     return narrow ? launch<128, 64, VDA_A_CONV3X3>(a, s) : launch<128, 128, VDA_A_CONV3X3>(a, s);
 }
 
 extern "C" int vda_gemm_built(int family, int bm, int bn, int per_cu, int a_mode, int epilogue) {
     const bool dense = a_mode == VDA_A_DENSE, conv = a_mode == VDA_A_CONV3X3, wide = bn == 256 || bn == 128;
-    if (epilogue < 0 || epilogue > VDA_EPI_LN_GELU_F16 || !(dense || conv)) return 0;
+    if (epilogue < 0 || epilogue > VDA_EPI_CONVT_FOLD_F16 || !(dense || conv)) return 0;
+    // the folded ConvTranspose + conv: conv A on the 128-row kernel's 128 x 128 tile and the 8-phase 256 x 256 tile, nowhere else
+    if (epilogue == VDA_EPI_CONVT_FOLD_F16)
+        return conv && per_cu == 1 && ((family == VDA_GEMM_FAM_128 && bm == 128 && bn == 128) || (family == VDA_GEMM_FAM_8P && bm == 256 && bn == 256));
     switch (family) {
         case VDA_GEMM_FAM_128: return bm == 128 && (bn == 64 || bn == 128) && per_cu == 1;
         case VDA_GEMM_FAM_256: return bm == 256 && wide && per_cu == 1 && (dense ? VDA_EPI_BUILT(VDA_EPIS_DENSE_MFMA32, epilogue) : VDA_EPI_BUILT(VDA_EPIS_CONV, epilogue));
@@ -379,7 +405,7 @@ static int validate(vda_gemm_args& a, bool operands) {
     VDA_REQUIRE(a.N % 4 == 0 && a.ldc % 4 == 0, "vda_gemm_f16: N=%d and ldc=%d must be multiples of 4", a.N, a.ldc);
     VDA_REQUIRE(VDA_PTR(((uintptr_t)a.A & 15) == 0 && ((uintptr_t)a.W & 15) == 0 && ((uintptr_t)a.out & 15) == 0),
                 "vda_gemm_f16: operands must be 16-byte aligned");
-    VDA_REQUIRE(a.epilogue >= 0 && a.epilogue <= VDA_EPI_LN_GELU_F16, "vda_gemm_f16: bad epilogue %d", a.epilogue);
+    VDA_REQUIRE(a.epilogue >= 0 && a.epilogue <= VDA_EPI_CONVT_FOLD_F16, "vda_gemm_f16: bad epilogue %d", a.epilogue);
     if (a.a_mode == VDA_A_DENSE) {
         VDA_REQUIRE(a.relu_in == 0, "vda_gemm_f16: relu_in is only built for the conv A operand");
         VDA_REQUIRE((a.lda >= a.K || a.lda == 0) && a.lda % 8 == 0, "vda_gemm_f16: lda=%d must be >= K (or 0 = broadcast row) and a multiple of 8", a.lda);
@@ -434,6 +460,13 @@ static int validate(vda_gemm_args& a, bool operands) {
             VDA_REQUIRE(a.tK > 0 && a.tCout > 0 && a.tCout % 4 == 0 && a.N == a.tK * a.tK * a.tCout && a.M % (a.tH * a.tW) == 0,
                         "vda_gemm_f16: bad ConvTranspose geometry");
             break;
+        case VDA_EPI_CONVT_FOLD_F16:
+            VDA_REQUIRE(a.a_mode == VDA_A_CONV3X3 && a.cStride == 1, "vda_gemm_f16: the folded ConvTranspose epilogue needs the conv A operand at stride 1");
+            VDA_REQUIRE(a.tK >= 2 && a.tCout > 0 && a.tCout % 8 == 0 && a.N == a.tK * a.tK * a.tCout && a.tH == a.cH && a.tW == a.cW && a.ldc % 8 == 0,
+                        "vda_gemm_f16: bad folded ConvTranspose geometry (k=%d Cout=%d N=%d, %d x %d on a %d x %d grid)", a.tK, a.tCout, a.N, a.tH, a.tW, a.cH, a.cW);
+            VDA_REQUIRE(VDA_PTR(a.bias != nullptr), "vda_gemm_f16: the folded ConvTranspose epilogue needs bias (the class-bias table of vda_fold_convt_weight)");
+            VDA_REQUIRE((long long)a.M * a.tK * a.tK * a.ldc < (1ll << 31), "vda_gemm_f16: folded ConvTranspose output too large for 32-bit offsets");
+            break;
         default:
             break;
     }
@@ -457,6 +490,8 @@ static int plan_one(const GemmTuning& t, const vda_gemm_args& a, int Mp, int ncu
     // Narrow-output 3x3 convs (Cout <= 64: the ViT-S head) run as a patch-in-LDS direct convolution instead of an implicit GEMM
     // (variant 7 forces it, any other explicit variant or VDA_CONV_LDS=0 keeps the GEMM: A/B and cross-checks).
     if (!dense && ((v < 0 && t.conv_lds) || v == 7) && vda_conv3x3_lds_covers(a) && pick(VDA_GEMM_FAM_CONV_LDS, 0, a.N <= 32 ? 32 : 64, 1, a.relu_in)) return 0;
+    const bool fold = a.epilogue == VDA_EPI_CONVT_FOLD_F16;
+    if (fold) r->bn = 128;
     const bool fits32 = (dense ? (long long)a.M * a.lda : 0ll) + a.K < (1ll << 31) && (long long)a.N * a.K < (1ll << 31);
     VDA_REQUIRE(fits32 || v <= 0, "vda_gemm_f16: operand too large for the 256-row kernel's 32-bit offsets");
     if (!fits32) return 0;
@@ -479,6 +514,7 @@ static int plan_one(const GemmTuning& t, const vda_gemm_args& a, int Mp, int ncu
         big = 0;                            // its epilogue owns 8-column (16-byte) row segments
     }
     if (!big) return 0;
+    if (fold && !(eight && big == 256)) return 0;          // built for the 8-phase 256 x 256 tile only: anything else is the 128-row kernel's
     // ---- the option word
     int opt = a.relu_in;
     if (!t.stagger) opt |= VDA_FLAG_NO_STAGGER << VDA_OPT_FLAGS_SHIFT;
@@ -521,7 +557,7 @@ static int plan_one(const GemmTuning& t, const vda_gemm_args& a, int Mp, int ncu
     if (eight) {
         // the name reports the schedule ASKED for (vda_gemm8p_dense_bn256_sched falls back to the default one for other epilogues)
         r->ksched = sched8 == 1 ? 0 : sched8 == 2 ? 2 : 1;
-        r->dyn = a.sched != nullptr && r->ksched == 1;
+        r->dyn = a.sched != nullptr && r->ksched == 1 && !fold;        // (the folded mode has no dynamic-draw instantiation)
     }
     return 0;
 }
@@ -558,7 +594,9 @@ extern "C" int vda_gemm_plan(const vda_gemm_args* args, int m_plan, int ncu, int
 
 extern "C" int vda_gemm_launch_name(const vda_gemm_launch* r, char* name, int len) {
     switch (r->family) {
-        case VDA_GEMM_FAM_128: return snprintf(name, len, "gemm_kernel<%d, %d, %d>", r->bm, r->bn, r->a_mode);
+        case VDA_GEMM_FAM_128:
+            if (r->epilogue == VDA_EPI_CONVT_FOLD_F16) return snprintf(name, len, "gemm_fold_kernel<%d, %d>", r->bm, r->bn);
+            return snprintf(name, len, "gemm_kernel<%d, %d, %d>", r->bm, r->bn, r->a_mode);
         case VDA_GEMM_FAM_256: return snprintf(name, len, "gemm256_kernel<%d, %d, %d>", r->bn, r->a_mode, r->epilogue);
         case VDA_GEMM_FAM_256S: return snprintf(name, len, "gemm256s_kernel<%d, %d, %d, %d, %d>", r->bn, r->a_mode, r->epilogue, r->bm, r->per_cu);
         case VDA_GEMM_FAM_8P:   // (every template argument, defaults included, as the profiler prints them)
@@ -596,7 +634,7 @@ static int launch_record(const vda_gemm_launch& r, const vda_gemm_args& a0, hipS
         case VDA_GEMM_FAM_8P:
             if (r.bm == 192) rc = vda_gemm8p_dense_bn256_bm192(a, s);
             else if (!wide) rc = dense ? vda_gemm8p_dense_bn128(a, s) : vda_gemm8p_conv_bn128(a, s);
-            else if (!dense) rc = vda_gemm8p_conv_bn256(a, s);
+            else if (!dense) rc = a.epilogue == VDA_EPI_CONVT_FOLD_F16 ? vda_gemm8p_conv_fold_bn256(a, s) : vda_gemm8p_conv_bn256(a, s);
             else rc = r.ksched != 1 ? vda_gemm8p_dense_bn256_sched(a, s, r.ksched == 0 ? 1 : 2) : vda_gemm8p_dense_bn256(a, s);
             break;
         default: break;

@@ -50,6 +50,12 @@ __device__ __forceinline__ void vm_wait_keep() {
 template <int BN, int AMODE, int EPI, int SCHED = 1, int BM = 256, bool DYN = false>
 __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
     static_assert(BM == 256 || (BM == 192 && BN == 256 && AMODE == VDA_A_DENSE), "192-row tiles: dense A, 256 columns");
+    // FOLD (VDA_EPI_CONVT_FOLD_F16, vda.h): a ConvTranspose folded into the 3x3 conv behind it = a 3x3 conv on the tap grid whose
+    // column tile (one output phase at Cout = 256, four at 64) reaches only SOME of the nine taps: the K loop visits the K tiles of
+    // those taps alone (set_sources: cv_mask; tap_of / tap_next step over its set bits), so a tile has popcount * Cin / 64 K tiles -
+    // 4, 8 or 16 at k = 4, Cin = 256 - instead of 36. Tiles of unequal length need the ROTATED walk of tile_of below.
+    constexpr bool FOLD = EPI == VDA_EPI_CONVT_FOLD_F16;
+    static_assert(!FOLD || (AMODE == VDA_A_CONV3X3 && BN == 256 && BM == 256 && !DYN), "the folded mode: conv A, 256 x 256 tiles, static walk");
     constexpr int WN = BN == 256 ? 4 : 2;          // waves along N
     constexpr int WM = NW / WN;                    // waves along M
     constexpr int WTM = BM / WM, WTN = BN / WN;    // wave tile: 128x64 (BN=256) or 64x64 (BN=128)
@@ -97,8 +103,8 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
     // asks for it (measured +1 % slower there); debug bit 4 switches it off everywhere (A/B).
     const int cgw = (nbn % 4 == 0 && (nbn == 8 || nbn == 16 || nbn == 32 || (nbn == 4 && (dbg2 & VDA_DEBUG_BLOCKED_MORE)))) ? 4 : (((nbn == 12 || nbn == 24) && (dbg2 & VDA_DEBUG_BLOCKED_MORE)) ? 6 : 0);
     const int cgroups = cgw ? nbn / cgw : 1;
-    const bool blocked = cgw != 0 && per_xcd == 32 && !DYN && !(dbg2 & VDA_DEBUG_NEVER_BLOCKED) && full_rounds > 0;
-    auto tile_of = [&](int round) {
+    const bool blocked = cgw != 0 && per_xcd == 32 && !DYN && !FOLD && !(dbg2 & VDA_DEBUG_NEVER_BLOCKED) && full_rounds > 0;
+    auto tile_of_plain = [&](int round) {
         if (blocked) {
             // the group's tiles in row-major order (CG wide), dealt 32 at a time to its XCDs: XCD i of the group takes chunk r * xpg + i
             const int x = bid & 7, slot = bid >> 3, xpg = 8 / cgroups;
@@ -111,6 +117,24 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
             return j < rem ? round * nwg + j : ntiles;
         }
         return round * nwg + (bid & 7) * per_xcd + (bid >> 3);
+    };
+    // FOLD: in the walk above a workgroup keeps its column panel from round to round whenever nbn | nwg (16 | 256) - the one that
+    // drew a 16-K-tile phase would run 16-K-tile phases all launch long and the launch would end at ITS pace (4x the lightest). The
+    // column is therefore ROTATED by FOLD_ROT panels per round: row panel bm takes the rotation of the round it falls in, a function
+    // of bm alone, so the map stays a bijection of the tile set for any grid, and a round still covers the same tiles (same A / W
+    // panels shared in an XCD's L2). FOLD_ROT = 5: coprime with every nbn in use (4, 16), and at k = 4 a step of 5 = (+1 row, +1
+    // column) of the 4 x 4 phase grid, which walks heavy and light phases alternately: over the 11 rounds of the ViT-L launch the
+    // heaviest workgroup carries 27 K-tile units against a mean of 24.75 (+9 %), where a step of 1 leaves 29 (+17 %).
+    constexpr int FOLD_ROT = 5;
+    auto tile_of = [&](int round) {
+        int t = tile_of_plain(round);
+        if constexpr (FOLD) {
+            if (t < ntiles) {
+                const int bm = t / nbn, bn = t - bm * nbn;
+                t = bm * nbn + (bn + (bm * nbn / nwg) * FOLD_ROT) % nbn;
+            }
+        }
+        return t;
     };
 
     // DYNAMIC tile schedule (p.sched != NULL: eight zeroed int32 counters, one per XCD). XCD x owns the contiguous tile range
@@ -139,12 +163,15 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
     // per K tile the address is one scalar (tap offset + channel slice) added to a lane constant, like the dense operand's.
     int a_base[AJ], a_mask[AJ];
     int tm0 = 0, tn0 = 0;             // origin of the tile being staged
+    [[maybe_unused]] int cv_mask = 0x1FF;      // FOLD: the taps the tile's output phases reach (gemm_epilogue.h, fold_tap_mask)
+    [[maybe_unused]] const int cv_cpt = FOLD ? p.cCin / BK : 1;       // FOLD: K tiles per tap
     [[maybe_unused]] const auto a_rsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<void*>(p.A), 0, AMODE == VDA_A_CONV3X3 ? (unsigned)(p.cB * p.cH * p.cW * p.cCin) * 2u : 0u, 0x00020000);
     auto set_sources = [&](int t) {
         const int bm = t / nbn, bn = t - bm * nbn;
         tm0 = bm * BM;
         tn0 = bn * BN;
+        if constexpr (FOLD) cv_mask = vda_gemm::fold_tap_mask(tn0, min(tn0 + BN, p.N), p.tK, p.tCout);
         if constexpr (AMODE == VDA_A_CONV3X3) {
 #pragma unroll
             for (int j = 0; j < AJ; ++j) {
@@ -171,9 +198,19 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
     // conv: which 3x3 tap and which 64-channel slice K tile kt is. A division by the runtime channel count: used at the tile
     // seams only - inside the K loop the pair is advanced incrementally (a ~40-instruction dependent chain in a load section
     // outlasts the partner's MFMA section: the 8-phase conv was 16 % slower than the one-barrier kernel because of it).
+    // FOLD: K tile kt is channel slice kt % cv_cpt of the (kt / cv_cpt)-th SET tap of cv_mask, and W's K offset follows the tap
+    // (tap * Cin + ci0, not kt * 64). W(kt) is staged in two halves, the second a phase after the pair has moved on to K tile
+    // kt + 1: cv_wk keeps the offset of the K tile whose A was staged last (tap_next) - the prologue's K tiles 0 and 1 set it in
+    // tap_of, and tap_of(2), which only positions the pair, leaves it at K tile 1's for that tile's second half.
     int cv_tap = 0, cv_ci0 = 0;
+    [[maybe_unused]] int cv_wk = 0;
     auto tap_of = [&](int kt) {
-        if constexpr (AMODE == VDA_A_CONV3X3) {
+        if constexpr (FOLD) {
+            const int idx = kt / cv_cpt;
+            cv_tap = vda_gemm::fold_nth_tap(cv_mask, idx);
+            cv_ci0 = (kt - idx * cv_cpt) * BK;
+            if (kt < 2) cv_wk = cv_tap * p.cCin + cv_ci0;
+        } else if constexpr (AMODE == VDA_A_CONV3X3) {
             const int k0 = kt * BK;
             cv_tap = k0 / p.cCin;
             cv_ci0 = k0 - cv_tap * p.cCin;
@@ -181,10 +218,16 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
     };
     auto tap_next = [&]() {
         if constexpr (AMODE == VDA_A_CONV3X3) {
+            if constexpr (FOLD) cv_wk = cv_tap * p.cCin + cv_ci0;
             cv_ci0 += BK;
             if (cv_ci0 >= p.cCin) {
                 cv_ci0 = 0;
-                ++cv_tap;
+                if constexpr (FOLD) {
+                    const int rest = cv_mask >> (cv_tap + 1);
+                    cv_tap = rest ? cv_tap + 1 + __builtin_ctz(rest) : 9;
+                } else {
+                    ++cv_tap;
+                }
             }
         }
     };
@@ -212,7 +255,7 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
         }
     };
     auto stage_w = [&](int kt, char* wbuf, int j0 = 0, int j1 = BN / 8 / NW) {
-        const int k0 = kt * BK;
+        const int k0 = FOLD ? cv_wk : kt * BK;
 #pragma unroll
         for (int j = j0; j < j1; ++j) {
             const int n = min(tn0 + (wave + NW * j) * 8 + lrow, p.N - 1);
@@ -246,7 +289,7 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
         for (int j = 0; j < NJ; ++j) f.w[j] = *reinterpret_cast<const h16x8*>(buf + w_off + j * 16 * ROW_BYTES + coff);
     };
 
-    const int nt = p.K / BK;
+    int nt = p.K / BK;                   // (FOLD: per tile, set at the tile's top)
     static_assert(WTN == 64, "epilogue staging assumes a 64-column wave tile");
     // epilogue staging (8 waves x 8 KiB) = A slots 1 and 2: free once the K loop's reads are done, while A slot 0 / W slot 0
     // already receive the next tile's first K tile
@@ -274,7 +317,8 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
         for (int j = 0; j < NJ; ++j) {
             const int n = bnn * BN + wn * WTN + j * 16 + (lane >> 4) * 4;
             // (LayerNorm-folded epilogues add their constant AFTER the row scaling: the accumulators start at zero)
-            nbias[j] = (!vda_gemm::is_ln_epi<EPI> && p.bias != nullptr && n + 3 < p.N) ? *reinterpret_cast<const f32x4*>(p.bias + n) : f32x4{0.f, 0.f, 0.f, 0.f};
+            // (FOLD: bias is the class table, added per row in the epilogue: zero as well)
+            nbias[j] = (!vda_gemm::is_ln_epi<EPI> && !FOLD && p.bias != nullptr && n + 3 < p.N) ? *reinterpret_cast<const f32x4*>(p.bias + n) : f32x4{0.f, 0.f, 0.f, 0.f};
         }
     };
 
@@ -383,6 +427,7 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
         AF fa;
         WF fw;
         if (round > 0) set_sources(tile);       // recomputed rather than kept live across the epilogue
+        if constexpr (FOLD) nt = __builtin_popcount(cv_mask) * cv_cpt;
         if (nt > 1) {                           // K tile 1 -> A slot 1 (the epilogue staging area: released by the tile-end barrier)
             tap_of(1);
             stage_a(1, 0, smem + A_BYTES);
@@ -669,7 +714,7 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
                 // in flight hipcc waits vmcnt(0) - every store included - at each of those loads (dbg bit 2 switches this off)
                 // (the LayerNorm-folded epilogues' 8-byte row statistics do not count: measured -20 us on fc1 with the early prefetch)
                 constexpr bool ROW_AUX = EPI == VDA_EPI_SCALE_RES_F32 || EPI == VDA_EPI_SCALE_RES_F32_H || EPI == VDA_EPI_RES_F16 || EPI == VDA_EPI_PATCH_F32 ||
-                                         EPI == VDA_EPI_SCALE_RES_SPLIT;
+                                         EPI == VDA_EPI_SCALE_RES_SPLIT || FOLD;
                 const int pf_block = ((ROW_AUX && !(dbg & VDA_FLAG_PREFETCH_EARLY)) || (dbg & VDA_FLAG_PREFETCH_LATE)) ? MI / 2 - 1 : 0;          // dbg 8: A/B, late for every epilogue
                 if (i == pf_block && next < ntiles && !(dbg & VDA_FLAG_PREFETCH_FIRST)) {
                     load_bias(next);
@@ -707,7 +752,7 @@ int launch256(const vda_gemm_args& a, hipStream_t s) {
     static_assert(smem <= 160 * 1024, "LDS budget");
     const int nbm = (a.M + BM - 1) / BM, nbn = (a.N + BN - 1) / BN;
     const int ntiles = nbm * nbn;
-    if constexpr (SCHED == 1) {
+    if constexpr (SCHED == 1 && EPI != VDA_EPI_CONVT_FOLD_F16) {      // (the folded mode balances its unequal tiles by the rotated static walk)
         if (a.sched != nullptr) {                 // dynamic tile draw: its own instantiation (see DYN above)
             static VdaKernelDeviceState dyn_state;
             const int ncu = vda_prepare_kernel(reinterpret_cast<const void*>(&gemm8p_kernel<BN, AMODE, EPI, SCHED, BM, true>), smem, dyn_state);
@@ -738,6 +783,7 @@ int launch256(const vda_gemm_args& a, hipStream_t s) {
 VDA_8P_FAMILY(launch_dense, VDA_EPIS_DENSE, VDA_A_DENSE, 256)
 VDA_8P_FAMILY(launch_dense_bm192, VDA_EPIS_8P_BM192, VDA_A_DENSE, 192)
 VDA_8P_FAMILY(launch_conv, VDA_EPIS_CONV, VDA_A_CONV3X3, 256)
+VDA_8P_FAMILY(launch_conv_fold, VDA_EPIS_CONV_FOLD, VDA_A_CONV3X3, 256)
 #undef VDA_8P_CASE
 #undef VDA_8P_FAMILY
 

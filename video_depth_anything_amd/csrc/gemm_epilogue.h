@@ -14,6 +14,7 @@
 #define VDA_EPIS_DENSE(X, ...) \
     VDA_EPIS_DENSE_MFMA32(X, __VA_ARGS__) X(VDA_EPI_SCALE_RES_SPLIT, __VA_ARGS__) X(VDA_EPI_LN_BIAS_F16, __VA_ARGS__) X(VDA_EPI_LN_GELU_F16, __VA_ARGS__)
 #define VDA_EPIS_CONV(X, ...) X(VDA_EPI_BIAS_F16, __VA_ARGS__) X(VDA_EPI_BIAS_RELU_F16, __VA_ARGS__) X(VDA_EPI_RES_F16, __VA_ARGS__)
+#define VDA_EPIS_CONV_FOLD(X, ...) X(VDA_EPI_CONVT_FOLD_F16, __VA_ARGS__)      // conv A, 8-phase 256 x 256 only (and the 128-row kernel)
 #define VDA_EPIS_8P_BM192(X, ...) \
     X(VDA_EPI_BIAS_F16, __VA_ARGS__) X(VDA_EPI_SCALE_RES_F32, __VA_ARGS__) X(VDA_EPI_SCALE_RES_SPLIT, __VA_ARGS__) X(VDA_EPI_LN_BIAS_F16, __VA_ARGS__)
 #define VDA_EPIS_256S_BM192_X2(X, ...) \
@@ -49,6 +50,38 @@ __device__ __forceinline__ void split_h16(float x, h16& hi, h16& lo) {
     lo = to_h16(x - (float)hi);
 }
 
+// ---- VDA_EPI_CONVT_FOLD_F16 (vda.h): which of the 3 x 3 taps of the tap grid the output phases of columns [n0, n1) reach, bit
+// 3*(dy+1) + (dx+1). Phase row py reaches dy = 0, dy = -1 only when py == 0 and dy = +1 only when py == k - 1 (the same in x).
+__device__ __forceinline__ int fold_tap_mask(int n0, int n1, int k, int Co) {
+    int mk = 0;
+    for (int ph = n0 / Co, ph1 = (n1 - 1) / Co; ph <= ph1; ++ph) {
+        const int py = ph / k, px = ph - py * k;
+        const int ym = 2 | (py == 0 ? 1 : 0) | (py == k - 1 ? 4 : 0), xm = 2 | (px == 0 ? 1 : 0) | (px == k - 1 ? 4 : 0);
+        mk |= ((ym & 1) | ((ym & 2) << 2) | ((ym & 4) << 4)) * xm;
+    }
+    return mk;
+}
+// the idx-th set bit of a tap mask (9 when it has fewer)
+__device__ __forceinline__ int fold_nth_tap(int mask, int idx) {
+    for (int i = 0; i < idx; ++i) mask &= mask - 1;
+    return mask ? __builtin_ctz(mask) : 9;
+}
+// Row m = (b, y, x) of the tap grid, columns n.. of one phase: the element offset of the scattered output row segment and the
+// address of its class bias. Only phase row 0 reaches dy = -1 and only phase row k - 1 reaches dy = +1, so the class matters for
+// those alone - and on a 1-high grid, where the row is first AND last, each of the two gets the class that cuts ITS outside tap.
+__device__ __forceinline__ const float* fold_row(const vda_gemm_args& p, int m, int n, int& out_off) {
+    const int k = p.tK, Co = p.tCout;
+    const int ph = n / Co, co = n - ph * Co;
+    const int py = ph / k, px = ph - py * k;
+    const int hw = p.tH * p.tW;
+    const int b = m / hw, rem = m - b * hw;
+    const int y = rem / p.tW, x = rem - y * p.tW;
+    const int cy = (y == 0 && py == 0) ? 0 : (y == p.tH - 1 && py == k - 1) ? 2 : 1;
+    const int cx = (x == 0 && px == 0) ? 0 : (x == p.tW - 1 && px == k - 1) ? 2 : 1;
+    out_off = (((b * p.tH + y) * k + py) * (p.tW * k) + x * k + px) * p.ldc + co;        // (validated to fit 31 bits)
+    return p.bias + ((ph * 9 + cy * 3 + cx) * Co + co);
+}
+
 template <int CTRL>
 __device__ __forceinline__ float epi_dpp(float v) {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
@@ -75,6 +108,13 @@ __device__ __forceinline__ void store_one(const vda_gemm_args& p, int m, int n, 
         }
         h16x4 o = {to_h16(v[0]), to_h16(v[1]), to_h16(v[2]), to_h16(v[3])};
         *reinterpret_cast<h16x4*>((h16*)p.out + (size_t)m * p.ldc + n) = o;
+        return;
+    }
+    if constexpr (EPI == VDA_EPI_CONVT_FOLD_F16) {
+        int off;
+        v += *reinterpret_cast<const f32x4*>(fold_row(p, m, n, off));
+        h16x4 o = {to_h16(v[0]), to_h16(v[1]), to_h16(v[2]), to_h16(v[3])};
+        *reinterpret_cast<h16x4*>((h16*)p.out + off) = o;
         return;
     }
     if (p.bias) v += *reinterpret_cast<const f32x4*>(p.bias + n);
@@ -252,6 +292,7 @@ struct RowAux {
     h16x8 h0, h1;
     float s0, s1;        // LayerNorm-folded epilogues: the row's (mean, rstd)
     mutable float o0, o1;   // VDA_EPI_SCALE_RES_SPLIT: (sum, centred sum of squares) of the row's 64 columns, for the caller to store
+    int i0;              // VDA_EPI_CONVT_FOLD_F16: element offset of the scattered output segment (f0, f1: its class bias)
 };
 
 // [column block][row] layout of the partial statistics: the 8 rows a wave instruction covers are one 64-byte run
@@ -294,6 +335,11 @@ __device__ __forceinline__ void load_row_aux(const vda_gemm_args& p, int m, int 
         const float2 st = *reinterpret_cast<const float2*>(p.stats + 2 * (size_t)m);
         x.s0 = st.x;
         x.s1 = st.y;
+    } else if constexpr (EPI == VDA_EPI_CONVT_FOLD_F16) {
+        // one unconditional table load per row: the class only moves the address (no branch for hipcc to drain vmcnt at)
+        const float* t = fold_row(p, m, n, x.i0);
+        x.f0 = *reinterpret_cast<const f32x4*>(t);
+        x.f1 = *reinterpret_cast<const f32x4*>(t + 4);
     }
 }
 
@@ -381,6 +427,13 @@ __device__ __forceinline__ void finish_row8(const vda_gemm_args& p, int m, int n
         const int y = rem / p.tW, xx = rem - y * p.tW;
         const size_t orow = ((size_t)b * p.tH * k + (size_t)y * k + ky) * ((size_t)p.tW * k) + (size_t)xx * k + kx;
         store8h<NT>((h16*)p.out + orow * p.ldc + co, v);
+    } else if constexpr (EPI == VDA_EPI_CONVT_FOLD_F16) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            v[i] += x.f0[i];
+            v[4 + i] += x.f1[i];
+        }
+        store8h<NT>((h16*)p.out + x.i0, v);
     }
 }
 
@@ -404,7 +457,7 @@ __device__ __forceinline__ void finish_row4(const vda_gemm_args& p, int m, int n
     }
 }
 
-// Run `f(tag)` with the runtime epilogue id lifted to a compile-time constant.
+// Run `f(tag)` with the runtime epilogue id lifted to a compile-time constant (VDA_EPI_CONVT_FOLD_F16 has kernels of its own).
 template <class F>
 __device__ __forceinline__ void dispatch_epilogue(int epilogue, F&& f) {
     switch (epilogue) {

@@ -190,6 +190,11 @@ struct vda_model {
     // head_overlap. ON: in-process A/B, both orders, ViT-L 51.32 -> 50.36 and 51.41 -> 50.47 ms per clip (A/A spread 0.16 ms), ViT-S
     // 8.23 -> 7.83 and 8.20 -> 7.89 ms (A/A spread 0.14 ms); profiles/r10/head_lanes/.
     int head_lanes = 1;
+    // vda_set_option("convt_fold") (environment default VDA_CONVT_FOLD): resize_layers[i] + layer{i+1}_rn (i = 0, 1) as one folded
+    // GEMM on the projection's grid (VDA_EPI_CONVT_FOLD_F16) where Run::fold_level says so. folded[i]: what the LAST forward did at
+    // level i - its "l1" / "l2" were then never written and vda_debug_copy rebuilds them. DESIGN section 4 [r11].
+    int convt_fold = 1;
+    bool folded[2] = {false, false};
     int mlp_fused = 0;                        // vda_set_option("mlp_fused"): fc1 + GELU + fc2 + residual in one kernel where built (D = 384; needs ln_fold).
                                               // OFF: measured slower than the two GEMM launches (ViT-S clip 8.69 -> 9.00 ms, mlp_fused.hip's header)
     // Split-stream overflow report (ln_fold): one sticky word in pinned host memory, set by the device at the end of a forward whose
@@ -454,6 +459,21 @@ int pack_all(vda_model* h, int prec) {
     const std::string sc = hd + "scratch.";
     for (int i = 0; i < 4; ++i)
         VDA_TRY(conv("rn" + std::to_string(i + 1) + ".w", sc + "layer" + std::to_string(i + 1) + "_rn.weight", Fe, oc[i], Fe, ocp[i]));
+    if constexpr (std::is_same<T, h16>::value) {
+        // option convt_fold: resize_layers[i] composed with layer{i+1}_rn (vda_fold_convt_weight), fp16 path only. resize{i}.w / .b
+        // above stay: the fp32 path, the option's off setting and vda_debug_copy's rebuild of "l1" / "l2" run the unfused pair.
+        for (int i = 0; i < 2; ++i) {
+            const int kk = i == 0 ? 4 : 2;
+            const std::string k = "rn" + std::to_string(i + 1) + ".fold";
+            T* d = nullptr;
+            VDA_TRY(mat(k + ".w", (size_t)kk * kk * Fe * 9 * ocp[i], &d));
+            void* bp = nullptr;
+            VDA_TRY(dev_alloc(h, (size_t)kk * kk * 9 * Fe * sizeof(float), &bp));
+            h->vec[k + ".b"] = (float*)bp;
+            VDA_TRY(vda_fold_convt_weight(raw(hd + "resize_layers." + std::to_string(i) + ".weight"), raw(hd + "resize_layers." + std::to_string(i) + ".bias"),
+                                          raw(sc + "layer" + std::to_string(i + 1) + "_rn.weight"), d, (float*)bp, kk, oc[i], oc[i], Fe, ocp[i], s));
+        }
+    }
     for (int i = 1; i <= 4; ++i) {
         const std::string r = sc + "refinenet" + std::to_string(i) + ".", k = "ref" + std::to_string(i) + ".";
         VDA_TRY(lin(k + "out.w", r + "out_conv.weight", Fe, Fe, Fe, Fe));
@@ -645,6 +665,42 @@ struct Run {
         a.A = x, a.W = W(wname), a.out = out, a.bias = bias, a.res = res, a.res2 = res2;
         a.M = B * Ho * Wo, a.N = Cout, a.K = 9 * Cin, a.a_mode = VDA_A_CONV3X3, a.epilogue = epi, a.relu_in = relu_in ? 1 : 0;
         a.cB = B, a.cH = H, a.cW = Wd, a.cCin = Cin, a.cHo = Ho, a.cWo = Wo, a.cStride = stride;
+        return gemm(a);
+    }
+    // resize_layers[i] (ConvTranspose2d, k == stride; dpt.py:71-82) on the ph x pw projection t -> out [B, k*ph, k*pw, C]
+    int convt(const void* t, int i, void* out, int B, int ph, int pw, int C) {
+        const std::string k = "resize" + std::to_string(i);
+        const int kk = i == 0 ? 4 : 2;
+        vda_gemm_args a = {};
+        a.A = t, a.W = W(k + ".w"), a.out = out, a.bias = V(k + ".b");
+        a.M = B * ph * pw, a.N = kk * kk * C, a.K = C, a.ldc = C, a.a_mode = VDA_A_DENSE, a.epilogue = VDA_EPI_CONVT_F16;
+        a.tK = kk, a.tH = ph, a.tW = pw, a.tCout = C;
+        return gemm(a);
+    }
+    // Option convt_fold at level i: active on the fp16 path when the unfused layer{i+1}_rn conv (on the k*ph x k*pw map) would run on
+    // the 8-phase 256 x 256 tile or the 128-row kernel - the two families the folded mode is built for. ViT-S's 64-channel convs run
+    // in conv_lds.hip and stay unfused. A dry pass always lays out the unfused pair (the same buffers; the larger launch count).
+    bool fold_level(int i, int B, int ph, int pw, int C, int Fe) const {
+        if (dry || prec != VDA_PREC_F16 || !h->convt_fold) return false;
+        const int kk = i == 0 ? 4 : 2, H = kk * ph, Wd = kk * pw;
+        if ((long long)B * H * Wd * Fe >= (1ll << 31)) return false;
+        vda_gemm_args a = {};
+        a.M = B * H * Wd, a.N = Fe, a.K = 9 * C, a.lda = a.K, a.ldc = Fe, a.a_mode = VDA_A_CONV3X3, a.epilogue = VDA_EPI_BIAS_F16;
+        a.cB = B, a.cH = H, a.cW = Wd, a.cCin = C, a.cHo = H, a.cWo = Wd, a.cStride = 1;
+        vda_gemm_plan_t plan;
+        if (vda_gemm_plan(&a, 0, 0, 1, &plan) != 0) return false;
+        const vda_gemm_launch& r = plan.rec[0];
+        return r.family == VDA_GEMM_FAM_128 || (r.family == VDA_GEMM_FAM_8P && r.bm == 256 && r.bn == 256);
+    }
+    // the folded pair: t [B, ph, pw, C] -> out [B, k*ph, k*pw, Fe] = layer{i+1}_rn(resize_layers[i](t)) in one implicit GEMM
+    int convt_fold(const void* t, int i, void* out, int B, int ph, int pw, int C, int Fe) {
+        const std::string k = "rn" + std::to_string(i + 1) + ".fold";
+        const int kk = i == 0 ? 4 : 2;
+        vda_gemm_args a = {};
+        a.A = t, a.W = W(k + ".w"), a.out = out, a.bias = V(k + ".b");
+        a.M = B * ph * pw, a.N = kk * kk * Fe, a.K = 9 * C, a.ldc = Fe, a.a_mode = VDA_A_CONV3X3, a.epilogue = VDA_EPI_CONVT_FOLD_F16;
+        a.cB = B, a.cH = ph, a.cW = pw, a.cCin = C, a.cHo = ph, a.cWo = pw, a.cStride = 1;
+        a.tK = kk, a.tH = ph, a.tW = pw, a.tCout = Fe;
         return gemm(a);
     }
     int layernorm(const float* x, void* out, const float* w, const float* b, float eps, int rows, int D, int group = 0, int skip = 0,
@@ -926,25 +982,17 @@ struct Run {
             void* l1 = act("l1", (size_t)BT * h1 * w1 * ocp[0]);
             void* l2 = act("l2", (size_t)BT * h2 * w2 * ocp[1]);
             void* l3t = nullptr;
+            // option convt_fold: a folded level skips its ConvTranspose here and runs the folded GEMM where layer{i+1}_rn stood
+            const bool f0 = fold_level(0, BT, ph, pw, ocp[0], Fe), f1 = fold_level(1, BT, ph, pw, ocp[1], Fe);
+            void *t0 = nullptr, *t1 = nullptr;
             if (part & 1) {
-                void* t0 = act("t0", (size_t)BT * P * ocp[0]);
+                if (!dry) h->folded[0] = f0, h->folded[1] = f1;
+                t0 = act("t0", (size_t)BT * P * ocp[0]);
                 VDA_TRY(dense(taps[0], W("proj0.w"), t0, VDA_EPI_BIAS_F16, BT * P, ocp[0], D, V("proj0.b")));
-                {
-                    vda_gemm_args a = {};
-                    a.A = t0, a.W = W("resize0.w"), a.out = l1, a.bias = V("resize0.b");
-                    a.M = BT * P, a.N = 16 * ocp[0], a.K = ocp[0], a.ldc = ocp[0], a.a_mode = VDA_A_DENSE, a.epilogue = VDA_EPI_CONVT_F16;
-                    a.tK = 4, a.tH = ph, a.tW = pw, a.tCout = ocp[0];
-                    VDA_TRY(gemm(a));
-                }
-                void* t1 = act("t1", (size_t)BT * P * ocp[1]);
+                if (!f0) VDA_TRY(convt(t0, 0, l1, BT, ph, pw, ocp[0]));
+                t1 = act("t1", (size_t)BT * P * ocp[1]);
                 VDA_TRY(dense(taps[1], W("proj1.w"), t1, VDA_EPI_BIAS_F16, BT * P, ocp[1], D, V("proj1.b")));
-                {
-                    vda_gemm_args a = {};
-                    a.A = t1, a.W = W("resize1.w"), a.out = l2, a.bias = V("resize1.b");
-                    a.M = BT * P, a.N = 4 * ocp[1], a.K = ocp[1], a.ldc = ocp[1], a.a_mode = VDA_A_DENSE, a.epilogue = VDA_EPI_CONVT_F16;
-                    a.tK = 2, a.tH = ph, a.tW = pw, a.tCout = ocp[1];
-                    VDA_TRY(gemm(a));
-                }
+                if (!f1) VDA_TRY(convt(t1, 1, l2, BT, ph, pw, ocp[1]));
             }
             if (part & 2) {
                 void* l3 = act("l3", (size_t)BT * P * ocp[2]);
@@ -953,9 +1001,11 @@ struct Run {
             }
             if (part & 1) {
                 l1r = act("l1r", (size_t)BT * h1 * w1 * Fe);
-                VDA_TRY(conv3x3(l1, "rn1.w", l1r, BT, h1, w1, ocp[0], Fe, VDA_EPI_BIAS_F16, 1, nullptr));
+                if (f0) VDA_TRY(convt_fold(t0, 0, l1r, BT, ph, pw, ocp[0], Fe));
+                else VDA_TRY(conv3x3(l1, "rn1.w", l1r, BT, h1, w1, ocp[0], Fe, VDA_EPI_BIAS_F16, 1, nullptr));
                 l2r = act("l2r", (size_t)BT * h2 * w2 * Fe);
-                VDA_TRY(conv3x3(l2, "rn2.w", l2r, BT, h2, w2, ocp[1], Fe, VDA_EPI_BIAS_F16, 1, nullptr));
+                if (f1) VDA_TRY(convt_fold(t1, 1, l2r, BT, ph, pw, ocp[1], Fe));
+                else VDA_TRY(conv3x3(l2, "rn2.w", l2r, BT, h2, w2, ocp[1], Fe, VDA_EPI_BIAS_F16, 1, nullptr));
             }
             if (part & 2) {
                 l3r = act("l3r", (size_t)BT * P * Fe);
@@ -1197,6 +1247,11 @@ int head_lanes_default() {
     return v != 0;
 }
 
+int convt_fold_default() {
+    static const int v = getenv("VDA_CONVT_FOLD") ? atoi(getenv("VDA_CONVT_FOLD")) : 1;      // (A/B through an unmodified caller)
+    return v != 0;
+}
+
 int enc_split_default() {
     static const int v = getenv("VDA_ENC_SPLIT") ? atoi(getenv("VDA_ENC_SPLIT")) : 1;      // (A/B through an unmodified caller)
     return v != 0;
@@ -1244,6 +1299,7 @@ extern "C" int vda_create(const vda_config* cfg, vda_model** out) {
     h->ovf_host = (volatile int32_t*)ring;
     h->enc_split = enc_split_default();
     h->head_lanes = head_lanes_default();
+    h->convt_fold = convt_fold_default();
     *out = h;
     return 0;
 }
@@ -1424,13 +1480,22 @@ static int vda_debug_copy_impl(vda_model* h, const char* name, void* dst, int64_
     auto b = it->second.bufs.find(name);
     VDA_REQUIRE(b != it->second.bufs.end(), "vda_debug_copy: no buffer named %s", name);
     VDA_REQUIRE(bytes > 0 && (size_t)bytes <= b->second.second, "vda_debug_copy: %s holds %lld bytes", name, (long long)b->second.second);
+    // "l1" / "l2" of a forward that ran the level folded (option convt_fold) were never written: rebuilt here, into their own block,
+    // from the level's projection with the ConvTranspose GEMM the unfused forward runs - same arguments, same kernel, same bits
+    const int lvl = strcmp(name, "l1") == 0 ? 0 : strcmp(name, "l2") == 0 ? 1 : -1;
+    if (lvl >= 0 && h->last_key[4] == VDA_PREC_F16 && h->folded[lvl]) {
+        VDA_TRY(require_device(h, "vda_debug_copy"));
+        Run r{h, VDA_PREC_F16, false, &it->second, (hipStream_t)stream, (size_t)2};
+        const int BT = h->last_key[0] * h->last_key[1], ph = h->last_key[2] / PATCH, pw = h->last_key[3] / PATCH;
+        VDA_TRY(r.convt(r.act(lvl == 0 ? "t0" : "t1", 0), lvl, r.act(name, 0), BT, ph, pw, h->ocp[lvl]));
+    }
     VDA_HIP(hipMemcpyAsync(dst, (char*)h->ws + b->second.first, (size_t)bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return 0;
 }
 
 // Tuning / A-B switches of the launch sequence: "residual_in_ln" (default 0), "ln_fold" (default 1), "dyn_sched" (default 0), "oc1_fused"
 // (default 1), "mlp_fused" (default 0), "head_overlap" (default 0), "enc_split" (default 1, or VDA_ENC_SPLIT), "head_lanes" (default 1,
-// or VDA_HEAD_LANES): see Run::forward.
+// or VDA_HEAD_LANES), "convt_fold" (default 1, or VDA_CONVT_FOLD): see Run::forward.
 extern "C" int vda_set_option(vda_model* h, const char* name, int value) {
     VDA_REQUIRE(h && name, "vda_set_option: null argument");
     if (strcmp(name, "residual_in_ln") == 0) {
@@ -1463,6 +1528,10 @@ extern "C" int vda_set_option(vda_model* h, const char* name, int value) {
     }
     if (strcmp(name, "head_lanes") == 0) {               // (< 0: the default, VDA_HEAD_LANES or 1). The layout does not depend on it.
         h->head_lanes = value < 0 ? head_lanes_default() : value != 0;
+        return 0;
+    }
+    if (strcmp(name, "convt_fold") == 0) {               // (< 0: the default, VDA_CONVT_FOLD or 1). The layout does not depend on it.
+        h->convt_fold = value < 0 ? convt_fold_default() : value != 0;
         return 0;
     }
     if (strcmp(name, "mlp_fused") == 0) {

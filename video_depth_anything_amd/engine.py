@@ -37,6 +37,8 @@ Algebraic rewrite (exact in real arithmetic): FeatureFusionBlock's `out_conv(bil
 bilinear resize commute (interpolation weights sum to 1, so the bias commutes too), which
 cuts the 1x1 conv's FLOPs 4x.
 """
+import ctypes
+import os
 from typing import Dict, List
 
 import torch
@@ -66,6 +68,8 @@ class Engine:
         self._pos_cache: Dict[tuple, torch.Tensor] = {}
         self.loaded = False
         self.residual_in_ln = False                 # A/B option of the fp16 path (see _forward); off: measured slower end to end
+        # the handle's option "convt_fold" (same default): resize_layers[i] + layer{i+1}_rn as one folded GEMM where _fold_level says so
+        self.convt_fold = int(os.environ.get("VDA_CONVT_FOLD", "1")) != 0
 
     # ------------------------------------------------------------------ weights
     def load_state_dict(self, sd, strict=True):
@@ -135,6 +139,11 @@ class Engine:
         sc = h + "scratch."
         for i in range(4):
             w[f"rn{i + 1}.w"] = conv(f"{sc}layer{i + 1}_rn.weight", Fe, ocp[i])
+        if dt == F16:
+            # composed by the SAME device entry the handle packs with (vda_fold_convt_weight): the fp32 summation order is part of the bits
+            for i in (0, 1):
+                w[f"rn{i + 1}.fold.w"], w[f"rn{i + 1}.fold.b"] = ops.fold_convt_weight(
+                    f32(f"{h}resize_layers.{i}.weight"), f32(f"{h}resize_layers.{i}.bias"), f32(f"{sc}layer{i + 1}_rn.weight"), ocp[i])
         for i in (1, 2, 3, 4):
             r = f"{sc}refinenet{i}."
             w[f"ref{i}.out.w"], w[f"ref{i}.out.b"] = lin(r + "out_conv.weight"), f32(r + "out_conv.bias")
@@ -205,6 +214,23 @@ class Engine:
         ops.gemm(x, self.w[wname], out, epi, M=B * Ho * Wo, N=Cout, K=9 * Cin, bias=bias, res=res, res2=res2,
                  relu_in=relu_in, conv=(B, H, W, Cin, Ho, Wo, stride))
         return Ho, Wo
+
+    def _fold_level(self, i, B, ph, pw, C, Fe):
+        """csrc/host.hip, Run::fold_level: the folded GEMM replaces the pair at level i when the unfused layer{i+1}_rn conv would run on
+        the 8-phase 256 x 256 tile or the 128-row kernel."""
+        if self.act != F16 or not self.convt_fold:
+            return False
+        k = 4 if i == 0 else 2
+        H, W = k * ph, k * pw
+        if B * H * W * Fe >= 1 << 31:
+            return False
+        a = _lib.GemmArgs(M=B * H * W, N=Fe, K=9 * C, lda=9 * C, ldc=Fe, a_mode=_lib.A_CONV3X3, epilogue=_lib.EPI_BIAS_F16,
+                          cB=B, cH=H, cW=W, cCin=C, cHo=H, cWo=W, cStride=1)
+        plan = _lib.GemmPlan()
+        if _lib.lib.vda_gemm_plan(ctypes.byref(a), 0, 0, 1, ctypes.byref(plan)) != 0:
+            return False
+        r = plan.rec[0]
+        return r.family == _lib.FAM_128 or (r.family == _lib.FAM_8P and r.bm == 256 and r.bn == 256)
 
     # ------------------------------------------------------------------ temporal module
     def temporal(self, m, x, B, T, hw, Cc, tag):
@@ -361,13 +387,25 @@ class Engine:
         t0 = self.buf("t0", (BT * P, ocp[0]), self.act)
         ops.gemm(taps[0], w["proj0.w"], t0, _lib.EPI_BIAS_F16, M=BT * P, N=ocp[0], K=D, bias=w["proj0.b"])
         l1 = self.buf("l1", (BT * h1 * w1, ocp[0]), self.act)
-        ops.gemm(t0, w["resize0.w"], l1, _lib.EPI_CONVT_F16, M=BT * P, N=16 * ocp[0], K=ocp[0], ldc=ocp[0], bias=w["resize0.b"],
-                 convt=(4, ph, pw, ocp[0]))
+        fold0, fold1 = self._fold_level(0, BT, ph, pw, ocp[0], Fe), self._fold_level(1, BT, ph, pw, ocp[1], Fe)
+
+        def convt(i, t, out):
+            k = 4 if i == 0 else 2
+            ops.gemm(t, w[f"resize{i}.w"], out, _lib.EPI_CONVT_F16, M=BT * P, N=k * k * ocp[i], K=ocp[i], ldc=ocp[i], bias=w[f"resize{i}.b"],
+                     convt=(k, ph, pw, ocp[i]))
+
+        def convt_fold(i, t, out):
+            k = 4 if i == 0 else 2
+            ops.gemm(t, w[f"rn{i + 1}.fold.w"], out, _lib.EPI_CONVT_FOLD_F16, M=BT * P, N=k * k * Fe, K=9 * ocp[i], ldc=Fe,
+                     bias=w[f"rn{i + 1}.fold.b"], conv=(BT, ph, pw, ocp[i], ph, pw, 1), convt=(k, ph, pw, Fe))
+
+        if not fold0:
+            convt(0, t0, l1)
         t1 = self.buf("t1", (BT * P, ocp[1]), self.act)
         ops.gemm(taps[1], w["proj1.w"], t1, _lib.EPI_BIAS_F16, M=BT * P, N=ocp[1], K=D, bias=w["proj1.b"])
         l2 = self.buf("l2", (BT * h2 * w2, ocp[1]), self.act)
-        ops.gemm(t1, w["resize1.w"], l2, _lib.EPI_CONVT_F16, M=BT * P, N=4 * ocp[1], K=ocp[1], ldc=ocp[1], bias=w["resize1.b"],
-                 convt=(2, ph, pw, ocp[1]))
+        if not fold1:
+            convt(1, t1, l2)
         l3 = self.buf("l3", (BT * P, ocp[2]), self.act)
         ops.gemm(taps[2], w["proj2.w"], l3, _lib.EPI_BIAS_F16, M=BT * P, N=ocp[2], K=D, bias=w["proj2.b"])
         t3 = self.buf("t3", (BT * P, ocp[3]), self.act)
@@ -381,9 +419,15 @@ class Engine:
 
         # ---- layer_rn (no bias) and the fusion pyramid (dpt_temporal.py:78-91)
         l1r = self.buf("l1r", (BT * h1 * w1, Fe), self.act)
-        self.conv3x3(l1, "rn1.w", l1r, BT, h1, w1, ocp[0], Fe, _lib.EPI_BIAS_F16)
+        if fold0:
+            convt_fold(0, t0, l1r)
+        else:
+            self.conv3x3(l1, "rn1.w", l1r, BT, h1, w1, ocp[0], Fe, _lib.EPI_BIAS_F16)
         l2r = self.buf("l2r", (BT * h2 * w2, Fe), self.act)
-        self.conv3x3(l2, "rn2.w", l2r, BT, h2, w2, ocp[1], Fe, _lib.EPI_BIAS_F16)
+        if fold1:
+            convt_fold(1, t1, l2r)
+        else:
+            self.conv3x3(l2, "rn2.w", l2r, BT, h2, w2, ocp[1], Fe, _lib.EPI_BIAS_F16)
         l3r = self.buf("l3r", (BT * P, Fe), self.act)
         self.conv3x3(l3, "rn3.w", l3r, BT, ph, pw, ocp[2], Fe, _lib.EPI_BIAS_F16)
         l4r = self.buf("l4r", (BT * h4 * w4, Fe), self.act)
@@ -419,6 +463,11 @@ class Engine:
             ops.head_out(c2, w["oc3.w"], self.oc3_bias, depth, BT * H * W, 32)
         # video_depth.py:162-163: bilinear to (H,W) is the identity here (H == 14*ph) and the ReLU is idempotent.
         if stages is not None:
+            # a folded level never wrote layer_1 / layer_2: what the unfused forward holds there, from the same projection
+            if fold0:
+                convt(0, t0, l1)
+            if fold1:
+                convt(1, t1, l2)
             stages.update(layer_1=(l1, h1, w1, ocp[0]), layer_2=(l2, h2, w2, ocp[1]), layer_3=(l3, ph, pw, ocp[2]),
                           layer_4=(l4, h4, w4, ocp[3]), path_4=(p4, ph, pw, Fe), path_3=(p3, h2, w2, Fe),
                           path_2=(p2, h1, w1, Fe))

@@ -84,7 +84,8 @@ def zero_page(device):
 def gemm(A, W, out, epi, *, M, N, K, lda=None, ldc=None, bias=None, res=None, res2=None, gamma=None, pos=None,
          relu_in=False, conv=None, P=0, convt=None, out2=None, stats=None, sched=None, stats_ld=0, tile_rows=0):
     """out = epilogue(A[M,K] W[N,K]^T). conv = (B,H,W,Cin,Ho,Wo,stride) switches A to the
-    implicit 3x3 window of an NHWC tensor; convt = (k, h, w, Cout) for VDA_EPI_CONVT_F16."""
+    implicit 3x3 window of an NHWC tensor; convt = (k, h, w, Cout) for VDA_EPI_CONVT_F16 and, with conv on the same h x w grid,
+    for VDA_EPI_CONVT_FOLD_F16 (W, bias = fold_convt_weight's Wf, Bc)."""
     _act(A, "A"), _req(W, A.dtype, "W"), _req(bias, F32, "bias"), _req(gamma, F32, "gamma"), _req(pos, F32, "pos")
     fn, fname = (lib.vda_gemm_f32, "vda_gemm_f32") if A.dtype == F32 else (lib.vda_gemm_f16, "vda_gemm_f16")
     a = GemmArgs()
@@ -154,6 +155,21 @@ def fold_ln_weight(W, bias, ln_w, ln_b, Wf, c1, c2, N, K):
         _req(t, F32, n)
     _req(Wf, F16, "Wf")
     check(lib.vda_fold_ln_weight(_p(W), _p(bias), _p(ln_w), _p(ln_b), _p(Wf), _p(c1), _p(c2), N, K, _stream(W)), "vda_fold_ln_weight")
+
+
+def fold_convt_weight(wt, bt, wr, cin_pad=None):
+    """ConvTranspose2d(k == stride) weight wt [Ci,Cm,k,k] and bias bt [Cm] composed with the bias-free 3x3 conv weight wr [Co,Cm,3,3]
+    behind it, on the device (vda_fold_convt_weight): (Wf fp16 [k*k*Co, 9*cin_pad], Bc fp32 [k*k, 9, Co]) for VDA_EPI_CONVT_FOLD_F16."""
+    _req(wt, F32, "wt"), _req(bt, F32, "bt"), _req(wr, F32, "wr")
+    Ci, Cm, k, _ = wt.shape
+    Co = wr.shape[0]
+    if wr.shape[1] != Cm or bt.numel() != Cm or tuple(wr.shape[2:]) != (3, 3) or wt.shape[3] != k:
+        raise ValueError("fold_convt_weight: wt [Ci,Cm,k,k], bt [Cm], wr [Co,Cm,3,3]")
+    cin_pad = Ci if cin_pad is None else cin_pad
+    wf = torch.empty(k * k * Co, 9 * cin_pad, dtype=F16, device=wt.device)
+    bc = torch.empty(k * k, 9, Co, dtype=F32, device=wt.device)
+    check(lib.vda_fold_convt_weight(_p(wt), _p(bt), _p(wr), _p(wf), _p(bc), k, Ci, Cm, Co, cin_pad, _stream(wt)), "vda_fold_convt_weight")
+    return wf, bc
 
 
 def mlp_permute_w2(w2, w2p, D, hidden):
