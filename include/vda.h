@@ -487,6 +487,56 @@ int vda_pointcloud_f32(const float* depth, const uint8_t* rgb, void* records, in
  * synchronisation, no atomics. */
 int vda_depth_vis_u8(const float* depth, long long n, const float* minmax, const uint8_t* lut, uint8_t* out, vda_stream_t stream);
 
+/* ---- validation losses on the device (the reference's utils/loss_MiDas.py and utils/loss.py: Loss_ssi, Loss_tgm) ---------------
+ * What train.py's validation pass ranks checkpoints by, as inference-time arithmetic (no gradients). pred, y: dense fp32
+ * [nframes, px] (nframes = B * N, px = H * W); mask: bytes of the same shape, 0 = excluded, or NULL for all valid. Every fp32
+ * value is widened exactly and all arithmetic is fp64, each operation rounded once (no fused multiply-add). Finite inputs only.
+ * Deterministic: fp64 partial rows per block, a fixed tree, rows combined in index order by one-workgroup finishers, no
+ * floating-point atomics; a result depends on blocks_per_plane, never on timing. All calls queue on `stream`, nothing returns to
+ * the host in between, no allocation. All pointers are device pointers; pred, y, med need 4-byte alignment only (a plane may start
+ * at any dword, a mask plane at any byte), the fp64 buffers 8-byte. Refused before any launch: null or misaligned pointers, a size
+ * < 1, blocks_per_plane outside 1..4096, more than 65535 planes, more than 2^22 partial rows (or image rows in the mad form).
+ *   stats : 8 doubles per frame.  lsq: {n, mu_d, mu_y, s, t, loss, -, -}   mad: {med_d, sc_d, med_y, sc_y, n, -, -, -}
+ *
+ * Loss_ssi of loss_MiDas.py ("lsq"), three passes, vda_loss_lsq_partial then vda_loss_lsq_finish with the same `pass` each:
+ *   pass 0  rows {n, sum d, sum y} over the valid pixels           -> stats n, mu_d = sum d / max(n, 1), mu_y likewise
+ *   pass 1  rows {sum (d - mu_d)(y - mu_y), sum (d - mu_d)^2}      -> stats s = num / (den + eps), t = mu_y - s * mu_d
+ *   pass 2  rows {sum ((s * d + t) - y)^2}                         -> stats loss = sum / max(n, 1);
+ *           result[0] = the mean of loss over ALL nframes frames (a frame without a valid pixel counts as 0), result[1 + f] = loss
+ * The row of (frame f, block b) is partial[(f * blocks_per_plane + b) * K ...], K = 3, 2, 1. result: 1 + nframes doubles (pass 2
+ * only; may be NULL in passes 0 and 1). */
+int vda_loss_lsq_partial(const float* pred, const float* y, const unsigned char* mask, int nframes, long long px, int pass, const double* stats,
+                         double* partial, int blocks_per_plane, vda_stream_t stream);
+int vda_loss_lsq_finish(const double* partial, int nframes, int blocks_per_plane, int pass, double eps, double* stats, double* result,
+                        vda_stream_t stream);
+/* Exact masked LOWER median per plane (torch.median's rule): med[f] = element (n - 1) / 2 of the sorted valid values of pred's
+ * frame f, med[nframes + f] the same of y's (y may be NULL: only pred's are written); 0.0f for a plane without a valid pixel. The
+ * value is an input element bit for bit, chosen by a radix select over order-preserving 32-bit keys (-0 sorts before +0): one
+ * workgroup of 1024 threads per plane, four passes of 8 bits, integer LDS histograms, no global atomics. px < 2^31. */
+int vda_loss_median(const float* pred, const float* y, const unsigned char* mask, int nframes, long long px, float* med, vda_stream_t stream);
+/* Loss_ssi of loss.py ("mad"), after vda_loss_median: rows {n, sum |d - med_d|, sum |y - med_y|} at partial[(f * blocks_per_plane
+ * + b) * 3 ...]; the finisher leaves stats {med_d, sc_d, med_y, sc_y, n} with sc = sum / n + eps (eps alone when n = 0). */
+int vda_loss_mad_scale_partial(const float* pred, const float* y, const unsigned char* mask, int nframes, long long px, const float* med,
+                               double* partial, int blocks_per_plane, vda_stream_t stream);
+int vda_loss_mad_scale_finish(const double* partial, int nframes, int blocks_per_plane, double eps, const float* med, double* stats,
+                              vda_stream_t stream);
+/* rho = ((d - med_d) / sc_d - (y - med_y) / sc_y)^2 on valid pixels. loss.py normalises PER IMAGE ROW: rows[(f * H + r) * 2 ...] =
+ * {sum rho, count of valid pixels} of row r of frame f (one wave per image row, so these do not depend on any launch parameter).
+ * The finisher: result[1 + f] = the mean over frame f's H rows of sum / max(count, 1), result[0] = the mean over all nframes * H
+ * rows; a row without a valid pixel counts as 0. rows: 2 * nframes * H doubles; result: 1 + nframes doubles. */
+int vda_loss_mad_rows(const float* pred, const float* y, const unsigned char* mask, int nframes, int H, int W, const double* stats, double* rows,
+                      vda_stream_t stream);
+int vda_loss_mad_finish(const double* rows, int nframes, int H, double* result, vda_stream_t stream);
+/* Loss_tgm (the same in both files) over B clips of N >= 2 frames, P = B * (N - 1) pairs of neighbouring frames: per pair
+ *   valid = mask_i & mask_{i+1};  static = valid & (|y_{i+1} - y_i| < 0.05)   (fp64 difference, the double 0.05)
+ * rows {n_valid, n_static, sum over static of | |d_{i+1} - d_i| - |y_{i+1} - y_i| |} at partial[(p * blocks_per_plane + b) * 3 ...].
+ * The finisher: result[1 + p] = sum / n_static, or NaN for a skipped pair (n_valid = 0 or n_static = 0); result[1 + P + p] =
+ * n_static; result[0] = the mean over clips of (sum of the clip's pairs in order) / (N - 1), skipped pairs staying in the divisor.
+ * result: 1 + 2 P doubles. */
+int vda_loss_tgm_partial(const float* pred, const float* y, const unsigned char* mask, int B, int N, long long px, double* partial,
+                         int blocks_per_plane, vda_stream_t stream);
+int vda_loss_tgm_finish(const double* partial, int B, int N, int blocks_per_plane, double* result, vda_stream_t stream);
+
 /* ================================================================ handle API: the model behind one pointer
  * What a C / C++ host binds in place of the reference's Python class (the seam of SURVEY.md section 8b):
  *   VideoDepthAnything(**model_configs[enc])          run.py:45, video_depth.py:38-63      vda_create

@@ -123,6 +123,15 @@ SIGNATURES = {
     "vda_pointcloud_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
     "vda_pointcloud_f32": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_size_t, _i, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, _f, _i, _vp]),
     "vda_depth_vis_u8": (_i, [_vp, _ll, _vp, _vp, _vp, _vp]),
+    "vda_loss_lsq_partial": (_i, [_vp, _vp, _vp, _i, _ll, _i, _vp, _vp, _i, _vp]),
+    "vda_loss_lsq_finish": (_i, [_vp, _i, _i, _i, C.c_double, _vp, _vp, _vp]),
+    "vda_loss_median": (_i, [_vp, _vp, _vp, _i, _ll, _vp, _vp]),
+    "vda_loss_mad_scale_partial": (_i, [_vp, _vp, _vp, _i, _ll, _vp, _vp, _i, _vp]),
+    "vda_loss_mad_scale_finish": (_i, [_vp, _i, _i, C.c_double, _vp, _vp, _vp]),
+    "vda_loss_mad_rows": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "vda_loss_mad_finish": (_i, [_vp, _i, _i, _vp, _vp]),
+    "vda_loss_tgm_partial": (_i, [_vp, _vp, _vp, _i, _i, _ll, _vp, _i, _vp]),
+    "vda_loss_tgm_finish": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     # handle API
     "vda_create": (_i, [C.POINTER(Config), C.POINTER(_vp)]),
     "vda_destroy": (_i, [_vp]),

@@ -24,8 +24,10 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=f
 # expression and restates torch's fp64 elementwise arithmetic after it. resize.hip restates cv2's float32 bilinear resize, whose
 # contract counts every rounding (a*b + c*d as three). pointcloud.hip restates numpy's fp64 (x - cx) / fx * z: the division and
 # the product are each rounded once. visualize.hip restates numpy's float32 (d - d_min) / span * 255: three roundings.
+# losses.hip restates torch's fp64 s * d + t - y (three roundings) and its centred sums.
 PER_FILE = {"stitch.hip": ["-ffp-contract=off"], "eval.hip": ["-ffp-contract=off"], "tae.hip": ["-ffp-contract=off"],
-            "resize.hip": ["-ffp-contract=off"], "pointcloud.hip": ["-ffp-contract=off"], "visualize.hip": ["-ffp-contract=off"]}
+            "resize.hip": ["-ffp-contract=off"], "pointcloud.hip": ["-ffp-contract=off"], "visualize.hip": ["-ffp-contract=off"],
+            "losses.hip": ["-ffp-contract=off"]}
 # attention: the softmax row sums are 32 scalar fp32 adds per tile; SLP packs 22 of them into v_pk_add_f32, which costs several
 # times two v_add_f32 next to MFMAs (MI355X_MICROARCH.md, "price of one filler") in a loop that is VALU-bound.
 PER_PREFIX = {"gemm": ["-fno-slp-vectorize"], "attention.hip": ["-fno-slp-vectorize"], "mlp_fused.hip": ["-fno-slp-vectorize"],

@@ -504,6 +504,75 @@ def depth_vis(depth, minmax, lut, out, n=None):
     check(lib.vda_depth_vis_u8(_p(depth), n, _p(minmax), _p(lut), _p(out), _stream(depth)), "vda_depth_vis_u8")
 
 
+# ---- validation losses (csrc/losses.hip; losses.py lays the buffers out) --------------------------------------------------------
+LOSS_STATS = 8               # doubles per frame in `stats` (include/vda.h)
+
+
+def _loss_planes(pred, y, mask, what):
+    """Checks shared by the loss passes; pred / y device fp32 of one shape with at least two axes [.., H, W], mask uint8 or None.
+    Returns (frames, H, W)."""
+    _req(pred, F32, "pred"), _req(y, F32, "y"), _req(mask, torch.uint8, "mask")
+    if pred.dim() < 3 or pred.shape != y.shape or pred.numel() == 0 or (mask is not None and mask.shape != pred.shape):
+        raise ValueError(f"{what}: pred {tuple(pred.shape)}, y {tuple(y.shape)} and mask "
+                         f"{None if mask is None else tuple(mask.shape)} must be one non-empty [..,H,W]")
+    if len({t.device for t in (pred, y) + (() if mask is None else (mask,))}) != 1:
+        raise ValueError(f"{what}: the operands live on different devices")
+    H, W = pred.shape[-2:]
+    return pred.numel() // (H * W), H, W
+
+
+def _f64_room(t, n, name, what):
+    _req(t, torch.float64, name)
+    if t.numel() < n:
+        raise ValueError(f"{what}: {name} holds {t.numel()} doubles, needs {n}")
+
+
+def loss_lsq_pass(pred, y, mask, step, eps, stats, workspace, bpp, result=None):
+    """Pass `step` (0 means, 1 centred sums, 2 residual) of the least-squares SSI loss and its finisher (include/vda.h)."""
+    F, H, W = _loss_planes(pred, y, mask, "loss_lsq_pass")
+    _f64_room(stats, LOSS_STATS * F, "stats", "loss_lsq_pass"), _f64_room(workspace, 3 * F * bpp, "workspace", "loss_lsq_pass")
+    if step == 2:
+        _f64_room(result, 1 + F, "result", "loss_lsq_pass")
+    check(lib.vda_loss_lsq_partial(_p(pred), _p(y), _p(mask), F, H * W, step, _p(stats), _p(workspace), bpp, _stream(pred)), "vda_loss_lsq_partial")
+    check(lib.vda_loss_lsq_finish(_p(workspace), F, bpp, step, float(eps), _p(stats), _p(result), _stream(pred)), "vda_loss_lsq_finish")
+
+
+def loss_median(x, y, mask, med):
+    """med (device fp32 [F] or, with y, [2 F]) = the exact masked lower medians of x's (and y's) planes."""
+    F, H, W = _loss_planes(x, x if y is None else y, mask, "loss_median")
+    _req(med, F32, "med")
+    if med.numel() < (1 if y is None else 2) * F or med.device != x.device:
+        raise ValueError(f"loss_median: med holds {med.numel()} floats on {med.device}, needs {(1 if y is None else 2) * F} on {x.device}")
+    check(lib.vda_loss_median(_p(x), _p(y), _p(mask), F, H * W, _p(med), _stream(x)), "vda_loss_median")
+
+
+def loss_mad(pred, y, mask, eps, med, stats, workspace, bpp, rows, result):
+    """The median / mean-deviation SSI loss after loss_median: scales, per-image-row sums and the finisher (include/vda.h)."""
+    F, H, W = _loss_planes(pred, y, mask, "loss_mad")
+    _req(med, F32, "med")
+    if med.numel() < 2 * F:
+        raise ValueError("loss_mad: med too small")
+    _f64_room(stats, LOSS_STATS * F, "stats", "loss_mad"), _f64_room(workspace, 3 * F * bpp, "workspace", "loss_mad")
+    _f64_room(rows, 2 * F * H, "rows", "loss_mad"), _f64_room(result, 1 + F, "result", "loss_mad")
+    s = _stream(pred)
+    check(lib.vda_loss_mad_scale_partial(_p(pred), _p(y), _p(mask), F, H * W, _p(med), _p(workspace), bpp, s), "vda_loss_mad_scale_partial")
+    check(lib.vda_loss_mad_scale_finish(_p(workspace), F, bpp, float(eps), _p(med), _p(stats), s), "vda_loss_mad_scale_finish")
+    check(lib.vda_loss_mad_rows(_p(pred), _p(y), _p(mask), F, H, W, _p(stats), _p(rows), s), "vda_loss_mad_rows")
+    check(lib.vda_loss_mad_finish(_p(rows), F, H, _p(result), s), "vda_loss_mad_finish")
+
+
+def loss_tgm(pred, y, mask, workspace, bpp, result):
+    """The temporal gradient matching loss of pred / y [B,N,H,W] (N >= 2): result = {tgm, per pair [B (N-1)], n_static [B (N-1)]}."""
+    _loss_planes(pred, y, mask, "loss_tgm")
+    if pred.dim() != 4 or pred.shape[1] < 2:
+        raise ValueError(f"loss_tgm: pred must be [B,N,H,W] with N >= 2, got {tuple(pred.shape)}")
+    B, N, H, W = pred.shape
+    P = B * (N - 1)
+    _f64_room(workspace, 3 * P * bpp, "workspace", "loss_tgm"), _f64_room(result, 1 + 2 * P, "result", "loss_tgm")
+    check(lib.vda_loss_tgm_partial(_p(pred), _p(y), _p(mask), B, N, H * W, _p(workspace), bpp, _stream(pred)), "vda_loss_tgm_partial")
+    check(lib.vda_loss_tgm_finish(_p(workspace), B, N, bpp, _p(result), _stream(pred)), "vda_loss_tgm_finish")
+
+
 # ---------------------------------------------------------------------------
 # Weight layouts the kernels expect (done once at load time, on the host or device)
 # ---------------------------------------------------------------------------
