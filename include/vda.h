@@ -332,6 +332,9 @@ int vda_depth_tail_f16(const void* in, const void* w2, const float* b2, const fl
 /* A/B switch of the resizing form: 0 (default) = the persistent kernel with the weights resident in LDS (C <= 128), 1 = the round-1
  * kernel (one 8 x 32 tile per workgroup). Same arithmetic, bit-identical results. */
 int vda_depth_tail_set_variant(int v);
+/* The kernel the last vda_depth_tail_f16 of this thread launched ("" before the first): "depth_tail_kernel<0>" (no resize),
+ * "depth_tail_kernel<1>" (resize, one 8 x 32 tile per workgroup) or "depth_tail_up_kernel" (resize, persistent). */
+const char* vda_depth_tail_last_kernel(void);
 
 /* output_conv1 applied to the 2x-upsampled output of refinenet1 (dpt.py:117 over util/blocks.py:156-160's
  * F.interpolate(scale_factor=2, mode="bilinear", align_corners=True)) in one pass: NHWC fp16 in [B,h,w,C] ->

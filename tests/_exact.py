@@ -14,7 +14,11 @@ and tests/test_kernels_f16_edges_gpu.py, and lists that file's launches as shape
 in tests/test_gemm_plan.py.
 
 The last part builds inputs whose SOFTMAX is exact - one key that wins by 52 bits, or every weight 1 - for the fp16 attention
-kernels and tests/test_attention_edges_gpu.py, with their preconditions (assert_selector_safe, assert_tattn_selector_safe)."""
+kernels and tests/test_attention_edges_gpu.py, with their preconditions (assert_selector_safe, assert_tattn_selector_safe).
+
+The part after that does it for the fused upsample convolutions (conv_up.hip, tail.hip) and tests/test_upsample_edges_gpu.py: constant
+images, selector weights with a derived bound, dyadic resize scales; a plain restatement of resize + convolution (fused_emulate) in the
+kernels' own operation orders, with the mistakes of FUSED_MUTATIONS built in; replicas of the kernels' source-window arithmetic."""
 import torch
 import torch.nn.functional as F
 
@@ -854,3 +858,358 @@ def assert_tattn_selector_safe(qkv, pi, T, hw, C, heads):
     assert float(others.max()) <= 2.0 ** -26 and float(others.sum(-1).max()) <= 2.0 ** -26, f"the other frames weigh up to {float(others.sum(-1).max()):.3g} > 2**-26"
     leak = float((others @ v.abs()).max())
     assert leak <= 2.0 ** -13, f"the other frames contribute up to {leak:.3g} > 2**-13"
+
+
+# ================================================================================================ the fused upsample convolutions (conv_up.hip, tail.hip)
+# A bilinear resize is not linear in small integers: its weights are fractions. Three families of inputs still leave a correct kernel
+# no room (tests/test_upsample_edges_gpu.py; shown sound, and shown able to fail, in tests/test_exact_inputs.py):
+#   constant   every pixel of a (frame, channel) holds one small integer v: the four weights sum to 1 within a few 2**-24, the fp16
+#              rounding of v times that sum is v, and the convolution behind it is the integer convolution of a constant image;
+#   selector   every cout has ONE weight 1: the output IS one interpolated patch value, rounded once - a derived bound of ~0.03
+#              against errors of tens for a wrong pixel, tap, channel, k-step or cout block;
+#   dyadic     scales in {0, 1/4, 1/2, 1, 3/2, 2}: every weight is a multiple of 1/4 per axis, every interpolated value of small
+#              integers a multiple of 1/16 - exact in fp16 at every step of any evaluation order.
+FUSED_MUTATIONS = ["row_off", "clamp_pad", "halo_zero", "taps_swapped", "stale_kstep", "cout_shift", "frame"]
+
+
+def ac_coords(n_in, n_out, contracted=False):
+    """align_corners=True source positions as the kernels and torch compute them in fp32: scale = fl32((in - 1) / (out - 1)),
+    src = fl32(scale * dst), i0 = min(floor(src), in - 1), i1 = min(i0 + 1, in - 1), w = fl32(src - i0) (an exact difference).
+    contracted: w = fl32(scale * dst - i0), one rounding - what a compiler that fuses the product into the subtraction computes.
+    Returns (i0, i1, w as fp64 [n_out], scale)."""
+    one = torch.ones((), dtype=F32)
+    scale = (one * (n_in - 1)) / (one * (n_out - 1)) if n_out > 1 else torch.zeros((), dtype=F32)
+    dst = torch.arange(n_out, dtype=F32)
+    src = scale * dst
+    i0 = src.floor().long().clamp_max(n_in - 1)
+    i1 = (i0 + 1).clamp_max(n_in - 1)
+    w = (scale.double() * dst.double() - i0.double()).float().double() if contracted else (src - i0.float()).double()
+    return i0, i1, w, float(scale)
+
+
+def interp_image(x, H, W, mode="f64", contracted=False, row_off=None):
+    """x [B, C, h, w] -> the align_corners bilinear resize [B, C, H, W] as fp64 values, evaluated as `mode` says:
+      f64       a00 (1-wx)(1-wy) + a01 wx (1-wy) + a10 (1-wx) wy + a11 wx wy in fp64 on the fp32 coordinates: the definition;
+      sum4_f32  conv_up.hip: the four weights as fp32 products, the four-term sum left to right in fp32, one rounding to fp16;
+      pk_f16    tail.hip (bilinear8): the four weights rounded to fp16, a product and three fused multiply-adds in fp16;
+      lerp_f32  resample.hip: top = a00 (1-wx) + a01 wx, bot likewise, top (1-wy) + bot wy in fp32 (not rounded to fp16 here).
+    row_off = Y: output row Y takes its source rows one too low in the image (a mistake to be seen)."""
+    B, C, h, w = x.shape
+    ya, yb, wy, _ = ac_coords(h, H, contracted)
+    xa, xb, wx, _ = ac_coords(w, W, contracted)
+    if row_off is not None:
+        ya, yb = ya.clone(), yb.clone()
+        ya[row_off] = min(int(ya[row_off]) + 1, h - 1)
+        yb[row_off] = min(int(ya[row_off]) + 1, h - 1)
+    xd = x.double()
+    top, bot = xd[:, :, ya], xd[:, :, yb]
+    a00, a01, a10, a11 = top[..., xa], top[..., xb], bot[..., xa], bot[..., xb]
+    wy, wx = wy.view(1, 1, H, 1), wx.view(1, 1, 1, W)
+    if mode == "f64":
+        return a00 * ((1 - wx) * (1 - wy)) + a01 * (wx * (1 - wy)) + a10 * ((1 - wx) * wy) + a11 * (wx * wy)
+    fx, fy = wx.float(), wy.float()
+    ux, uy = 1 - fx, 1 - fy
+    if mode == "lerp_f32":
+        t, b = a00.float() * ux + a01.float() * fx, a10.float() * ux + a11.float() * fx
+        return (t * uy + b * fy).double()
+    w00, w01, w10, w11 = ux * uy, fx * uy, ux * fy, fx * fy
+    if mode == "sum4_f32":
+        return (a00.float() * w00 + a01.float() * w01 + a10.float() * w10 + a11.float() * w11).to(F16).double()
+    assert mode == "pk_f16"
+    w00, w01, w10, w11 = (t.to(F16).double() for t in (w00, w01, w10, w11))
+    o = (a00 * w00).to(F16).double()
+    for a, q in ((a01, w01), (a10, w10), (a11, w11)):
+        o = (a * q + o).to(F16).double()
+    return o
+
+
+def fused_mutation_applies(m, B, h, H, W, C, N, tile, kc):
+    return dict(row_off=h > 1, halo_zero=H > tile[0] or W > tile[1], stale_kstep=C >= 2 * kc, cout_shift=N > 32, frame=B > 1).get(m, True)
+
+
+def conv_image(p, w, mutation=None, tile=(16, 32), kc=16):
+    """p [B, C, H, W] fp64 (the resized image), w [N, C, 3, 3] fp64 -> conv3x3 with zero padding, [B, H, W, N] fp64, no bias.
+    With one mistake of a tiled kernel built in:
+      clamp_pad     the border repeats the edge pixel;          halo_zero    a tile's first row (column, where there is one tile row)
+      taps_swapped  the centre tap and the one right of it;                  reads zeros above (left of) it inside the image;
+      stale_kstep   the last kc channels are those of the step before;      cout_shift   cout n holds cout n + 32's result;
+      frame         frame b is computed from frame b - 1."""
+    B, C, H, W = p.shape
+    N = w.shape[0]
+    if mutation == "frame":
+        p = p[[0] + list(range(B - 1))]
+    if mutation == "stale_kstep":
+        p = p.clone()
+        p[:, C - kc:] = p[:, C - 2 * kc:C - kc]
+    if mutation == "taps_swapped":
+        w = w.clone()
+        w[:, :, 1, 1], w[:, :, 1, 2] = w[:, :, 1, 2].clone(), w[:, :, 1, 1].clone()
+    pp = F.pad(p, (1, 1, 1, 1), mode="replicate" if mutation == "clamp_pad" else "constant")
+    out = F.conv2d(pp, w).permute(0, 2, 3, 1).contiguous()
+    if mutation == "halo_zero":
+        wz = torch.zeros_like(w)
+        if H > tile[0]:
+            wz[:, :, 0] = w[:, :, 0]
+            rows = torch.arange(tile[0], H, tile[0])
+            out[:, rows] -= F.conv2d(pp, wz).permute(0, 2, 3, 1)[:, rows]
+        else:
+            wz[:, :, :, 0] = w[:, :, :, 0]
+            cols = torch.arange(tile[1], W, tile[1])
+            out[:, :, cols] -= F.conv2d(pp, wz).permute(0, 2, 3, 1)[:, :, cols]
+    if mutation == "cout_shift":
+        out = out[..., [(n + 32) % N for n in range(N)]]
+    return out
+
+
+def fused_emulate(x, w, H, W, mode, mutation=None, tile=(16, 32), kc=16, contracted=False):
+    """conv3x3(resize(x)) [B, H, W, N] in fp64 on the resize evaluated as `mode`, with an optional mistake (FUSED_MUTATIONS)."""
+    p = interp_image(x, H, W, mode, contracted, row_off=H // 2 if mutation == "row_off" else None)
+    return conv_image(p, w.double(), None if mutation == "row_off" else mutation, tile, kc)
+
+
+def src_window_extent(n_in, n_out, tile):
+    """The largest number of source rows (columns) under the halo'd patch of one `tile`-wide output tile, by the kernels' own
+    arithmetic: first = min(int(scale * max(o0 - 1, 0)), in - 1), last = the i1 of the patch's last pixel inside the image. Also
+    asserts that no source index lies before `first` (the kernels clamp such an index to the window: it would be a wrong pixel)."""
+    i0, i1, _, _ = ac_coords(n_in, n_out)
+    ext = 1
+    for o0 in range(0, n_out, tile):
+        lo, hi = max(o0 - 1, 0), min(o0 + tile, n_out - 1)
+        first = int(i0[lo])
+        assert int(i0[lo:hi + 1].min()) >= first
+        ext = max(ext, int(i1[lo:hi + 1].max()) - first + 1)
+    return ext
+
+
+# ------------------------------------------------------------------------------------------------ vda_conv3x3_up2_f16
+# (B, h, w, C, N, ldc): out [B, 2h, 2w, N] = conv3x3(bilinear2x(x)) + bias. 16 x 32 output tiles, grid = tiles rounded up to 8,
+# 16-channel k-steps, 32-cout blocks (CB = 1, 2, 4), the wide store path where N % 8 == 0 and ldc % 8 == 0 and out is 16-byte aligned.
+UP2_TH, UP2_TW, UP2_SH, UP2_SW, UP2_KC = 16, 32, 11, 19, 16
+UP2_CASES = [
+    (1, 1, 1, 16, 4, 4),             # both scales 0; nk = 1; narrow store; 7 idle workgroups
+    (1, 8, 16, 16, 32, 32),          # exactly one full 16 x 32 tile
+    (2, 9, 17, 32, 24, 32),          # exactly 8 tiles; the last tiles 2 rows / 2 columns wide; partial cout block in the wide path; nk = 2
+    (3, 9, 17, 48, 40, 44),          # 12 tiles in a grid of 16: per_xcd = 2, tile >= ntiles; CB = 2, partial second block; narrow; odd nk
+    (1, 17, 33, 64, 128, 128),       # CB = 4; the largest source window: 10 of 11 rows, 18 of 19 columns
+    (1, 17, 33, 32, 100, 104),       # CB = 4, partial last block, narrow
+    (1, 1, 40, 16, 32, 32),          # a single source row
+    (1, 40, 1, 16, 32, 32),          # a single source column
+    (1, 148, 2, 16, 32, 32),         # the workload's extent: source rows up to 147
+    (1, 2, 148, 16, 32, 32),         # ... and columns
+]
+UP2_OFFSET_CASES = [UP2_CASES[3], UP2_CASES[2]]      # repeated with out 8 bytes into its allocation: a narrow case, and a wide one made narrow by that alone
+
+
+def up2_id(c):
+    return "B%d-%dx%d-C%d-N%d-ldc%d" % c
+
+
+def up2_geometry(case):
+    """What the launch of one case looks like: tiles, grid, per_xcd, idle workgroups, k-steps, cout blocks, store path, window extents."""
+    B, h, w, C, N, ldc = case
+    tiles_x, tiles_y = -(-2 * w // UP2_TW), -(-2 * h // UP2_TH)
+    ntiles = tiles_x * tiles_y * B
+    grid = -(-ntiles // 8) * 8
+    return dict(tiles_x=tiles_x, tiles_y=tiles_y, ntiles=ntiles, grid=grid, per_xcd=grid // 8, idle=grid - ntiles, nk=C // UP2_KC,
+                CB=1 if N <= 32 else 2 if N <= 64 else 4, wide=N % 8 == 0 and ldc % 8 == 0, partial_block=N % 32 != 0,
+                rows=src_window_extent(h, 2 * h, UP2_TH), cols=src_window_extent(w, 2 * w, UP2_TW))
+
+
+def up2_const_inputs(case):
+    """x [B, C, h, w] = v[b, c] in [-3, 3] at every pixel, w [N, C, 3, 3] in [-2, 2], bias [N] in [-4, 4]."""
+    B, h, w, C, N, _ = case
+    s = 11000 + 17 * (UP2_CASES.index(case) if case in UP2_CASES else 31) + C
+    v = ints((B, C), -3, 3, s)
+    return dict(x=v[:, :, None, None].expand(B, C, h, w).contiguous(), w=ints((N, C, 3, 3), -2, 2, s + 1), bias=ints((N,), -4, 4, s + 2))
+
+
+def up2_const_ref(case, inp):
+    """The fp64 reference [B, 2h, 2w, N] of the constant family, its preconditions asserted:
+      * the four fp32 weights of every output pixel sum to 1 within 2**-22 (each is a product of two fp32 numbers in [0, 1], rounded
+        once: 4 x 2**-25, plus what 1 - w loses: nothing, w being a multiple of 2**-24 below 1). v times the weights, summed in fp32
+        in any order with or without fused multiply-adds, is then within |v| (2**-22 + 4 x 2**-24) of v, and half an fp16 ulp of an
+        integer |v| <= 3 is |v| 2**-12 or more: the patch holds v itself, and exact zeros outside the image;
+      * the fp32 evaluation of the kernel's own expression gives exactly that (a check of the argument, not a replacement for it);
+      * every partial sum of the convolution stays below 2**24 and every output is an integer of magnitude <= 2048."""
+    B, h, w, C, N, _ = case
+    H, W = 2 * h, 2 * w
+    d = {k: v.double() for k, v in inp.items()}
+    assert bool((d["x"] == d["x"][:, :, :1, :1]).all()) and float(d["x"].abs().max()) <= 3
+    ones = torch.ones(1, 1, h, w, dtype=F64)
+    for contracted in (False, True):
+        assert float((interp_image(ones, H, W, "f64", contracted) - 1).abs().max()) <= 2.0 ** -22
+    big = d["x"].expand(B, C, h, w)[:, :, :1, :1].expand(B, C, H, W)
+    assert torch.equal(interp_image(inp["x"], H, W, "sum4_f32"), big), "the interpolated constant is the constant"
+    ref = conv_image(big, d["w"]) + d["bias"]
+    assert_exact_safe_f16([conv_image(big.abs(), d["w"].abs()) + d["bias"].abs()], [ref])
+    return ref
+
+
+def up2_selector_x(case):
+    """x [B, C, h, w]: integers in [-64, 64]; a step of one frame, row, column or channel changes the value by 29, 37, 11 or 7 mod 129."""
+    B, h, w, C, _, _ = case
+    b, c, y, x = torch.meshgrid(torch.arange(B), torch.arange(C), torch.arange(h), torch.arange(w), indexing="ij")
+    return ((29 * b + 37 * y + 11 * x + 7 * c + 5) % 129 - 64).to(F32)
+
+
+def up2_selector_sets(case):
+    """[(w [N, C, 3, 3] of zeros and one 1 per cout, picks [(tap, channel)] per cout)]: as many sets as it takes for every
+    (tap, 16-channel k-step, 8-channel chunk) to be some cout's pick; the channel inside the chunk varies with the cout."""
+    _, _, _, C, N, _ = case
+    nk = C // UP2_KC
+    ncombo = 9 * nk * 2
+    sets = []
+    for s in range(-(-ncombo // N)):
+        w, picks = torch.zeros(N, C, 3, 3), []
+        for n in range(N):
+            jj = s * N + n
+            j = jj % ncombo
+            tap, ks, chunk = j % 9, (j // 9) % nk, j // (9 * nk)
+            ch = 16 * ks + 8 * chunk + (3 * jj + jj // ncombo) % 8
+            w[n, ch, tap // 3, tap % 3] = 1.0
+            picks.append((tap, ch))
+        sets.append((w, picks))
+    return sets
+
+
+def up2_selector_coverage(case):
+    """The (tap, k-step, chunk) triples picked by some cout of some set."""
+    return {(tap, ch // 16, (ch // 8) % 2) for _, picks in up2_selector_sets(case) for tap, ch in picks}
+
+
+def up2_selector_bound(r, h, w, amax):
+    """|y - r| <= ulp16(r) / 2 + 2**-22 max(h, w) amax + 2**-22 amax for the fp16 output y of a kernel that evaluates the definition
+    r (interp_image "f64": a00 (1-wx)(1-wy) + ... in fp64 on the fp32 coordinates of ac_coords) in fp32, in any order. Derivation,
+    with y' the kernel's fp32 value, |y - r| <= |y - y'| + |y' - r|:
+      * ulp16(r) / 2 - the one rounding of y' to fp16 (ulp16 floors at the subnormal spacing 2**-24, so the term never vanishes).
+      * 2**-22 max(h, w) amax - the coordinate. We take w = src - i0 of src = fl32(scale dst), an exact difference. A compiler
+        that contracts scale dst - i0 into one fused operation sees the unrounded product instead: its weight differs by the rounding
+        of src, at most half an ulp of a number below max(h, w): 2**-24 max(h, w). The value is bilinear in (wx, wy) with slopes
+        |a01 - a00|, |a10 - a00|, ... <= 2 amax, and there are two axes: 2 x 2 amax x 2**-24 max(h, w).
+      * 2**-22 amax - the fp32 evaluation on given weights. 1 - w is exact from the second source cell on (w is a multiple of 2**-23
+        there); a weight product u v <= 1 is rounded by <= 2**-25, four of them against |a| <= amax: 2**-23 amax; the four products
+        a w and the three additions are rounded by <= 2**-24 of partial sums that are convex combinations of the corners,
+        |.| <= amax, or not at all where they are fused: <= 2**-23 amax once the products' errors are weighted by the w that sum to 1.
+    This is a first-order count: it does not add the cross terms, the first source cell's 1 - w (2**-25 more per axis) or the
+    contracted weight's own rounding, which a strict worst case with every error aligned would - one more 2**-22 amax, against
+    slack of at least that size in the coordinate term wherever max(h, w) is not just past a power of two. It is therefore CHECKED,
+    not trusted: tests/test_exact_inputs.py evaluates two orders (conv_up.hip's four-weight sum; torch's F.interpolate in fp32)
+    against the plain and the contracted coordinates for every case and at (17, 33), (148, 5), (5, 148), (148, 148), (1, 7):
+    the worst error is 0.98 of the bound, nearly all of it the fp16 rounding. A wrong pixel, tap or channel is an error of 7 or more."""
+    return ulp16(r) / 2 + 2.0 ** -22 * max(h, w) * amax + 2.0 ** -22 * amax
+
+
+# ------------------------------------------------------------------------------------------------ vda_depth_tail_f16 with a resize, dyadic scales
+# (B, h, w, H, W) x C: resize h x w -> H x W, conv3x3(C -> 32) + ReLU, conv1x1(32 -> 1) + ReLU, fp32 out
+TAILUP_CASES = [
+    (1, 1, 1, 5, 7),             # both scales 0
+    (2, 9, 17, 17, 33),          # 1/2 in both axes; two tile rows and columns of the 16 x 32 persistent tile, the second one pixel wide
+    (1, 5, 9, 17, 33),           # 1/4 in both axes
+    (1, 9, 9, 17, 33),           # 1/2 in y, 1/4 in x
+    (1, 17, 9, 17, 33),          # rows identical, columns 1/4
+    (1, 17, 17, 17, 33),         # rows identical, columns 1/2: the source region exceeds 256 pixels -> depth_tail_kernel<1>
+    (1, 33, 65, 17, 33),         # downsampling by 2: the same fallback
+    (1, 7, 5, 5, 9),             # 3/2 in y, 1/2 in x
+]
+TAILUP_C = [32, 64, 128]
+TAIL_KERNELS = ("depth_tail_kernel<0>", "depth_tail_kernel<1>", "depth_tail_up_kernel")     # vda_depth_tail_last_kernel: identity, resize, persistent resize
+TAIL_SRC_ROWS = 256              # v2::SRC_ROWS of tail.hip
+
+
+def tailup_many_tiles_case(ncu):
+    """More 16 x 32 tiles (9 per frame) than compute units: a persistent workgroup takes a second tile."""
+    return (ncu // 9 + 1, 17, 33, 33, 65)
+
+
+def tailup_id(c):
+    return "B%d-%dx%d-to-%dx%d" % c
+
+
+def tail_src_extent(n_in, n_out, tile):
+    """v2::src_extent of tail.hip (halo_lo = -1): the source rows / columns the dispatcher sizes a tile's region with."""
+    scale = torch.tensor(ac_coords(n_in, n_out)[3], dtype=F32)
+    ext = 1
+    for o0 in range(0, n_out, tile):
+        lo, hi = max(o0 - 1, 0), min(o0 + tile, n_out - 1)
+        a = min(int(scale * torch.tensor(float(lo), dtype=F32)), n_in - 1)
+        b = min(int(scale * torch.tensor(float(hi), dtype=F32)) + 1, n_in - 1)
+        ext = max(ext, b - a + 1)
+    return ext
+
+
+def tailup_kernel(case, variant=0):
+    """The kernel vda_depth_tail_f16 must run for a case under vda_depth_tail_set_variant(variant)."""
+    B, h, w, H, W = case
+    if h == H and w == W:
+        return TAIL_KERNELS[0]
+    fits = tail_src_extent(h, H, 16) * tail_src_extent(w, W, 32) <= TAIL_SRC_ROWS
+    return TAIL_KERNELS[2] if fits and variant != 1 else TAIL_KERNELS[1]
+
+
+def assert_dyadic(h, w, H, W):
+    """Both align_corners scales are in {0, 1/4, 1/2, 1, 3/2, 2} - exact in fp32, every src = scale * dst exact, every weight a multiple of 1/4."""
+    for n_in, n_out in ((h, H), (w, W)):
+        s = ac_coords(n_in, n_out)[3]
+        assert s in (0.0, 0.25, 0.5, 1.0, 1.5, 2.0), f"scale {s} of {n_in} -> {n_out}"
+        assert n_out == 1 or s * (n_out - 1) == n_in - 1, "the fp32 scale is the exact ratio"
+        wgt = ac_coords(n_in, n_out)[2] * 4
+        assert bool((wgt == wgt.round()).all())
+
+
+def tailup_inputs(case, Cc):
+    """As tail16_inputs, but w3 in [-1, 3] and b3 in [0, 4]: with symmetric ranges the last ReLU leaves half of a small case's
+    outputs (all 35 of the 1 x 1 image's, at C = 64) at zero, where nothing can be seen."""
+    B, h, w, H, W = case
+    s = 12000 + 17 * (TAILUP_CASES.index(case) if case in TAILUP_CASES else 29) + Cc
+    return dict(x=ints((B, Cc, h, w), -3, 3, s), w2=ints((32, Cc, 3, 3), -2, 2, s + 1), b2=ints((32,), -4, 4, s + 2), w3=ints((32,), -1, 3, s + 3),
+                b3=float(ints((1,), 0, 4, s + 4)))
+
+
+def dyadic_resize_ref(x, H, W):
+    """fp64 resize [B, C, H, W] of integer x with |x| <= 3 at dyadic scales, its exactness asserted: a multiple of 1/16 with |v| <= 3,
+    equal to torch's own fp64 F.interpolate. Products a * w (w a multiple of 1/16 <= 1) and every partial sum of the four are then
+    multiples of 1/16 below 16: fp16 values, so the packed-fp16 chain of bilinear8, the fp32 four-term sum and the nested fp32
+    lerp all give this value without a rounding."""
+    assert_dyadic(x.shape[2], x.shape[3], H, W)
+    assert bool((x == x.round()).all()) and float(x.abs().max()) <= 3
+    up = interp_image(x, H, W, "f64")
+    assert bool((up * 16 == (up * 16).round()).all()) and float(up.abs().max()) <= 3
+    assert torch.equal(up, F.interpolate(x.double(), size=(H, W), mode="bilinear", align_corners=True))
+    return up
+
+
+def tailup_ref(case, inp, b3):
+    """fp64 reference [B, H, W] with its preconditions: the resize is exact (dyadic_resize_ref), and in units of 1/16 every partial
+    sum of both convolutions stays below 2**24 - the fp32 MFMA chain and the fp32 epilogue are exact in any order."""
+    B, h, w, H, W = case
+    d = {k: v.double() for k, v in inp.items()}
+    a = {k: v.abs() for k, v in d.items()}
+    up, upa = dyadic_resize_ref(d["x"], H, W), dyadic_resize_ref(a["x"], H, W)
+    assert bool((upa >= up.abs()).all())
+    assert_exact_safe(16 * tail16_ref(dict(a, x=upa), abs(b3)), 16 * F.conv2d(upa, a["w2"], a["b2"], padding=1))
+    return tail16_ref(dict(d, x=up), b3)
+
+
+def tail_epilogue(lin, d, b3):
+    """[B, H, W, 32] conv sums -> ReLU(sum_co ReLU(lin + b2) w3 + b3)."""
+    return F.relu((F.relu(lin + d["b2"]) * d["w3"]).sum(-1) + b3)
+
+
+# ------------------------------------------------------------------------------------------------ vda_bilinear_nhwc_f16 / _f32, dyadic scales
+BILINEAR_DYADIC_C = [32, 192]
+
+
+def bilinear_dyadic_inputs(case, Cc):
+    B, h, w, H, W = case
+    s = 13000 + 17 * TAILUP_CASES.index(case) + Cc
+    return dict(x=ints((B, Cc, h, w), -3, 3, s), add=ints((B, Cc, H, W), -4, 4, s + 1))
+
+
+def bilinear_dyadic_refs(case, inp):
+    """(resize, resize + add) as fp64 NHWC [B, H, W, C]: multiples of 1/16 up to 7, fp16 values - the kernel's nested fp32 lerp, the
+    addition and the fp16 store are all exact."""
+    B, h, w, H, W = case
+    up = dyadic_resize_ref(inp["x"].double(), H, W)
+    both = up + inp["add"].double()
+    assert_exact_safe_f16([16 * (up.abs() + inp["add"].double().abs())], [up, both], step=1.0 / 16)
+    return up.permute(0, 2, 3, 1).contiguous(), both.permute(0, 2, 3, 1).contiguous()

@@ -56,6 +56,17 @@ def test_refusal_needs_no_gpu(libpath):
     assert b"null" in _lib.lib.vda_last_error()
 
 
+def test_depth_tail_last_kernel_needs_no_gpu(libpath):
+    """vda_depth_tail_last_kernel is declared, bound and exported (the three tests above), names no kernel before the first launch, and a
+    refused call leaves it so."""
+    from video_depth_anything_amd import _lib
+    lib = _lib.lib
+    assert _lib.SIGNATURES["vda_depth_tail_last_kernel"] == (ctypes.c_char_p, [])
+    assert lib.vda_depth_tail_last_kernel() == b""
+    assert lib.vda_depth_tail_f16(None, None, None, None, 0.0, None, None, 1, 4, 4, 8, 8, 32, None) != 0
+    assert b"null" in lib.vda_last_error() and lib.vda_depth_tail_last_kernel() == b""
+
+
 def test_cpp_host_demo_builds_and_links(libpath):
     """examples/host_demo.cpp (a C++ host of the handle API) compiles against include/vda.h and links against the library;
     argument checking happens before any HIP call."""

@@ -9,7 +9,8 @@ For every dense, conv3x3, ConvTranspose and patch-embed case of tests/_exact.py:
 A case whose inputs let a mistake through would make its GPU test vacuous for that mistake: the inputs are changed, not the check.
 
 The second half of the file does the same for the fp16 GEMM's cases (tests/test_kernels_f16_edges_gpu.py), the last part for the fp16
-attention kernels' exact-softmax inputs (tests/test_attention_edges_gpu.py), see there."""
+attention kernels' exact-softmax inputs (tests/test_attention_edges_gpu.py), the part behind it for the fused upsample convolutions'
+constant, selector and dyadic inputs (tests/test_upsample_edges_gpu.py), see there."""
 import functools
 
 import pytest
@@ -492,3 +493,194 @@ def test_attention_helpers_refuse_what_they_should():
     off = E.counting_expected(1, 65, 1).to(F16)
     nudged = (off.view(torch.int16) + 2).view(F16)              # two fp16 steps: refused; one: allowed
     assert not E.counting_check(nudged, 1, 65, 1)[0] and E.counting_check((off.view(torch.int16) + 1).view(F16), 1, 65, 1)[0]
+
+
+# ================================================================================================ the fused upsample convolutions' cases
+# tests/test_upsample_edges_gpu.py: every case reaches the branch it is listed for (window extents, tile counts, store path, tap x
+# k-step x chunk coverage, the tail's kernel), every reference equals an fp32 / fp16 emulation of the kernel's own operation order (or
+# bounds it, for the selector family), and a restatement with one mistake built in (E.FUSED_MUTATIONS) fails the GPU test's assertion.
+
+def test_up2_cases_reach_their_branches():
+    g = [E.up2_geometry(c) for c in E.UP2_CASES]
+    assert len(E.UP2_CASES) == 10 and all(c[3] % 16 == 0 and c[4] % 4 == 0 and c[5] % 4 == 0 and c[5] >= c[4] for c in E.UP2_CASES)
+    assert E.ac_coords(1, 2)[3] == 0.0 and (g[0]["nk"], g[0]["wide"], g[0]["idle"], g[0]["ntiles"]) == (1, False, 7, 1)
+    assert (g[1]["ntiles"], 2 * E.UP2_CASES[1][1], 2 * E.UP2_CASES[1][2]) == (1, E.UP2_TH, E.UP2_TW)
+    assert (g[2]["ntiles"], g[2]["idle"], g[2]["wide"], g[2]["partial_block"], g[2]["nk"]) == (8, 0, True, True, 2) and 18 % E.UP2_TH == 2 and 34 % E.UP2_TW == 2
+    assert (g[3]["ntiles"], g[3]["grid"], g[3]["per_xcd"], g[3]["CB"], g[3]["partial_block"], g[3]["wide"], g[3]["nk"]) == (12, 16, 2, 2, True, False, 3)
+    assert (g[4]["CB"], g[4]["wide"], g[4]["rows"], g[4]["cols"]) == (4, True, 10, 18)
+    assert (g[5]["CB"], g[5]["wide"], g[5]["partial_block"], g[5]["rows"], g[5]["cols"]) == (4, False, True, 10, 18)
+    assert (g[6]["rows"], g[7]["cols"]) == (1, 1) and E.UP2_CASES[6][1] == 1 and E.UP2_CASES[7][2] == 1
+    assert E.UP2_CASES[8][1] == 148 and E.UP2_CASES[9][2] == 148 and int(E.ac_coords(148, 296)[1].max()) == 147
+    assert all(x["rows"] <= E.UP2_SH and x["cols"] <= E.UP2_SW for x in g)
+    assert [c for c in E.UP2_CASES if 9 * c[3] % 64 == 0] == [E.UP2_CASES[4]], "the cases the conv GEMM can take"
+    assert all(not E.up2_geometry(c)["wide"] or c is E.UP2_CASES[2] for c in E.UP2_OFFSET_CASES)
+    # 17 and 33 are the smallest sizes whose windows reach 10 rows / 18 columns, and no size up to 299 needs the 11th row / 19th column
+    rows = {n: E.src_window_extent(n, 2 * n, E.UP2_TH) for n in range(1, 300)}
+    cols = {n: E.src_window_extent(n, 2 * n, E.UP2_TW) for n in range(1, 300)}
+    assert min(n for n, e in rows.items() if e == 10) == 17 and max(rows.values()) == 10 < E.UP2_SH
+    assert min(n for n, e in cols.items() if e == 18) == 33 and max(cols.values()) == 18 < E.UP2_SW
+
+
+@pytest.mark.parametrize("case", E.UP2_CASES, ids=E.up2_id)
+def test_up2_selector_sets_cover_every_tap_kstep_and_chunk(case):
+    C, N = case[3], case[4]
+    assert E.up2_selector_coverage(case) == {(t, k, c) for t in range(9) for k in range(C // 16) for c in range(2)}
+    for w, picks in E.up2_selector_sets(case):
+        assert bool((w.sum((1, 2, 3)) == 1).all()) and bool(((w == 0) | (w == 1)).all()) and len(picks) == N
+        assert all(picks[n] != picks[n + 32] for n in range(N - 32)), "a cout block shifted by 32 selects something else"
+    x = E.up2_selector_x(case)
+    assert float(x.abs().max()) <= 64 and bool((x == x.round()).all()) and torch.equal(x.to(torch.float16).float(), x)
+
+
+def fused_seen(mut, ref, bound=None):
+    """Does the mistaken result fail the GPU test's assertion: inequality (bound None) or an error above the bound after the fp16 store."""
+    if bound is None:
+        return not torch.equal(mut, ref)
+    return bool(((mut.to(torch.float16).double() - ref).abs() > bound).any())
+
+
+@pytest.mark.parametrize("case", E.UP2_CASES + [(1, 3, 3, 256, 128, 128)], ids=E.up2_id)
+def test_up2_constant_case_is_exact_and_sensitive(case):
+    """(The last case is no GPU case: the value ranges hold the preconditions at C = 256, the model's width, too.)"""
+    B, h, w, C, N, ldc = case
+    H, W = 2 * h, 2 * w
+    inp = E.up2_const_inputs(case)
+    ref = E.up2_const_ref(case, inp)
+    d = dbl(inp)
+    for contracted in (False, True):
+        assert torch.equal(E.fused_emulate(inp["x"], d["w"], H, W, "sum4_f32", contracted=contracted) + d["bias"], ref), "the kernel's operation order gives the reference"
+    assert torch.equal(E.fused_emulate(inp["x"], d["w"], H, W, "sum4_f32", "row_off") + d["bias"], ref), "(a constant image cannot see a wrong source row: the selector family does)"
+    for m in E.FUSED_MUTATIONS[1:]:
+        if E.fused_mutation_applies(m, B, h, H, W, C, N, (E.UP2_TH, E.UP2_TW), E.UP2_KC):
+            assert fused_seen(E.fused_emulate(inp["x"], d["w"], H, W, "sum4_f32", m) + d["bias"], ref), f"{m} goes unnoticed on these inputs"
+    differs(E.fused_emulate(inp["x"], d["w"], H, W, "sum4_f32") + d["bias"].roll(1), ref, "bias on the wrong cout")
+
+
+SELECTOR_GEOM = [(17, 33), (148, 5), (5, 148), (148, 148), (1, 7)]
+
+
+def selector_ratio(x, H, W):
+    """Worst error / bound of two fp32 evaluation orders (conv_up.hip's four-weight sum on plain and on contracted coordinates,
+    torch's own F.interpolate) against the fp64 definition on plain and on contracted coordinates."""
+    h, w = x.shape[2:]
+    amax = float(x.abs().max())
+    ys = [E.interp_image(x, H, W, "sum4_f32"), E.interp_image(x, H, W, "sum4_f32", contracted=True),
+          F.interpolate(x, size=(H, W), mode="bilinear", align_corners=True).to(torch.float16).double()]
+    worst = 0.0
+    for contracted in (False, True):
+        r = E.interp_image(x, H, W, "f64", contracted)
+        bound = E.up2_selector_bound(r, h, w, amax)
+        worst = max([worst] + [float(((y - r).abs() / bound).max()) for y in ys])
+    return worst
+
+
+@pytest.mark.parametrize("h,w", SELECTOR_GEOM)
+def test_selector_bound_holds_at_the_stated_geometries(h, w):
+    worst = selector_ratio(E.up2_selector_x((1, h, w, 16, 4, 4)), 2 * h, 2 * w)
+    assert worst <= 1.0, worst
+
+
+@pytest.mark.parametrize("case", E.UP2_CASES, ids=E.up2_id)
+def test_up2_selector_case_is_bounded_and_sensitive(case):
+    B, h, w, C, N, ldc = case
+    H, W = 2 * h, 2 * w
+    x = E.up2_selector_x(case)
+    assert selector_ratio(x, H, W) <= 1.0
+    amax = float(x.abs().max())
+    seen = set()
+    for wsel, picks in E.up2_selector_sets(case):
+        wd = wsel.double()
+        ref = E.fused_emulate(x, wd, H, W, "f64")
+        bound = E.up2_selector_bound(ref, h, w, amax)
+        assert float(bound.max()) < 0.05, "the bound is a few hundredths"
+        # the reference is a gather of the interpolated image: cout n holds the image at (tap, channel), zero outside
+        img = F.pad(E.interp_image(x, H, W, "f64"), (1, 1, 1, 1))
+        for n in (0, N - 1):
+            tap, ch = picks[n]
+            assert torch.equal(ref[..., n], img[:, ch, tap // 3:tap // 3 + H, tap % 3:tap % 3 + W])
+        for contracted in (False, True):
+            assert not fused_seen(E.fused_emulate(x, wd, H, W, "sum4_f32", contracted=contracted), ref, bound), "the kernel's operation order stays inside the bound"
+        for m in E.FUSED_MUTATIONS:
+            if E.fused_mutation_applies(m, B, h, H, W, C, N, (E.UP2_TH, E.UP2_TW), E.UP2_KC) and fused_seen(E.fused_emulate(x, wd, H, W, "sum4_f32", m), ref, bound):
+                seen.add(m)
+    for m in E.FUSED_MUTATIONS:
+        if E.fused_mutation_applies(m, B, h, H, W, C, N, (E.UP2_TH, E.UP2_TW), E.UP2_KC):
+            assert m in seen, f"{m} stays inside the bound on these inputs"
+
+
+def test_every_fused_mutation_fails_in_a_listed_case():
+    """The per-case tests above assert that every mutation that APPLIES to a case fails there (selector family: all seven; constant
+    family: all but the wrong source row); here: each applies to several listed cases."""
+    for m in E.FUSED_MUTATIONS:
+        hit = [c for c in E.UP2_CASES if E.fused_mutation_applies(m, c[0], c[1], 2 * c[1], 2 * c[2], c[3], c[4], (E.UP2_TH, E.UP2_TW), E.UP2_KC)]
+        assert len(hit) >= 2, m
+
+
+# ------------------------------------------------------------------------------------------------ the resizing depth tail, dyadic scales
+TAILUP_ALL = E.TAILUP_CASES + [E.tailup_many_tiles_case(256)]
+
+
+def test_tailup_cases_run_the_kernel_they_are_listed_for():
+    names = [E.tailup_kernel(c) for c in E.TAILUP_CASES]
+    assert names == [E.TAIL_KERNELS[2]] * 5 + [E.TAIL_KERNELS[1]] * 2 + [E.TAIL_KERNELS[2]]
+    assert all(E.tailup_kernel(c, 1) == E.TAIL_KERNELS[1] for c in TAILUP_ALL) and E.tailup_kernel((1, 5, 7, 5, 7)) == E.TAIL_KERNELS[0]
+    assert E.tail_src_extent(17, 17, 16) * E.tail_src_extent(17, 33, 32) > E.TAIL_SRC_ROWS
+    assert E.tail_src_extent(33, 17, 16) * E.tail_src_extent(65, 33, 32) > E.TAIL_SRC_ROWS
+    B, h, w, H, W = E.TAILUP_CASES[1]
+    assert (-(-H // 16), -(-W // 32), H % 16, W % 32) == (2, 2, 1, 1)
+    for ncu in (8, 64, 256, 304):
+        c = E.tailup_many_tiles_case(ncu)
+        assert c[0] * -(-c[3] // 16) * -(-c[4] // 32) > ncu and E.tailup_kernel(c) == E.TAIL_KERNELS[2]
+    scales = {(E.ac_coords(c[1], c[3])[3], E.ac_coords(c[2], c[4])[3]) for c in E.TAILUP_CASES}
+    assert scales == {(0.0, 0.0), (0.5, 0.5), (0.25, 0.25), (0.5, 0.25), (1.0, 0.25), (1.0, 0.5), (2.0, 2.0), (1.5, 0.5)}
+
+
+@pytest.mark.parametrize("case,Cc", [(c, Cc) for c in E.TAILUP_CASES for Cc in E.TAILUP_C] + [(TAILUP_ALL[-1], 32)],
+                         ids=lambda v: E.tailup_id(v) if isinstance(v, tuple) else str(v))
+def test_tailup_case_is_exact_and_sensitive(case, Cc):
+    B, h, w, H, W = case
+    inp = E.tailup_inputs(case, Cc)
+    b3 = inp.pop("b3")
+    assert all(is_f16(inp[k]) for k in ("x", "w2"))
+    ref = E.tailup_ref(case, inp, b3)
+    assert bool((ref > 0).any()), "something survives the last ReLU"
+    d = dbl(inp)
+    tile = (16, 32) if E.tailup_kernel(case) == E.TAIL_KERNELS[2] else (8, 32)
+    emu = lambda m=None: E.tail_epilogue(E.fused_emulate(inp["x"], d["w2"], H, W, "pk_f16", m, tile, 32), d, b3)      # noqa: E731
+    assert torch.equal(emu(), ref), "bilinear8's packed-fp16 chain gives the reference"
+    assert torch.equal(E.tail_epilogue(E.fused_emulate(inp["x"], d["w2"], H, W, "pk_f16", None, tile, 32).float(), {k: v.float() for k, v in d.items()}, b3).double(), ref)
+    for m in E.FUSED_MUTATIONS:
+        if m != "cout_shift" and E.fused_mutation_applies(m, B, h, H, W, Cc, 32, tile, 32):
+            differs(emu(m), ref, m)
+
+
+def test_upsample_helpers_refuse_what_they_should():
+    with pytest.raises(AssertionError, match="scale"):
+        E.assert_dyadic(9, 17, 16, 33)
+    E.assert_dyadic(7, 5, 5, 9)
+    case = E.UP2_CASES[1]
+    inp = E.up2_const_inputs(case)
+    with pytest.raises(AssertionError):
+        E.up2_const_ref(case, dict(inp, x=inp["x"] * 400))                       # outputs past 2048
+    bad = inp["x"].clone()
+    bad[0, 0, 0, 0] += 1
+    with pytest.raises(AssertionError):
+        E.up2_const_ref(case, dict(inp, x=bad))                                  # not a constant image
+    from video_depth_anything_amd import _lib
+    assert _lib.lib.vda_depth_tail_last_kernel() in (b"",) + tuple(k.encode() for k in E.TAIL_KERNELS)
+
+
+# ------------------------------------------------------------------------------------------------ vda_bilinear_nhwc at dyadic scales
+@pytest.mark.parametrize("Cc", E.BILINEAR_DYADIC_C)
+@pytest.mark.parametrize("case", E.TAILUP_CASES, ids=E.tailup_id)
+def test_bilinear_dyadic_case_is_exact_and_sensitive(case, Cc):
+    B, h, w, H, W = case
+    inp = E.bilinear_dyadic_inputs(case, Cc)
+    up, both = E.bilinear_dyadic_refs(case, inp)
+    lerp = E.interp_image(inp["x"], H, W, "lerp_f32").permute(0, 2, 3, 1)
+    assert torch.equal(lerp, up), "the kernel's nested fp32 lerp gives the reference"
+    add = inp["add"].permute(0, 2, 3, 1)
+    assert torch.equal((lerp.float() + add).to(torch.float16).double(), both) and torch.equal((lerp.float() + add).double(), both)
+    differs(both, up, "forgetting the addend")
+    if h > 1:
+        differs(E.interp_image(inp["x"], H, W, "lerp_f32", row_off=H // 2).permute(0, 2, 3, 1), up, "a source row off by one")

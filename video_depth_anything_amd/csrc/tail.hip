@@ -551,6 +551,10 @@ extern "C" int vda_depth_tail_set_variant(int v) {
     return 0;
 }
 
+// which of the three kernels the last vda_depth_tail_f16 of this thread launched (tests: a case written for one must not run another)
+static thread_local const char* g_tail_last_kernel = "";
+extern "C" const char* vda_depth_tail_last_kernel(void) { return g_tail_last_kernel; }
+
 extern "C" int vda_depth_tail_f16(const void* in, const void* w2, const float* b2, const float* w3, float b3, float* out,
                                   const void* zero_page, int B, int h, int w, int H, int W, int C, vda_stream_t stream) {
     VDA_REQUIRE(in && w2 && b2 && w3 && out && zero_page, "vda_depth_tail: null pointer");
@@ -583,6 +587,7 @@ extern "C" int vda_depth_tail_f16(const void* in, const void* w2, const float* b
         hipLaunchKernelGGL(fn, dim3(grid2), dim3(v2::NT2), v2::SMEM2, s, (const h16*)in, (const h16*)w2, b2, w3, b3, out, h, w, H, W, C,
                            tx2, ty2, (int)nt2, ys, xs, SH | ((g_tail_variant & 8) ? 1 << 16 : 0), SW);
         VDA_LAUNCH_CHECK();
+        g_tail_last_kernel = "depth_tail_up_kernel";
         return 0;
     }
     if (h == H && w == W)
@@ -592,5 +597,6 @@ extern "C" int vda_depth_tail_f16(const void* in, const void* w2, const float* b
         hipLaunchKernelGGL((depth_tail_kernel<1>), grid, dim3(256), 0, s, (const h16*)in, (const h16*)w2, b2, w3, b3, out, (const h16*)zero_page, h, w,
                            H, W, C, tiles_x, tiles_y, (int)ntiles, ys, xs);
     VDA_LAUNCH_CHECK();
+    g_tail_last_kernel = h == H && w == W ? "depth_tail_kernel<0>" : "depth_tail_kernel<1>";
     return 0;
 }
