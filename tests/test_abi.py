@@ -41,6 +41,14 @@ def test_library_exports_every_declared_symbol(libpath):
     assert lib.vda_abi_version() == 8
 
 
+def test_every_file_of_the_fp64_reduction_is_built_without_contraction():
+    """csrc/reduce64.h's arithmetic (scale * x + shift, the 2x2 solve, the callers' centred sums) means what it says only unfused."""
+    from video_depth_anything_amd import build
+    users = [f for f in build._sources() if re.search(r'#include\s+"reduce64\.h"', open(os.path.join(build.CSRC, f)).read())]
+    assert sorted(users) == ["eval.hip", "losses.hip", "stitch.hip", "tae.hip"]
+    assert all("-ffp-contract=off" in build.PER_FILE.get(f, []) for f in users), users
+
+
 def test_binding_table_matches_header(libpath):
     from video_depth_anything_amd import _lib
     assert sorted(_lib.SIGNATURES) == declared_symbols()

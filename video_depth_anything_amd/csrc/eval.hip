@@ -1,5 +1,5 @@
 // Benchmark scorer on the device: the arithmetic of the reference's benchmark/eval/eval.py:67-122 and metric.py as two streaming
-// reductions, each with a one-workgroup finisher, in the pattern of stitch.hip (fp64 partials, fixed combination order, no atomics).
+// reductions, each with a one-workgroup finisher: fp64 partials, fixed combination order, no atomics - the pattern stated in reduce64.h.
 //
 //   pass 1 (eval_lsq_*)    over every valid pixel of the whole video: count, sum x, sum x^2, sum y, sum x*y with x = clip(pred, 1e-3)
 //                          and y = 1 / (gt + 1e-8); the finisher solves the 2x2 normal equations and leaves {scale, shift, n_valid}
@@ -14,26 +14,13 @@
 //
 // Both passes are HBM-bound streams (8 or 12 bytes per pixel); the fp64 divisions (one in pass 1, five in pass 2) are IEEE.
 // THIS FILE IS BUILT WITH -ffp-contract=off (build.py PER_FILE): scale * x + shift rounds twice, as numpy evaluates it.
-#include "vda_common.h"
+#include "reduce64.h"
 
 namespace {
 
-constexpr int EV_T = 256;
+constexpr int EV_T = R64_T;
 constexpr int LSQ_K = 5;      // count, sum x, sum x^2, sum y, sum x*y
 constexpr int MET_K = 7;      // n, sum |p-g|/g, sum (p-g)^2/g, sum (p-g)^2, c1, c2, c3
-
-// `red[k][t]` holds thread t's value of quantity k; afterwards red[k][0] is the block's. Fixed tree: the same order every run.
-template <int K>
-__device__ __forceinline__ void block_tree_sum(double (&red)[K][EV_T]) {
-    __syncthreads();
-    for (int w = EV_T / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + w];
-        }
-        __syncthreads();
-    }
-}
 
 // valid = (gt > 1e-3) & (gt < max_depth), compared in gt's OWN type as numpy compares an array with a python scalar: a float32
 // ground truth meets float32(1e-3), which is not the double 1e-3.
@@ -42,16 +29,11 @@ __device__ __forceinline__ bool gt_valid(GT g, GT hi) {
     return g > (GT)1e-3 && g < hi;
 }
 
-// np.clip(infs, 1e-3, None) on the float32 array (NaN stays NaN)
-__device__ __forceinline__ float clip_pred(float p) { return p < 1e-3f ? 1e-3f : p; }
-
 template <typename GT>
 __global__ void __launch_bounds__(EV_T) eval_lsq_partial_kernel(const float* __restrict__ pred, const GT* __restrict__ gt, long long n, double max_depth,
                                                                 double* __restrict__ partial) {
     const GT hi = (GT)max_depth;
-    double s[LSQ_K] = {0.0, 0.0, 0.0, 0.0, 0.0};
-#pragma unroll 4
-    for (long long i = (long long)blockIdx.x * EV_T + threadIdx.x; i < n; i += (long long)gridDim.x * EV_T) {
+    plane_partial<LSQ_K>(n, partial + (size_t)blockIdx.x * LSQ_K, [&](long long i, double (&s)[LSQ_K]) {
         const GT g = gt[i];
         if (gt_valid(g, hi)) {
             const double x = (double)clip_pred(pred[i]);
@@ -62,31 +44,16 @@ __global__ void __launch_bounds__(EV_T) eval_lsq_partial_kernel(const float* __r
             s[3] += y;
             s[4] += x * y;
         }
-    }
-    __shared__ double red[LSQ_K][EV_T];
-#pragma unroll
-    for (int k = 0; k < LSQ_K; ++k) red[k][threadIdx.x] = s[k];
-    block_tree_sum(red);
-    if (threadIdx.x < LSQ_K) partial[(size_t)blockIdx.x * LSQ_K + threadIdx.x] = red[threadIdx.x][0];
+    });
 }
 
 // Rows summed in index order; fit = {scale, shift, n_valid}. Fewer than two points or a singular system: scale = shift = NaN.
 __global__ void eval_lsq_finish_kernel(const double* __restrict__ partial, int nrows, double* __restrict__ fit) {
-    __shared__ double tot[LSQ_K];
-    if (threadIdx.x < LSQ_K) {
-        double a = 0.0;
-        for (int b = 0; b < nrows; ++b) a += partial[(size_t)b * LSQ_K + threadIdx.x];
-        tot[threadIdx.x] = a;
-    }
-    __syncthreads();
+    const double* tot = column_sums<LSQ_K>(partial, nrows);
     if (threadIdx.x == 0) {
         const double a11 = tot[0], a01 = tot[1], a00 = tot[2], b1 = tot[3], b0 = tot[4];
-        const double det = a00 * a11 - a01 * a01;
         double sc = __builtin_nan(""), sh = __builtin_nan("");
-        if (a11 >= 2.0 && det != 0.0) {
-            sc = (a11 * b0 - a01 * b1) / det;
-            sh = (a00 * b1 - a01 * b0) / det;
-        }
+        if (a11 >= 2.0) solve_2x2(a00, a01, a11, b0, b1, sc, sh);
         fit[0] = sc;
         fit[1] = sh;
         fit[2] = a11;
@@ -101,18 +68,12 @@ __global__ void __launch_bounds__(EV_T) eval_metric_partial_kernel(const float* 
     const GT hi = (GT)max_depth;
     const float* __restrict__ pf = pred + (size_t)blockIdx.y * px;
     const GT* __restrict__ gf = gt + (size_t)blockIdx.y * px;
-    double s[MET_K] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-#pragma unroll 2
-    for (long long i = (long long)blockIdx.x * EV_T + threadIdx.x; i < px; i += (long long)gridDim.x * EV_T) {
+    double* row = partial + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * MET_K;
+    plane_partial<MET_K, 2>(px, row, [&](long long i, double (&s)[MET_K]) {
         const GT g32 = gf[i];
         if (gt_valid(g32, hi)) {
             const double g = (double)g32;
-            const double m = scale * (double)clip_pred(pf[i]);
-            double al = m + shift;                              // two roundings (-ffp-contract=off)
-            al = al < 1e-3 ? 1e-3 : al;
-            double p = 1.0 / al;
-            p = p < 1e-3 ? 1e-3 : p;
-            p = p > dmax ? dmax : p;
+            const double p = aligned_depth(pf[i], scale, shift, dmax);
             const double d = p - g;
             const double r1 = p / g, r2 = g / p;
             const double r = r1 > r2 ? r1 : r2;
@@ -124,12 +85,7 @@ __global__ void __launch_bounds__(EV_T) eval_metric_partial_kernel(const float* 
             s[5] += r < 1.25 * 1.25 ? 1.0 : 0.0;
             s[6] += r < 1.25 * 1.25 * 1.25 ? 1.0 : 0.0;
         }
-    }
-    __shared__ double red[MET_K][EV_T];
-#pragma unroll
-    for (int k = 0; k < MET_K; ++k) red[k][threadIdx.x] = s[k];
-    block_tree_sum(red);
-    if (threadIdx.x < MET_K) partial[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * MET_K + threadIdx.x] = red[threadIdx.x][0];
+    });
 }
 
 // One workgroup. Thread t owns frames t, t + 256, ...: it sums a frame's block rows in index order, forms the frame's ratios and adds
@@ -139,11 +95,8 @@ __global__ void __launch_bounds__(EV_T) eval_metric_partial_kernel(const float* 
 __global__ void __launch_bounds__(EV_T) eval_metric_finish_kernel(const double* __restrict__ partial, int nframes, int bpf, double* __restrict__ result) {
     double s[MET_K] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // frames used, then the six per-frame metrics
     for (int f = threadIdx.x; f < nframes; f += EV_T) {
-        double a[MET_K] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        for (int b = 0; b < bpf; ++b) {
-#pragma unroll
-            for (int k = 0; k < MET_K; ++k) a[k] += partial[((size_t)f * bpf + b) * MET_K + k];
-        }
+        double a[MET_K];
+        plane_rows_sum(partial, f, bpf, a);
         if (a[0] > 0.0) {
             const float nf = (float)a[0];
             s[0] += 1.0;
@@ -168,22 +121,16 @@ __global__ void __launch_bounds__(EV_T) eval_metric_finish_kernel(const double* 
     }
 }
 
-constexpr int EV_MAX_BLOCKS = 4096;          // pass 1 blocks per call; pass 2 blocks per frame
-constexpr int EV_MAX_ROWS = 1 << 22;         // partial rows one finisher walks
-constexpr int EV_MAX_FRAMES = 65535;         // gridDim.y
-
-inline bool aligned8(const void* p) { return ((uintptr_t)p & 7) == 0; }
-
 }  // namespace
 
 extern "C" int vda_eval_lsq_partial(const float* pred, const void* gt, int gt_is_f64, long long n, double max_depth, double* partial, int row_offset,
                                     int nblk, vda_stream_t stream) {
     VDA_REQUIRE(pred && gt && partial, "vda_eval_lsq_partial: null pointer");
     VDA_REQUIRE(n > 0, "vda_eval_lsq_partial: bad size n=%lld", n);
-    VDA_REQUIRE(nblk > 0 && nblk <= EV_MAX_BLOCKS, "vda_eval_lsq_partial: bad block count %d (1..%d)", nblk, EV_MAX_BLOCKS);
-    VDA_REQUIRE(row_offset >= 0 && row_offset <= EV_MAX_ROWS - nblk, "vda_eval_lsq_partial: bad row offset %d", row_offset);
+    VDA_REQUIRE(nblk > 0 && nblk <= R64_MAX_BLOCKS, "vda_eval_lsq_partial: bad block count %d (1..%d)", nblk, R64_MAX_BLOCKS);
+    VDA_REQUIRE(row_offset >= 0 && row_offset <= R64_MAX_ROWS - nblk, "vda_eval_lsq_partial: bad row offset %d", row_offset);
     VDA_REQUIRE(gt_is_f64 == 0 || gt_is_f64 == 1, "vda_eval_lsq_partial: gt_is_f64 must be 0 or 1");
-    VDA_REQUIRE(aligned8(partial) && ((uintptr_t)pred & 3) == 0 && ((uintptr_t)gt & (gt_is_f64 ? 7 : 3)) == 0,
+    VDA_REQUIRE(aligned_to(partial, 8) && aligned_to(pred, 4) && aligned_to(gt, gt_is_f64 ? 8 : 4),
                 "vda_eval_lsq_partial: misaligned pointer (the fp64 workspace needs 8-byte alignment)");
     double* rows = partial + (size_t)row_offset * LSQ_K;
     hipStream_t s = (hipStream_t)stream;
@@ -197,8 +144,8 @@ extern "C" int vda_eval_lsq_partial(const float* pred, const void* gt, int gt_is
 
 extern "C" int vda_eval_lsq_finish(const double* partial, int nrows, double* fit, vda_stream_t stream) {
     VDA_REQUIRE(partial && fit, "vda_eval_lsq_finish: null pointer");
-    VDA_REQUIRE(nrows > 0 && nrows <= EV_MAX_ROWS, "vda_eval_lsq_finish: bad row count n=%d (1..%d)", nrows, EV_MAX_ROWS);
-    VDA_REQUIRE(aligned8(partial) && aligned8(fit), "vda_eval_lsq_finish: misaligned pointer (fp64 needs 8-byte alignment)");
+    VDA_REQUIRE(nrows > 0 && nrows <= R64_MAX_ROWS, "vda_eval_lsq_finish: bad row count n=%d (1..%d)", nrows, R64_MAX_ROWS);
+    VDA_REQUIRE(aligned_to(partial, 8) && aligned_to(fit, 8), "vda_eval_lsq_finish: misaligned pointer (fp64 needs 8-byte alignment)");
     hipLaunchKernelGGL(eval_lsq_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, partial, nrows, fit);
     VDA_LAUNCH_CHECK();
     return 0;
@@ -207,13 +154,9 @@ extern "C" int vda_eval_lsq_finish(const double* partial, int nrows, double* fit
 extern "C" int vda_eval_metric_partial(const float* pred, const void* gt, int gt_is_f64, int nframes, long long px, double max_depth, const double* fit,
                                        double* partial, int frame_offset, int blocks_per_frame, vda_stream_t stream) {
     VDA_REQUIRE(pred && gt && fit && partial, "vda_eval_metric_partial: null pointer");
-    VDA_REQUIRE(nframes > 0 && nframes <= EV_MAX_FRAMES && px > 0, "vda_eval_metric_partial: bad size n=%d frames of %lld pixels", nframes, px);
-    VDA_REQUIRE(blocks_per_frame > 0 && blocks_per_frame <= EV_MAX_BLOCKS, "vda_eval_metric_partial: bad block count %d per frame (1..%d)",
-                blocks_per_frame, EV_MAX_BLOCKS);
-    VDA_REQUIRE(frame_offset >= 0 && ((long long)frame_offset + nframes) * blocks_per_frame <= EV_MAX_ROWS,
-                "vda_eval_metric_partial: bad frame offset %d (too many partial rows)", frame_offset);
+    if (check_plane_rows("vda_eval_metric_partial", "frame", nframes, R64_MAX_PLANES, px, blocks_per_frame, frame_offset)) return 1;
     VDA_REQUIRE(gt_is_f64 == 0 || gt_is_f64 == 1, "vda_eval_metric_partial: gt_is_f64 must be 0 or 1");
-    VDA_REQUIRE(aligned8(partial) && aligned8(fit) && ((uintptr_t)pred & 3) == 0 && ((uintptr_t)gt & (gt_is_f64 ? 7 : 3)) == 0,
+    VDA_REQUIRE(aligned_to(partial, 8) && aligned_to(fit, 8) && aligned_to(pred, 4) && aligned_to(gt, gt_is_f64 ? 8 : 4),
                 "vda_eval_metric_partial: misaligned pointer (the fp64 workspace needs 8-byte alignment)");
     double* rows = partial + (size_t)frame_offset * blocks_per_frame * MET_K;
     hipStream_t s = (hipStream_t)stream;
@@ -228,9 +171,8 @@ extern "C" int vda_eval_metric_partial(const float* pred, const void* gt, int gt
 
 extern "C" int vda_eval_metric_finish(const double* partial, int nframes, int blocks_per_frame, double* result, vda_stream_t stream) {
     VDA_REQUIRE(partial && result, "vda_eval_metric_finish: null pointer");
-    VDA_REQUIRE(nframes > 0 && blocks_per_frame > 0 && blocks_per_frame <= EV_MAX_BLOCKS && (long long)nframes * blocks_per_frame <= EV_MAX_ROWS,
-                "vda_eval_metric_finish: bad sizes n=%d frames, %d blocks per frame", nframes, blocks_per_frame);
-    VDA_REQUIRE(aligned8(partial) && aligned8(result), "vda_eval_metric_finish: misaligned pointer (fp64 needs 8-byte alignment)");
+    if (check_plane_rows("vda_eval_metric_finish", "frame", nframes, R64_MAX_ROWS, 1, blocks_per_frame)) return 1;
+    VDA_REQUIRE(aligned_to(partial, 8) && aligned_to(result, 8), "vda_eval_metric_finish: misaligned pointer (fp64 needs 8-byte alignment)");
     hipLaunchKernelGGL(eval_metric_finish_kernel, dim3(1), dim3(EV_T), 0, (hipStream_t)stream, partial, nframes, blocks_per_frame, result);
     VDA_LAUNCH_CHECK();
     return 0;

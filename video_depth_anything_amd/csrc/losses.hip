@@ -1,7 +1,7 @@
 // Validation losses on the device: the arithmetic of the reference's utils/loss_MiDas.py (Loss_ssi, Loss_tgm: what train.py's
 // validation pass ranks checkpoints by) and utils/loss.py (the Depth-Anything form of Loss_ssi) restated as streaming fp64 reductions
-// in the pattern of eval.hip: fp64 partial rows per block, a fixed LDS tree, rows combined in index order by a one-block finisher,
-// ordinary vector stores, no floating-point atomics. Every float32 input is widened exactly to fp64 and all arithmetic is fp64.
+// in the pattern stated in reduce64.h: fp64 partial rows per block, a fixed LDS tree, rows combined in index order by a one-block
+// finisher, ordinary vector stores, no floating-point atomics. Every float32 input is widened exactly to fp64 and all arithmetic is fp64.
 // Nothing returns to the host between the passes; the result depends on the block counts, never on timing.
 //
 //   ssi "lsq" (loss_MiDas.py)   pass 0 {n, sum d, sum y} -> means; pass 1 {sum (d-mu_d)(y-mu_y), sum (d-mu_d)^2} -> s, t;
@@ -22,43 +22,16 @@
 // No inter-workgroup synchronisation, no global atomics; after four passes the prefix IS the key of an input element, bit for bit,
 // whatever the launch geometry. -0 sorts before +0.
 // THIS FILE IS BUILT WITH -ffp-contract=off (build.py PER_FILE): s * d + t rounds twice, as numpy evaluates it.
-#include "vda_common.h"
+#include "reduce64.h"
 
 namespace {
 
-constexpr int LS_T = 256;
+constexpr int LS_T = R64_T;
 constexpr int LS_STATS = 8;          // doubles per frame in `stats`
 // lsq: n, mu_d, mu_y, s, t, loss
 enum { ST_N = 0, ST_MU_D = 1, ST_MU_Y = 2, ST_S = 3, ST_T = 4, ST_LOSS = 5 };
 // mad: med_d, sc_d, med_y, sc_y, n
 enum { SM_MED_D = 0, SM_SC_D = 1, SM_MED_Y = 2, SM_SC_Y = 3, SM_N = 4 };
-
-template <int K>
-__device__ __forceinline__ void block_tree_sum(double (&red)[K][LS_T]) {
-    __syncthreads();
-    for (int w = LS_T / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + w];
-        }
-        __syncthreads();
-    }
-}
-
-// One block's share of a plane of px pixels: f(i, s) adds pixel i's terms to the thread's sums; the block's K sums go to `row`.
-template <int K, typename F>
-__device__ __forceinline__ void plane_partial(long long px, double* __restrict__ row, F f) {
-    double s[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) s[k] = 0.0;
-#pragma unroll 4
-    for (long long i = (long long)blockIdx.x * LS_T + threadIdx.x; i < px; i += (long long)gridDim.x * LS_T) f(i, s);
-    __shared__ double red[K][LS_T];
-#pragma unroll
-    for (int k = 0; k < K; ++k) red[k][threadIdx.x] = s[k];
-    block_tree_sum(red);
-    if ((int)threadIdx.x < K) row[threadIdx.x] = red[threadIdx.x][0];
-}
 
 // ------------------------------------------------------------------------------------------------ ssi, least-squares form
 // grid (blocks per plane, frames); row of (frame f, block b) = partial[(f * gridDim.x + b) * K ...], K = 3, 2, 1 for pass 0, 1, 2
@@ -112,12 +85,7 @@ __global__ void __launch_bounds__(LS_T) loss_lsq_finish_kernel(const double* __r
     double total = 0.0;
     for (int f = threadIdx.x; f < nframes; f += LS_T) {
         double a[K];
-#pragma unroll
-        for (int k = 0; k < K; ++k) a[k] = 0.0;
-        for (int b = 0; b < bpp; ++b) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) a[k] += partial[((size_t)f * bpp + b) * K + k];
-        }
+        plane_rows_sum(partial, f, bpp, a);
         double* st = stats + (size_t)f * LS_STATS;
         if constexpr (PASS == 0) {
             const double n = a[0] > 1.0 ? a[0] : 1.0;
@@ -138,10 +106,8 @@ __global__ void __launch_bounds__(LS_T) loss_lsq_finish_kernel(const double* __r
         }
     }
     if constexpr (PASS == 2) {
-        __shared__ double red[1][LS_T];
-        red[0][threadIdx.x] = total;
-        block_tree_sum(red);
-        if (threadIdx.x == 0) result[0] = red[0][0] / (double)nframes;
+        total = block_total(total);
+        if (threadIdx.x == 0) result[0] = total / (double)nframes;
     }
 }
 
@@ -259,11 +225,8 @@ __global__ void __launch_bounds__(LS_T) loss_mad_scale_partial_kernel(const floa
 __global__ void __launch_bounds__(LS_T) loss_mad_scale_finish_kernel(const double* __restrict__ partial, int nframes, int bpp, double eps,
                                                                      const float* __restrict__ med, double* __restrict__ stats) {
     for (int f = threadIdx.x; f < nframes; f += LS_T) {
-        double a[3] = {0.0, 0.0, 0.0};
-        for (int b = 0; b < bpp; ++b) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) a[k] += partial[((size_t)f * bpp + b) * 3 + k];
-        }
+        double a[3];
+        plane_rows_sum(partial, f, bpp, a);
         double* st = stats + (size_t)f * LS_STATS;
         st[SM_MED_D] = (double)med[f];
         st[SM_MED_Y] = (double)med[(size_t)nframes + f];
@@ -296,11 +259,8 @@ __global__ void __launch_bounds__(LS_T) loss_mad_rows_kernel(const float* __rest
             cnt += 1.0;
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        sum += __shfl_xor(sum, o, 64);
-        cnt += __shfl_xor(cnt, o, 64);
-    }
+    sum = wave_sum(sum);
+    cnt = wave_sum(cnt);
     if (lane == 0) {
         rows[(size_t)r * 2] = sum;
         rows[(size_t)r * 2 + 1] = cnt;
@@ -318,17 +278,14 @@ __global__ void __launch_bounds__(LS_T) loss_mad_finish_kernel(const double* __r
             const double* row = rows + ((size_t)f * H + r) * 2;
             s += row[0] / (row[1] > 1.0 ? row[1] : 1.0);
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-        if (lane == 0) result[1 + f] = s;                      // the frame's sum; divided by H below
+        s = wave_sum(s);
+        if (lane == 0) result[1 + f] = s;                     // the frame's sum; divided by H below
     }
     __syncthreads();                                           // the frames' sums are read by other threads of this block
     double total = 0.0;
     for (int f = threadIdx.x; f < nframes; f += LS_T) total += result[1 + f];
-    __shared__ double red[1][LS_T];
-    red[0][threadIdx.x] = total;
-    block_tree_sum(red);                                       // its barriers also order the reads above before the writes below
-    if (threadIdx.x == 0) result[0] = red[0][0] / ((double)nframes * (double)H);
+    total = block_total(total);                                // its barriers also order the reads above before the writes below
+    if (threadIdx.x == 0) result[0] = total / ((double)nframes * (double)H);
     for (int f = threadIdx.x; f < nframes; f += LS_T) result[1 + f] = result[1 + f] / (double)H;
 }
 
@@ -365,11 +322,8 @@ __global__ void __launch_bounds__(LS_T) loss_tgm_partial_kernel(const float* __r
 __global__ void __launch_bounds__(LS_T) loss_tgm_finish_kernel(const double* __restrict__ partial, int B, int N, int bpp, double* __restrict__ result) {
     const int P = B * (N - 1);
     for (int p = threadIdx.x; p < P; p += LS_T) {
-        double a[3] = {0.0, 0.0, 0.0};
-        for (int b = 0; b < bpp; ++b) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) a[k] += partial[((size_t)p * bpp + b) * 3 + k];
-        }
+        double a[3];
+        plane_rows_sum(partial, p, bpp, a);
         result[1 + p] = (a[0] > 0.0 && a[1] > 0.0) ? a[2] / a[1] : __builtin_nan("");
         result[1 + P + p] = a[1];
     }
@@ -383,33 +337,23 @@ __global__ void __launch_bounds__(LS_T) loss_tgm_finish_kernel(const double* __r
         }
         total += s / (double)(N - 1);
     }
-    __shared__ double red[1][LS_T];
-    red[0][threadIdx.x] = total;
-    block_tree_sum(red);
-    if (threadIdx.x == 0) result[0] = red[0][0] / (double)B;
+    total = block_total(total);
+    if (threadIdx.x == 0) result[0] = total / (double)B;
 }
-
-constexpr int LS_MAX_BLOCKS = 4096;          // blocks per plane
-constexpr int LS_MAX_ROWS = 1 << 22;         // partial rows one finisher walks; image rows of the mad form
-constexpr int LS_MAX_PLANES = 65535;         // gridDim.y
-
-inline bool al8(const void* p) { return ((uintptr_t)p & 7) == 0; }
-inline bool al4(const void* p) { return ((uintptr_t)p & 3) == 0; }
 
 }  // namespace
 
-#define LOSS_REQUIRE_PLANES(name, planes, px, bpp)                                                                                          \
-    VDA_REQUIRE((planes) > 0 && (planes) <= LS_MAX_PLANES && (px) > 0, name ": bad size n=%d planes of %lld pixels", (int)(planes),         \
-                (long long)(px));                                                                                                           \
-    VDA_REQUIRE((bpp) > 0 && (bpp) <= LS_MAX_BLOCKS, name ": bad block count %d per plane (1..%d)", (int)(bpp), LS_MAX_BLOCKS);             \
-    VDA_REQUIRE((long long)(planes) * (bpp) <= LS_MAX_ROWS, name ": too many partial rows (%d planes x %d blocks)", (int)(planes), (int)(bpp))
+// every finisher here is refused what its partial launch is: at most gridDim.y planes
+#define LOSS_REQUIRE_PLANES(name, planes, px, bpp) \
+    if (check_plane_rows(name, "plane", planes, R64_MAX_PLANES, px, bpp)) return 1
 
 extern "C" int vda_loss_lsq_partial(const float* pred, const float* y, const unsigned char* mask, int nframes, long long px, int pass,
                                     const double* stats, double* partial, int blocks_per_plane, vda_stream_t stream) {
     VDA_REQUIRE(pred && y && stats && partial, "vda_loss_lsq_partial: null pointer");
     LOSS_REQUIRE_PLANES("vda_loss_lsq_partial", nframes, px, blocks_per_plane);
     VDA_REQUIRE(pass >= 0 && pass <= 2, "vda_loss_lsq_partial: pass must be 0, 1 or 2, got %d", pass);
-    VDA_REQUIRE(al4(pred) && al4(y) && al8(stats) && al8(partial), "vda_loss_lsq_partial: misaligned pointer (the fp64 buffers need 8-byte alignment)");
+    VDA_REQUIRE(aligned_to(pred, 4) && aligned_to(y, 4) && aligned_to(stats, 8) && aligned_to(partial, 8),
+                "vda_loss_lsq_partial: misaligned pointer (the fp64 buffers need 8-byte alignment)");
     const dim3 grid(blocks_per_plane, nframes);
     hipStream_t s = (hipStream_t)stream;
     if (pass == 0)
@@ -427,7 +371,8 @@ extern "C" int vda_loss_lsq_finish(const double* partial, int nframes, int block
     VDA_REQUIRE(partial && stats && (result || pass != 2), "vda_loss_lsq_finish: null pointer");
     LOSS_REQUIRE_PLANES("vda_loss_lsq_finish", nframes, 1, blocks_per_plane);
     VDA_REQUIRE(pass >= 0 && pass <= 2, "vda_loss_lsq_finish: pass must be 0, 1 or 2, got %d", pass);
-    VDA_REQUIRE(al8(partial) && al8(stats) && al8(result), "vda_loss_lsq_finish: misaligned pointer (fp64 needs 8-byte alignment)");
+    VDA_REQUIRE(aligned_to(partial, 8) && aligned_to(stats, 8) && aligned_to(result, 8),
+                "vda_loss_lsq_finish: misaligned pointer (fp64 needs 8-byte alignment)");
     hipStream_t s = (hipStream_t)stream;
     if (pass == 0)
         hipLaunchKernelGGL(loss_lsq_finish_kernel<0>, dim3(1), dim3(LS_T), 0, s, partial, nframes, blocks_per_plane, eps, stats, result);
@@ -442,9 +387,9 @@ extern "C" int vda_loss_lsq_finish(const double* partial, int nframes, int block
 extern "C" int vda_loss_median(const float* pred, const float* y, const unsigned char* mask, int nframes, long long px, float* med,
                                vda_stream_t stream) {
     VDA_REQUIRE(pred && med, "vda_loss_median: null pointer");
-    VDA_REQUIRE(nframes > 0 && nframes <= LS_MAX_PLANES && px > 0, "vda_loss_median: bad size n=%d planes of %lld pixels", nframes, px);
+    VDA_REQUIRE(nframes > 0 && nframes <= R64_MAX_PLANES && px > 0, "vda_loss_median: bad size n=%d planes of %lld pixels", nframes, px);
     VDA_REQUIRE(px < (1ll << 31), "vda_loss_median: a plane of %lld pixels is too large (the counts are 32-bit)", px);
-    VDA_REQUIRE(al4(pred) && al4(y) && al4(med), "vda_loss_median: misaligned pointer");
+    VDA_REQUIRE(aligned_to(pred, 4) && aligned_to(y, 4) && aligned_to(med, 4), "vda_loss_median: misaligned pointer");
     hipLaunchKernelGGL(loss_median_kernel, dim3(nframes, y ? 2 : 1), dim3(SEL_T), 0, (hipStream_t)stream, pred, y, mask, px, nframes, med);
     VDA_LAUNCH_CHECK();
     return 0;
@@ -454,7 +399,7 @@ extern "C" int vda_loss_mad_scale_partial(const float* pred, const float* y, con
                                           double* partial, int blocks_per_plane, vda_stream_t stream) {
     VDA_REQUIRE(pred && y && med && partial, "vda_loss_mad_scale_partial: null pointer");
     LOSS_REQUIRE_PLANES("vda_loss_mad_scale_partial", nframes, px, blocks_per_plane);
-    VDA_REQUIRE(al4(pred) && al4(y) && al4(med) && al8(partial),
+    VDA_REQUIRE(aligned_to(pred, 4) && aligned_to(y, 4) && aligned_to(med, 4) && aligned_to(partial, 8),
                 "vda_loss_mad_scale_partial: misaligned pointer (the fp64 workspace needs 8-byte alignment)");
     hipLaunchKernelGGL(loss_mad_scale_partial_kernel, dim3(blocks_per_plane, nframes), dim3(LS_T), 0, (hipStream_t)stream, pred, y, mask, px, med,
                        partial);
@@ -466,7 +411,8 @@ extern "C" int vda_loss_mad_scale_finish(const double* partial, int nframes, int
                                          vda_stream_t stream) {
     VDA_REQUIRE(partial && med && stats, "vda_loss_mad_scale_finish: null pointer");
     LOSS_REQUIRE_PLANES("vda_loss_mad_scale_finish", nframes, 1, blocks_per_plane);
-    VDA_REQUIRE(al8(partial) && al4(med) && al8(stats), "vda_loss_mad_scale_finish: misaligned pointer (fp64 needs 8-byte alignment)");
+    VDA_REQUIRE(aligned_to(partial, 8) && aligned_to(med, 4) && aligned_to(stats, 8),
+                "vda_loss_mad_scale_finish: misaligned pointer (fp64 needs 8-byte alignment)");
     hipLaunchKernelGGL(loss_mad_scale_finish_kernel, dim3(1), dim3(LS_T), 0, (hipStream_t)stream, partial, nframes, blocks_per_plane, eps, med, stats);
     VDA_LAUNCH_CHECK();
     return 0;
@@ -476,8 +422,9 @@ extern "C" int vda_loss_mad_rows(const float* pred, const float* y, const unsign
                                  double* rows, vda_stream_t stream) {
     VDA_REQUIRE(pred && y && stats && rows, "vda_loss_mad_rows: null pointer");
     VDA_REQUIRE(nframes > 0 && H > 0 && W > 0, "vda_loss_mad_rows: bad size n=%d frames of %d x %d", nframes, H, W);
-    VDA_REQUIRE((long long)nframes * H <= LS_MAX_ROWS, "vda_loss_mad_rows: too many image rows (%d frames x %d)", nframes, H);
-    VDA_REQUIRE(al4(pred) && al4(y) && al8(stats) && al8(rows), "vda_loss_mad_rows: misaligned pointer (the fp64 buffers need 8-byte alignment)");
+    VDA_REQUIRE((long long)nframes * H <= R64_MAX_ROWS, "vda_loss_mad_rows: too many image rows (%d frames x %d)", nframes, H);
+    VDA_REQUIRE(aligned_to(pred, 4) && aligned_to(y, 4) && aligned_to(stats, 8) && aligned_to(rows, 8),
+                "vda_loss_mad_rows: misaligned pointer (the fp64 buffers need 8-byte alignment)");
     const long long nrows = (long long)nframes * H;
     const int per_block = LS_T / 64;
     hipLaunchKernelGGL(loss_mad_rows_kernel, dim3((unsigned)((nrows + per_block - 1) / per_block)), dim3(LS_T), 0, (hipStream_t)stream, pred, y, mask,
@@ -489,8 +436,8 @@ extern "C" int vda_loss_mad_rows(const float* pred, const float* y, const unsign
 extern "C" int vda_loss_mad_finish(const double* rows, int nframes, int H, double* result, vda_stream_t stream) {
     VDA_REQUIRE(rows && result, "vda_loss_mad_finish: null pointer");
     VDA_REQUIRE(nframes > 0 && H > 0, "vda_loss_mad_finish: bad size n=%d frames of %d rows", nframes, H);
-    VDA_REQUIRE((long long)nframes * H <= LS_MAX_ROWS, "vda_loss_mad_finish: too many image rows (%d frames x %d)", nframes, H);
-    VDA_REQUIRE(al8(rows) && al8(result), "vda_loss_mad_finish: misaligned pointer (fp64 needs 8-byte alignment)");
+    VDA_REQUIRE((long long)nframes * H <= R64_MAX_ROWS, "vda_loss_mad_finish: too many image rows (%d frames x %d)", nframes, H);
+    VDA_REQUIRE(aligned_to(rows, 8) && aligned_to(result, 8), "vda_loss_mad_finish: misaligned pointer (fp64 needs 8-byte alignment)");
     hipLaunchKernelGGL(loss_mad_finish_kernel, dim3(1), dim3(LS_T), 0, (hipStream_t)stream, rows, nframes, H, result);
     VDA_LAUNCH_CHECK();
     return 0;
@@ -499,9 +446,10 @@ extern "C" int vda_loss_mad_finish(const double* rows, int nframes, int H, doubl
 extern "C" int vda_loss_tgm_partial(const float* pred, const float* y, const unsigned char* mask, int B, int N, long long px, double* partial,
                                     int blocks_per_plane, vda_stream_t stream) {
     VDA_REQUIRE(pred && y && partial, "vda_loss_tgm_partial: null pointer");
-    VDA_REQUIRE(B > 0 && N >= 2 && (long long)B * (N - 1) <= LS_MAX_PLANES, "vda_loss_tgm_partial: bad size n=%d clips of %d frames (N >= 2)", B, N);
+    VDA_REQUIRE(B > 0 && N >= 2 && (long long)B * (N - 1) <= R64_MAX_PLANES, "vda_loss_tgm_partial: bad size n=%d clips of %d frames (N >= 2)", B, N);
     LOSS_REQUIRE_PLANES("vda_loss_tgm_partial", B * (N - 1), px, blocks_per_plane);
-    VDA_REQUIRE(al4(pred) && al4(y) && al8(partial), "vda_loss_tgm_partial: misaligned pointer (the fp64 workspace needs 8-byte alignment)");
+    VDA_REQUIRE(aligned_to(pred, 4) && aligned_to(y, 4) && aligned_to(partial, 8),
+                "vda_loss_tgm_partial: misaligned pointer (the fp64 workspace needs 8-byte alignment)");
     hipLaunchKernelGGL(loss_tgm_partial_kernel, dim3(blocks_per_plane, B * (N - 1)), dim3(LS_T), 0, (hipStream_t)stream, pred, y, mask, N, px, partial);
     VDA_LAUNCH_CHECK();
     return 0;
@@ -509,9 +457,9 @@ extern "C" int vda_loss_tgm_partial(const float* pred, const float* y, const uns
 
 extern "C" int vda_loss_tgm_finish(const double* partial, int B, int N, int blocks_per_plane, double* result, vda_stream_t stream) {
     VDA_REQUIRE(partial && result, "vda_loss_tgm_finish: null pointer");
-    VDA_REQUIRE(B > 0 && N >= 2 && (long long)B * (N - 1) <= LS_MAX_PLANES, "vda_loss_tgm_finish: bad size n=%d clips of %d frames (N >= 2)", B, N);
+    VDA_REQUIRE(B > 0 && N >= 2 && (long long)B * (N - 1) <= R64_MAX_PLANES, "vda_loss_tgm_finish: bad size n=%d clips of %d frames (N >= 2)", B, N);
     LOSS_REQUIRE_PLANES("vda_loss_tgm_finish", B * (N - 1), 1, blocks_per_plane);
-    VDA_REQUIRE(al8(partial) && al8(result), "vda_loss_tgm_finish: misaligned pointer (fp64 needs 8-byte alignment)");
+    VDA_REQUIRE(aligned_to(partial, 8) && aligned_to(result, 8), "vda_loss_tgm_finish: misaligned pointer (fp64 needs 8-byte alignment)");
     hipLaunchKernelGGL(loss_tgm_finish_kernel, dim3(1), dim3(LS_T), 0, (hipStream_t)stream, partial, B, N, blocks_per_plane, result);
     VDA_LAUNCH_CHECK();
     return 0;

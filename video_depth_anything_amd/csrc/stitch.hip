@@ -3,59 +3,38 @@
 // Per window k > 0 the reference (numpy, host) does: least-squares scale/shift of the window's first two frames
 // against the two reference key frames, affine + clamp of frames 2..31, an 8-frame linear cross-fade into the
 // previous window's tail, and appends the rest. Here that is one deterministic reduction (fp64 partials, fixed
-// combination order, no atomics) and one fused element-wise kernel; scale/shift never leave the device, so the
-// stitch of window k queues behind its forward on the same stream and costs ~20 us instead of ~15 ms of numpy.
+// combination order, no atomics: the pattern stated in reduce64.h) and one fused element-wise kernel; scale/shift
+// never leave the device, so the stitch of window k queues behind its forward on the same stream and costs ~20 us
+// instead of ~15 ms of numpy.
 //
 // Both kernels are HBM-bound streaming passes (64 MB per 518x518 window).
-#include "vda_common.h"
+#include "reduce64.h"
 
 namespace {
 
-constexpr int LSQ_T = 256;
+constexpr int LSQ_T = R64_T;
+constexpr int LSQ_K = 4;
+constexpr int LSQ_UNROLL = 1;     // not unrolled: a hint of 4 doubles the kernel's registers (20 -> 42 VGPRs), HBM-bound either way
 
 // partial[b] = { sum p*p, sum p, sum p*t, sum t } of block b's grid-stride slice, fp64
 __global__ void __launch_bounds__(LSQ_T) lsq_partial_kernel(const float* __restrict__ pred, const float* __restrict__ target, long long n,
                                                             double* __restrict__ partial) {
-    double s[4] = {0.0, 0.0, 0.0, 0.0};
-    for (long long i = (long long)blockIdx.x * LSQ_T + threadIdx.x; i < n; i += (long long)gridDim.x * LSQ_T) {
+    plane_partial<LSQ_K, LSQ_UNROLL>(n, partial + (size_t)blockIdx.x * LSQ_K, [&](long long i, double (&s)[LSQ_K]) {
         const double p = (double)pred[i], t = (double)target[i];
         s[0] += p * p;
         s[1] += p;
         s[2] += p * t;
         s[3] += t;
-    }
-    __shared__ double red[4][LSQ_T];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) red[j][threadIdx.x] = s[j];
-    __syncthreads();
-    for (int w = LSQ_T / 2; w > 0; w >>= 1) {                 // fixed tree: the same sum order every run
-        if ((int)threadIdx.x < w) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) red[j][threadIdx.x] += red[j][threadIdx.x + w];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x < 4) partial[(size_t)blockIdx.x * 4 + threadIdx.x] = red[threadIdx.x][0];
+    });
 }
 
 // utils/util.py:40-62 with the all-ones mask: a_11 = n. The reference evaluates the closed form on fp32 sums, where
-// det = a00*a11 - a01^2 cancels most of its digits; fp64 here, rounded to fp32 at the end.
+// det = a00*a11 - a01^2 cancels most of its digits; fp64 here, rounded to fp32 at the end. A singular system: scale 1, shift 0.
 __global__ void lsq_finish_kernel(const double* __restrict__ partial, int nblk, double n, float* __restrict__ scale_shift) {
-    __shared__ double tot[4];
-    if (threadIdx.x < 4) {
-        double a = 0.0;
-        for (int b = 0; b < nblk; ++b) a += partial[(size_t)b * 4 + threadIdx.x];
-        tot[threadIdx.x] = a;
-    }
-    __syncthreads();
+    const double* tot = column_sums<LSQ_K>(partial, nblk);
     if (threadIdx.x == 0) {
-        const double a00 = tot[0], a01 = tot[1], b0 = tot[2], b1 = tot[3], a11 = n;
-        const double det = a00 * a11 - a01 * a01;
         double sc = 1.0, sh = 0.0;
-        if (det != 0.0) {
-            sc = (a11 * b0 - a01 * b1) / det;
-            sh = (-a01 * b0 + a00 * b1) / det;
-        }
+        solve_2x2(tot[0], tot[1], n, tot[2], tot[3], sc, sh);
         scale_shift[0] = (float)sc;
         scale_shift[1] = (float)sh;
     }
@@ -120,7 +99,7 @@ extern "C" int vda_affine_clamp_f32(const float* in, const float* scale_shift, f
 extern "C" int vda_lsq_scale_shift_f32(const float* pred, const float* target, long long n, double* workspace, int nblk, float* scale_shift,
                                        vda_stream_t stream) {
     VDA_REQUIRE(pred && target && workspace && scale_shift, "vda_lsq_scale_shift_f32: null pointer");
-    VDA_REQUIRE(n > 0 && nblk > 0 && nblk <= 4096, "vda_lsq_scale_shift_f32: bad sizes n=%lld nblk=%d", n, nblk);
+    VDA_REQUIRE(n > 0 && nblk > 0 && nblk <= R64_MAX_BLOCKS, "vda_lsq_scale_shift_f32: bad sizes n=%lld nblk=%d", n, nblk);
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(lsq_partial_kernel, dim3(nblk), dim3(LSQ_T), 0, s, pred, target, n, workspace);
     hipLaunchKernelGGL(lsq_finish_kernel, dim3(1), dim3(64), 0, s, (const double*)workspace, nblk, (double)n, scale_shift);

@@ -14,46 +14,23 @@
 // LAST WINS. The reference splats with depth_proj[valid_Y, valid_X] = valid_Z, an index assignment with duplicate indices; on the CPU
 // the source pixels are visited in row-major order and the last one stays, whatever its sign. "Last in row-major order" is "largest
 // flat index", and an integer max does not depend on the order of arrival: the winner plane, and with it every count, is the same in
-// every run. It is the only atomic in this file; all sums are fp64 rows combined in a fixed order (the pattern of eval.hip).
+// every run. It is the only atomic in this file; all sums are fp64 rows combined in a fixed order (the pattern stated in reduce64.h).
 //
 // Both passes read pred through 16-byte loads when a plane's pixel count is a multiple of 4 (scalar, still coalesced, otherwise); the
 // gather of the winner's source pixel in the compare pass is the one irregular access. pred is float32, everything derived from it
 // is double. THIS FILE IS BUILT WITH -ffp-contract=off (build.py PER_FILE): every product and sum rounds on its own, as in eval.hip,
 // and the two passes' Qz are the same IEEE operations in the same order.
-#include "vda_common.h"
+#include "reduce64.h"
 
 namespace {
 
-constexpr int EV_T = 256;                    // threads per block, as eval.hip
+constexpr int EV_T = R64_T;                  // threads per block
 constexpr int TAE_V = 4;                     // pixels per thread and step
 constexpr int TAE_K = 2;                     // sum |dst - proj| / dst, count
 constexpr int TAE_CAM = 28;                  // doubles per pair: fx, fy, cx, cy, R|t of i -> i+1 (3x4 row-major), R|t of i+1 -> i
-constexpr int EV_MAX_BLOCKS = 4096;          // compare blocks per plane
-constexpr int EV_MAX_ROWS = 1 << 22;         // partial rows the finisher walks
-constexpr int TAE_MAX_PAIRS = 32767;         // 2 planes per pair on gridDim.y
+constexpr int TAE_MAX_PAIRS = R64_MAX_PLANES / 2;   // 2 planes per pair on gridDim.y
 
-// eval.hip's fixed LDS tree: red[k][0] is the block's sum, the same order every run.
-template <int K>
-__device__ __forceinline__ void block_tree_sum(double (&red)[K][EV_T]) {
-    __syncthreads();
-    for (int w = EV_T / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + w];
-        }
-        __syncthreads();
-    }
-}
-
-// clip(1 / clip(scale * clip(pred, 1e-3) + shift, 1e-3), 1e-3, max_depth): eval.hip's pass 2, here for EVERY pixel
-__device__ __forceinline__ double aligned_depth(float p, double scale, double shift, double dmax) {
-    const double m = scale * (double)(p < 1e-3f ? 1e-3f : p);
-    double al = m + shift;
-    al = al < 1e-3 ? 1e-3 : al;
-    double d = 1.0 / al;
-    d = d < 1e-3 ? 1e-3 : d;
-    return d > dmax ? dmax : d;
-}
+// aligned_depth (reduce64.h) is eval.hip's pass 2, here for EVERY pixel
 
 struct Cam {
     double fx, fy, cx, cy;
@@ -163,8 +140,8 @@ __global__ void __launch_bounds__(EV_T) tae_compare_kernel(const float* __restri
     const float* __restrict__ dst = pred + (size_t)(pair + 1 - dir) * px;
     const unsigned char* __restrict__ mk = mask ? mask + (size_t)(pair + 1 - dir) * px : nullptr;
     const unsigned* __restrict__ win = winner + (size_t)blockIdx.y * px;
-    double s = 0.0, c = 0.0;
-    for (long long i0 = ((long long)blockIdx.x * EV_T + threadIdx.x) * TAE_V; i0 < px; i0 += (long long)gridDim.x * EV_T * TAE_V) {
+    double s[TAE_K] = {0.0, 0.0};
+    for (long long i0 =((long long)blockIdx.x * EV_T + threadIdx.x) * TAE_V; i0 < px; i0 += (long long)gridDim.x * EV_T * TAE_V) {
         unsigned w[TAE_V], m[TAE_V] = {1u, 1u, 1u, 1u};
         float t[TAE_V];
         load_v<VEC>(win, i0, px, w);
@@ -177,17 +154,13 @@ __global__ void __launch_bounds__(EV_T) tae_compare_kernel(const float* __restri
                 const double proj = source_qz(k, sx, sy, aligned_depth(src[si], scale, shift, max_depth));
                 const double d = aligned_depth(t[e], scale, shift, max_depth);
                 if (proj > 0.0 && d > 0.0) {
-                    s += fabs(d - proj) / d;
-                    c += 1.0;
+                    s[0] += fabs(d - proj) / d;
+                    s[1] += 1.0;
                 }
             }
         }
     }
-    __shared__ double red[TAE_K][EV_T];
-    red[0][threadIdx.x] = s;
-    red[1][threadIdx.x] = c;
-    block_tree_sum(red);
-    if (threadIdx.x < TAE_K) partial[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * TAE_K + threadIdx.x] = red[threadIdx.x][0];
+    block_store_sums(s, partial + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * TAE_K);
 }
 
 // One workgroup. Thread t owns planes t, t + 256, ...: rows in index order, e = sum / count (0 without a count). Thread 0 then adds
@@ -195,13 +168,10 @@ __global__ void __launch_bounds__(EV_T) tae_compare_kernel(const float* __restri
 // result = {tae, error[nplanes], count[nplanes]}
 __global__ void __launch_bounds__(EV_T) tae_finish_kernel(const double* __restrict__ partial, int nplanes, int bpp, double* __restrict__ result) {
     for (int p = threadIdx.x; p < nplanes; p += EV_T) {
-        double s = 0.0, c = 0.0;
-        for (int b = 0; b < bpp; ++b) {
-            s += partial[((size_t)p * bpp + b) * TAE_K];
-            c += partial[((size_t)p * bpp + b) * TAE_K + 1];
-        }
-        result[1 + p] = c > 0.0 ? s / c : 0.0;
-        result[1 + nplanes + p] = c;
+        double a[TAE_K];
+        plane_rows_sum(partial, p, bpp, a);
+        result[1 + p] = a[1] > 0.0 ? a[0] / a[1] : 0.0;
+        result[1 + nplanes + p] = a[1];
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -211,14 +181,12 @@ __global__ void __launch_bounds__(EV_T) tae_finish_kernel(const double* __restri
     }
 }
 
-inline bool aligned8(const void* p) { return ((uintptr_t)p & 7) == 0; }
-
 // the shared refusals of the two passes; returns 0 when the arguments are fine
 int check_planes(const char* who, const void* pred, const void* fit, const void* cam, const void* winner, int npairs, int H, int W) {
     VDA_REQUIRE(pred && fit && cam && winner, "%s: null pointer", who);
     VDA_REQUIRE(npairs > 0 && npairs <= TAE_MAX_PAIRS && H > 0 && W > 0, "%s: bad size n=%d pairs of %d x %d", who, npairs, H, W);
     VDA_REQUIRE((long long)H * W < 2147483647LL, "%s: plane too large (%d x %d: a source index + 1 must fit 31 bits)", who, H, W);
-    VDA_REQUIRE(aligned8(fit) && aligned8(cam) && ((uintptr_t)pred & 3) == 0 && ((uintptr_t)winner & 3) == 0,
+    VDA_REQUIRE(aligned_to(fit, 8) && aligned_to(cam, 8) && aligned_to(pred, 4) && aligned_to(winner, 4),
                 "%s: misaligned pointer (the fp64 arrays need 8-byte alignment)", who);
     return 0;
 }
@@ -248,12 +216,10 @@ extern "C" int vda_tae_compare(const float* pred, const unsigned char* mask, int
                                vda_stream_t stream) {
     if (check_planes("vda_tae_compare", pred, fit, cam, winner, npairs, H, W)) return 1;
     VDA_REQUIRE(partial, "vda_tae_compare: null pointer");
-    VDA_REQUIRE(blocks_per_plane > 0 && blocks_per_plane <= EV_MAX_BLOCKS, "vda_tae_compare: bad block count %d per plane (1..%d)", blocks_per_plane,
-                EV_MAX_BLOCKS);
-    VDA_REQUIRE(pair_offset >= 0 && ((long long)pair_offset + npairs) * 2 * blocks_per_plane <= EV_MAX_ROWS,
-                "vda_tae_compare: bad pair offset %d (too many partial rows)", pair_offset);
-    VDA_REQUIRE(aligned8(partial), "vda_tae_compare: misaligned pointer (the fp64 workspace needs 8-byte alignment)");
+    VDA_REQUIRE(pair_offset >= 0, "vda_tae_compare: bad pair offset %d", pair_offset);
     const long long px = (long long)H * W;
+    if (check_plane_rows("vda_tae_compare", "plane", 2LL * npairs, R64_MAX_PLANES, px, blocks_per_plane, 2LL * pair_offset)) return 1;
+    VDA_REQUIRE(aligned_to(partial, 8), "vda_tae_compare: misaligned pointer (the fp64 workspace needs 8-byte alignment)");
     double* rows = partial + (size_t)pair_offset * 2 * blocks_per_plane * TAE_K;
     const dim3 grid(blocks_per_plane, 2 * npairs);
     hipStream_t s = (hipStream_t)stream;
@@ -267,10 +233,8 @@ extern "C" int vda_tae_compare(const float* pred, const unsigned char* mask, int
 
 extern "C" int vda_tae_finish(const double* partial, int npairs, int blocks_per_plane, double* result, vda_stream_t stream) {
     VDA_REQUIRE(partial && result, "vda_tae_finish: null pointer");
-    VDA_REQUIRE(npairs > 0 && npairs <= EV_MAX_ROWS && blocks_per_plane > 0 && blocks_per_plane <= EV_MAX_BLOCKS &&
-                    (long long)npairs * 2 * blocks_per_plane <= EV_MAX_ROWS,
-                "vda_tae_finish: bad sizes n=%d pairs, %d blocks per plane", npairs, blocks_per_plane);
-    VDA_REQUIRE(aligned8(partial) && aligned8(result), "vda_tae_finish: misaligned pointer (fp64 needs 8-byte alignment)");
+    if (check_plane_rows("vda_tae_finish", "plane", 2LL * npairs, R64_MAX_ROWS, 1, blocks_per_plane)) return 1;
+    VDA_REQUIRE(aligned_to(partial, 8) && aligned_to(result, 8), "vda_tae_finish: misaligned pointer (fp64 needs 8-byte alignment)");
     hipLaunchKernelGGL(tae_finish_kernel, dim3(1), dim3(EV_T), 0, (hipStream_t)stream, partial, 2 * npairs, blocks_per_plane, result);
     VDA_LAUNCH_CHECK();
     return 0;

@@ -155,6 +155,49 @@ def evaluate_depth_numpy(pred, gt, max_depth, max_eval_len=None, resize=False):
     return _result((scale, shift, n), res + [int(used.sum())])
 
 
+# ---------------------------------------------------------------------------------------------- host steps the device scorers share
+def _as_tensor(a, name, dtypes, what):
+    import torch
+
+    if not isinstance(a, torch.Tensor):
+        a = torch.from_numpy(np.asarray(a))
+    if a.dtype not in dtypes:
+        raise ValueError(f"{what}: {name} must be {' or '.join(str(d) for d in dtypes)}, got {a.dtype}")
+    return a
+
+
+def _one_device(tensors, device, what):
+    """The device the CUDA tensors among `tensors` (None entries skipped) share, or torch.device(device) when none is on a device."""
+    import torch
+
+    on_dev = [t.device for t in tensors if t is not None and t.is_cuda]
+    dev = on_dev[0] if on_dev else torch.device(device)
+    if dev.type != "cuda" or any(d != dev for d in on_dev):
+        raise ValueError(f"{what}: needs one cuda device, got {device!r} / {[str(d) for d in on_dev]}")
+    return dev
+
+
+def _chunk_feeds(pred, gt, dev, size):
+    """(pred_chunk, gt_chunk): frames lo .. hi-1 on the device, the prediction at gt's `size` (deterministic: the same bits every pass)."""
+    on_device = lambda t, lo, hi: t[lo:hi].to(dev, non_blocking=False).contiguous()  # noqa: E731
+    return (lambda lo, hi: resize_prediction(on_device(pred, lo, hi), size)), (lambda lo, hi: on_device(gt, lo, hi))
+
+
+def _fit_chunks(N, step, px):
+    """Pass 1's calls over N frames, `step` at a time: (lo, hi, blocks); a block leaves one partial row of 5 doubles."""
+    return [(lo, min(lo + step, N), min(LSQ_MAX_BLOCKS, -(-min(step, N - lo) * px // EVAL_T))) for lo in range(0, N, step)]
+
+
+def _fit_scale_shift(ops, chunks, pred_chunk, gt_chunk, max_depth, work, fit):
+    """Pass 1 over `chunks` (their rows one after the other in `work`) and its finisher: fit = {scale, shift, n_valid} on the device.
+    `ops` is the kernel binding module its caller has imported already (a relative import per call costs microseconds)."""
+    row = 0
+    for lo, hi, nb in chunks:
+        ops.eval_lsq_partial(pred_chunk(lo, hi), gt_chunk(lo, hi), max_depth, work, row, nb)
+        row += nb
+    ops.eval_lsq_finish(work, row, fit)
+
+
 def evaluate_depth(pred, gt, max_depth, max_eval_len=None, device="cuda", chunk_frames=None, resize=False):
     """Metrics of `pred` (float32 [N,H,W]) against `gt` (float32 or float64 [N,H,W]) on the device; numpy arrays or CUDA tensors.
     Device-resident tensors are used in place; host arrays are uploaded `chunk_frames` frames at a time (all at once when None), once
@@ -164,48 +207,27 @@ def evaluate_depth(pred, gt, max_depth, max_eval_len=None, device="cuda", chunk_
     import torch
     from . import ops
 
-    def as_tensor(a, name, dtypes):
-        if not isinstance(a, torch.Tensor):
-            a = torch.from_numpy(np.asarray(a))
-        if a.dtype not in dtypes:
-            raise ValueError(f"evaluate_depth: {name} must be {' or '.join(str(d) for d in dtypes)}, got {a.dtype}")
-        return a
-
-    pred = as_tensor(pred, "pred", (torch.float32,))
-    gt = as_tensor(gt, "gt", (torch.float32, torch.float64))
+    pred = _as_tensor(pred, "pred", (torch.float32,), "evaluate_depth")
+    gt = _as_tensor(gt, "gt", (torch.float32, torch.float64), "evaluate_depth")
     pred, gt = _check_pair(pred, gt, max_eval_len, resize)
-    on_dev = [t.device for t in (pred, gt) if t.is_cuda]
-    dev = on_dev[0] if on_dev else torch.device(device)
-    if dev.type != "cuda" or any(d != dev for d in on_dev):
-        raise ValueError(f"evaluate_depth: needs one cuda device, got {device!r} / {[str(d) for d in on_dev]}")
+    dev = _one_device((pred, gt), device, "evaluate_depth")
     N, H, W = gt.shape
     px = H * W
     step = N if chunk_frames is None else int(chunk_frames)
     if step <= 0:
         raise ValueError("evaluate_depth: chunk_frames must be positive")
-    chunks = [(lo, min(lo + step, N)) for lo in range(0, N, step)]
-    nblk = [min(LSQ_MAX_BLOCKS, -(-(hi - lo) * px // EVAL_T)) for lo, hi in chunks]
+    chunks = _fit_chunks(N, step, px)
     bpf = min(METRIC_MAX_BLOCKS, -(-px // EVAL_T))
     max_depth = float(max_depth)
 
     with torch.cuda.device(dev):
-        work = torch.empty(max(5 * sum(nblk), 7 * N * bpf), dtype=torch.float64, device=dev)
+        work = torch.empty(max(5 * sum(nb for _, _, nb in chunks), 7 * N * bpf), dtype=torch.float64, device=dev)
         out = torch.empty(10, dtype=torch.float64, device=dev)          # fit {scale, shift, n_valid} | result[7]
         fit, res = out[:3], out[3:]
-
-        def on_device(t, lo, hi):
-            return t[lo:hi].to(dev, non_blocking=False).contiguous()
-
-        def pred_chunk(lo, hi):                                         # at gt's size: deterministic, so both passes see the same bits
-            return resize_prediction(on_device(pred, lo, hi), (H, W))
-
-        row = 0
-        for (lo, hi), nb in zip(chunks, nblk):
-            ops.eval_lsq_partial(pred_chunk(lo, hi), on_device(gt, lo, hi), max_depth, work, row, nb)
-            row += nb
-        ops.eval_lsq_finish(work, row, fit)
-        for lo, hi in chunks:
-            ops.eval_metric_partial(pred_chunk(lo, hi), on_device(gt, lo, hi), max_depth, fit, work, lo, bpf)
+        pred_chunk, gt_chunk = _chunk_feeds(pred, gt, dev, (H, W))
+        _fit_scale_shift(ops, chunks, pred_chunk, gt_chunk, max_depth, work, fit)
+        for lo, hi, _ in chunks:
+            ops.eval_metric_partial(pred_chunk(lo, hi), gt_chunk(lo, hi), max_depth, fit, work, lo, bpf)
         ops.eval_metric_finish(work, N, bpf, res)
         host = out.cpu().numpy()                                        # the one device-to-host copy (synchronises)
     return _result(host[:3], host[3:])
@@ -318,21 +340,11 @@ def evaluate_tae(pred, gt, K, poses, max_depth, mask=None, device="cuda", chunk_
     import torch
     from . import ops
 
-    def as_tensor(a, name, dtypes):
-        if not isinstance(a, torch.Tensor):
-            a = torch.from_numpy(np.asarray(a))
-        if a.dtype not in dtypes:
-            raise ValueError(f"evaluate_tae: {name} must be {' or '.join(str(d) for d in dtypes)}, got {a.dtype}")
-        return a
-
-    pred = as_tensor(pred, "pred", (torch.float32,))
-    gt = as_tensor(gt, "gt", (torch.float32, torch.float64))
-    mask = None if mask is None else as_tensor(mask, "mask", (torch.bool, torch.uint8))
+    pred = _as_tensor(pred, "pred", (torch.float32,), "evaluate_tae")
+    gt = _as_tensor(gt, "gt", (torch.float32, torch.float64), "evaluate_tae")
+    mask = None if mask is None else _as_tensor(mask, "mask", (torch.bool, torch.uint8), "evaluate_tae")
     cam_host = _check_tae(pred, gt, K, poses, mask, resize)
-    on_dev = [t.device for t in (pred, gt, mask) if t is not None and t.is_cuda]
-    dev = on_dev[0] if on_dev else torch.device(device)
-    if dev.type != "cuda" or any(d != dev for d in on_dev):
-        raise ValueError(f"evaluate_tae: needs one cuda device, got {device!r} / {[str(d) for d in on_dev]}")
+    dev = _one_device((pred, gt, mask), device, "evaluate_tae")
     N, H, W = gt.shape
     px, P = H * W, N - 1
     if px >= 2 ** 31 - 1:
@@ -340,33 +352,22 @@ def evaluate_tae(pred, gt, K, poses, max_depth, mask=None, device="cuda", chunk_
     step = P if chunk_pairs is None else int(chunk_pairs)
     if step <= 0:
         raise ValueError("evaluate_tae: chunk_pairs must be positive")
-    fit_chunks = [(lo, min(lo + TAE_FIT_FRAMES, N)) for lo in range(0, N, TAE_FIT_FRAMES)]
-    nblk = [min(LSQ_MAX_BLOCKS, -(-(hi - lo) * px // EVAL_T)) for lo, hi in fit_chunks]
+    fit_chunks = _fit_chunks(N, TAE_FIT_FRAMES, px)
     bpp = min(TAE_MAX_BLOCKS, -(-px // TAE_PX_PER_BLOCK))
     max_depth = float(max_depth)
 
     with torch.cuda.device(dev):
-        work = torch.empty(max(5 * sum(nblk), 4 * P * bpp), dtype=torch.float64, device=dev)
+        work = torch.empty(max(5 * sum(nb for _, _, nb in fit_chunks), 4 * P * bpp), dtype=torch.float64, device=dev)
         out = torch.empty(3 + 1 + 4 * P, dtype=torch.float64, device=dev)       # fit {scale, shift, n_valid} | tae, errors, counts
         fit, res = out[:3], out[3:]
         cam = torch.from_numpy(cam_host).to(dev)
         winner = torch.empty((2 * min(step, P), H, W), dtype=torch.int32, device=dev)
-
-        def on_device(t, lo, hi):
-            return t[lo:hi].to(dev, non_blocking=False).contiguous()
-
-        def pred_chunk(lo, hi):                                                 # at gt's size: deterministic, the same bits every time
-            return resize_prediction(on_device(pred, lo, hi), (H, W))
-
-        row = 0
-        for (lo, hi), nb in zip(fit_chunks, nblk):
-            ops.eval_lsq_partial(pred_chunk(lo, hi), on_device(gt, lo, hi), max_depth, work, row, nb)
-            row += nb
-        ops.eval_lsq_finish(work, row, fit)
+        pred_chunk, gt_chunk = _chunk_feeds(pred, gt, dev, (H, W))
+        _fit_scale_shift(ops, fit_chunks, pred_chunk, gt_chunk, max_depth, work, fit)
         for lo in range(0, P, step):
             hi = min(lo + step, P)                                              # pairs lo .. hi-1 touch frames lo .. hi
             p = pred_chunk(lo, hi + 1)
-            m = None if mask is None else on_device(mask, lo, hi + 1).to(torch.uint8)
+            m = None if mask is None else mask[lo:hi + 1].to(dev).contiguous().to(torch.uint8)
             ops.tae_splat(p, max_depth, fit, cam[lo:hi], winner)
             ops.tae_compare(p, m, max_depth, fit, cam[lo:hi], winner, work, lo, bpp)
         ops.tae_finish(work, P, bpp, res)

@@ -26,6 +26,8 @@ CPU path. The contract is in DESIGN.md 6g; in short, with every float32 value wi
 """
 import numpy as np
 
+from .evaluate import _one_device
+
 VARIANTS = ("lsq", "mad")
 LOSS_T = 256                 # threads per block of the reductions (csrc/losses.hip LS_T)
 LOSS_MAX_BLOCKS = 64         # blocks per plane
@@ -183,12 +185,8 @@ def _device_inputs(pred, y, mask, device, what):
     import torch
 
     shape = _shape_checks(pred, y, mask, what)
-
     ts = [_as_tensor(pred), _as_tensor(y)] + ([] if mask is None else [_as_tensor(mask)])
-    on_dev = [t.device for t in ts if t.is_cuda]
-    dev = on_dev[0] if on_dev else torch.device(device)
-    if dev.type != "cuda" or any(d != dev for d in on_dev):
-        raise ValueError(f"{what}: needs one cuda device, got {device!r} / {[str(d) for d in on_dev]}")
+    dev = _one_device(ts, device, what)
     with torch.cuda.device(dev):
         ts = [t.detach().to(dev).reshape(shape).contiguous() for t in ts]
         m = None
