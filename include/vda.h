@@ -490,6 +490,33 @@ int vda_pointcloud_f32(const float* depth, const uint8_t* rgb, void* records, in
  * synchronisation, no atomics. */
 int vda_depth_vis_u8(const float* depth, long long n, const float* minmax, const uint8_t* lut, uint8_t* out, vda_stream_t stream);
 
+/* ---- frames as baseline JPEG scans, for a Motion-JPEG AVI (video_depth_anything_amd/mjpeg.py: encode_jpeg_numpy is the contract) ----
+ * frames: device uint8 [n,h,w,channels], channels 3 (RGB, coded as Y Cb Cr 4:4:4) or 1 (gray); any h, w in 1..65535, the right and
+ * bottom edges padded to a multiple of 8 by replicating the last column / row. All integer arithmetic (>> is the arithmetic shift):
+ *   Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16
+ *   Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16       Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16
+ *   s = sample - 128;  Ci[k][n] = rint(8192 c_k cos((2n+1) k pi / 16)), c_0 = sqrt(1/8), c_k = 1/2
+ *   t[k][x] = (sum_n Ci[k][n] s[n][x] + 128) >> 8;   F[k][l] = (sum_m Ci[l][m] t[k][m] + 16384) >> 15     (F = 8 x the coefficient)
+ *   q = sign(F) ((2 |F| + 8 Q) / (16 Q)), AC clamped to +-1023
+ * qtables: HOST uint16, 64 luminance divisors then (channels = 3) 64 chrominance divisors, natural row-major order, each 1..255.
+ * Entropy coding: baseline sequential with the four Huffman tables of ITU T.81 Annex K, zig-zag order, one MCU = the Y, Cb, Cr
+ * blocks of one 8x8 tile, ONE RESTART INTERVAL PER MCU ROW (DRI = ceil(w / 8)): DC predictors reset, the interval's last byte
+ * padded with 1-bits, FF -> FF 00, RSTm (m cycling 0..7) between intervals, EOI behind the last. out: the n scans back to back,
+ * frame i at the sum of lengths[0 .. i), lengths[i] (device int64) bytes long, EOI included; a complete JPEG is the header
+ * (SOI, APP0, DQT, SOF0, DHT, DRI, SOS: mjpeg.jpeg_header) followed by that slice. Deterministic: the bits of neighbouring
+ * blocks meet in shared words through integer OR-atomics only, and the lengths are integer sums.
+ * A block's bits are at most 64 * 26 before stuffing and twice that after, so with bh = ceil(h / 8), nb = ceil(w / 8) * channels
+ *   vda_mjpeg_out_bytes       = n * (bh * (nb * 416 + 2) + 2)             the capacity `out` needs; the encoder never truncates
+ *   vda_mjpeg_workspace_bytes = n * bh * nb * (128 + 208 + 416) + the two length tables      device bytes, contents irrelevant
+ * (both 0 for a size < 1 or > 65535 or channels outside {1, 3}). Refused before any launch: a null frames, qtables, workspace,
+ * out or lengths; n, h or w < 1; h or w > 65535; channels not 1 or 3; a table entry outside 1..255; more than 2^31 - 1
+ * workgroups; a frame whose bound does not fit an int; workspace not 16-byte or lengths not 8-byte aligned; workspace_bytes or
+ * out_capacity below the bound. Three launches on `stream` (transform, entropy, pack), no allocation, no synchronisation. */
+size_t vda_mjpeg_workspace_bytes(int n, int h, int w, int channels);
+size_t vda_mjpeg_out_bytes(int n, int h, int w, int channels);
+int vda_mjpeg_encode_u8(const uint8_t* frames, int n, int h, int w, int channels, const uint16_t* qtables, void* workspace,
+                        size_t workspace_bytes, uint8_t* out, size_t out_capacity, long long* lengths, vda_stream_t stream);
+
 /* ---- validation losses on the device (the reference's utils/loss_MiDas.py and utils/loss.py: Loss_ssi, Loss_tgm) ---------------
  * What train.py's validation pass ranks checkpoints by, as inference-time arithmetic (no gradients). pred, y: dense fp32
  * [nframes, px] (nframes = B * N, px = H * W); mask: bytes of the same shape, 0 = excluded, or NULL for all valid. Every fp32

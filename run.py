@@ -3,7 +3,8 @@
 
 Frame I/O is utils/dc_utils.py (same two helpers as the reference's): `--input_video` may be an .npy / .npz (key `frames`)
 of uint8 [N,H,W,3] RGB frames, a directory of images, a GIF, or a video file when decord or cv2 is importable; the
-visualisations are mp4 through imageio when present and animated GIFs otherwise; `--save_npz` adds <name>_depths.npz.
+visualisations are mp4 through imageio when present and animated GIFs otherwise, or with `--mjpeg` Motion-JPEG .avi files that
+need no encoder library (the JPEG coding runs on the device too, csrc/mjpeg.hip); `--save_npz` adds <name>_depths.npz.
 <name>_vis carries the reference's colours: depth is mapped through matplotlib's 256-entry inferno table, which ships in
 video_depth_anything_amd/visualize.py (not through the polynomial fit utils/dc_utils.py keeps as save_video's default), and on a
 GPU the mapping itself runs on the device (csrc/visualize.hip) - the same bytes as on the host.
@@ -85,6 +86,8 @@ if __name__ == '__main__':
     parser.add_argument('--save_exr', action='store_true', help='save depths as exr')
     parser.add_argument('--metric', action='store_true', help='metric-depth checkpoint and stitching (metric_depth/run.py)')
     parser.add_argument('--stream', action='store_true', help='bounded memory: infer_video_depth_stream, depths written to <name>_depths.npy piece by piece')
+    parser.add_argument('--mjpeg', action='store_true', help='write <name>_src.avi / <name>_vis.avi (Motion-JPEG, no encoder library) instead of mp4 / GIF')
+    parser.add_argument('--mjpeg_quality', type=int, default=90, help='JPEG quality of --mjpeg, 1..100')
     parser.add_argument('--checkpoint', type=str, default=None, help='override ./checkpoints/<name>.pth; "synthetic" = seeded random weights')
     args = parser.parse_args()
 
@@ -119,9 +122,11 @@ if __name__ == '__main__':
         depths, fps = video_depth_anything.infer_video_depth(frames, target_fps, input_size=args.input_size, device=DEVICE, fp32=args.fp32)
 
     # run.py:57-62: <name>_src.mp4 and <name>_vis.mp4 (GIFs when no H.264 encoder is importable)
-    src_path = save_video(frames, stem + '_src.mp4', fps=fps)
+    vis_device = DEVICE if DEVICE == 'cuda' else None
+    codec = dict(codec='mjpeg', quality=args.mjpeg_quality) if args.mjpeg else {}      # <name>_src.avi / <name>_vis.avi then
+    src_path = save_video(frames, stem + '_src.mp4', fps=fps, device=vis_device if args.mjpeg else None, **codec)
     vis_path = save_video(depths, stem + '_vis.mp4', fps=fps, is_depths=True, grayscale=args.grayscale, palette=inferno_table(),
-                          device=DEVICE if DEVICE == 'cuda' else None, **d_range)
+                          device=vis_device, **d_range, **codec)
     if args.save_npz:
         np.savez_compressed(stem + '_depths.npz', depths=depths)
     if args.save_exr:

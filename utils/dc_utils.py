@@ -5,8 +5,10 @@ Not on the accelerated path. The reference decodes
 imageio-ffmpeg; none of those exist offline, so each is used when importable and otherwise replaced by what the image has:
 
   read_video_frames: .npy / .npz (`frames`, optional `fps`), a directory of still images, or any multi-frame file PIL opens
-                     (GIF, APNG, TIFF); a video file needs decord or cv2.
-  save_video       : mp4 through imageio when present, else an animated GIF (PIL) next to the requested name.
+                     (GIF, APNG, TIFF); a video file needs decord or cv2 - except the Motion-JPEG .avi that save_video writes,
+                     which is read here (mjpeg.read_avi + PIL) when neither is importable.
+  save_video       : mp4 through imageio when present, else an animated GIF (PIL) next to the requested name; with
+                     codec="mjpeg" a Motion-JPEG .avi that needs neither (video_depth_anything_amd/mjpeg.py).
 
 Frames larger than `max_res` are scaled like the reference's cv2 branch (round(size * max_res / max(h, w)), bilinear, half-pixel
 centres, no antialiasing = cv2.INTER_LINEAR's definition); cv2 is not here to pin that bit for bit.
@@ -58,6 +60,11 @@ def _decode(video_path):
     try:
         import cv2
     except ImportError as e:
+        if ext == ".avi":                                  # what save_video(codec="mjpeg") writes: the container is read here, the frames by PIL
+            from video_depth_anything_amd import mjpeg
+            if mjpeg.is_mjpeg_avi(video_path):
+                jpegs, fps, _, _ = mjpeg.read_avi(video_path)
+                return mjpeg.decode_jpegs(jpegs), fps
         raise RuntimeError(f"cannot decode {video_path}: neither decord nor cv2 is importable here; "
                            "pass frames as .npy / .npz, a directory of images or a GIF") from e
     cap = cv2.VideoCapture(video_path)
@@ -118,7 +125,8 @@ def _inferno(u8):
 SAVE_BLOCK = 32                                        # frames mapped to uint8 / colour at a time by save_video
 
 
-def save_video(frames, output_video_path, fps=10, is_depths=False, grayscale=False, d_min=None, d_max=None, palette=None, device=None):
+def save_video(frames, output_video_path, fps=10, is_depths=False, grayscale=False, d_min=None, d_max=None, palette=None, device=None,
+               codec=None, quality=90):
     """dc_utils.py:73-88. Depth is mapped through its GLOBAL min / max to uint8 (then a colour map unless `grayscale`).
     Returns the path written (the reference returns None): the .mp4 asked for, or a .gif when there is no encoder.
     Works SAVE_BLOCK frames at a time and hands each frame to the writer as it is mapped, so `frames` may be a memory map of a video
@@ -129,7 +137,14 @@ def save_video(frames, output_video_path, fps=10, is_depths=False, grayscale=Fal
     palette = uint8 [256,3] indexes that table instead - video_depth_anything_amd.visualize.inferno_table() is the reference's own
     (the contract of visualize.colorize_numpy, which adds a clamp for NaN / out-of-range pixels and treats a range
     narrower than 1e-12 as it is rather than as 1e-12). device = a cuda device maps each block on the GPU (visualize.colorize,
-    csrc/visualize.hip): the same bytes as the host path for the same palette (None = inferno_table() then)."""
+    csrc/visualize.hip): the same bytes as the host path for the same palette (None = inferno_table() then).
+    codec: None is all of the above. "mjpeg" writes <stem>.avi instead, Motion-JPEG at `quality` (1..100) in an AVI container
+    (video_depth_anything_amd.mjpeg), with no encoder library: each mapped block is coded by encode_jpeg_numpy, or
+    with `device` by csrc/mjpeg.hip - the block is uploaded once, colour-mapped and coded on the device, and only the compressed
+    bytes come back; the file is the same, byte for byte, either way. Source frames (is_depths=False) and gray depth take the
+    same route."""
+    if codec not in (None, "mjpeg"):
+        raise ValueError(f"save_video: codec must be None or 'mjpeg', got {codec!r}")
     if not isinstance(frames, np.ndarray):
         frames = np.asarray(frames)
     n = frames.shape[0]
@@ -146,17 +161,38 @@ def save_video(frames, output_video_path, fps=10, is_depths=False, grayscale=Fal
         from video_depth_anything_amd import visualize
         to_bytes = visualize.colorize_numpy if device is None else visualize.colorize
 
+    def mapped_block(b):
+        if table_path:
+            return to_bytes(frames[b], d_min, d_max, grayscale, palette, device)
+        if is_depths:
+            norm = ((frames[b] - d_min) / span * 255).astype(np.uint8)
+            return norm if grayscale else _inferno(norm)
+        return frames[b]
+
     def mapped():
         for b in blocks:
-            if table_path:
-                vis = to_bytes(frames[b], d_min, d_max, grayscale, palette, device)
-            elif is_depths:
-                norm = ((frames[b] - d_min) / span * 255).astype(np.uint8)
-                vis = norm if grayscale else _inferno(norm)
-            else:
-                vis = frames[b]
-            for f in vis:
+            for f in mapped_block(b):
                 yield f
+
+    if codec == "mjpeg":
+        from video_depth_anything_amd import mjpeg
+        path = os.path.splitext(output_video_path)[0] + ".avi"
+        h, w = frames.shape[1:3]
+
+        def jpegs():
+            for b in blocks:
+                if device is None:
+                    yield from mjpeg.encode_jpeg_numpy(np.ascontiguousarray(mapped_block(b)), quality)
+                else:
+                    import torch
+                    x = torch.from_numpy(np.array(frames[b])).to(device)                 # the only upload: depth or source frames
+                    if is_depths:
+                        x = visualize.colorize(x, d_min, d_max, grayscale, palette)
+                    payload, lengths = mjpeg.encode_jpeg(x, quality)
+                    yield from mjpeg.split_payload(mjpeg.jpeg_header(h, w, 3 if x.dim() == 4 else 1, quality), payload, lengths)
+
+        mjpeg.write_avi(path, jpegs(), fps, w, h)
+        return path
 
     try:
         import imageio

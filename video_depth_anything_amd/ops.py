@@ -504,6 +504,35 @@ def depth_vis(depth, minmax, lut, out, n=None):
     check(lib.vda_depth_vis_u8(_p(depth), n, _p(minmax), _p(lut), _p(out), _stream(depth)), "vda_depth_vis_u8")
 
 
+# ---- frames as baseline JPEG scans (csrc/mjpeg.hip; mjpeg.py is the contract and owns the header and the container) ------------
+def mjpeg_workspace_bytes(n, h, w, channels):
+    return int(lib.vda_mjpeg_workspace_bytes(n, h, w, channels))
+
+
+def mjpeg_out_bytes(n, h, w, channels):
+    """The capacity mjpeg_encode's `out` needs for n frames: no stream of that shape is longer."""
+    return int(lib.vda_mjpeg_out_bytes(n, h, w, channels))
+
+
+def mjpeg_encode(frames, qtables, workspace, out, lengths):
+    """out (device uint8) = the JPEG scans (entropy-coded data + EOI) of frames (device uint8 [n,h,w,3] RGB or [n,h,w] gray) back
+    to back, lengths (device int64 [n]) their sizes: include/vda.h. qtables: HOST numpy uint16 [2,64] ([1,64] for gray), natural order."""
+    import numpy as np
+    _req(frames, torch.uint8, "frames"), _req(workspace, torch.uint8, "workspace"), _req(out, torch.uint8, "out"), _req(lengths, torch.int64, "lengths")
+    if frames.dim() not in (3, 4) or (frames.dim() == 4 and frames.shape[3] != 3) or frames.numel() == 0:
+        raise ValueError(f"mjpeg_encode: frames must be [n,h,w,3] or [n,h,w] and not empty, got {tuple(frames.shape)}")
+    n, h, w = frames.shape[:3]
+    ch = 3 if frames.dim() == 4 else 1
+    if not isinstance(qtables, np.ndarray) or qtables.dtype != np.uint16 or qtables.size != 64 * (2 if ch == 3 else 1) or not qtables.flags.c_contiguous:
+        raise ValueError(f"mjpeg_encode: qtables must be a contiguous host uint16 array of {64 * (2 if ch == 3 else 1)} entries")
+    if lengths.numel() < n:
+        raise ValueError(f"mjpeg_encode: lengths holds {lengths.numel()} entries, needs {n}")
+    if len({t.device for t in (frames, workspace, out, lengths)}) != 1:
+        raise ValueError("mjpeg_encode: the operands live on different devices")
+    check(lib.vda_mjpeg_encode_u8(_p(frames), n, h, w, ch, qtables.ctypes.data_as(C.c_void_p), _p(workspace), workspace.numel(), _p(out), out.numel(),
+                                  _p(lengths), _stream(frames)), "vda_mjpeg_encode_u8")
+
+
 # ---- validation losses (csrc/losses.hip; losses.py lays the buffers out) --------------------------------------------------------
 LOSS_STATS = 8               # doubles per frame in `stats` (include/vda.h)
 
