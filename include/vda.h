@@ -517,6 +517,35 @@ size_t vda_mjpeg_out_bytes(int n, int h, int w, int channels);
 int vda_mjpeg_encode_u8(const uint8_t* frames, int n, int h, int w, int channels, const uint16_t* qtables, void* workspace,
                         size_t workspace_bytes, uint8_t* out, size_t out_capacity, long long* lengths, vda_stream_t stream);
 
+/* ---- baseline JPEG scans back to pixels (video_depth_anything_amd/mjpeg.py: decode_jpeg_numpy is the contract) -------------------
+ * n frames of one geometry and one set of tables: h x w in 1..65535, components 1 (gray) or 3 (Y Cb Cr) with luma sampling
+ * hs x vs = 1x1, 2x1 or 2x2 over 1x1 chroma (4:4:4, 4:2:2, 4:2:0). The caller has parsed the headers and cut the scans at their
+ * restart markers (mjpeg.parse_jpeg, mjpeg.device_call_inputs):
+ *   scan       device bytes, the frames' entropy-coded data back to back (scan_bytes of them, at most 2^31 - 16)
+ *   intervals  HOST int [n_intervals][5]: frame, byte offset into scan, byte length, first MCU, MCU count - validated here, before
+ *              any launch: the frame in [0, n), the bytes inside scan_bytes, the MCUs inside the frame; then copied to the device
+ *   tables     HOST, one MjdTables record of csrc/mjpeg_decode_core.h (mjpeg.decode_tables): per component its DC and AC Huffman
+ *              table, and the zig-zag order; the decoder masks every index it takes from them
+ *   qtables    HOST uint16 [components][64], natural row-major order, each 1..255
+ * out: device uint8 [n,h,w,3] RGB or [n,h,w]; status: device int [n], 0 = decoded, otherwise the largest error code of the frame's
+ * intervals (MJD_* of mjpeg_decode_core.h, mjpeg.DECODE_STATUS) - such a frame's pixels are defined (the coefficients decoded
+ * before the error, zeros behind it) but mean nothing. All integer arithmetic that wraps; libjpeg's islow IDCT, fancy upsampling
+ * and 16-bit fixed-point colour conversion: bit for bit the twin, for corrupt scans too. No input, however
+ * malformed, is read outside its interval's bytes or written outside its MCUs' blocks.
+ *   vda_mjpeg_decode_workspace_bytes = the interval table + the tables + 192 bytes per 8x8 block (int16 coefficients, uint8 planes);
+ *   0 for a size < 1 or > 65535, components outside {1, 3}, a sampling other than the above or intervals < 0.
+ * Refused before any launch, each by its own message: a null pointer; n, h or w < 1; h or w > 65535; components; sampling;
+ * scan_bytes > 2^31 - 16; n_intervals < 1; more than 2^31 - 1 workgroups; workspace not 16-byte or status not 4-byte aligned;
+ * workspace_bytes or out_capacity below the bound; a table entry outside 1..255; a bad interval. Two small copies, two memsets
+ * and three launches on `stream` (entropy: a lane per interval; IDCT; upsample + colour), no allocation. NOT free of host
+ * synchronisation: the interval table and the tables are copied from the caller's pageable host memory, which hipMemcpyAsync does
+ * synchronously through a staging buffer, so the call waits on the host until those two copies (and what `stream` holds before
+ * them) are done, the host arrays may be freed when it returns, and the call cannot be captured into a graph. */
+size_t vda_mjpeg_decode_workspace_bytes(int n, int h, int w, int components, int hs, int vs, int intervals);
+int vda_mjpeg_decode_u8(const uint8_t* scan, size_t scan_bytes, const int* intervals, int n_intervals, const void* tables,
+                        const uint16_t* qtables, int n, int h, int w, int components, int hs, int vs, void* workspace,
+                        size_t workspace_bytes, uint8_t* out, size_t out_capacity, int* status, vda_stream_t stream);
+
 /* ---- validation losses on the device (the reference's utils/loss_MiDas.py and utils/loss.py: Loss_ssi, Loss_tgm) ---------------
  * What train.py's validation pass ranks checkpoints by, as inference-time arithmetic (no gradients). pred, y: dense fp32
  * [nframes, px] (nframes = B * N, px = H * W); mask: bytes of the same shape, 0 = excluded, or NULL for all valid. Every fp32

@@ -2,7 +2,8 @@
 """CLI with the reference's flags and defaults (/root/reference/run.py:24-34) over the MI355X engine.
 
 Frame I/O is utils/dc_utils.py (same two helpers as the reference's): `--input_video` may be an .npy / .npz (key `frames`)
-of uint8 [N,H,W,3] RGB frames, a directory of images, a GIF, or a video file when decord or cv2 is importable; the
+of uint8 [N,H,W,3] RGB frames, a directory of images, a GIF, a Motion-JPEG .avi (decoded on the device, csrc/mjpeg_decode.hip; with
+`--stream` a window's frames at a time, so a long .avi runs in bounded memory), or a video file when decord or cv2 is importable; the
 visualisations are mp4 through imageio when present and animated GIFs otherwise, or with `--mjpeg` Motion-JPEG .avi files that
 need no encoder library (the JPEG coding runs on the device too, csrc/mjpeg.hip); `--save_npz` adds <name>_depths.npz.
 <name>_vis carries the reference's colours: depth is mapped through matplotlib's 256-entry inferno table, which ships in
@@ -14,6 +15,7 @@ piece into <name>_depths.npy on disk and the visualisation is made from that fil
 depth is ever held in memory as one array.
 """
 import argparse
+import itertools
 import os
 import struct
 
@@ -21,6 +23,7 @@ import numpy as np
 import torch
 
 from utils.dc_utils import read_video_frames, save_video
+from video_depth_anything_amd import mjpeg
 from video_depth_anything_amd.visualize import inferno_table
 from video_depth_anything_amd.video_depth import MetricVideoDepthAnything, VideoDepthAnything
 
@@ -71,6 +74,18 @@ def write_depth_stream(stream, path, n_frames=None):
     return np.load(path, mmap_mode="r")
 
 
+def limit_frames(blocks, max_len):
+    """The [m,...] blocks of an iterable cut to `max_len` frames in all (no limit when it is not positive)."""
+    left = max_len
+    for b in blocks:
+        if max_len > 0:
+            if left <= 0:
+                return
+            b = b[:left]
+            left -= len(b)
+        yield b
+
+
 if __name__ == '__main__':
     parser = argparse.ArgumentParser(description='Video Depth Anything (MI355X)')
     parser.add_argument('--input_video', type=str, default='./assets/example_videos/davis_rollercoaster.mp4')
@@ -108,7 +123,19 @@ if __name__ == '__main__':
     video_depth_anything.load_state_dict(sd, strict=True)
     video_depth_anything = video_depth_anything.to(DEVICE).eval()
 
-    frames, target_fps = read_video_frames(args.input_video, args.max_len, args.target_fps, args.max_res)   # run.py:53
+    # A Motion-JPEG .avi is decoded on the device (csrc/mjpeg_decode.hip) instead of by decord / cv2 / PIL. With --stream, and when
+    # no frame has to be dropped or scaled, it is never read as a whole: avi_frame_blocks decodes it a window's frames at a time.
+    mjpeg_in = DEVICE == 'cuda' and args.input_video.lower().endswith('.avi') and os.path.isfile(args.input_video) and mjpeg.is_mjpeg_avi(args.input_video)
+    avi_blocks = None
+    if mjpeg_in and args.stream and args.target_fps < 0:
+        src_fps, src_w, src_h = next(mjpeg.iter_avi(args.input_video))
+        if not (args.max_res > 0 and max(src_w, src_h) > args.max_res):
+            avi_blocks = limit_frames(mjpeg.avi_frame_blocks(args.input_video, device=DEVICE), args.max_len)
+    if avi_blocks is not None:
+        frames, target_fps = avi_blocks, src_fps
+    else:
+        frames, target_fps = read_video_frames(args.input_video, args.max_len, args.target_fps, args.max_res,
+                                               device=DEVICE if mjpeg_in else None)                        # run.py:53
     video_name = os.path.basename(args.input_video)
     os.makedirs(args.output_dir, exist_ok=True)
     stem = os.path.join(args.output_dir, os.path.splitext(video_name)[0])
@@ -118,13 +145,24 @@ if __name__ == '__main__':
         depths = write_depth_stream(stream, stem + '_depths.npy', len(frames) if isinstance(frames, np.ndarray) else None)
         fps = stream.fps
         d_range = dict(d_min=stream.depth_min, d_max=stream.depth_max)      # the stream kept the range: no second pass over the file
+        if avi_blocks is not None:
+            # <name>_src shows the source frames: --mjpeg copies the source's own JPEGs (nothing is decoded or held), otherwise
+            # the file is decoded once more, now as a whole, for the mp4 / GIF writer
+            if args.mjpeg:
+                jpegs = mjpeg.iter_avi(args.input_video)
+                next(jpegs)                                                  # (fps, width, height)
+                mjpeg.write_avi(stem + '_src.avi', itertools.islice(jpegs, args.max_len if args.max_len > 0 else None), fps, src_w, src_h)
+                frames = None
+            else:
+                frames = read_video_frames(args.input_video, args.max_len, args.target_fps, args.max_res, device=DEVICE)[0]
     else:
         depths, fps = video_depth_anything.infer_video_depth(frames, target_fps, input_size=args.input_size, device=DEVICE, fp32=args.fp32)
 
     # run.py:57-62: <name>_src.mp4 and <name>_vis.mp4 (GIFs when no H.264 encoder is importable)
     vis_device = DEVICE if DEVICE == 'cuda' else None
     codec = dict(codec='mjpeg', quality=args.mjpeg_quality) if args.mjpeg else {}      # <name>_src.avi / <name>_vis.avi then
-    src_path = save_video(frames, stem + '_src.mp4', fps=fps, device=vis_device if args.mjpeg else None, **codec)
+    if frames is not None:
+        src_path = save_video(frames, stem + '_src.mp4', fps=fps, device=vis_device if args.mjpeg else None, **codec)
     vis_path = save_video(depths, stem + '_vis.mp4', fps=fps, is_depths=True, grayscale=args.grayscale, palette=inferno_table(),
                           device=vis_device, **d_range, **codec)
     if args.save_npz:

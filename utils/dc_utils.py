@@ -5,8 +5,9 @@ Not on the accelerated path. The reference decodes
 imageio-ffmpeg; none of those exist offline, so each is used when importable and otherwise replaced by what the image has:
 
   read_video_frames: .npy / .npz (`frames`, optional `fps`), a directory of still images, or any multi-frame file PIL opens
-                     (GIF, APNG, TIFF); a video file needs decord or cv2 - except the Motion-JPEG .avi that save_video writes,
-                     which is read here (mjpeg.read_avi + PIL) when neither is importable.
+                     (GIF, APNG, TIFF); a video file needs decord or cv2 - except a Motion-JPEG .avi (what save_video writes,
+                     webcams, `ffmpeg -c:v mjpeg`): with `device` it is decoded on the GPU (mjpeg.decode_jpeg), without it
+                     it is read here (mjpeg.read_avi + PIL) when neither decord nor cv2 is importable.
   save_video       : mp4 through imageio when present, else an animated GIF (PIL) next to the requested name; with
                      codec="mjpeg" a Motion-JPEG .avi that needs neither (video_depth_anything_amd/mjpeg.py).
 
@@ -27,9 +28,15 @@ def _resize_bilinear(frames, height, width):
     return y.round().clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous().numpy()
 
 
-def _decode(video_path):
-    """-> (uint8 [N,H,W,3] RGB, source fps)"""
+def _decode(video_path, device=None):
+    """-> (uint8 [N,H,W,3] RGB, source fps). device: a cuda device decodes a Motion-JPEG .avi there (mjpeg.decode_jpeg, block by
+    block) before decord or cv2 are tried; None changes nothing."""
     ext = os.path.splitext(video_path)[1].lower()
+    if device is not None and ext == ".avi" and os.path.isfile(video_path):
+        from video_depth_anything_amd import mjpeg
+        if mjpeg.is_mjpeg_avi(video_path):
+            fps = next(mjpeg.iter_avi(video_path))[0]
+            return np.concatenate(list(mjpeg.avi_frame_blocks(video_path, device=device, block=SAVE_BLOCK))), fps
     if os.path.isdir(video_path):
         from PIL import Image
         names = sorted(n for n in os.listdir(video_path) if n.lower().endswith(IMAGE_EXT + (".npy",)))
@@ -79,10 +86,11 @@ def _decode(video_path):
     return np.stack(out), float(fps)
 
 
-def read_video_frames(video_path, process_length, target_fps=-1, max_res=-1):
+def read_video_frames(video_path, process_length, target_fps=-1, max_res=-1, device=None):
     """dc_utils.py:18-70: every `stride`-th frame (stride = max(round(src_fps / fps), 1)), at most `process_length`
-    frames read, frames larger than `max_res` scaled down. Returns (uint8 [N,H,W,3], fps)."""
-    frames, src_fps = _decode(video_path)
+    frames read, frames larger than `max_res` scaled down. Returns (uint8 [N,H,W,3], fps). device (not in the reference): a cuda
+    device on which a Motion-JPEG .avi is decoded (csrc/mjpeg_decode.hip); every other input, and None, go the way they always went."""
+    frames, src_fps = _decode(video_path, device)
     if not isinstance(frames, np.ndarray):
         frames = np.asarray(frames)
     if frames.ndim != 4 or frames.shape[-1] != 3:

@@ -25,7 +25,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=f
 # contract counts every rounding (a*b + c*d as three). pointcloud.hip restates numpy's fp64 (x - cx) / fx * z: the division and
 # the product are each rounded once. visualize.hip restates numpy's float32 (d - d_min) / span * 255: three roundings.
 # losses.hip restates torch's fp64 s * d + t - y (three roundings) and its centred sums.
-# (mjpeg.hip, the JPEG encoder, is integer arithmetic from end to end: it reproduces its host twin under the default flags.)
+# (mjpeg.hip and mjpeg_decode.hip, the JPEG encoder and decoder, are integer arithmetic from end to end: they reproduce their host
+# twins under the default flags.)
 PER_FILE = {"stitch.hip": ["-ffp-contract=off"], "eval.hip": ["-ffp-contract=off"], "tae.hip": ["-ffp-contract=off"],
             "resize.hip": ["-ffp-contract=off"], "pointcloud.hip": ["-ffp-contract=off"], "visualize.hip": ["-ffp-contract=off"],
             "losses.hip": ["-ffp-contract=off"]}

@@ -417,3 +417,581 @@ def decode_jpegs(jpegs):
 
     from PIL import Image
     return np.stack([np.asarray(Image.open(io.BytesIO(j)).convert("RGB")) for j in jpegs])
+
+
+# ------------------------------------------------------------------------------------------------------------------ the decoder
+# Baseline JPEG back to pixels. `decode_jpeg_numpy` is the contract: the entropy decoder is the loop of
+# csrc/mjpeg_decode_core.h restated in Python, and every later step is int32 arithmetic that wraps, so the device
+# (csrc/mjpeg_decode.hip) reproduces it bit for bit - for corrupt streams too, whose frames end in a status instead of pixels.
+#
+#   parse      SOI, APPn / COM (skipped), DQT (8-bit), SOF0 (8-bit, 1 or 3 components; luma 1x1, 2x1 or 2x2 over 1x1 chroma), DHT,
+#              DRI, one interleaved SOS (Ss = 0, Se = 63, Ah = Al = 0). A frame without DHT gets the Annex K tables (the AVI MJPG
+#              convention). Anything else raises UnsupportedJpeg naming what was found.
+#   entropy    the scan is cut at FF D0..D7 (the RSTm numbers are not trusted); interval i holds MCUs [i DRI, (i + 1) DRI); FF xx
+#              inside an interval is the byte FF; canonical codes, EXTEND of T.81 F.2.2.1; DC predictors start at 0 per interval;
+#              coefficients are int16 at natural positions; an error ends the interval and gives the frame a status (the largest
+#              code of its intervals; DECODE_STATUS has the names).
+#   pixels     d = coef * Q; libjpeg's `islow` IDCT (CONST_BITS 13, PASS1_BITS 2; columns descaled by 11, rows by 18, + 128,
+#              clamped); chroma cropped to ceil(W / 2) (x ceil(H / 2)) and upsampled by libjpeg's "fancy" triangle filters with
+#              replicated edges; R = Y + ((91881 cr + 32768) >> 16), G = Y + ((-22554 cb - 46802 cr + 32768) >> 16),
+#              B = Y + ((116130 cb + 32768) >> 16), clamped.
+# These are the pixels of PIL (libjpeg-turbo) byte for byte when the frame is at least 5 pixels wide; with subsampled chroma and
+# W <= 4, H >= 2 libjpeg-turbo's upsampler takes another edge path (tests/golden/mjpeg_decode_streams.npz has no such frame).
+class UnsupportedJpeg(ValueError):
+    """A JPEG this decoder does not read (progressive, 12-bit, CMYK, other sampling, ...): callers fall back to PIL."""
+
+
+DECODE_STATUS = {0: "ok", 1: "code not in the Huffman table", 2: "DC category above 11 or AC size above 10", 3: "run past coefficient 63",
+                 4: "interval ends before its MCUs are decoded", 5: "wrong number of restart intervals", 6: "DC predictor outside int16",
+                 7: "scan is not ended by EOI"}
+_ST_CODE, _ST_SIZE, _ST_RUN, _ST_SHORT, _ST_COUNT, _ST_DC, _ST_EOI = 1, 2, 3, 4, 5, 6, 7
+_ANNEX_K_DC = ((_DC_L_BITS, _DC_VALS), (_DC_C_BITS, _DC_VALS))
+_ANNEX_K_AC = ((_AC_L_BITS, _AC_L_VALS), (_AC_C_BITS, _AC_C_VALS))
+HUFF_DTYPE = np.dtype([("look", "<u2", 256), ("maxcode", "<i4", 18), ("valoff", "<i4", 18), ("vals", "u1", 256)])     # MjdHuff, 912 bytes
+TABLES_DTYPE = np.dtype([("dc", HUFF_DTYPE, 3), ("ac", HUFF_DTYPE, 3), ("zigzag", "u1", 64)])                         # MjdTables
+
+
+class JpegInfo:
+    """What parse_jpeg found: height, width, components, hs / vs (luma sampling), qtables uint16 [components, 64] in natural
+    order, dc / ac: per component its (bits, vals), dri, scan_offset (the first byte behind SOS), header (the bytes before it)."""
+    __slots__ = ("height", "width", "components", "hs", "vs", "qtables", "dc", "ac", "dri", "scan_offset", "header")
+
+    @property
+    def mcus(self):
+        return -(-self.width // (8 * self.hs)), -(-self.height // (8 * self.vs))       # across, down
+
+    @property
+    def geometry(self):
+        """(comp_off, comp_bw, frame_blocks): each component's block grid within a frame's coefficients (MjdGeom)."""
+        mw, mh = self.mcus
+        off, bw, at = [0, 0, 0], [0, 0, 0], 0
+        for c in range(self.components):
+            hc, vc = (self.hs, self.vs) if c == 0 else (1, 1)
+            off[c], bw[c] = at, mw * hc
+            at += mw * hc * mh * vc
+        return off, bw, at
+
+
+def _huff_decode_table(bits, vals):
+    """One MjdHuff record from a DHT's 16 counts and its values."""
+    bits, vals = [int(b) for b in bits], bytes(vals)
+    if sum(bits) > 256 or len(vals) < sum(bits):
+        raise UnsupportedJpeg(f"mjpeg: a DHT table counts {sum(bits)} codes for {len(vals)} values")
+    t = np.zeros((), HUFF_DTYPE)
+    t["maxcode"][:] = -1
+    t["vals"][:len(vals[:256])] = np.frombuffer(vals[:256], np.uint8)
+    code, k = 0, 0
+    for ln in range(1, 17):
+        nb = bits[ln - 1]
+        if code + nb > (1 << ln):
+            raise UnsupportedJpeg(f"mjpeg: a DHT table has more codes of length {ln} than the code space holds")
+        if nb:
+            t["valoff"][ln], t["maxcode"][ln] = k - code, code + nb - 1
+            if ln <= 8:
+                for i in range(nb):
+                    t["look"][(code + i) << (8 - ln):(code + i + 1) << (8 - ln)] = (ln << 8) | vals[k + i]
+        code, k = (code + nb) << 1, k + nb
+    return t
+
+
+def parse_jpeg(data):
+    """JpegInfo of one baseline JPEG; UnsupportedJpeg (a ValueError) names what this decoder does not read."""
+    data = bytes(data)
+    if data[:2] != b"\xff\xd8":
+        raise UnsupportedJpeg("mjpeg: no SOI at the start")
+    info = JpegInfo()
+    info.dri = 0
+    qt, dht, sof, p = {}, {}, None, 2
+    while True:
+        if p + 4 > len(data):
+            raise UnsupportedJpeg("mjpeg: the header ends before SOS")
+        if data[p] != 0xFF:
+            raise UnsupportedJpeg(f"mjpeg: byte {data[p]:#04x} at {p} where a marker should be")
+        m = data[p + 1]
+        if m == 0xFF:                                                                      # a fill byte
+            p += 1
+            continue
+        ln = struct.unpack_from(">H", data, p + 2)[0]
+        seg = data[p + 4:p + 2 + ln]
+        if ln < 2 or p + 2 + ln > len(data):
+            raise UnsupportedJpeg(f"mjpeg: segment {m:#04x} at {p} runs past the end")
+        p += 2 + ln
+        if 0xE0 <= m <= 0xEF or m == 0xFE:
+            continue
+        if m == 0xDB:
+            s = 0
+            while s < len(seg):
+                if seg[s] >> 4:
+                    raise UnsupportedJpeg("mjpeg: 16-bit DQT table")
+                if (seg[s] & 15) > 3 or s + 65 > len(seg):
+                    raise UnsupportedJpeg("mjpeg: bad DQT segment")
+                t = np.zeros(64, np.uint16)
+                t[ZIGZAG] = np.frombuffer(seg[s + 1:s + 65], np.uint8)
+                qt[seg[s] & 15] = t
+                s += 65
+        elif m == 0xC4:
+            s = 0
+            while s < len(seg):
+                if s + 17 > len(seg) or (seg[s] >> 4) > 1 or (seg[s] & 15) > 3:
+                    raise UnsupportedJpeg("mjpeg: bad DHT segment")
+                bits = tuple(seg[s + 1:s + 17])
+                if s + 17 + sum(bits) > len(seg):
+                    raise UnsupportedJpeg("mjpeg: bad DHT segment")
+                dht[seg[s]] = (bits, seg[s + 17:s + 17 + sum(bits)])
+                s += 17 + sum(bits)
+        elif m == 0xC0:
+            if sof is not None or len(seg) < 6:
+                raise UnsupportedJpeg("mjpeg: bad or second SOF0")
+            prec, h, w, nc = struct.unpack_from(">BHHB", seg)
+            if prec != 8:
+                raise UnsupportedJpeg(f"mjpeg: {prec}-bit samples")
+            if nc not in (1, 3):
+                raise UnsupportedJpeg(f"mjpeg: {nc} components")
+            if h < 1 or w < 1 or len(seg) < 6 + 3 * nc:
+                raise UnsupportedJpeg(f"mjpeg: bad SOF0 ({h} x {w})")
+            sof = [(seg[6 + 3 * i], seg[7 + 3 * i] >> 4, seg[7 + 3 * i] & 15, seg[8 + 3 * i]) for i in range(nc)]
+            samp = [(c[1], c[2]) for c in sof]
+            if nc == 3 and (samp[0] not in ((1, 1), (2, 1), (2, 2)) or samp[1:] != [(1, 1), (1, 1)]):
+                raise UnsupportedJpeg(f"mjpeg: sampling factors {samp}")
+            info.height, info.width, info.components = h, w, nc
+            info.hs, info.vs = samp[0] if nc == 3 else (1, 1)                              # one component: a block per MCU, whatever its factors
+        elif 0xC1 <= m <= 0xCF and m not in (0xC8, 0xCC):
+            raise UnsupportedJpeg(f"mjpeg: SOF{m - 0xC0} (only baseline SOF0 is read)")
+        elif m == 0xDD:
+            if len(seg) != 2:
+                raise UnsupportedJpeg("mjpeg: bad DRI segment")
+            info.dri = struct.unpack(">H", seg)[0]
+        elif m == 0xDA:
+            if sof is None:
+                raise UnsupportedJpeg("mjpeg: SOS before SOF0")
+            ns = seg[0] if seg else 0
+            if ns != info.components or len(seg) != 4 + 2 * ns:
+                raise UnsupportedJpeg(f"mjpeg: a scan of {ns} of {info.components} components (several scans)")
+            if [seg[1 + 2 * i] for i in range(ns)] != [c[0] for c in sof]:
+                raise UnsupportedJpeg("mjpeg: the scan's components are not the frame's, in order")
+            if tuple(seg[1 + 2 * ns:]) != (0, 63, 0):
+                raise UnsupportedJpeg(f"mjpeg: scan parameters Ss, Se, AhAl = {tuple(seg[1 + 2 * ns:])}")
+            info.dc, info.ac, q = [], [], []
+            for i in range(ns):
+                td, ta = seg[2 + 2 * i] >> 4, seg[2 + 2 * i] & 15
+                if not dht:                                                                # no DHT at all: the Annex K tables (AVI MJPG)
+                    if td > 1 or ta > 1:
+                        raise UnsupportedJpeg(f"mjpeg: no DHT and table selectors {td}, {ta}")
+                    info.dc.append(_ANNEX_K_DC[td])
+                    info.ac.append(_ANNEX_K_AC[ta])
+                else:
+                    if td not in dht or (0x10 | ta) not in dht:
+                        raise UnsupportedJpeg(f"mjpeg: the scan names Huffman tables {td}, {ta} that no DHT defines")
+                    info.dc.append(dht[td])
+                    info.ac.append(dht[0x10 | ta])
+                if sof[i][3] not in qt:
+                    raise UnsupportedJpeg(f"mjpeg: the frame names quantisation table {sof[i][3]} that no DQT defines")
+                q.append(qt[sof[i][3]])
+            info.qtables = np.stack(q)
+            info.scan_offset, info.header = p, data[:p]
+            return info
+        elif m in (0xD9, 0xD8) or 0xD0 <= m <= 0xD7 or m == 0x01:
+            raise UnsupportedJpeg(f"mjpeg: marker {m:#04x} before SOS")
+        else:
+            raise UnsupportedJpeg(f"mjpeg: segment {m:#04x} is not read")
+
+
+def decode_tables(info):
+    """The MjdTables record (TABLES_DTYPE) of a parsed frame: what both the twin and the device decode with."""
+    t = np.zeros((), TABLES_DTYPE)
+    for c in range(info.components):
+        t["dc"][c] = _huff_decode_table(*info.dc[c])
+        t["ac"][c] = _huff_decode_table(*info.ac[c])
+    t["zigzag"][:] = ZIGZAG
+    return t
+
+
+def scan_intervals(data, info):
+    """The restart intervals of one frame's scan, found with a vectorised search (FF D0..D7 cannot occur inside stuffed data):
+    (int64 [k, 4] of byte offset into `data`, byte length, first MCU, MCU count; host status). The scan ends at the first FF xx
+    with xx neither 00 nor D0..D7: status 7 unless that is EOI. Another number of intervals than the frame has: status 5, and the
+    intervals both counts have are decoded."""
+    a = np.frombuffer(data, np.uint8)[info.scan_offset:]
+    ff = np.flatnonzero(a[:-1] == 0xFF) if a.size else np.zeros(0, np.int64)
+    nxt = a[ff + 1]
+    mark = nxt != 0
+    ff, nxt = ff[mark], nxt[mark]
+    rst = (nxt >= 0xD0) & (nxt <= 0xD7)
+    stop = np.flatnonzero(~rst)
+    status = 0
+    if stop.size:
+        end = int(ff[stop[0]])
+        if nxt[stop[0]] != 0xD9:
+            status = _ST_EOI
+        ff = ff[:stop[0]]
+    else:
+        end, status = a.size, _ST_EOI
+    starts = np.concatenate([[0], ff + 2])
+    ends = np.concatenate([ff, [end]])
+    mw, mh = info.mcus
+    total = mw * mh
+    per = info.dri or total
+    want = -(-total // per)
+    if starts.size != want:
+        status = max(status, _ST_COUNT)
+    k = min(starts.size, want)
+    first = np.arange(k, dtype=np.int64) * per
+    iv = np.stack([starts[:k] + info.scan_offset, ends[:k] - starts[:k], first, np.minimum(per, total - first)], axis=-1).astype(np.int64)
+    return iv, status
+
+
+def _decode_interval(data, lo, length, first_mcu, mcu_count, info, tabs, coef):
+    """mjd_decode_interval of csrc/mjpeg_decode_core.h, line by line: `coef` int16 [frame_blocks, 64] is written in place and the
+    status returned."""
+    mw, mh = info.mcus
+    comp_off, comp_bw, _ = info.geometry
+    zz = [int(z) for z in ZIGZAG]
+    p, end, acc, cnt = lo, lo + length, 0, 0
+    pred = [0, 0, 0]
+
+    def symbol(t):
+        nonlocal p, acc, cnt
+        while cnt <= 24 and p < end:
+            v = data[p]
+            p += 2 if v == 0xFF else 1
+            acc, cnt = ((acc << 8) | v) & 0xFFFFFFFF, cnt + 8
+        code = (acc >> (cnt - 16)) & 0xFFFF if cnt >= 16 else ((acc << (16 - cnt)) | ((1 << (16 - cnt)) - 1)) & 0xFFFF
+        e = t[0][code >> 8]
+        ln, sym = e >> 8, e & 255
+        if e == 0:
+            for ln in range(9, 17):
+                c = code >> (16 - ln)
+                if c <= t[1][ln]:
+                    sym = t[3][(t[2][ln] + c) & 255]
+                    break
+            else:
+                return -_ST_SHORT if cnt < 16 else -_ST_CODE
+        if ln > cnt:
+            return -_ST_SHORT
+        cnt -= ln
+        return sym
+
+    def receive_extend(size):
+        nonlocal p, acc, cnt
+        while cnt <= 24 and p < end:
+            v = data[p]
+            p += 2 if v == 0xFF else 1
+            acc, cnt = ((acc << 8) | v) & 0xFFFFFFFF, cnt + 8
+        if size > cnt:
+            return None
+        v = (acc >> (cnt - size)) & ((1 << size) - 1)
+        cnt -= size
+        return v - (1 << size) + 1 if v < (1 << (size - 1)) else v
+
+    for mcu in range(first_mcu, min(first_mcu + mcu_count, mw * mh)):
+        my, mx = divmod(mcu, mw)
+        for c in range(info.components):
+            hc, vc = (info.hs, info.vs) if c == 0 else (1, 1)
+            dc_t, ac_t = tabs[0][c], tabs[1][c]
+            for by in range(vc):
+                for bx in range(hc):
+                    out = coef[comp_off[c] + (my * vc + by) * comp_bw[c] + mx * hc + bx]
+                    s = symbol(dc_t)
+                    if s < 0:
+                        return -s
+                    if s > 11:
+                        return _ST_SIZE
+                    if s:
+                        d = receive_extend(s)
+                        if d is None:
+                            return _ST_SHORT
+                        pred[c] += d
+                    if not -32768 <= pred[c] <= 32767:
+                        return _ST_DC
+                    out[0] = pred[c]
+                    k = 1
+                    while k < 64:
+                        rs = symbol(ac_t)
+                        if rs < 0:
+                            return -rs
+                        r, s = rs >> 4, rs & 15
+                        if s == 0:
+                            if r != 15:
+                                break
+                            k += 16
+                            continue
+                        if s > 10:
+                            return _ST_SIZE
+                        k += r
+                        if k > 63:
+                            return _ST_RUN
+                        v = receive_extend(s)
+                        if v is None:
+                            return _ST_SHORT
+                        out[zz[k]] = v
+                        k += 1
+    return 0
+
+
+def _python_tables(tabs):
+    as_lists = lambda t: (t["look"].tolist(), t["maxcode"].tolist(), t["valoff"].tolist(), t["vals"].tolist())
+    return [as_lists(tabs["dc"][c]) for c in range(3)], [as_lists(tabs["ac"][c]) for c in range(3)]
+
+
+def decode_coefficients(data, info=None):
+    """(int16 [frame_blocks, 64] at natural positions, status) of one frame: the entropy stage of the twin alone."""
+    info = info or parse_jpeg(data)
+    data = bytes(data)
+    iv, status = scan_intervals(data, info)
+    tabs = _python_tables(decode_tables(info))
+    coef = np.zeros((info.geometry[2], 64), np.int16)
+    for lo, ln, first, count in iv.tolist():
+        status = max(status, _decode_interval(data, lo, ln, first, count, info, tabs, coef))
+    return coef, status
+
+
+_I32 = np.int32
+
+
+def _idct_pass(v, shift):
+    """The 8-point islow butterfly along the last axis of an int32 array (wrapping), descaled by `shift`."""
+    i0, i1, i2, i3, i4, i5, i6, i7 = (v[..., k] for k in range(8))
+    z1 = (i2 + i6) * _I32(4433)
+    t2 = z1 - i6 * _I32(15137)
+    t3 = z1 + i2 * _I32(6270)
+    t0, t1 = (i0 + i4) << 13, (i0 - i4) << 13
+    t10, t13, t11, t12 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
+    a0, a1, a2, a3 = i7, i5, i3, i1
+    z1, z2, z3, z4 = a0 + a3, a1 + a2, a0 + a2, a1 + a3
+    z5 = (z3 + z4) * _I32(9633)
+    a0, a1, a2, a3 = a0 * _I32(2446), a1 * _I32(16819), a2 * _I32(25172), a3 * _I32(12299)
+    z1, z2 = z1 * _I32(-7373), z2 * _I32(-20995)
+    z3, z4 = z3 * _I32(-16069) + z5, z4 * _I32(-3196) + z5
+    a0, a1, a2, a3 = a0 + (z1 + z3), a1 + (z2 + z4), a2 + (z2 + z3), a3 + (z1 + z4)
+    out = (t10 + a3, t11 + a2, t12 + a1, t13 + a0, t13 - a0, t12 - a1, t11 - a2, t10 - a3)
+    return np.stack([(o + _I32(1 << (shift - 1))) >> shift for o in out], axis=-1)
+
+
+def _planes(coef, info):
+    """int16 [n, frame_blocks, 64] -> per component its int32 sample plane [n, 8 block rows, 8 block columns]."""
+    mw, mh = info.mcus
+    comp_off, comp_bw, _ = info.geometry
+    out = []
+    with np.errstate(over="ignore"):
+        for c in range(info.components):
+            hc, vc = (info.hs, info.vs) if c == 0 else (1, 1)
+            bh, bw = mh * vc, mw * hc
+            d = coef[:, comp_off[c]:comp_off[c] + bh * bw].astype(np.int32) * info.qtables[c].astype(np.int32)
+            d = d.reshape(-1, bh, bw, 8, 8)
+            ws = _idct_pass(d.swapaxes(-1, -2), 11).swapaxes(-1, -2)                       # columns
+            px = np.clip(_idct_pass(ws, 18) + _I32(128), 0, 255)                          # rows
+            out.append(px.transpose(0, 1, 3, 2, 4).reshape(-1, bh * 8, bw * 8))
+    return out
+
+
+def _upsample(a, vertical):
+    """libjpeg's fancy upsampling of an int32 chroma plane [n, h, w]: h2v1, or h2v2 with `vertical`; edges replicate."""
+    if vertical:
+        up, dn = np.concatenate([a[:, :1], a[:, :-1]], 1), np.concatenate([a[:, 1:], a[:, -1:]], 1)
+        r = np.empty((a.shape[0], 2 * a.shape[1], a.shape[2]), np.int32)
+        r[:, 0::2], r[:, 1::2] = 3 * a + up, 3 * a + dn
+        bias, shift = (8, 7), 4
+    else:
+        r, bias, shift = a, (1, 2), 2
+    lf, rt = np.concatenate([r[..., :1], r[..., :-1]], -1), np.concatenate([r[..., 1:], r[..., -1:]], -1)
+    out = np.empty(r.shape[:2] + (2 * r.shape[2],), np.int32)
+    out[..., 0::2], out[..., 1::2] = (3 * r + lf + bias[0]) >> shift, (3 * r + rt + bias[1]) >> shift
+    return out
+
+
+def pixels_from_coefficients(coef, info):
+    """uint8 [n,H,W,3] (or [n,H,W]) from int16 [n, frame_blocks, 64]: dequantisation, IDCT, upsampling, colour - the twin's arithmetic."""
+    h, w = info.height, info.width
+    planes = _planes(coef, info)
+    if info.components == 1:
+        return planes[0][:, :h, :w].astype(np.uint8)
+    y = planes[0][:, :h, :w]
+    ch = []
+    for pl in planes[1:]:
+        if info.hs == 2:
+            pl = _upsample(pl[:, :-(-h // info.vs), :-(-w // 2)], info.vs == 2)
+        ch.append(pl[:, :h, :w] - _I32(128))
+    cb, cr = ch
+    r = y + ((91881 * cr + 32768) >> 16)
+    g = y + ((-22554 * cb - 46802 * cr + 32768) >> 16)
+    b = y + ((116130 * cb + 32768) >> 16)
+    return np.clip(np.stack([r, g, b], axis=-1), 0, 255).astype(np.uint8)
+
+
+def _same_geometry(a, b):
+    return (a.height, a.width, a.components) == (b.height, b.width, b.components)
+
+
+def _status_error(i, status):
+    return ValueError(f"mjpeg: frame {i} does not decode: {DECODE_STATUS[int(status)]} (status {int(status)})")
+
+
+def decode_jpeg_numpy(jpegs):
+    """uint8 [N,H,W,3] RGB (or [N,H,W] for 1-component frames) of N baseline JPEGs of one geometry: the contract of the decoder.
+    Pure numpy and Python (the entropy decoder is a Python loop: small frames). ValueError names the first frame whose stream is
+    corrupt and its status; UnsupportedJpeg what is not read."""
+    jpegs = [bytes(j) for j in jpegs]
+    if not jpegs:
+        raise ValueError("mjpeg: no frames")
+    out, first = [], None
+    for i, j in enumerate(jpegs):
+        info = parse_jpeg(j)
+        first = first or info
+        if not _same_geometry(first, info):
+            raise ValueError(f"mjpeg: frame {i} is {info.height} x {info.width} x {info.components}, frame 0 {first.height} x {first.width} x {first.components}")
+        coef, status = decode_coefficients(j, info)
+        if status:
+            raise _status_error(i, status)
+        out.append(pixels_from_coefficients(coef[None], info)[0])
+    return np.stack(out)
+
+
+def _device_groups(jpegs):
+    """Consecutive frames whose bytes up to the end of SOS are equal: [(info, first frame, frame count)]."""
+    groups = []
+    for i, j in enumerate(jpegs):
+        if groups and j.startswith(groups[-1][0].header):
+            groups[-1][2] += 1
+        else:
+            groups.append([parse_jpeg(j), i, 1])
+    return groups
+
+
+def device_call_inputs(jpegs, info):
+    """What one vda_mjpeg_decode_u8 call uploads for frames that share `info`'s header: (scan uint8 [bytes], intervals int32 [k, 5]
+    of frame, byte offset, byte length, first MCU, MCU count; host status int32 [n])."""
+    ivs, status, at, so = [], np.zeros(len(jpegs), np.int32), 0, info.scan_offset
+    for f, j in enumerate(jpegs):
+        iv, status[f] = scan_intervals(j, info)
+        iv[:, 0] += at - so
+        ivs.append(np.concatenate([np.full((iv.shape[0], 1), f, np.int64), iv], axis=1))
+        at += len(j) - so
+    if at > 0x7ffffff0:
+        raise ValueError(f"mjpeg: {at} bytes of scans in one call (at most 2^31 - 16): decode fewer frames at a time")
+    scan = np.frombuffer(b"".join(j[so:] for j in jpegs) or b"\0", np.uint8)            # (never an empty upload)
+    return scan, np.ascontiguousarray(np.concatenate(ivs), dtype=np.int32), status
+
+
+def decode_jpeg(jpegs, device="cuda", to_host=True):
+    """decode_jpeg_numpy's pixels from the device (vda_mjpeg_decode_u8, csrc/mjpeg_decode.hip): a numpy array, or with
+    to_host=False a cuda uint8 tensor. The headers are parsed and the restart markers found on the host; consecutive frames with the
+    same header (all frames of a video) go in one call: three launches - entropy decoding with one lane per restart interval,
+    IDCT, upsampling and colour. A stream WITHOUT restart markers is one interval per frame, so one lane decodes the whole frame:
+    correct, and slow by nature (tools/mjpeg_decode_bench.py puts a number on it). Raises as the twin does."""
+    import torch
+    jpegs = [bytes(j) for j in jpegs]
+    if not jpegs:
+        raise ValueError("mjpeg: no frames")
+    dev = torch.device("cuda" if device is None else device)
+    if dev.type != "cuda":
+        raise ValueError(f"mjpeg: needs a cuda device, got {device!r}; decode_jpeg_numpy is the host twin")
+    from . import ops
+    groups = _device_groups(jpegs)
+    first = groups[0][0]
+    for info, i, _ in groups:
+        if not _same_geometry(first, info):
+            raise ValueError(f"mjpeg: frame {i} is {info.height} x {info.width} x {info.components}, frame 0 {first.height} x {first.width} x {first.components}")
+    n, h, w, ch = len(jpegs), first.height, first.width, first.components
+    with torch.cuda.device(dev):
+        out = torch.empty((n, h, w) + ((3,) if ch == 3 else ()), dtype=torch.uint8, device=dev)
+        status = np.zeros(n, np.int32)
+        for info, i, m in groups:
+            scan, iv, host_status = device_call_inputs(jpegs[i:i + m], info)
+            scan_d = torch.from_numpy(scan.copy()).to(dev, non_blocking=True)
+            work = torch.empty(ops.mjpeg_decode_workspace_bytes(m, h, w, ch, info.hs, info.vs, iv.shape[0]), dtype=torch.uint8, device=dev)
+            st = torch.empty(m, dtype=torch.int32, device=dev)
+            ops.mjpeg_decode(scan_d, iv, decode_tables(info), info.qtables, info.hs, info.vs, work, out[i:i + m], st)
+            status[i:i + m] = np.maximum(st.cpu().numpy(), host_status)
+        bad = np.flatnonzero(status)
+        if bad.size:
+            raise _status_error(bad[0], status[bad[0]])
+        return out.cpu().numpy() if to_host else out
+
+
+def iter_avi(path):
+    """A RIFF AVI with one MJPG stream, read incrementally: first (fps, width, height), then the body of every 00dc chunk of movi
+    in file order. Only the chunk in hand is in memory (read_avi holds the file and checks idx1 against it; this does neither)."""
+    with open(path, "rb") as f:
+        head = f.read(12)
+        if len(head) < 12 or head[:4] != b"RIFF" or head[8:12] != b"AVI ":
+            raise ValueError(f"iter_avi: {path} is not a RIFF AVI file")
+        info, told = {}, False
+        while True:
+            hd = f.read(8)
+            if len(hd) < 8:
+                break
+            tag, size = hd[:4], struct.unpack("<I", hd[4:])[0]
+            if tag == b"LIST":
+                kind = f.read(4)
+                if kind != b"movi":
+                    continue                                                               # hdrl, strl, ...: their chunks are read as they come
+                if b"strh" not in info or b"strf" not in info:
+                    raise ValueError(f"iter_avi: {path} has no stream header before movi")
+                strh = struct.unpack_from("<4s4sIHHIIII", info[b"strh"])
+                width, height = struct.unpack_from("<ii", info[b"strf"], 4)
+                if strh[0] != b"vids" or strh[1] != b"MJPG":
+                    raise ValueError(f"iter_avi: the stream of {path} is {strh[0]!r} / {strh[1]!r}, not vids / MJPG")
+                yield strh[7] / strh[6], width, height
+                told, left = True, size - 4
+                while left >= 8:
+                    hd = f.read(8)
+                    if len(hd) < 8:
+                        raise ValueError(f"iter_avi: {path} ends inside its movi list")
+                    tag, n = struct.unpack("<4sI", hd)
+                    left -= 8
+                    if tag == b"LIST":                                                     # a 'rec ' list: its chunks follow
+                        f.read(4)
+                        left -= 4
+                        continue
+                    take = n + (n & 1)
+                    if n > left:
+                        raise ValueError(f"iter_avi: chunk {tag!r} of {path} runs past movi")
+                    if tag == b"00dc":
+                        body = f.read(n)
+                        if len(body) != n:
+                            raise ValueError(f"iter_avi: {path} ends inside a frame")
+                        f.seek(n & 1, 1)
+                        yield body
+                    else:
+                        f.seek(take, 1)
+                    left -= take
+                return
+            body = f.read(size)
+            f.seek(size & 1, 1)
+            info[tag] = body
+        if not told:
+            raise ValueError(f"iter_avi: {path} has no movi list")
+
+
+def _decode_block(jpegs, device):
+    """uint8 [m,H,W,3] of a block of frames: on the device, or on the host by PIL when it is there and by the twin otherwise; what
+    this decoder does not read goes to PIL."""
+    try:
+        if device is not None:
+            x = decode_jpeg(jpegs, device)
+        else:
+            try:
+                return decode_jpegs(jpegs)
+            except ImportError:
+                x = decode_jpeg_numpy(jpegs)
+    except UnsupportedJpeg:
+        return decode_jpegs(jpegs)
+    return x if x.ndim == 4 else np.repeat(x[..., None], 3, axis=-1)
+
+
+def avi_frame_blocks(path, device=None, block=None):
+    """uint8 [m,H,W,3] blocks of `block` frames (default scheduler.STEP, a window's new frames) of a Motion-JPEG AVI, decoded as
+    the file is read: what infer_video_depth_stream takes, so a long .avi runs in bounded memory."""
+    if block is None:
+        from .scheduler import STEP
+        block = STEP
+    frames = iter_avi(path)
+    next(frames)
+    held = []
+    for j in frames:
+        held.append(j)
+        if len(held) == block:
+            yield _decode_block(held, device)
+            held = []
+    if held:
+        yield _decode_block(held, device)

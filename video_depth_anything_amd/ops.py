@@ -533,6 +533,38 @@ def mjpeg_encode(frames, qtables, workspace, out, lengths):
                                   _p(lengths), _stream(frames)), "vda_mjpeg_encode_u8")
 
 
+# ---- baseline JPEG scans back to pixels (csrc/mjpeg_decode.hip; mjpeg.py parses the headers and is the contract) ----------------
+def mjpeg_decode_workspace_bytes(n, h, w, components, hs, vs, intervals):
+    return int(lib.vda_mjpeg_decode_workspace_bytes(n, h, w, components, hs, vs, intervals))
+
+
+def mjpeg_decode(scan, intervals, tables, qtables, hs, vs, workspace, out, status):
+    """out (device uint8 [n,h,w,3] or [n,h,w]) = the pixels of the n frames whose scans lie back to back in scan (device uint8),
+    status (device int32 [n]) their decode status: include/vda.h. HOST numpy: intervals int32 [k,5], tables one
+    mjpeg.TABLES_DTYPE record, qtables uint16 [components,64] in natural order."""
+    import numpy as np
+    from .mjpeg import TABLES_DTYPE
+    _req(scan, torch.uint8, "scan"), _req(workspace, torch.uint8, "workspace"), _req(out, torch.uint8, "out"), _req(status, torch.int32, "status")
+    if out.dim() not in (3, 4) or (out.dim() == 4 and out.shape[3] != 3) or out.numel() == 0:
+        raise ValueError(f"mjpeg_decode: out must be [n,h,w,3] or [n,h,w] and not empty, got {tuple(out.shape)}")
+    n, h, w = out.shape[:3]
+    ch = 3 if out.dim() == 4 else 1
+    if not isinstance(intervals, np.ndarray) or intervals.dtype != np.int32 or intervals.ndim != 2 or intervals.shape[1] != 5 or not intervals.flags.c_contiguous:
+        raise ValueError("mjpeg_decode: intervals must be a contiguous host int32 array [k,5]")
+    if not isinstance(tables, np.ndarray) or tables.dtype != TABLES_DTYPE or tables.size != 1:
+        raise ValueError("mjpeg_decode: tables must be one host record of mjpeg.TABLES_DTYPE")
+    if not isinstance(qtables, np.ndarray) or qtables.dtype != np.uint16 or qtables.size != 64 * ch or not qtables.flags.c_contiguous:
+        raise ValueError(f"mjpeg_decode: qtables must be a contiguous host uint16 array of {64 * ch} entries")
+    if status.numel() < n:
+        raise ValueError(f"mjpeg_decode: status holds {status.numel()} entries, needs {n}")
+    if len({t.device for t in (scan, workspace, out, status)}) != 1:
+        raise ValueError("mjpeg_decode: the operands live on different devices")
+    tables = np.ascontiguousarray(tables)
+    check(lib.vda_mjpeg_decode_u8(_p(scan), scan.numel(), intervals.ctypes.data_as(C.c_void_p), intervals.shape[0], tables.ctypes.data_as(C.c_void_p),
+                                  qtables.ctypes.data_as(C.c_void_p), n, h, w, ch, hs, vs, _p(workspace), workspace.numel(), _p(out), out.numel(),
+                                  _p(status), _stream(scan)), "vda_mjpeg_decode_u8")
+
+
 # ---- validation losses (csrc/losses.hip; losses.py lays the buffers out) --------------------------------------------------------
 LOSS_STATS = 8               # doubles per frame in `stats` (include/vda.h)
 
