@@ -452,6 +452,21 @@ int vda_tae_finish(const double* partial, int npairs, int blocks_per_plane, doub
  * a row of more than 2^30 pixels, n * H or n * h beyond 31 bits. One launch on `stream`, no allocation, no synchronisation. */
 int vda_resize_linear_f32(const float* in, float* out, int n, int h, int w, int H, int W, vda_stream_t stream);
 
+/* ---- frames larger than max_res scaled down (the reference's cv2 branch of read_video_frames: cv2.resize(frame, (width, height))) ----
+ * n dense interleaved uint8 images [h, w, c] -> n images [H, W, c], c = 1 or 3: cv2's INTER_LINEAR for 8-bit images restated from
+ * its published algorithm. The coordinates, the column rule and the row rule are vda_resize_linear_f32's; the rest is integer:
+ *   a0 = 1.f - fx, a1 = fx, b0 = 1.f - fy, b1 = fy, each the 16-bit integer rint(a * 2048.f) (half to even, saturated to short)
+ *   T   = S[x0] * a0 + S[x1] * a1                                                   int32 (at most 255 * 2048), per source row
+ *   out = (((b0 * (T0 >> 4)) >> 16) + ((b1 * (T1 >> 4)) >> 16) + 2) >> 2
+ * so equal sizes reproduce the input and an exact halving of both axes gives (p00 + p01 + p10 + p11 + 2) >> 2. Deterministic; a
+ * host restatement reproduces it byte for byte. Refused: null pointers, a size < 1 or c outside {1, 3}, in == out, a row of more
+ * than 2^30 bytes, n * H or n * h beyond 31 bits. No pointer alignment is asked for; two fast paths take what is aligned and fall
+ * back otherwise, with the same bytes either way: a 4-aligned `in` with source rows (w * c) of a multiple of 4 bytes is staged
+ * through LDS with dword loads (when the part a workgroup needs fits 64 KB), anything else is read byte by byte; a 4-aligned `out`
+ * with output rows (W * c) of a multiple of 4 bytes is stored a dword at a time, anything else byte by byte. One launch on `stream`
+ * (up to 64 KB of dynamic LDS), no allocation, no synchronisation. */
+int vda_resize_linear_u8(const uint8_t* in, uint8_t* out, int n, int h, int w, int c, int H, int W, vda_stream_t stream);
+
 /* ---- metric depth unprojected to coloured points, as the bytes of a PLY vertex list (metric_depth/depth_to_pointcloud.py) ----
  * For frame i, pixel (row r, column c), z = depth[i, r, c], every operation in fp64 and rounded once (no fused multiply-add):
  *   X = (((double)c - cx) / fx) * (double)z      Y = (((double)r - cy) / fy) * (double)z      Z = (double)z

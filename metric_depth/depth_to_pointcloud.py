@@ -55,7 +55,9 @@ if __name__ == '__main__':
     video_depth_anything.load_state_dict(sd, strict=True)
     video_depth_anything = video_depth_anything.to(DEVICE).eval()
 
-    frames, target_fps = read_video_frames(args.input_video, args.max_len, args.target_fps, args.max_res)
+    # on a GPU a Motion-JPEG .avi is decoded there and frames larger than --max_res are scaled there (csrc/resize_u8.hip)
+    frames, target_fps = read_video_frames(args.input_video, args.max_len, args.target_fps, args.max_res,
+                                           device=DEVICE if DEVICE == 'cuda' else None)
     os.makedirs(args.output_dir, exist_ok=True)
     cloud = dict(fx=args.focal_length_x, fy=args.focal_length_y, max_depth=args.max_depth, dtype='float32' if args.float32 else 'float64',
                  device=DEVICE)

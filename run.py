@@ -3,16 +3,20 @@
 
 Frame I/O is utils/dc_utils.py (same two helpers as the reference's): `--input_video` may be an .npy / .npz (key `frames`)
 of uint8 [N,H,W,3] RGB frames, a directory of images, a GIF, a Motion-JPEG .avi (decoded on the device, csrc/mjpeg_decode.hip; with
-`--stream` a window's frames at a time, so a long .avi runs in bounded memory), or a video file when decord or cv2 is importable; the
+`--stream` a window's frames at a time, so a long .avi runs in bounded memory), or a video file when decord or cv2 is importable;
+frames larger than `--max_res` are scaled down on the device with cv2's 8-bit arithmetic (csrc/resize_u8.hip), with `--stream` a
+block at a time (utils.dc_utils.read_video_blocks), so an HD .avi or .npy keeps its bounded memory; the
 visualisations are mp4 through imageio when present and animated GIFs otherwise, or with `--mjpeg` Motion-JPEG .avi files that
 need no encoder library (the JPEG coding runs on the device too, csrc/mjpeg.hip); `--save_npz` adds <name>_depths.npz.
 <name>_vis carries the reference's colours: depth is mapped through matplotlib's 256-entry inferno table, which ships in
 video_depth_anything_amd/visualize.py (not through the polynomial fit utils/dc_utils.py keeps as save_video's default), and on a
 GPU the mapping itself runs on the device (csrc/visualize.hip) - the same bytes as on the host.
 `--metric` selects the metric-depth variant (metric_depth/run.py: ViT-L, no scale/shift alignment).
-`--stream` runs infer_video_depth_stream instead: the frames (a memory map for .npy) are fed to the stream, the depths go piece by
-piece into <name>_depths.npy on disk and the visualisation is made from that file block by block, so neither the video nor its
-depth is ever held in memory as one array.
+`--stream` runs infer_video_depth_stream instead: an .npy (a memory map) and, on a GPU, a Motion-JPEG .avi are fed to the stream block
+by block, the depths go piece by piece into <name>_depths.npy on disk and the visualisation is made from that file block by block,
+so neither such a video nor its depth is ever held in memory as one array - with one exception: without `--mjpeg`, <name>_src of an
+input that had to be scaled or thinned is written from the scaled frames as one array (the mp4 / GIF writers take no blocks). Every
+other kind of input is decoded whole by its decoder, once.
 """
 import argparse
 import itertools
@@ -22,8 +26,9 @@ import struct
 import numpy as np
 import torch
 
-from utils.dc_utils import read_video_frames, save_video
+from utils.dc_utils import read_video_blocks, read_video_frames, reads_in_blocks, save_video
 from video_depth_anything_amd import mjpeg
+from video_depth_anything_amd.scale import scaled_size
 from video_depth_anything_amd.visualize import inferno_table
 from video_depth_anything_amd.video_depth import MetricVideoDepthAnything, VideoDepthAnything
 
@@ -74,16 +79,43 @@ def write_depth_stream(stream, path, n_frames=None):
     return np.load(path, mmap_mode="r")
 
 
-def limit_frames(blocks, max_len):
-    """The [m,...] blocks of an iterable cut to `max_len` frames in all (no limit when it is not positive)."""
-    left = max_len
+def write_src_from_source_jpegs(path, input_video, max_len, target_fps, max_res, fps, device):
+    """<name>_src.avi as a copy of the source's own JPEGs: nothing is decoded or held. Only for a Motion-JPEG .avi that is decoded on
+    the device and of which no frame was dropped or scaled (then those JPEGs ARE the frames the model saw); False otherwise."""
+    if device is None or not (input_video.lower().endswith('.avi') and os.path.isfile(input_video) and mjpeg.is_mjpeg_avi(input_video)):
+        return False
+    jpegs = mjpeg.iter_avi(input_video, limit=max_len if max_len > 0 else None)
+    src_fps, src_w, src_h = next(jpegs)
+    if (target_fps >= 0 and max(round(src_fps / target_fps), 1) != 1) or scaled_size(src_h, src_w, max_res) != (src_h, src_w):
+        return False
+    mjpeg.write_avi(path, jpegs, fps, src_w, src_h)
+    return True
+
+
+def stream_input(source, device):
+    """What run.py --stream feeds infer_video_depth_stream from source = (input_video, max_len, target_fps, max_res): (frames, fps,
+    whole). An .npy and (on a device) a Motion-JPEG .avi come as read_video_blocks' iterator and whole is None: neither the file nor
+    its scaled frames are ever held as one array. Every other source is decoded whole whichever way it is read, so it is read once,
+    by read_video_frames, and whole is that array, kept for <name>_src."""
+    if reads_in_blocks(source[0], device):
+        blocks, fps = read_video_blocks(*source, device=device)
+        return blocks, fps, None
+    frames, fps = read_video_frames(*source, device=device)
+    return frames, fps, frames
+
+
+def frames_for_writer(source, device, whole):
+    """The frames save_video writes <name>_src from after a stream: the array stream_input kept, else read_video_frames of the source
+    once more. That is the memory map itself for an .npy of which nothing is scaled or dropped (save_video reads it a block at a
+    time: still bounded). For an .npy or .avi that IS scaled or thinned it is the scaled video as one array: the mp4 / GIF writers
+    take no blocks, so this is the one place where --stream without --mjpeg holds a whole (scaled) video."""
+    return whole if whole is not None else read_video_frames(*source, device=device)[0]
+
+
+def block_jpegs(blocks, quality, device):
+    """The JPEGs of uint8 [m,H,W,3] blocks, a block at a time: coded on the device when there is one, by the host twin otherwise."""
     for b in blocks:
-        if max_len > 0:
-            if left <= 0:
-                return
-            b = b[:left]
-            left -= len(b)
-        yield b
+        yield from (mjpeg.encode_jpeg_numpy(b, quality) if device is None else mjpeg.encode_jpeg(b, quality, device))
 
 
 if __name__ == '__main__':
@@ -123,38 +155,35 @@ if __name__ == '__main__':
     video_depth_anything.load_state_dict(sd, strict=True)
     video_depth_anything = video_depth_anything.to(DEVICE).eval()
 
-    # A Motion-JPEG .avi is decoded on the device (csrc/mjpeg_decode.hip) instead of by decord / cv2 / PIL. With --stream, and when
-    # no frame has to be dropped or scaled, it is never read as a whole: avi_frame_blocks decodes it a window's frames at a time.
-    mjpeg_in = DEVICE == 'cuda' and args.input_video.lower().endswith('.avi') and os.path.isfile(args.input_video) and mjpeg.is_mjpeg_avi(args.input_video)
-    avi_blocks = None
-    if mjpeg_in and args.stream and args.target_fps < 0:
-        src_fps, src_w, src_h = next(mjpeg.iter_avi(args.input_video))
-        if not (args.max_res > 0 and max(src_w, src_h) > args.max_res):
-            avi_blocks = limit_frames(mjpeg.avi_frame_blocks(args.input_video, device=DEVICE), args.max_len)
-    if avi_blocks is not None:
-        frames, target_fps = avi_blocks, src_fps
+    # On a GPU a Motion-JPEG .avi is decoded on the device (csrc/mjpeg_decode.hip) instead of by decord / cv2 / PIL, and frames larger
+    # than --max_res are scaled there (csrc/resize_u8.hip). With --stream an .npy and such an .avi are never held as a whole:
+    # read_video_blocks hands the stream a window's new frames at a time, dropped frames skipped and large frames scaled block by block.
+    io_device = DEVICE if DEVICE == 'cuda' else None
+    source = (args.input_video, args.max_len, args.target_fps, args.max_res)
+    if args.stream:
+        frames, target_fps, whole = stream_input(source, io_device)
     else:
-        frames, target_fps = read_video_frames(args.input_video, args.max_len, args.target_fps, args.max_res,
-                                               device=DEVICE if mjpeg_in else None)                        # run.py:53
+        frames, target_fps = read_video_frames(*source, device=io_device)                                  # run.py:53
     video_name = os.path.basename(args.input_video)
     os.makedirs(args.output_dir, exist_ok=True)
     stem = os.path.join(args.output_dir, os.path.splitext(video_name)[0])
     d_range = {}
     if args.stream:
         stream = video_depth_anything.infer_video_depth_stream(frames, target_fps, input_size=args.input_size, device=DEVICE, fp32=args.fp32)
-        depths = write_depth_stream(stream, stem + '_depths.npy', len(frames) if isinstance(frames, np.ndarray) else None)
+        depths = write_depth_stream(stream, stem + '_depths.npy', len(whole) if whole is not None else None)
         fps = stream.fps
         d_range = dict(d_min=stream.depth_min, d_max=stream.depth_max)      # the stream kept the range: no second pass over the file
-        if avi_blocks is not None:
-            # <name>_src shows the source frames: --mjpeg copies the source's own JPEGs (nothing is decoded or held), otherwise
-            # the file is decoded once more, now as a whole, for the mp4 / GIF writer
-            if args.mjpeg:
-                jpegs = mjpeg.iter_avi(args.input_video)
-                next(jpegs)                                                  # (fps, width, height)
-                mjpeg.write_avi(stem + '_src.avi', itertools.islice(jpegs, args.max_len if args.max_len > 0 else None), fps, src_w, src_h)
-                frames = None
-            else:
-                frames = read_video_frames(args.input_video, args.max_len, args.target_fps, args.max_res, device=DEVICE)[0]
+        # <name>_src shows the frames the model saw. A source that was read in blocks is read a second time: with --mjpeg still a
+        # block at a time (or its own JPEGs are copied); for the mp4 / GIF writer see frames_for_writer
+        if whole is None and args.mjpeg:
+            frames = None
+            if not write_src_from_source_jpegs(stem + '_src.avi', *source, fps, io_device):
+                blocks = read_video_blocks(*source, device=io_device)[0]
+                first = next(blocks)
+                mjpeg.write_avi(stem + '_src.avi', block_jpegs(itertools.chain([first], blocks), args.mjpeg_quality, io_device), fps,
+                                first.shape[2], first.shape[1])
+        else:
+            frames = frames_for_writer(source, io_device, whole)
     else:
         depths, fps = video_depth_anything.infer_video_depth(frames, target_fps, input_size=args.input_size, device=DEVICE, fp32=args.fp32)
 
@@ -162,7 +191,7 @@ if __name__ == '__main__':
     vis_device = DEVICE if DEVICE == 'cuda' else None
     codec = dict(codec='mjpeg', quality=args.mjpeg_quality) if args.mjpeg else {}      # <name>_src.avi / <name>_vis.avi then
     if frames is not None:
-        src_path = save_video(frames, stem + '_src.mp4', fps=fps, device=vis_device if args.mjpeg else None, **codec)
+        save_video(frames, stem + '_src.mp4', fps=fps, device=vis_device if args.mjpeg else None, **codec)
     vis_path = save_video(depths, stem + '_vis.mp4', fps=fps, is_depths=True, grayscale=args.grayscale, palette=inferno_table(),
                           device=vis_device, **d_range, **codec)
     if args.save_npz:

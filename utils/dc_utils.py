@@ -11,8 +11,14 @@ imageio-ffmpeg; none of those exist offline, so each is used when importable and
   save_video       : mp4 through imageio when present, else an animated GIF (PIL) next to the requested name; with
                      codec="mjpeg" a Motion-JPEG .avi that needs neither (video_depth_anything_amd/mjpeg.py).
 
+  read_video_blocks: read_video_frames as an iterator of blocks, for infer_video_depth_stream: with a device a Motion-JPEG .avi and
+                     an .npy are read, scaled and handed over a block at a time (bounded memory).
+
 Frames larger than `max_res` are scaled like the reference's cv2 branch (round(size * max_res / max(h, w)), bilinear, half-pixel
-centres, no antialiasing = cv2.INTER_LINEAR's definition); cv2 is not here to pin that bit for bit.
+centres, no antialiasing = cv2.INTER_LINEAR's definition); cv2 is not here to pin that bit for bit. With a `device` the scaling is
+cv2's 8-bit fixed-point arithmetic restated, on the GPU (video_depth_anything_amd/scale.py, csrc/resize_u8.hip); without one it
+is rounded float bilinear on the CPU (`_resize_bilinear`), as it always was: the two differ by one level in a few percent of the
+bytes (DESIGN.md 6j names this as the open inconsistency).
 """
 import os
 
@@ -28,15 +34,10 @@ def _resize_bilinear(frames, height, width):
     return y.round().clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous().numpy()
 
 
-def _decode(video_path, device=None):
-    """-> (uint8 [N,H,W,3] RGB, source fps). device: a cuda device decodes a Motion-JPEG .avi there (mjpeg.decode_jpeg, block by
-    block) before decord or cv2 are tried; None changes nothing."""
+def _decode(video_path):
+    """-> (uint8 [N,H,W,3] RGB, source fps), the whole video on the host. (A Motion-JPEG .avi that is to be decoded on a device does
+    not come here: read_video_blocks reads it block by block.)"""
     ext = os.path.splitext(video_path)[1].lower()
-    if device is not None and ext == ".avi" and os.path.isfile(video_path):
-        from video_depth_anything_amd import mjpeg
-        if mjpeg.is_mjpeg_avi(video_path):
-            fps = next(mjpeg.iter_avi(video_path))[0]
-            return np.concatenate(list(mjpeg.avi_frame_blocks(video_path, device=device, block=SAVE_BLOCK))), fps
     if os.path.isdir(video_path):
         from PIL import Image
         names = sorted(n for n in os.listdir(video_path) if n.lower().endswith(IMAGE_EXT + (".npy",)))
@@ -86,28 +87,128 @@ def _decode(video_path, device=None):
     return np.stack(out), float(fps)
 
 
-def read_video_frames(video_path, process_length, target_fps=-1, max_res=-1, device=None):
-    """dc_utils.py:18-70: every `stride`-th frame (stride = max(round(src_fps / fps), 1)), at most `process_length`
-    frames read, frames larger than `max_res` scaled down. Returns (uint8 [N,H,W,3], fps). device (not in the reference): a cuda
-    device on which a Motion-JPEG .avi is decoded (csrc/mjpeg_decode.hip); every other input, and None, go the way they always went."""
-    frames, src_fps = _decode(video_path, device)
+def _is_mjpeg_avi(video_path):
+    if os.path.splitext(video_path)[1].lower() != ".avi" or not os.path.isfile(video_path):
+        return False
+    from video_depth_anything_amd import mjpeg
+    return mjpeg.is_mjpeg_avi(video_path)
+
+
+def _fps_stride(src_fps, target_fps):
+    fps = src_fps if target_fps < 0 else target_fps
+    return fps, max(round(src_fps / fps), 1)
+
+
+def _source_frames(video_path, process_length):
+    """`_decode`'s frames (a memory map stays one) cut to `process_length` SOURCE frames, as the cv2 branch counts (dc_utils.py:57)."""
+    frames, src_fps = _decode(video_path)
     if not isinstance(frames, np.ndarray):
         frames = np.asarray(frames)
     if frames.ndim != 4 or frames.shape[-1] != 3:
         raise ValueError(f"expected frames [N,H,W,3], got {frames.shape}")
-    fps = src_fps if target_fps < 0 else target_fps
-    stride = max(round(src_fps / fps), 1)
-    if process_length > 0:
-        frames = frames[:process_length]              # the cv2 branch counts SOURCE frames (dc_utils.py:57)
+    return (frames[:process_length] if process_length > 0 else frames), src_fps
+
+
+def _scale(frames, max_res, device, one_block=False):
+    """uint8 [m,h,w,3] under `max_res`: on `device` with cv2's 8-bit arithmetic (scale.resize_frames, csrc/resize_u8.hip), without
+    one by `_resize_bilinear` as it always was (rounded float bilinear: the two differ by a level in places).
+    one_block: `frames` is a block that fits the device as it is - it is uploaded here and scaled in one call; otherwise
+    resize_frames stages the array through pinned buffers that it allocates per call (once per video, not once per block)."""
+    from video_depth_anything_amd.scale import resize_frames, scaled_size
+    h, w = frames.shape[1:3]
+    H, W = scaled_size(h, w, max_res)
+    if (H, W) == (h, w):
+        return frames
+    if device is None:
+        return _resize_bilinear(frames, H, W)
+    if one_block:
+        import torch
+        x = torch.from_numpy(frames if frames.flags.writeable else np.array(frames))      # a slice of a read-only memory map: paged in here
+        return resize_frames(x.to(device), H, W).cpu().numpy()
+    return resize_frames(frames, H, W, device)
+
+
+def read_video_frames(video_path, process_length, target_fps=-1, max_res=-1, device=None):
+    """dc_utils.py:18-70: every `stride`-th frame (stride = max(round(src_fps / fps), 1)), at most `process_length`
+    frames read, frames larger than `max_res` scaled down. Returns (uint8 [N,H,W,3], fps). device (not in the reference): a cuda
+    device on which a Motion-JPEG .avi is decoded (csrc/mjpeg_decode.hip) - only the frames that are kept - and on which frames
+    larger than `max_res` are scaled (csrc/resize_u8.hip), block by block, whatever they were read from; None goes the way it always
+    went."""
+    if device is not None and _is_mjpeg_avi(video_path):
+        blocks, fps = read_video_blocks(video_path, process_length, target_fps, max_res, device, block=SAVE_BLOCK)
+        return np.concatenate(list(blocks)), fps
+    frames, src_fps = _source_frames(video_path, process_length)
+    fps, stride = _fps_stride(src_fps, target_fps)
     h, w = frames.shape[1:3]
     lazy = isinstance(frames, np.memmap) and stride == 1 and frames.dtype == np.uint8 and not (max_res > 0 and max(h, w) > max_res)
     if lazy:
         return frames, fps                            # still on disk: infer_video_depth pages in what each window reads
-    frames = np.ascontiguousarray(frames[::stride], dtype=np.uint8)
-    if max_res > 0 and max(h, w) > max_res:
-        scale = max_res / max(h, w)
-        frames = _resize_bilinear(frames, round(h * scale), round(w * scale))
-    return frames, fps
+    return _scale(np.ascontiguousarray(frames[::stride], dtype=np.uint8), max_res, device), fps
+
+
+def reads_in_blocks(video_path, device=None):
+    """True for the two sources of which read_video_blocks never holds the whole: an .npy (a memory map) and, with a `device`, a
+    Motion-JPEG .avi. Every other source is decoded whole anyway: a caller that needs the frames twice should keep
+    read_video_frames' array instead of reading twice."""
+    if os.path.isdir(video_path):
+        return False
+    return os.path.splitext(video_path)[1].lower() == ".npy" or (device is not None and _is_mjpeg_avi(video_path))
+
+
+def _avi_blocks(video_path, process_length, stride, max_res, device, block):
+    """The kept frames of a Motion-JPEG .avi, `block` at a time: decoded and scaled on the device, only the scaled block comes back."""
+    import torch
+    from video_depth_anything_amd import mjpeg
+    from video_depth_anything_amd.scale import resize_frames, scaled_size
+
+    def pixels(jpegs):
+        try:
+            x = mjpeg.decode_jpeg(jpegs, device, to_host=False)
+        except mjpeg.UnsupportedJpeg:                                       # progressive, CMYK, ...: PIL reads it, the device scales it
+            x = torch.from_numpy(mjpeg.decode_jpegs(jpegs)).to(device)
+        if x.dim() == 3:
+            x = x[..., None].expand(-1, -1, -1, 3).contiguous()
+        H, W = scaled_size(x.shape[1], x.shape[2], max_res)
+        return (x if (H, W) == tuple(x.shape[1:3]) else resize_frames(x, H, W)).cpu().numpy()
+
+    jpegs = mjpeg.iter_avi(video_path, stride, process_length if process_length > 0 else None)
+    next(jpegs)
+    held = []
+    for j in jpegs:
+        held.append(j)
+        if len(held) == block:
+            yield pixels(held)
+            held = []
+    if held:
+        yield pixels(held)
+
+
+def read_video_blocks(video_path, process_length, target_fps=-1, max_res=-1, device=None, block=None):
+    """read_video_frames as an iterator: (blocks, fps), blocks yielding uint8 [m,H,W,3] of `block` frames (default scheduler.STEP,
+    a window's new frames; the last one may be shorter) whose concatenation is read_video_frames(same arguments), byte for byte. It
+    is to read_video_frames what infer_video_depth_stream is to infer_video_depth: with a cuda `device`, a Motion-JPEG .avi is read
+    a block at a time (dropped frames are skipped in the container, a block's JPEGs are decoded and scaled on the device and only
+    the scaled block crosses to the host) and an .npy stays a memory map of which one block's source frames are paged in, uploaded
+    and scaled - neither the source nor the scaled video is ever held as a whole. Every other source is decoded whole, as `_decode`
+    decodes it, and cut into blocks; with device=None a block is scaled by `_resize_bilinear`, as read_video_frames scales."""
+    if block is None:
+        from video_depth_anything_amd.scheduler import STEP
+        block = STEP
+    if block < 1:
+        raise ValueError(f"read_video_blocks: block must be positive, got {block}")
+    if device is not None and _is_mjpeg_avi(video_path):
+        from video_depth_anything_amd import mjpeg
+        fps, stride = _fps_stride(next(mjpeg.iter_avi(video_path))[0], target_fps)
+        return _avi_blocks(video_path, process_length, stride, max_res, device, block), fps
+    frames, src_fps = _source_frames(video_path, process_length)
+    fps, stride = _fps_stride(src_fps, target_fps)
+    kept = frames[::stride]                                                 # a view: a memory map is not read here
+
+    def blocks():
+        for i in range(0, kept.shape[0], block):
+            yield _scale(np.ascontiguousarray(kept[i:i + block], dtype=np.uint8), max_res, device, one_block=True)
+
+    return blocks(), fps
 
 
 def _inferno(u8):

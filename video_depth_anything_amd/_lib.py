@@ -120,6 +120,7 @@ SIGNATURES = {
     "vda_tae_compare": (_i, [_vp, _vp, _i, _i, _i, C.c_double, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "vda_tae_finish": (_i, [_vp, _i, _i, _vp, _vp]),
     "vda_resize_linear_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "vda_resize_linear_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "vda_pointcloud_frame_stride": (C.c_size_t, [_i, _i, _i]),
     "vda_pointcloud_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
     "vda_pointcloud_f32": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_size_t, _i, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, _f, _i, _vp]),

@@ -24,12 +24,13 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=f
 # expression and restates torch's fp64 elementwise arithmetic after it. resize.hip restates cv2's float32 bilinear resize, whose
 # contract counts every rounding (a*b + c*d as three). pointcloud.hip restates numpy's fp64 (x - cx) / fx * z: the division and
 # the product are each rounded once. visualize.hip restates numpy's float32 (d - d_min) / span * 255: three roundings.
-# losses.hip restates torch's fp64 s * d + t - y (three roundings) and its centred sums.
+# losses.hip restates torch's fp64 s * d + t - y (three roundings) and its centred sums. resize_u8.hip, cv2's 8-bit resize, is integer
+# arithmetic behind resize.hip's fp64 source coordinate (d + 0.5) * scale - 0.5: a product and a difference, each rounded.
 # (mjpeg.hip and mjpeg_decode.hip, the JPEG encoder and decoder, are integer arithmetic from end to end: they reproduce their host
 # twins under the default flags.)
 PER_FILE = {"stitch.hip": ["-ffp-contract=off"], "eval.hip": ["-ffp-contract=off"], "tae.hip": ["-ffp-contract=off"],
             "resize.hip": ["-ffp-contract=off"], "pointcloud.hip": ["-ffp-contract=off"], "visualize.hip": ["-ffp-contract=off"],
-            "losses.hip": ["-ffp-contract=off"]}
+            "losses.hip": ["-ffp-contract=off"], "resize_u8.hip": ["-ffp-contract=off"]}
 # attention: the softmax row sums are 32 scalar fp32 adds per tile; SLP packs 22 of them into v_pk_add_f32, which costs several
 # times two v_add_f32 next to MFMAs (MI355X_MICROARCH.md, "price of one filler") in a loop that is VALU-bound.
 PER_PREFIX = {"gemm": ["-fno-slp-vectorize"], "attention.hip": ["-fno-slp-vectorize"], "mlp_fused.hip": ["-fno-slp-vectorize"],

@@ -908,9 +908,11 @@ def decode_jpeg(jpegs, device="cuda", to_host=True):
         return out.cpu().numpy() if to_host else out
 
 
-def iter_avi(path):
+def iter_avi(path, stride=1, limit=None):
     """A RIFF AVI with one MJPG stream, read incrementally: first (fps, width, height), then the body of every 00dc chunk of movi
-    in file order. Only the chunk in hand is in memory (read_avi holds the file and checks idx1 against it; this does neither)."""
+    in file order. Only the chunk in hand is in memory (read_avi holds the file and checks idx1 against it; this does neither).
+    stride / limit: only frames 0, stride, 2 * stride, ... below `limit` (None: all) are yielded; the others are skipped in the
+    container, their bytes never read, and the walk ends at `limit`."""
     with open(path, "rb") as f:
         head = f.read(12)
         if len(head) < 12 or head[:4] != b"RIFF" or head[8:12] != b"AVI ":
@@ -932,8 +934,8 @@ def iter_avi(path):
                 if strh[0] != b"vids" or strh[1] != b"MJPG":
                     raise ValueError(f"iter_avi: the stream of {path} is {strh[0]!r} / {strh[1]!r}, not vids / MJPG")
                 yield strh[7] / strh[6], width, height
-                told, left = True, size - 4
-                while left >= 8:
+                told, left, frame = True, size - 4, 0
+                while left >= 8 and (limit is None or frame < limit):
                     hd = f.read(8)
                     if len(hd) < 8:
                         raise ValueError(f"iter_avi: {path} ends inside its movi list")
@@ -947,6 +949,8 @@ def iter_avi(path):
                     if n > left:
                         raise ValueError(f"iter_avi: chunk {tag!r} of {path} runs past movi")
                     if tag == b"00dc":
+                        frame += 1
+                    if tag == b"00dc" and (frame - 1) % stride == 0:
                         body = f.read(n)
                         if len(body) != n:
                             raise ValueError(f"iter_avi: {path} ends inside a frame")

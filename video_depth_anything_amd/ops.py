@@ -461,6 +461,19 @@ def resize_linear(x, out):
     check(lib.vda_resize_linear_f32(_p(x), _p(out), n, h, w, H, W, _stream(x)), "vda_resize_linear_f32")
 
 
+# ---- frames scaled to max_res (csrc/resize_u8.hip) -------------------------------------------------------------------------------
+def resize_linear_u8(x, out):
+    """out [n,H,W,3] or [n,H,W] = x [n,h,w,3] or [n,h,w] resized with cv2's INTER_LINEAR arithmetic for 8-bit images
+    (include/vda.h); both device uint8, contiguous (any byte offset), distinct, of one rank."""
+    _req(x, torch.uint8, "x"), _req(out, torch.uint8, "out")
+    if (x.dim() not in (3, 4) or out.dim() != x.dim() or x.shape[0] != out.shape[0] or x.numel() == 0 or out.numel() == 0
+            or x.device != out.device or (x.dim() == 4 and (x.shape[3] != 3 or out.shape[3] != 3))):
+        raise ValueError(f"resize_linear_u8: x {tuple(x.shape)} on {x.device} and out {tuple(out.shape)} on {out.device} must be "
+                         "[n,h,w,3] and [n,H,W,3], or [n,h,w] and [n,H,W]")
+    (n, h, w), (H, W) = x.shape[:3], out.shape[1:3]
+    check(lib.vda_resize_linear_u8(_p(x), _p(out), n, h, w, 3 if x.dim() == 4 else 1, H, W, _stream(x)), "vda_resize_linear_u8")
+
+
 # ---- metric depth unprojected to PLY vertex records (csrc/pointcloud.hip) -------------------------------------------------------
 def pointcloud_frame_stride(h, w, record_f32):
     """Bytes of one frame's slot in the record buffer: h * w records of 15 (record_f32) or 27 bytes, rounded up to 16."""
