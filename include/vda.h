@@ -345,6 +345,29 @@ int vda_conv3x3_up2_f16(const void* in, const void* w, const float* bias, void* 
                         vda_stream_t stream);
 /* Timing experiments of the fused kernel at N > 64 (results invalid): 1 = no interpolation, 2 = no MFMA groups; 0 = the kernel. */
 int vda_conv3x3_up2_set_variant(int v);
+
+/* ---- The same layer with the channel mixing at HALF resolution (option "oc1_mix"). refinenet1's out_conv (1x1: Wo [Fe, Fe], bo), the
+ * 2x align_corners upsample and output_conv1 (W1 [Fh, Fe, 3, 3], b1) are linear with no nonlinearity between them, and channel mixing
+ * commutes with spatial interpolation tap by tap. With r [B, h, w, Fe] the output of refinenet1's resConfUnit2:
+ *   z[b, y, x, tap*Fhp + co] = sum_ci Wz[tap*Fhp + co][ci] * r[b, y, x, ci] + bz[tap*Fhp + co]      one dense GEMM, N = ldz >= 9*Fhp, K = Fe
+ *   o1[b, Y, X, co] = b1[co] + sum over the taps (ky, kx) whose q = (Y + ky - 1, X + kx - 1) lies inside the 2h x 2w map (the others are
+ *                     the conv's zero padding) of sum_j a_j(q) * z[b, s_j(q), (3*ky + kx)*Fhp + co]        (z [B, h, w, ldz]: channels 9*Fhp .. ldz - 1 are never read)
+ * where s_j(q), a_j(q) are the four corners and weights of q on the h x w grid (align_corners: source = q * (h - 1) / (2h - 1), floor,
+ * clamp, fraction - vda_conv3x3_up2_f16's arithmetic).
+ * vda_fold_oc1_weight (pack time): Wz[tap*Fhp + co][ci] = fp16( sum_cm W1[co, cm, tap] * Wo[cm, ci] ), bz[tap*Fhp + co] =
+ *   sum_cm W1[co, cm, tap] * bo[cm], composed in fp32 (fmaf, cm order) and rounded once; rows co >= Fh and rows >= 9*Fhp are zero. Wz fp16
+ *   [ldz, Fe], bz fp32 [ldz]; Fhp >= Fh, Fhp and ldz multiples of 8.
+ * vda_oc1_mix_combine_f16: z fp16 [B, h, w, ldz] -> out fp16 [B, 2h, 2w, Fhp] by the second formula (bias = b1 fp32 [Fhp] or NULL): fp32
+ *   accumulation, one rounding at the store. No corner is read outside its own frame. Fhp and ldz multiples of 8.
+ * vda_oc1_mix_ldz: the z row vda_forward uses for that Fhp: 9*Fhp, padded to a multiple of 256 where that adds at most an eighth (the
+ *   GEMM planner's tile choice; csrc/oc1_mix.hip).
+ * vda_oc1_mix_frames: the frames per z buffer vda_forward runs the pair with (GEMM -> combine per chunk).
+ * vda_oc1_mix_default: the option's default for a head of that many `features` (or the environment's VDA_OC1_MIX). */
+int vda_fold_oc1_weight(const float* W1, const float* Wo, const float* bo, void* Wz, float* bz, int Fh, int Fe, int Fhp, int ldz, vda_stream_t stream);
+int vda_oc1_mix_combine_f16(const void* z, const float* bias, void* out, int B, int h, int w, int Fhp, int ldz, vda_stream_t stream);
+int vda_oc1_mix_ldz(int Fhp);
+int vda_oc1_mix_frames(void);
+int vda_oc1_mix_default(int features);
 /* The LDS-patch 3x3 convolution behind vda_gemm_f16 (N <= 64, stride 1): 0 (default) = the persistent C = 64 kernel where it applies,
  * 1 = the per-pass kernel for every shape. Bit-identical results; A/B only. */
 int vda_conv_lds_set_variant(int v);
@@ -678,7 +701,9 @@ int vda_forward_status(vda_model* h);
 /* Parity hook: copy `bytes` of a named intermediate of the last forward ("tap0".."tap3", "l1", "l2", "l3t", "l4t", "p4t",
  * "p3t", "p2", "p1"; activation dtype of that forward's precision, channels padded to multiples of 64) to device `dst`.
  * "l1" / "l2" of a forward that ran that level folded (option "convt_fold") were never written: they are rebuilt first, on `stream`,
- * from the level's projection ("t0" / "t1") with the unfused ConvTranspose GEMM - what the unfused forward holds there, bit for bit. */
+ * from the level's projection ("t0" / "t1") with the unfused ConvTranspose GEMM - what the unfused forward holds there, bit for bit.
+ * "p1c" (refinenet1's out_conv output at half size, fp16 path) of a forward that ran option "oc1_mix" likewise: rebuilt from
+ * resConfUnit2's output with the unfused out_conv GEMM. */
 int vda_debug_copy(vda_model* h, const char* name, void* dst, int64_t bytes, vda_stream_t stream);
 /* Test utility: occupy `wgs` workgroups (256 threads, lds_bytes of LDS each) for about `cycles` shader clocks on `stream` - a
  * stand-in for a communication kernel running beside the forward (tools/contention.py). Bounded: every wave leaves by itself. */
@@ -701,7 +726,12 @@ int vda_debug_occupy(int wgs, int lds_bytes, long long cycles, vda_stream_t stre
  * k == stride) and layer{i+1}_rn (3x3, no bias) for i = 0, 1 run as ONE implicit GEMM on the projection's grid (VDA_EPI_CONVT_FOLD_F16,
  * weights composed at pack time by vda_fold_convt_weight) wherever the unfused 3x3 conv would run on the 256 x 256 8-phase or the
  * 128-row GEMM kernel (ViT-L; not the 64-channel convs of ViT-S): "l1" / "l2" are then never written. Same workspace layout. Not
- * bit-identical to 0: one fp16 rounding of l1 / l2 less, one rounding of the composed weights more. */
+ * bit-identical to 0: one fp16 rounding of l1 / l2 less, one rounding of the composed weights more.
+ * "oc1_mix" (default vda_oc1_mix_default(features); fp16 path, where "oc1_fused" applies; < 0 restores that default): refinenet1 stops
+ * after resConfUnit2 and its out_conv + output_conv1 over the 2x upsample run as the z GEMM + vda_oc1_mix_combine_f16 (above), per
+ * chunk of "oc1_mix_chunk" frames (default vda_oc1_mix_frames(); changes the workspace size). "p1c" is then never written and
+ * vda_debug_copy rebuilds it from resConfUnit2's output with the unfused out_conv GEMM. Same workspace layout either way. Not
+ * bit-identical to 0: one fp16 rounding of the composed weight and one of z more, the rounding of "p1c" less. */
 int vda_set_option(vda_model* h, const char* name, int value);
 /* Measurement hook (bench.py): from vda_profile_start until vda_profile_stop every `every`-th GEMM / conv launch of each
  * (shape, epilogue) inside vda_forward is bracketed by two events on the launch stream. vda_profile_stop waits for them and

@@ -75,6 +75,11 @@ SIGNATURES = {
     "vda_layernorm_split_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _vp]),
     "vda_fold_ln_weight": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "vda_fold_convt_weight": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "vda_fold_oc1_weight": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "vda_oc1_mix_combine_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "vda_oc1_mix_ldz": (_i, [_i]),
+    "vda_oc1_mix_frames": (_i, []),
+    "vda_oc1_mix_default": (_i, [_i]),
     "vda_mlp_fused_supported": (_i, [_i, _i]),
     "vda_mlp_permute_w2_f16": (_i, [_vp, _vp, _i, _i, _vp]),
     "vda_mlp_fused_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),

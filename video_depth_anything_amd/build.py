@@ -33,7 +33,10 @@ PER_FILE = {"stitch.hip": ["-ffp-contract=off"], "eval.hip": ["-ffp-contract=off
             "losses.hip": ["-ffp-contract=off"], "resize_u8.hip": ["-ffp-contract=off"]}
 # attention: the softmax row sums are 32 scalar fp32 adds per tile; SLP packs 22 of them into v_pk_add_f32, which costs several
 # times two v_add_f32 next to MFMAs (MI355X_MICROARCH.md, "price of one filler") in a loop that is VALU-bound.
+# oc1_mix: SLP turns the combine pass's fp16-input FMAs (v_fma_mix_f32) into conversions + v_pk_fma_f32: six times the conversions
+# and the registers to hold them.
 PER_PREFIX = {"gemm": ["-fno-slp-vectorize"], "attention.hip": ["-fno-slp-vectorize"], "mlp_fused.hip": ["-fno-slp-vectorize"],
+              "oc1_mix.hip": ["-fno-slp-vectorize"],
               # the dynamic tile draw of gemm8p_kernel.h must stay a plain returning atomic (see the comment there)
               "gemm8p": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]}
 

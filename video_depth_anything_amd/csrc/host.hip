@@ -13,6 +13,7 @@
 // seen), so a steady-state forward is graph-capturable.
 #include "vda_common.h"
 #include <string.h>
+#include <algorithm>
 #include <exception>
 #include <type_traits>
 #include <array>
@@ -195,6 +196,12 @@ struct vda_model {
     // level i - its "l1" / "l2" were then never written and vda_debug_copy rebuilds them. DESIGN section 4 [r11].
     int convt_fold = 1;
     bool folded[2] = {false, false};
+    // vda_set_option("oc1_mix") (environment default VDA_OC1_MIX): refinenet1's out_conv + output_conv1 over the 2x upsample as one GEMM
+    // at half resolution (z, 9 * Fhp channels) + vda_oc1_mix_combine_f16, per chunk of oc1_mix_chunk frames out of one z buffer.
+    // mixed: what the LAST forward did - its "p1c" was then never written and vda_debug_copy rebuilds it. DESIGN section 4 [r12].
+    int oc1_mix = 0;
+    int oc1_mix_chunk = 0;
+    bool mixed = false;
     int mlp_fused = 0;                        // vda_set_option("mlp_fused"): fc1 + GELU + fc2 + residual in one kernel where built (D = 384; needs ln_fold).
                                               // OFF: measured slower than the two GEMM launches (ViT-S clip 8.69 -> 9.00 ms, mlp_fused.hip's header)
     // Split-stream overflow report (ln_fold): one sticky word in pinned host memory, set by the device at the end of a forward whose
@@ -460,6 +467,18 @@ int pack_all(vda_model* h, int prec) {
     for (int i = 0; i < 4; ++i)
         VDA_TRY(conv("rn" + std::to_string(i + 1) + ".w", sc + "layer" + std::to_string(i + 1) + "_rn.weight", Fe, oc[i], Fe, ocp[i]));
     if constexpr (std::is_same<T, h16>::value) {
+        // option oc1_mix: output_conv1 composed with refinenet1's out_conv (vda_fold_oc1_weight), fp16 path only. oc1.w / .b and
+        // ref1.out.* below stay: the fp32 path, the option's off setting and vda_debug_copy's rebuild of "p1c" run them.
+        {
+            T* d = nullptr;
+            const int ldz = vda_oc1_mix_ldz(Fhp);
+            VDA_TRY(mat("oc1.mix.w", (size_t)ldz * Fe, &d));
+            void* bp = nullptr;
+            VDA_TRY(dev_alloc(h, (size_t)ldz * sizeof(float), &bp));
+            h->vec["oc1.mix.b"] = (float*)bp;
+            VDA_TRY(vda_fold_oc1_weight(raw(sc + "output_conv1.weight"), raw(sc + "refinenet1.out_conv.weight"), raw(sc + "refinenet1.out_conv.bias"), d, (float*)bp,
+                                        Fh, Fe, Fhp, ldz, s));
+        }
         // option convt_fold: resize_layers[i] composed with layer{i+1}_rn (vda_fold_convt_weight), fp16 path only. resize{i}.w / .b
         // above stay: the fp32 path, the option's off setting and vda_debug_copy's rebuild of "l1" / "l2" run the unfused pair.
         for (int i = 0; i < 2; ++i) {
@@ -777,9 +796,9 @@ struct Run {
     }
     // util/blocks.py:135-162 with out_conv moved in front of the (commuting) bilinear resize
     // upsample = false: the caller's next conv does the resize itself (vda_conv3x3_up2_f16); *result is the out_conv output at H x Wd
-    // y1: see rcu
+    // y1: see rcu. no_out: stop after resConfUnit2 (never in a dry pass: it lays out and counts the whole block)
     int fusion(int i, const void* x0, const void* x1, int B, int H, int Wd, int Ho, int Wo, int Fe, const std::string& tag, void** result,
-               bool upsample = true, const void* y1 = nullptr) {
+               bool upsample = true, const void* y1 = nullptr, bool no_out = false) {
         const size_t rows = (size_t)B * H * Wd;
         const void* sm = x0;
         if (x1 != nullptr) {
@@ -790,6 +809,10 @@ struct Run {
         void* r = act(sp + "fus_r", rows * Fe);
         VDA_TRY(rcu(i, 2, sm, r, B, H, Wd, Fe));
         void* c = act(upsample ? sp + "fus_c" : tag, rows * Fe);
+        if (no_out) {                          // option oc1_mix: out_conv lives in the composed weight, *result is resConfUnit2's output
+            *result = r;
+            return 0;
+        }
         const std::string k = "ref" + std::to_string(i) + ".out.";
         VDA_TRY(dense(r, W(k + "w"), c, VDA_EPI_BIAS_F16, (int)rows, Fe, Fe, V(k + "b")));
         if (!upsample) {
@@ -1179,12 +1202,29 @@ struct Run {
         // refinenet1's 2x upsample (util/blocks.py:156-160) is folded into output_conv1 on the fp16 path: path_1 at 8 ph x 8 pw (1.4 GB
         // per ViT-L clip) never exists; "p1c" is refinenet1's out_conv output at 4 ph x 4 pw (bilinear and the 1x1 conv commute)
         const bool up_fused = prec == VDA_PREC_F16 && h->oc1_fused != 0 && Fhp <= 128 && Fe % 16 == 0;
-        VDA_TRY(fusion(1, p2, l1r, BT, h1, w1, 2 * h1, 2 * w1, Fe, up_fused ? "p1c" : "p1", &p1, !up_fused, hlanes ? y1[1] : nullptr));
+        // option oc1_mix (where up_fused applies): the channel mixing of out_conv + output_conv1 as ONE GEMM at h1 x w1 into z (9 * Fhp
+        // channels, pack-time weight vda_fold_oc1_weight) and the gather-and-add pass vda_oc1_mix_combine_f16; refinenet1 stops after
+        // resConfUnit2 and "p1c" is never written. z of a whole ViT-L clip is 1.6 GB: the pair runs per chunk of mixF frames out of one
+        // z buffer. The dry pass lays out "p1c" and z and counts the launches of both forms whatever the option says.
+        const int mixF = std::min(BT, h->oc1_mix_chunk > 0 ? h->oc1_mix_chunk : vda_oc1_mix_frames());
+        const int ldz = vda_oc1_mix_ldz(Fhp);      // z's row: 9 * Fhp channels (tap, cout), padded where the GEMM planner then tiles better
+        const bool mix_fits = (double)mixF * h1 * w1 * ldz < 2147483647.0;
+        const bool mix = up_fused && !dry && h->oc1_mix != 0 && mix_fits;
+        if (!dry) h->mixed = mix;
+        VDA_TRY(fusion(1, p2, l1r, BT, h1, w1, 2 * h1, 2 * w1, Fe, up_fused ? "p1c" : "p1", &p1, !up_fused, hlanes ? y1[1] : nullptr, mix));
         // ---- output convs (dpt.py:117-124, dpt_temporal.py:93-100)
         const int hh = 2 * h1, ww = 2 * w1;
         void* o1 = act("o1", (size_t)BT * hh * ww * Fhp);
+        if (up_fused && mix_fits && (mix || dry)) {
+            void* z = act("oc1_z", (size_t)mixF * h1 * w1 * ldz);
+            for (int f0 = 0; f0 < BT; f0 += mixF) {
+                const int nf = std::min(mixF, BT - f0);
+                VDA_TRY(dense((const h16*)p1 + (size_t)f0 * h1 * w1 * Fe, W("oc1.mix.w"), z, VDA_EPI_BIAS_F16, nf * h1 * w1, ldz, Fe, V("oc1.mix.b")));
+                if (!dry) VDA_TRY(vda_oc1_mix_combine_f16(z, V("oc1.b"), (h16*)o1 + (size_t)f0 * hh * ww * Fhp, nf, h1, w1, Fhp, ldz, s));
+            }
+        }
         if (up_fused) {
-            if (!dry) VDA_TRY(vda_conv3x3_up2_f16(p1, W("oc1.w"), V("oc1.b"), o1, BT, h1, w1, Fe, Fhp, Fhp, s));
+            if (!dry && !mix) VDA_TRY(vda_conv3x3_up2_f16(p1, W("oc1.w"), V("oc1.b"), o1, BT, h1, w1, Fe, Fhp, Fhp, s));
         } else
             VDA_TRY(conv3x3(p1, "oc1.w", o1, BT, hh, ww, Fe, Fhp, VDA_EPI_BIAS_F16, 1, V("oc1.b")));
         if (prec == VDA_PREC_F16) {
@@ -1252,6 +1292,8 @@ int convt_fold_default() {
     return v != 0;
 }
 
+int oc1_mix_default(const vda_model* h) { return vda_oc1_mix_default(h->cfg.features); }
+
 int enc_split_default() {
     static const int v = getenv("VDA_ENC_SPLIT") ? atoi(getenv("VDA_ENC_SPLIT")) : 1;      // (A/B through an unmodified caller)
     return v != 0;
@@ -1300,6 +1342,7 @@ extern "C" int vda_create(const vda_config* cfg, vda_model** out) {
     h->enc_split = enc_split_default();
     h->head_lanes = head_lanes_default();
     h->convt_fold = convt_fold_default();
+    h->oc1_mix = oc1_mix_default(h);
     *out = h;
     return 0;
 }
@@ -1489,13 +1532,26 @@ static int vda_debug_copy_impl(vda_model* h, const char* name, void* dst, int64_
         const int BT = h->last_key[0] * h->last_key[1], ph = h->last_key[2] / PATCH, pw = h->last_key[3] / PATCH;
         VDA_TRY(r.convt(r.act(lvl == 0 ? "t0" : "t1", 0), lvl, r.act(name, 0), BT, ph, pw, h->ocp[lvl]));
     }
+    // "p1c" of a forward that ran option oc1_mix was never written either: rebuilt from resConfUnit2's output ("fus_r": refinenet1 is
+    // its last writer) with the out_conv GEMM the unfused forward runs
+    if (strcmp(name, "p1c") == 0 && h->last_key[4] == VDA_PREC_F16 && h->mixed) {
+        VDA_TRY(require_device(h, "vda_debug_copy"));
+        Run r{h, VDA_PREC_F16, false, &it->second, (hipStream_t)stream, (size_t)2};
+        const int BT = h->last_key[0] * h->last_key[1], ph = h->last_key[2] / PATCH, pw = h->last_key[3] / PATCH, Fe = h->cfg.features;
+        const int keep = h->dyn_sched;            // (a launch outside the forward has no dynamic-schedule counters)
+        h->dyn_sched = 0;
+        const int rc = r.dense(r.act("fus_r", 0), r.W("ref1.out.w"), r.act("p1c", 0), VDA_EPI_BIAS_F16, BT * 16 * ph * pw, Fe, Fe, r.V("ref1.out.b"));
+        h->dyn_sched = keep;
+        VDA_TRY(rc);
+    }
     VDA_HIP(hipMemcpyAsync(dst, (char*)h->ws + b->second.first, (size_t)bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return 0;
 }
 
 // Tuning / A-B switches of the launch sequence: "residual_in_ln" (default 0), "ln_fold" (default 1), "dyn_sched" (default 0), "oc1_fused"
 // (default 1), "mlp_fused" (default 0), "head_overlap" (default 0), "enc_split" (default 1, or VDA_ENC_SPLIT), "head_lanes" (default 1,
-// or VDA_HEAD_LANES), "convt_fold" (default 1, or VDA_CONVT_FOLD): see Run::forward.
+// or VDA_HEAD_LANES), "convt_fold" (default 1, or VDA_CONVT_FOLD), "oc1_mix" (default vda_oc1_mix_default, or VDA_OC1_MIX),
+// "oc1_mix_chunk": see Run::forward.
 extern "C" int vda_set_option(vda_model* h, const char* name, int value) {
     VDA_REQUIRE(h && name, "vda_set_option: null argument");
     if (strcmp(name, "residual_in_ln") == 0) {
@@ -1532,6 +1588,15 @@ extern "C" int vda_set_option(vda_model* h, const char* name, int value) {
     }
     if (strcmp(name, "convt_fold") == 0) {               // (< 0: the default, VDA_CONVT_FOLD or 1). The layout does not depend on it.
         h->convt_fold = value < 0 ? convt_fold_default() : value != 0;
+        return 0;
+    }
+    if (strcmp(name, "oc1_mix") == 0) {                  // (< 0: the default, VDA_OC1_MIX or vda_oc1_mix_default). The layout does not depend on it.
+        h->oc1_mix = value < 0 ? oc1_mix_default(h) : value != 0;
+        return 0;
+    }
+    if (strcmp(name, "oc1_mix_chunk") == 0) {            // frames per z buffer (<= 0: vda_oc1_mix_frames())
+        h->oc1_mix_chunk = value;
+        h->layouts.clear();                  // the z buffer is that many frames
         return 0;
     }
     if (strcmp(name, "mlp_fused") == 0) {

@@ -70,6 +70,10 @@ class Engine:
         self.residual_in_ln = False                 # A/B option of the fp16 path (see _forward); off: measured slower end to end
         # the handle's option "convt_fold" (same default): resize_layers[i] + layer{i+1}_rn as one folded GEMM where _fold_level says so
         self.convt_fold = int(os.environ.get("VDA_CONVT_FOLD", "1")) != 0
+        # the handle's option "oc1_mix" (same default, same frames per chunk): refinenet1's out_conv + output_conv1 over the 2x upsample
+        # as the z GEMM at half resolution + vda_oc1_mix_combine_f16
+        self.oc1_mix = _lib.lib.vda_oc1_mix_default(cfg.features) != 0
+        self.oc1_mix_chunk = _lib.lib.vda_oc1_mix_frames()
 
     # ------------------------------------------------------------------ weights
     def load_state_dict(self, sd, strict=True):
@@ -153,6 +157,10 @@ class Engine:
                     w[f"ref{i}.rcu{u}.c{c}.b"] = f32(f"{r}resConfUnit{u}.conv{c}.bias")
         w["oc1.w"] = conv(sc + "output_conv1.weight", Fhp, Fe)
         w["oc1.b"] = padvec(sc + "output_conv1.bias", Fhp)
+        if dt == F16:
+            # composed by the SAME device entry the handle packs with (vda_fold_oc1_weight)
+            w["oc1.mix.w"], w["oc1.mix.b"] = ops.fold_oc1_weight(
+                f32(sc + "output_conv1.weight"), f32(sc + "refinenet1.out_conv.weight"), f32(sc + "refinenet1.out_conv.bias"), Fhp)
         w["oc2.w"] = conv(sc + "output_conv2.0.weight", 32, Fhp)
         w["oc2.b"] = f32(sc + "output_conv2.0.bias")
         w["oc3.w"] = f32(sc + "output_conv2.2.weight").reshape(-1)
@@ -272,8 +280,9 @@ class Engine:
         self.conv3x3(x, f"ref{i}.rcu{u}.c1.w", y, B, H, W, Fe, Fe, _lib.EPI_BIAS_RELU_F16, bias=w[f"ref{i}.rcu{u}.c1.b"], relu_in=True)
         self.conv3x3(y, f"ref{i}.rcu{u}.c2.w", out, B, H, W, Fe, Fe, _lib.EPI_RES_F16, bias=w[f"ref{i}.rcu{u}.c2.b"], res=x, res2=res2)
 
-    def fusion(self, i, x0, x1, B, H, W, Ho, Wo, Fe, tag, upsample=True):
-        """util/blocks.py:135-162 with out_conv moved in front of the resize (upsample=False: the caller's conv resizes itself)."""
+    def fusion(self, i, x0, x1, B, H, W, Ho, Wo, Fe, tag, upsample=True, no_out=False):
+        """util/blocks.py:135-162 with out_conv moved in front of the resize (upsample=False: the caller's conv resizes itself;
+        no_out: stop after resConfUnit2 and return its output - option oc1_mix)."""
         w = self.w
         rows = B * H * W
         s = x0
@@ -283,6 +292,8 @@ class Engine:
         r = self.buf("fus_r", (rows, Fe), self.act)
         self.rcu(i, 2, s, r, B, H, W, Fe)
         c = self.buf("fus_c" if upsample else tag, (rows, Fe), self.act)
+        if no_out:
+            return r
         ops.gemm(r, w[f"ref{i}.out.w"], c, _lib.EPI_BIAS_F16, M=rows, N=Fe, K=Fe, bias=w[f"ref{i}.out.b"])
         if not upsample:
             return c
@@ -440,12 +451,22 @@ class Engine:
         p2 = self.fusion(2, p3, l2r, BT, h2, w2, h1, w1, Fe, "p2")
         # fp16 path: refinenet1's 2x upsample is folded into output_conv1 (vda_conv3x3_up2_f16), as csrc/host.hip does by default
         up_fused = not fp32 and Fhp <= 128
-        p1 = self.fusion(1, p2, l1r, BT, h1, w1, 2 * h1, 2 * w1, Fe, "p1c" if up_fused else "p1", upsample=not up_fused)
+        # option oc1_mix: the z GEMM at h1 x w1 + the combine pass per chunk of frames (csrc/host.hip, Run::forward)
+        mixF = min(BT, self.oc1_mix_chunk)
+        ldz = _lib.lib.vda_oc1_mix_ldz(Fhp)
+        mix = up_fused and self.oc1_mix and mixF * h1 * w1 * ldz < (1 << 31) - 1
+        p1 = self.fusion(1, p2, l1r, BT, h1, w1, 2 * h1, 2 * w1, Fe, "p1c" if up_fused else "p1", upsample=not up_fused, no_out=mix)
 
         # ---- output convs (dpt.py:117-124, dpt_temporal.py:93-100)
         hh, ww = 2 * h1, 2 * w1
         o1 = self.buf("o1", (BT * hh * ww, Fhp), self.act)
-        if up_fused:
+        if mix:
+            z = self.buf("oc1_z", (mixF * h1 * w1, ldz), F16)
+            for f0 in range(0, BT, mixF):
+                nf = min(mixF, BT - f0)
+                ops.gemm(p1[f0 * h1 * w1:(f0 + nf) * h1 * w1], w["oc1.mix.w"], z, _lib.EPI_BIAS_F16, M=nf * h1 * w1, N=ldz, K=Fe, bias=w["oc1.mix.b"])
+                ops.oc1_mix_combine(z, w["oc1.b"], o1[f0 * hh * ww:(f0 + nf) * hh * ww], nf, h1, w1, Fhp, ldz)
+        elif up_fused:
             ops.conv3x3_up2(p1, w["oc1.w"], w["oc1.b"], o1, BT, h1, w1, Fe, Fhp, Fhp)
         else:
             self.conv3x3(p1, "oc1.w", o1, BT, hh, ww, Fe, Fhp, _lib.EPI_BIAS_F16, bias=w["oc1.b"])
@@ -471,6 +492,9 @@ class Engine:
             stages.update(layer_1=(l1, h1, w1, ocp[0]), layer_2=(l2, h2, w2, ocp[1]), layer_3=(l3, ph, pw, ocp[2]),
                           layer_4=(l4, h4, w4, ocp[3]), path_4=(p4, ph, pw, Fe), path_3=(p3, h2, w2, Fe),
                           path_2=(p2, h1, w1, Fe))
-            # (fused path: refinenet1's output before its 2x upsample)
+            # (fused path: refinenet1's output before its 2x upsample; option oc1_mix never ran its out_conv: the unfused GEMM, here)
+            if mix:
+                r1, p1 = p1, self.buf("p1c", (BT * h1 * w1, Fe), self.act)
+                ops.gemm(r1, w["ref1.out.w"], p1, _lib.EPI_BIAS_F16, M=BT * h1 * w1, N=Fe, K=Fe, bias=w["ref1.out.b"])
             stages.update(path_1_half=(p1, h1, w1, Fe)) if up_fused else stages.update(path_1=(p1, hh, ww, Fe))
         return depth

@@ -172,6 +172,32 @@ def fold_convt_weight(wt, bt, wr, cin_pad=None):
     return wf, bc
 
 
+def fold_oc1_weight(w1, wo, bo, cout_pad=None, ldz=None):
+    """output_conv1's weight w1 [Fh,Fe,3,3] composed with refinenet1's out_conv (wo [Fe,Fe,1,1], bo [Fe]) on the device
+    (vda_fold_oc1_weight): (Wz fp16 [ldz, Fe] with rows (tap, cout), zero from 9*cout_pad on, bz fp32 [ldz]) for the z GEMM of option
+    oc1_mix. ldz: z's row, default vda_oc1_mix_ldz(cout_pad)."""
+    _req(w1, F32, "w1"), _req(wo, F32, "wo"), _req(bo, F32, "bo")
+    Fh, Fe = w1.shape[0], w1.shape[1]
+    if tuple(w1.shape[2:]) != (3, 3) or wo.numel() != Fe * Fe or bo.numel() != Fe:
+        raise ValueError("fold_oc1_weight: w1 [Fh,Fe,3,3], wo [Fe,Fe(,1,1)], bo [Fe]")
+    Fhp = Fh if cout_pad is None else cout_pad
+    ldz = lib.vda_oc1_mix_ldz(Fhp) if ldz is None else ldz
+    wz = torch.empty(ldz, Fe, dtype=F16, device=w1.device)
+    bz = torch.empty(ldz, dtype=F32, device=w1.device)
+    check(lib.vda_fold_oc1_weight(_p(w1), _p(wo), _p(bo), _p(wz), _p(bz), Fh, Fe, Fhp, ldz, _stream(w1)), "vda_fold_oc1_weight")
+    return wz, bz
+
+
+def oc1_mix_combine(z, bias, out, B, h, w, Fhp, ldz=None):
+    """out [B,2h,2w,Fhp] = bias + the sum over the 3x3 taps inside the map of the 2x align_corners interpolation of z [B,h,w,ldz]'s
+    tap plane (vda_oc1_mix_combine_f16; ldz defaults to 9*Fhp)."""
+    ldz = 9 * Fhp if ldz is None else ldz
+    _req(z, F16, "z"), _req(out, F16, "out"), _req(bias, F32, "bias")
+    if z.numel() < B * h * w * ldz or out.numel() < B * 4 * h * w * Fhp or (bias is not None and bias.numel() < Fhp):
+        raise ValueError("oc1_mix_combine buffers too small")
+    check(lib.vda_oc1_mix_combine_f16(_p(z), _p(bias), _p(out), B, h, w, Fhp, ldz, _stream(z)), "vda_oc1_mix_combine_f16")
+
+
 def mlp_permute_w2(w2, w2p, D, hidden):
     """fc2's weight [D, hidden] with its hidden columns in the order the fused MLP kernel's register-resident activations have."""
     _req(w2, F16, "w2"), _req(w2p, F16, "w2p")
