@@ -165,7 +165,7 @@ struct vda_model {
     int ocp[4] = {0, 0, 0, 0}, Fhp = 0;
     std::array<int, 5> last_key = {0, 0, 0, 0, -1};
     Profile prof;
-    int residual_in_ln = 0;                   // vda_set_option("residual_in_ln"): see Run::forward (off: measured slower end to end)
+    int residual_in_ln = 0;                   // vda_set_option("residual_in_ln"): see Run::block_deferred (off: measured slower end to end)
     int dyn_sched = 0;                        // vda_set_option("dyn_sched"): dynamic tile draw in the 8-phase GEMM (vda_gemm_args.sched); for
                                               // processes that share the GPU with communication kernels (multi-rank runs turn it on)
     int ln_fold = VDA_LN_FOLD_DEFAULT;        // vda_set_option("ln_fold"): LayerNorm folded into the encoder GEMMs either side of it (fp16 path)
@@ -179,7 +179,7 @@ struct vda_model {
     };
     std::map<hipStream_t, Side> sides;        // one side stream + event pair per caller stream (two forwards may be in flight on two)
     // vda_set_option("enc_split") (environment default VDA_ENC_SPLIT): the fp16 ln_fold encoder runs as two frame halves, half B on a
-    // LANE stream (one per caller stream) forked after the token rows exist and joined back before the head - see Run::forward
+    // LANE stream (one per caller stream) forked after the token rows exist and joined back before the head - see Run::encoder
     // Not while a forward of this handle on ANOTHER caller stream is still in flight (two windows / clips in flight already fill each
     // other's idle time; splitting them too measured -4 %): `tails` holds the end of the last forward enqueued on each caller stream.
     int enc_split = 1;
@@ -187,7 +187,7 @@ struct vda_model {
     std::map<hipStream_t, hipEvent_t> tails;
     // vda_set_option("head_lanes") (environment default VDA_HEAD_LANES): after the encoder's join the head's branches that do not
     // depend on tap 3 (head_early and conv1 of resConfUnit1 in refinenets 3, 2, 1) run on the LANE stream beside the chain
-    // proj3 .. motion module 2 on the caller's stream - see Run::forward. Same exclusions as enc_split, and not together with
+    // proj3 .. motion module 2 on the caller's stream - see Run::head. Same exclusions as enc_split, and not together with
     // head_overlap. ON: in-process A/B, both orders, ViT-L 51.32 -> 50.36 and 51.41 -> 50.47 ms per clip (A/A spread 0.16 ms), ViT-S
     // 8.23 -> 7.83 and 8.20 -> 7.89 ms (A/A spread 0.14 ms); profiles/r10/head_lanes/.
     int head_lanes = 1;
@@ -587,18 +587,42 @@ int open_side(vda_model::Side& sd) {
 }
 
 // ------------------------------------------------------------------ one forward pass
+// the derived sizes of one clip: token grid, token rows, the head's four map sizes and widths
+struct Geom {
+    int B, T, H, W, BT, ph, pw, P, D, NH, Nt, rows, h1, w1, h2, w2, h4, w4, Fe, Fhp;
+    Geom(const vda_model* h, int B_, int T_, int H_, int W_) : B(B_), T(T_), H(H_), W(W_) {
+        BT = B * T, ph = H / PATCH, pw = W / PATCH, P = ph * pw, D = h->cfg.embed_dim, NH = h->cfg.num_heads, Nt = P + 1, rows = BT * Nt;
+        h1 = 4 * ph, w1 = 4 * pw, h2 = 2 * ph, w2 = 2 * pw, h4 = (ph - 1) / 2 + 1, w4 = (pw - 1) / 2 + 1, Fe = h->cfg.features, Fhp = h->Fhp;
+    }
+};
+
 struct Run {
     vda_model* h;
     int prec;                 // VDA_PREC_F16 / VDA_PREC_F32
-    bool dry;                 // sizing pass: record buffer requests, launch nothing
+    // Sizing pass: record buffer requests, launch nothing. The layout must not depend on an option that can change between two
+    // forwards (head_overlap, head_lanes, convt_fold, oc1_mix): wherever such an option picks between two forms, the dry pass
+    // requests the buffers of BOTH and counts the launches of the larger one - the members below say `dry` where they do so.
+    bool dry;
     Layout* lay;
-    hipStream_t s;
-    size_t ab;                // bytes per activation element
+    hipStream_t s;            // the launch stream and ...
+    std::string sp;           // ... the prefix of the helpers' scratch names below, switched together and only by `On`. head_early
+                              // takes "e." in every configuration (one layout, whichever stream it runs on) and so does everything
+                              // option head_lanes issues to the lane stream: work there never shares a block with the caller's stream's
+    const Geom g;
+    const size_t ab;          // bytes per activation element
     int32_t* sched = nullptr; // dynamic-schedule counters: 8 per GEMM launch of the forward, zeroed at its start
     int nsched = 0;           // launches so far (dry pass: the count that sizes the block)
-    std::string sp;           // prefix of the helpers' scratch names below. head_early sets "e." in every configuration (one layout,
-                              // whichever stream it runs on) and option head_lanes sets it for everything it issues to the lane
-                              // stream, so that work there never shares a block with the caller's stream's
+
+    Run(vda_model* h_, int prec_, bool dry_, Layout* lay_, hipStream_t s_, int B, int T, int H, int W)
+        : h(h_), prec(prec_), dry(dry_), lay(lay_), s(s_), g(h_, B, T, H, W), ab(prec_ == VDA_PREC_F32 ? 4 : 2) {}
+    // launches go to `stream`, scratch names take `prefix`, until the scope ends (however it ends)
+    struct On {
+        Run& r;
+        const hipStream_t s;
+        const std::string sp;
+        On(Run& r_, hipStream_t stream, const std::string& prefix) : r(r_), s(r_.s), sp(r_.sp) { r.s = stream, r.sp = prefix; }
+        ~On() { r.s = s, r.sp = sp; }
+    };
 
     void* buf(const std::string& name, size_t elems, size_t esize) {
         const size_t bytes = (elems * esize + 255) & ~(size_t)255;
@@ -631,10 +655,11 @@ struct Run {
         a.zero_page = h->zero_page;
         if (prec == VDA_PREC_F32) return dry ? 0 : bracket(a, nullptr);
         vda_gemm_plan_t plan;
-        if (h->dyn_sched) a.sched = sched;          // (planned as a dynamic-draw launch; each record gets its own counters below)
+        const bool dyn = h->dyn_sched && sched != nullptr;      // (inside a forward that laid the counters out: not vda_debug_copy's rebuilds)
+        if (dyn) a.sched = sched;                   // (planned as a dynamic-draw launch; each record gets its own counters below)
         VDA_TRY(vda_gemm_plan(&a, m_plan, 0, 1, &plan));
         for (int i = 0; i < plan.n; ++i) {
-            if (h->dyn_sched) a.sched = sched + 8 * nsched++;
+            if (dyn) a.sched = sched + 8 * nsched++;
             if (!dry) VDA_TRY(bracket(a, &plan.rec[i]));
         }
         return 0;
@@ -687,9 +712,9 @@ struct Run {
         return gemm(a);
     }
     // resize_layers[i] (ConvTranspose2d, k == stride; dpt.py:71-82) on the ph x pw projection t -> out [B, k*ph, k*pw, C]
-    int convt(const void* t, int i, void* out, int B, int ph, int pw, int C) {
+    int convt(const void* t, int i, void* out) {
         const std::string k = "resize" + std::to_string(i);
-        const int kk = i == 0 ? 4 : 2;
+        const int B = g.BT, ph = g.ph, pw = g.pw, C = h->ocp[i], kk = i == 0 ? 4 : 2;
         vda_gemm_args a = {};
         a.A = t, a.W = W(k + ".w"), a.out = out, a.bias = V(k + ".b");
         a.M = B * ph * pw, a.N = kk * kk * C, a.K = C, a.ldc = C, a.a_mode = VDA_A_DENSE, a.epilogue = VDA_EPI_CONVT_F16;
@@ -699,9 +724,9 @@ struct Run {
     // Option convt_fold at level i: active on the fp16 path when the unfused layer{i+1}_rn conv (on the k*ph x k*pw map) would run on
     // the 8-phase 256 x 256 tile or the 128-row kernel - the two families the folded mode is built for. ViT-S's 64-channel convs run
     // in conv_lds.hip and stay unfused. A dry pass always lays out the unfused pair (the same buffers; the larger launch count).
-    bool fold_level(int i, int B, int ph, int pw, int C, int Fe) const {
+    bool fold_level(int i) const {
         if (dry || prec != VDA_PREC_F16 || !h->convt_fold) return false;
-        const int kk = i == 0 ? 4 : 2, H = kk * ph, Wd = kk * pw;
+        const int B = g.BT, C = h->ocp[i], Fe = g.Fe, kk = i == 0 ? 4 : 2, H = kk * g.ph, Wd = kk * g.pw;
         if ((long long)B * H * Wd * Fe >= (1ll << 31)) return false;
         vda_gemm_args a = {};
         a.M = B * H * Wd, a.N = Fe, a.K = 9 * C, a.lda = a.K, a.ldc = Fe, a.a_mode = VDA_A_CONV3X3, a.epilogue = VDA_EPI_BIAS_F16;
@@ -712,9 +737,9 @@ struct Run {
         return r.family == VDA_GEMM_FAM_128 || (r.family == VDA_GEMM_FAM_8P && r.bm == 256 && r.bn == 256);
     }
     // the folded pair: t [B, ph, pw, C] -> out [B, k*ph, k*pw, Fe] = layer{i+1}_rn(resize_layers[i](t)) in one implicit GEMM
-    int convt_fold(const void* t, int i, void* out, int B, int ph, int pw, int C, int Fe) {
+    int convt_fold(const void* t, int i, void* out) {
         const std::string k = "rn" + std::to_string(i + 1) + ".fold";
-        const int kk = i == 0 ? 4 : 2;
+        const int B = g.BT, ph = g.ph, pw = g.pw, C = h->ocp[i], Fe = g.Fe, kk = i == 0 ? 4 : 2;
         vda_gemm_args a = {};
         a.A = t, a.W = W(k + ".w"), a.out = out, a.bias = V(k + ".b");
         a.M = B * ph * pw, a.N = kk * kk * Fe, a.K = 9 * C, a.ldc = Fe, a.a_mode = VDA_A_CONV3X3, a.epilogue = VDA_EPI_CONVT_FOLD_F16;
@@ -735,35 +760,35 @@ struct Run {
     }
 
     // motion_module.py:102-126,164-177 on token-major x [B*T*hw, C]; returns a new activation buffer
-    int temporal(int m, const void* x, int B, int T, int hw, int Cc, const std::string& tag, void** result) {
+    int temporal(int m, const void* x, int hw, int Cc, const std::string& tag, void** result) {
         const std::string k = "tm" + std::to_string(m) + ".";
-        const int BT = B * T, rows = BT * hw;
+        const int B = g.B, T = g.T, BT = g.BT, rows = BT * hw;
         int chunks = (hw + 31) / 32;
         chunks = chunks < 1 ? 1 : (chunks > 16 ? 16 : chunks);
         float* part = f32(sp + "gn_partial", (size_t)BT * chunks * GN_GROUPS * 2);
-        void* g = act(sp + "tm_g", (size_t)rows * Cc);
+        void* gn = act(sp + "tm_g", (size_t)rows * Cc);
         if (!dry)
-            VDA_TRY(prec == VDA_PREC_F32 ? vda_groupnorm_nhwc_f32((const float*)x, (float*)g, V(k + "gn.w"), V(k + "gn.b"), GN_EPS, BT, hw, Cc, GN_GROUPS, part, chunks, s)
-                                         : vda_groupnorm_nhwc_f16(x, g, V(k + "gn.w"), V(k + "gn.b"), GN_EPS, BT, hw, Cc, GN_GROUPS, part, chunks, s));
+            VDA_TRY(prec == VDA_PREC_F32 ? vda_groupnorm_nhwc_f32((const float*)x, (float*)gn, V(k + "gn.w"), V(k + "gn.b"), GN_EPS, BT, hw, Cc, GN_GROUPS, part, chunks, s)
+                                         : vda_groupnorm_nhwc_f16(x, gn, V(k + "gn.w"), V(k + "gn.b"), GN_EPS, BT, hw, Cc, GN_GROUPS, part, chunks, s));
         float* hs = f32(sp + "tm_hs", (size_t)rows * Cc);
-        VDA_TRY(dense(g, W(k + "in.w"), hs, VDA_EPI_BIAS_F32, rows, Cc, Cc, V(k + "in.b")));
+        VDA_TRY(dense(gn, W(k + "in.w"), hs, VDA_EPI_BIAS_F32, rows, Cc, Cc, V(k + "in.b")));
         void* n = act(sp + "tm_n", (size_t)rows * Cc);
-        void* qkv = act(sp + "tm_qkv", (size_t)rows * 3 * Cc);
-        void* ao = act(sp + "tm_ao", (size_t)rows * Cc);
+        void* tqkv = act(sp + "tm_qkv", (size_t)rows * 3 * Cc);
+        void* tao = act(sp + "tm_ao", (size_t)rows * Cc);
         for (int a = 0; a < 2; ++a) {
             const std::string ka = k + "a" + std::to_string(a) + ".";
             const bool rope = h->cfg.pe_rope != 0;                   // motion_module.py:221-224: no additive encoding, q and k rotated instead
             VDA_TRY(layernorm(hs, n, V(ka + "ln.w"), V(ka + "ln.b"), TMP_LN_EPS, rows, Cc, 0, 0, rope ? nullptr : V(ka + "pe"), hw, T));
-            VDA_TRY(dense(n, W(ka + "qkv.w"), qkv, VDA_EPI_BIAS_F16, rows, 3 * Cc, Cc));
+            VDA_TRY(dense(n, W(ka + "qkv.w"), tqkv, VDA_EPI_BIAS_F16, rows, 3 * Cc, Cc));
             for (int b = 0; b < B && !dry; ++b) {
                 const size_t r0 = (size_t)b * T * hw;
                 if (rope)
-                    VDA_TRY(prec == VDA_PREC_F32 ? vda_rope_qk_f32((float*)qkv + r0 * 3 * Cc, T, hw, Cc, s) : vda_rope_qk_f16((h16*)qkv + r0 * 3 * Cc, T, hw, Cc, s));
+                    VDA_TRY(prec == VDA_PREC_F32 ? vda_rope_qk_f32((float*)tqkv + r0 * 3 * Cc, T, hw, Cc, s) : vda_rope_qk_f16((h16*)tqkv + r0 * 3 * Cc, T, hw, Cc, s));
                 VDA_TRY(prec == VDA_PREC_F32
-                            ? vda_temporal_attention_f32((const float*)qkv + r0 * 3 * Cc, (float*)ao + r0 * Cc, T, hw, Cc, TEMPORAL_HEADS, s)
-                            : vda_temporal_attention_f16((const h16*)qkv + r0 * 3 * Cc, (h16*)ao + r0 * Cc, T, hw, Cc, TEMPORAL_HEADS, s));
+                            ? vda_temporal_attention_f32((const float*)tqkv + r0 * 3 * Cc, (float*)tao + r0 * Cc, T, hw, Cc, TEMPORAL_HEADS, s)
+                            : vda_temporal_attention_f16((const h16*)tqkv + r0 * 3 * Cc, (h16*)tao + r0 * Cc, T, hw, Cc, TEMPORAL_HEADS, s));
             }
-            VDA_TRY(dense(ao, W(ka + "out.w"), hs, VDA_EPI_SCALE_RES_F32, rows, Cc, Cc, V(ka + "out.b"), hs));
+            VDA_TRY(dense(tao, W(ka + "out.w"), hs, VDA_EPI_SCALE_RES_F32, rows, Cc, Cc, V(ka + "out.b"), hs));
         }
         VDA_TRY(layernorm(hs, n, V(k + "ffln.w"), V(k + "ffln.b"), TMP_LN_EPS, rows, Cc));
         void* gg = act(sp + "tm_gg", (size_t)rows * 4 * Cc);
@@ -779,35 +804,36 @@ struct Run {
     // util/blocks.py:68-91: conv2(relu(conv1(relu(x)))) + x (+ res2: the fusion block's skip add)
     // rcu_conv1 is y = relu(conv1(relu(x))) alone. It reads x only, so option head_lanes runs it ahead on the lane stream for
     // resConfUnit1 of refinenets 3, 2, 1 and hands the result to rcu as y1 (!= nullptr: conv1 already done, here is y)
-    int rcu_conv1(int i, int u, const void* x, void* y, int B, int H, int Wd, int Fe) {
+    int rcu_conv1(int i, int u, const void* x, void* y, int H, int Wd) {
         const std::string k = "ref" + std::to_string(i) + ".rcu" + std::to_string(u) + ".";
-        return conv3x3(x, k + "c1.w", y, B, H, Wd, Fe, Fe, VDA_EPI_BIAS_RELU_F16, 1, V(k + "c1.b"), true);
+        return conv3x3(x, k + "c1.w", y, g.BT, H, Wd, g.Fe, g.Fe, VDA_EPI_BIAS_RELU_F16, 1, V(k + "c1.b"), true);
     }
-    int rcu(int i, int u, const void* x, void* out, int B, int H, int Wd, int Fe, const void* res2 = nullptr, const void* y1 = nullptr) {
+    int rcu(int i, int u, const void* x, void* out, int H, int Wd, const void* res2 = nullptr, const void* y1 = nullptr) {
         const std::string k = "ref" + std::to_string(i) + ".rcu" + std::to_string(u) + ".";
         const void* y = y1;
         if (y1 == nullptr) {
-            void* t = act(sp + "rcu_y", (size_t)B * H * Wd * Fe);
-            VDA_TRY(rcu_conv1(i, u, x, t, B, H, Wd, Fe));
+            void* t = act(sp + "rcu_y", (size_t)g.BT * H * Wd * g.Fe);
+            VDA_TRY(rcu_conv1(i, u, x, t, H, Wd));
             y = t;
         }
-        VDA_TRY(conv3x3(y, k + "c2.w", out, B, H, Wd, Fe, Fe, VDA_EPI_RES_F16, 1, V(k + "c2.b"), false, x, res2));
+        VDA_TRY(conv3x3(y, k + "c2.w", out, g.BT, H, Wd, g.Fe, g.Fe, VDA_EPI_RES_F16, 1, V(k + "c2.b"), false, x, res2));
         return 0;
     }
     // util/blocks.py:135-162 with out_conv moved in front of the (commuting) bilinear resize
     // upsample = false: the caller's next conv does the resize itself (vda_conv3x3_up2_f16); *result is the out_conv output at H x Wd
     // y1: see rcu. no_out: stop after resConfUnit2 (never in a dry pass: it lays out and counts the whole block)
-    int fusion(int i, const void* x0, const void* x1, int B, int H, int Wd, int Ho, int Wo, int Fe, const std::string& tag, void** result,
-               bool upsample = true, const void* y1 = nullptr, bool no_out = false) {
+    int fusion(int i, const void* x0, const void* x1, int H, int Wd, int Ho, int Wo, const std::string& tag, void** result, bool upsample = true,
+               const void* y1 = nullptr, bool no_out = false) {
+        const int B = g.BT, Fe = g.Fe;
         const size_t rows = (size_t)B * H * Wd;
         const void* sm = x0;
         if (x1 != nullptr) {
             void* t = act(sp + "fus_s", rows * Fe);
-            VDA_TRY(rcu(i, 1, x1, t, B, H, Wd, Fe, x0, y1));
+            VDA_TRY(rcu(i, 1, x1, t, H, Wd, x0, y1));
             sm = t;
         }
         void* r = act(sp + "fus_r", rows * Fe);
-        VDA_TRY(rcu(i, 2, sm, r, B, H, Wd, Fe));
+        VDA_TRY(rcu(i, 2, sm, r, H, Wd));
         void* c = act(upsample ? sp + "fus_c" : tag, rows * Fe);
         if (no_out) {                          // option oc1_mix: out_conv lives in the composed weight, *result is resConfUnit2's output
             *result = r;
@@ -825,406 +851,417 @@ struct Run {
         return 0;
     }
 
-    int forward(const float* x, float* depth, int B, int T, int H, int Wd) {
-        const vda_config& c = h->cfg;
-        const int BT = B * T, ph = H / PATCH, pw = Wd / PATCH;
-        const int P = ph * pw, D = c.embed_dim, NH = c.num_heads, Nt = P + 1, rows = BT * Nt;
-        bool capturing = false;              // (a captured forward stays one linear stream)
-        if (!dry) {
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(s, &cs) != hipSuccess) {
-                (void)hipGetLastError();          // (e.g. the legacy stream while another stream captures): treated as capturing
-                cs = hipStreamCaptureStatusActive;
+    // ---- streams. `sd`'s stream (created at first use) takes up behind this point of the launch stream. The joins stay explicit
+    // hipEventRecord / hipStreamWaitEvent pairs where they are placed: with head_lanes their placement is the measured part.
+    int fork(vda_model::Side& sd) {
+        VDA_TRY(open_side(sd));
+        VDA_HIP(hipEventRecord(sd.fork, s));
+        VDA_HIP(hipStreamWaitEvent(sd.stream, sd.fork, 0));
+        return 0;
+    }
+    // Options enc_split and head_lanes apply only while this forward is `alone`: not on a capturing stream, and not while a forward
+    // of this handle on another caller stream is in flight (others_idle; vda_model::tails). head_lanes and head_overlap exclude
+    // each other.
+    bool want_lanes() const { return !dry && prec == VDA_PREC_F16 && h->head_lanes != 0 && !h->head_overlap; }
+    bool others_idle() const {
+        for (auto& kv : h->tails) {
+            if (kv.first == s || kv.second == nullptr) continue;
+            if (hipEventQuery(kv.second) != hipSuccess) {
+                (void)hipGetLastError();      // (hipErrorNotReady: that forward is still running)
+                return false;
             }
-            capturing = cs != hipStreamCaptureStatusNone;
         }
-        // dynamic-schedule counters of every GEMM launch below: sized by the dry pass, zeroed here once per forward
-        if (prec == VDA_PREC_F16 && h->dyn_sched) {
-            const int cap = dry ? 4096 : lay->gemm_launches;
-            sched = (int32_t*)buf("sched", (size_t)8 * (cap > 0 ? cap : 1), 4);
-            if (!dry) VDA_HIP(hipMemsetAsync(sched, 0, (size_t)32 * lay->gemm_launches, s));
-            nsched = 0;
+        return true;
+    }
+
+    // ---- the state of one forward
+    struct Part {             // frames [f0, f0 + nf) of the clip, launched on st
+        int f0, nf;
+        hipStream_t st;
+    };
+    Part parts[2] = {};       // the encoder's frame halves (option enc_split), or the whole clip as one part
+    int nparts = 1;
+    bool capturing = false, alone = true;
+    bool fold = false, defer = false, mlp1 = false;      // the encoder's block form, chosen once per forward (encoder)
+    bool xn_ready = false;                               // block_deferred: norm1 of block i already ran (fused with block i-1's fc2 residual)
+    bool early_done = false;                             // head_early ran (or, dry pass, was laid out) under the encoder
+    float *tok = nullptr, *lnpart = nullptr, *lnstat = nullptr;
+    void *thi = nullptr, *tlo = nullptr, *xn = nullptr, *qkv = nullptr, *ao = nullptr, *hid = nullptr, *yb = nullptr;
+    int32_t* ovf = nullptr;
+    int ntap = 0;
+    vda_model::Side *lane = nullptr, *side = nullptr;
+    void *l1r = nullptr, *l2r = nullptr, *l3r = nullptr;   // head_early's results
+
+    // fn(part) for every part, each on its own stream; the callers go op by op (A.qkv, B.qkv, A.attention, B.attention, ...) so
+    // that neither queue runs dry on the host side
+    template <typename Fn>
+    int each(Fn&& fn) {
+        for (int j = 0; j < nparts; ++j) {
+            On on(*this, parts[j].st, sp);
+            VDA_TRY(fn(parts[j]));
         }
-        // ---- encoder (dinov2.py:212-219, dinov2_layers/block.py:105-106)
+        return 0;
+    }
+    int ln_gemm(const std::string& wk, void* out, int epi, int N, const Part& p) {   // LayerNorm(x) @ W^T + b on the hi plane
+        const size_t r0 = (size_t)p.f0 * g.Nt;
+        vda_gemm_args a = {};
+        a.A = (const h16*)thi + r0 * g.D, a.W = W(wk + ".weight.ln"), a.out = (h16*)out + r0 * N, a.bias = V(wk + ".c2"), a.gamma = V(wk + ".c1");
+        a.stats = lnstat + r0 * 2;
+        a.M = p.nf * g.Nt, a.N = N, a.K = g.D, a.a_mode = VDA_A_DENSE, a.epilogue = epi;
+        return gemm(a, nparts > 1 ? g.rows : 0);
+    }
+    int res_gemm(const void* A, const std::string& wk, const std::string& gk, int K, const Part& p) {   // x += gamma * (A @ W^T + b)
+        const size_t r0 = (size_t)p.f0 * g.Nt;
+        const int nr = p.nf * g.Nt, np = g.D / 64, D = g.D;
+        vda_gemm_args a = {};
+        a.A = (const h16*)A + r0 * K, a.W = W(wk + ".weight"), a.bias = V(wk + ".bias"), a.gamma = V(gk);
+        a.out = (h16*)thi + r0 * D, a.out2 = (h16*)tlo + r0 * D, a.res = a.out, a.res2 = a.out2;
+        a.stats = lnpart + r0 * np * 2;      // the part's own [np, nr, 2] block of partial statistics
+        a.pos = lnstat + r0 * 2;             // re-centre by the mean the LayerNorm before this branch saw
+        a.M = nr, a.N = D, a.K = K, a.a_mode = VDA_A_DENSE, a.epilogue = VDA_EPI_SCALE_RES_SPLIT;
+        VDA_TRY(gemm(a, nparts > 1 ? g.rows : 0));
+        // (after the last block nothing reads the statistics: that finalize runs for its overflow check alone, 5 us per clip)
+        if (!dry) VDA_TRY(vda_ln_stats_finalize(lnpart + r0 * np * 2, lnstat + r0 * 2, ENC_LN_EPS, nr, np, ovf, s));
+        return 0;
+    }
+    // the encoder's final norm of the part's rows; out is the whole tensor (group > 0: compacted, group - skip rows per frame)
+    int tap_ln(void* out, int group, int skip, const Part& p) {
+        if (!fold) return layernorm(tok, out, V("norm.w"), V("norm.b"), ENC_LN_EPS, g.rows, g.D, group, skip);   // (one part: the clip)
+        if (dry) return 0;
+        const size_t r0 = (size_t)p.f0 * g.Nt, o0 = group > 0 ? (size_t)p.f0 * (g.Nt / group) * (group - skip) : r0;
+        return vda_layernorm_split_f16((const h16*)thi + r0 * g.D, (const h16*)tlo + r0 * g.D, (h16*)out + o0 * g.D, V("norm.w"), V("norm.b"), ENC_LN_EPS,
+                                       p.nf * g.Nt, g.D, group, skip, s);
+    }
+    int ln_res(const float* gamma, void* out, const float* w, const float* b, int group, int skip) {
+        if (dry) return 0;
+        return vda_layernorm_residual_f32_f16(tok, yb, gamma, out, w, b, ENC_LN_EPS, g.rows, g.D, group, skip, s);
+    }
+    int attention() {
+        if (dry) return 0;
+        return each([&](const Part& p) {
+            const size_t r0 = (size_t)p.f0 * g.Nt;
+            return prec == VDA_PREC_F32 ? vda_attention_f32((const float*)qkv + r0 * 3 * g.D, (float*)ao + r0 * g.D, p.nf, g.Nt, g.NH, s)
+                                        : vda_attention_f16((const h16*)qkv + r0 * 3 * g.D, (h16*)ao + r0 * g.D, p.nf, g.Nt, g.NH, s);
+        });
+    }
+    // use_clstoken (dpt_temporal.py:56-59): the tap becomes GELU(Linear([patch token, cls])); the tap's final norm dropped the cls
+    // row, so norm the whole token matrix again (cls kept) and gather [patch | cls] rows for one K = 2D GEMM
+    int readout(void* tp) {
+        const int D = g.D, P = g.P;
+        void* full = act("rd_full", (size_t)g.rows * D);
+        void* cat = act("rd_cat", (size_t)g.BT * P * 2 * D);
+        const std::string kr = "readout" + std::to_string(ntap);
+        return each([&](const Part& p) -> int {
+            const size_t r0 = (size_t)p.f0 * g.Nt, q0 = (size_t)p.f0 * P;      // (token rows, patch rows) before the part
+            VDA_TRY(tap_ln(full, 0, 0, p));
+            if (!dry)
+                VDA_TRY(prec == VDA_PREC_F32 ? vda_readout_concat_f32((const float*)full + r0 * D, (float*)cat + q0 * 2 * D, p.nf, P, D, s)
+                                             : vda_readout_concat_f16((const h16*)full + r0 * D, (h16*)cat + q0 * 2 * D, p.nf, P, D, s));
+            return dense((const char*)cat + q0 * 2 * D * ab, W(kr + ".w"), (char*)tp + q0 * D * ab, VDA_EPI_BIAS_GELU_F16, p.nf * P, D, 2 * D,
+                         V(kr + ".b"), nullptr, nullptr, 0, nparts > 1 ? g.BT * P : 0);
+        });
+    }
+
+    // ---- one encoder block in each of its three forms; tp != nullptr: the block is a tap, tp takes its final norm (cls dropped)
+    // Option ln_fold (fp16 path, default): no LayerNorm pass at all inside the encoder. The residual stream lives as two fp16
+    // planes (x = hi + lo; VDA_EPI_SCALE_RES_SPLIT reads and writes both, 8 bytes per element like the fp32 stream, and leaves
+    // per-row partial statistics); qkv / fc1 take the hi plane as their A operand with LayerNorm's affine folded into their
+    // weights and apply rstd * (acc - mean * c1) + c2 in their epilogue (VDA_EPI_LN_*). Only the four taps still run a LayerNorm.
+    // mlp1 (option mlp_fused; mlp.py:35-41 + block.py:106): the whole MLP branch in one kernel where vda_mlp_fused_f16 is built for
+    // the width (ViT-S): hid stays in registers, one launch instead of two. Off by default: in-process A/B it loses to the two launches.
+    int block_split(int i, void* tp) {
+        const std::string k = "b" + std::to_string(i) + ".";
+        const int D = g.D;
+        VDA_TRY(each([&](const Part& p) { return ln_gemm(k + "attn.qkv", qkv, VDA_EPI_LN_BIAS_F16, 3 * D, p); }));
+        VDA_TRY(attention());
+        VDA_TRY(each([&](const Part& p) { return res_gemm(ao, k + "attn.proj", k + "ls1.gamma", D, p); }));
+        if (mlp1) {
+            if (!dry) {
+                VDA_TRY(vda_mlp_fused_f16(thi, lnstat, W(k + "mlp.fc1.weight.ln"), V(k + "mlp.fc1.c1"), V(k + "mlp.fc1.c2"), W(k + "mlp.fc2.weight.perm"),
+                                          V(k + "mlp.fc2.bias"), V(k + "ls2.gamma"), thi, tlo, lnpart, g.rows, D, 4 * D, g.rows, s));
+                VDA_TRY(vda_ln_stats_finalize(lnpart, lnstat, ENC_LN_EPS, g.rows, D / 64, ovf, s));
+            }
+        } else {
+            VDA_TRY(each([&](const Part& p) { return ln_gemm(k + "mlp.fc1", hid, VDA_EPI_LN_GELU_F16, 4 * D, p); }));
+            VDA_TRY(each([&](const Part& p) { return res_gemm(hid, k + "mlp.fc2", k + "ls2.gamma", 4 * D, p); }));
+        }
+        if (tp != nullptr) VDA_TRY(each([&](const Part& p) { return tap_ln(tp, g.Nt, 1, p); }));
+        return 0;
+    }
+    // The fp32 residual stream (ln_fold off, and the fp32 precision): the residual add of a block's two projections (attn.proj,
+    // mlp.fc2) is the GEMM's own fp32 in-place epilogue (VDA_EPI_SCALE_RES_F32)
+    int block_f32_stream(int i, void* tp) {
+        const std::string k = "b" + std::to_string(i) + ".";
+        const int D = g.D, rows = g.rows;
+        VDA_TRY(layernorm(tok, xn, V(k + "norm1.weight"), V(k + "norm1.bias"), ENC_LN_EPS, rows, D));
+        VDA_TRY(dense(xn, W(k + "attn.qkv.weight"), qkv, VDA_EPI_BIAS_F16, rows, 3 * D, D, V(k + "attn.qkv.bias")));
+        VDA_TRY(attention());
+        VDA_TRY(dense(ao, W(k + "attn.proj.weight"), tok, VDA_EPI_SCALE_RES_F32, rows, D, D, V(k + "attn.proj.bias"), tok, V(k + "ls1.gamma")));
+        VDA_TRY(layernorm(tok, xn, V(k + "norm2.weight"), V(k + "norm2.bias"), ENC_LN_EPS, rows, D));
+        VDA_TRY(dense(xn, W(k + "mlp.fc1.weight"), hid, VDA_EPI_BIAS_GELU_F16, rows, 4 * D, D, V(k + "mlp.fc1.bias")));
+        VDA_TRY(dense(hid, W(k + "mlp.fc2.weight"), tok, VDA_EPI_SCALE_RES_F32, rows, D, 4 * D, V(k + "mlp.fc2.bias"), tok, V(k + "ls2.gamma")));
+        if (tp != nullptr) VDA_TRY(tap_ln(tp, g.Nt, 1, parts[0]));
+        return 0;
+    }
+    // Option residual_in_ln (fp16 path): the projection stores its bias-added output y as fp16 and x += gamma * y rides on the
+    // LayerNorm that follows (vda_layernorm_residual_f32_f16). Measured on ViT-L 1x32x518x518: the projection GEMMs get 15 % faster
+    // (1040 vs 902 TFLOP/s) but the LayerNorm doubles its bytes (12 B per element at 5.05 TB/s): +1.1 ms per clip net (57.9 vs
+    // 56.8 ms). Kept as an A/B option, off.
+    int block_deferred(int i, void* tp) {
+        const std::string k = "b" + std::to_string(i) + ".";
+        const int D = g.D, rows = g.rows;
+        const bool last = i + 1 == h->cfg.depth;
+        if (!xn_ready) VDA_TRY(layernorm(tok, xn, V(k + "norm1.weight"), V(k + "norm1.bias"), ENC_LN_EPS, rows, D));
+        xn_ready = false;
+        VDA_TRY(dense(xn, W(k + "attn.qkv.weight"), qkv, VDA_EPI_BIAS_F16, rows, 3 * D, D, V(k + "attn.qkv.bias")));
+        VDA_TRY(attention());
+        VDA_TRY(dense(ao, W(k + "attn.proj.weight"), yb, VDA_EPI_BIAS_F16, rows, D, D, V(k + "attn.proj.bias")));
+        VDA_TRY(ln_res(V(k + "ls1.gamma"), xn, V(k + "norm2.weight"), V(k + "norm2.bias"), 0, 0));
+        VDA_TRY(dense(xn, W(k + "mlp.fc1.weight"), hid, VDA_EPI_BIAS_GELU_F16, rows, 4 * D, D, V(k + "mlp.fc1.bias")));
+        VDA_TRY(dense(hid, W(k + "mlp.fc2.weight"), yb, VDA_EPI_BIAS_F16, rows, D, 4 * D, V(k + "mlp.fc2.bias")));
+        if (last && tp != nullptr) return ln_res(V(k + "ls2.gamma"), tp, V("norm.w"), V("norm.b"), g.Nt, 1);     // residual + final norm, cls dropped
+        const std::string kn = "b" + std::to_string(last ? i : i + 1) + ".";                                       // residual + the next block's norm1
+        VDA_TRY(ln_res(V(k + "ls2.gamma"), xn, V(kn + "norm1.weight"), V(kn + "norm1.bias"), 0, 0));
+        xn_ready = true;
+        if (tp != nullptr) VDA_TRY(tap_ln(tp, g.Nt, 1, parts[0]));
+        return 0;
+    }
+
+    // patch embedding (dinov2.py:212-219): tok = the clip's token rows, fp32
+    int embed(const float* x) {
+        const int BT = g.BT, P = g.P, D = g.D;
         void* a0 = act("a0", (size_t)BT * P * KPATCH);
         if (!dry) {
             // the K padding (588 -> 640) must be zero: the buffer is shared with nothing else, but the block is caller memory
             VDA_HIP(hipMemsetAsync(a0, 0, (size_t)BT * P * KPATCH * ab, s));
-            VDA_TRY(prec == VDA_PREC_F32 ? vda_patchify_f32_f32(x, (float*)a0, BT, H, Wd, KPATCH, s) : vda_patchify_f32_f16(x, a0, BT, H, Wd, KPATCH, s));
+            VDA_TRY(prec == VDA_PREC_F32 ? vda_patchify_f32_f32(x, (float*)a0, BT, g.H, g.W, KPATCH, s) : vda_patchify_f32_f16(x, a0, BT, g.H, g.W, KPATCH, s));
         }
-        float* tok = f32("tok", (size_t)rows * D);
-        const float* pos = dry ? nullptr : h->pos_cache.at({H, Wd});
-        {
-            vda_gemm_args a = {};
-            a.A = a0, a.W = W("patch.w"), a.out = tok, a.bias = V("patch.b"), a.pos = pos;
-            a.M = BT * P, a.N = D, a.K = KPATCH, a.a_mode = VDA_A_DENSE, a.epilogue = VDA_EPI_PATCH_F32, a.P = P;
-            VDA_TRY(gemm(a));
-        }
+        tok = f32("tok", (size_t)g.rows * D);
+        const float* pos = dry ? nullptr : h->pos_cache.at({g.H, g.W});
+        vda_gemm_args a = {};
+        a.A = a0, a.W = W("patch.w"), a.out = tok, a.bias = V("patch.b"), a.pos = pos;
+        a.M = BT * P, a.N = D, a.K = KPATCH, a.a_mode = VDA_A_DENSE, a.epilogue = VDA_EPI_PATCH_F32, a.P = P;
+        VDA_TRY(gemm(a));
         if (!dry) VDA_TRY(vda_cls_rows_f32(tok, V("cls"), pos, BT, P, D, s));
-        void* xn = act("xn", (size_t)rows * D);
-        void* qkv = act("qkv", (size_t)rows * 3 * D);
-        void* ao = act("ao", (size_t)rows * D);
-        void* hid = nullptr;                     // (allocated below, unless the fused MLP kernel makes it unnecessary)
-        void* taps[4] = {nullptr, nullptr, nullptr, nullptr};
-        int ntap = 0;
-        // Residual add of a block's two projections (attn.proj, mlp.fc2). Default: the GEMM's own fp32 in-place epilogue
-        // (VDA_EPI_SCALE_RES_F32). Option residual_in_ln (fp16 path): the projection stores its bias-added output y as fp16 and
-        // x += gamma * y rides on the LayerNorm that follows (vda_layernorm_residual_f32_f16). Measured on ViT-L 1x32x518x518: the
-        // projection GEMMs get 15 % faster (1040 vs 902 TFLOP/s) but the LayerNorm doubles its bytes (12 B per element at
-        // 5.05 TB/s): +1.1 ms per clip net (57.9 vs 56.8 ms). Kept as an A/B option, off.
-        const bool defer = prec == VDA_PREC_F16 && h->residual_in_ln != 0;
-        // Option ln_fold (fp16 path, default): no LayerNorm pass at all inside the encoder. The residual stream lives as two fp16
-        // planes (x = hi + lo; VDA_EPI_SCALE_RES_SPLIT reads and writes both, 8 bytes per element like the fp32 stream, and leaves
-        // per-row partial statistics); qkv / fc1 take the hi plane as their A operand with LayerNorm's affine folded into their
-        // weights and apply rstd * (acc - mean * c1) + c2 in their epilogue (VDA_EPI_LN_*). Only the four taps still run a LayerNorm.
-        const bool fold = prec == VDA_PREC_F16 && h->ln_fold != 0 && !defer && D % 64 == 0;
-        // mlp.py:35-41 + block.py:106: the whole MLP branch in one kernel where vda_mlp_fused_f16 is built for the width (ViT-S): hid
-        // stays in registers, one launch instead of two. An OPTION, off by default: in-process A/B it loses to the two launches.
-        const bool mlp1 = fold && h->mlp_fused != 0 && vda_mlp_fused_supported(D, 4 * D) != 0;
-        if (!mlp1) hid = act("hid", (size_t)rows * 4 * D);
-        void* thi = fold ? buf("tok_hi", (size_t)rows * D, 2) : nullptr;
-        void* tlo = fold ? buf("tok_lo", (size_t)rows * D, 2) : nullptr;
-        float* lnpart = fold ? f32("ln_part", (size_t)rows * (D / 64) * 2) : nullptr;
-        float* lnstat = fold ? f32("ln_stat", (size_t)rows * 2) : nullptr;
+        return 0;
+    }
+    // ---- encoder (dinov2.py:212-219, dinov2_layers/block.py:105-106) -> taps[0..3], the final-norm'd patch tokens of the tap blocks
+    // Frame halves (option enc_split; fp16 ln_fold path). The encoder is exactly per frame: attention mixes the tokens of one frame
+    // only and every GEMM / LayerNorm row is independent. So frames [0, F) and [F, BT) run as two launch chains, half A on the
+    // caller's stream and half B on the handle's lane stream, and each chain's kernels fill the tail rounds, launch boundaries and
+    // small launches the other leaves idle. Every op is a row range of the same buffers, and each GEMM half is dispatched as the
+    // whole-clip GEMM would be (gemm's m_plan): the result is bit-identical to one chain. The head (its motion modules mix frames) runs
+    // after the join at full T. A captured forward keeps one stream (a linear graph); the dry pass takes the uncaptured decision
+    // (the larger launch count, which sizes the dynamic-schedule counters).
+    int encoder(const float* x, void** taps) {
+        const vda_config& c = h->cfg;
+        const int BT = g.BT, D = g.D, rows = g.rows;
+        VDA_TRY(embed(x));
+        xn = act("xn", (size_t)rows * D);
+        qkv = act("qkv", (size_t)rows * 3 * D);
+        ao = act("ao", (size_t)rows * D);
+        defer = prec == VDA_PREC_F16 && h->residual_in_ln != 0;
+        fold = prec == VDA_PREC_F16 && h->ln_fold != 0 && !defer && D % 64 == 0;
+        mlp1 = fold && h->mlp_fused != 0 && vda_mlp_fused_supported(D, 4 * D) != 0;
+        hid = mlp1 ? nullptr : act("hid", (size_t)rows * 4 * D);      // (the fused MLP kernel makes it unnecessary)
+        thi = fold ? buf("tok_hi", (size_t)rows * D, 2) : nullptr;
+        tlo = fold ? buf("tok_lo", (size_t)rows * D, 2) : nullptr;
+        lnpart = fold ? f32("ln_part", (size_t)rows * (D / 64) * 2) : nullptr;
+        lnstat = fold ? f32("ln_stat", (size_t)rows * 2) : nullptr;
         // overflow flag of this forward (see vda_model::ovf_host): raised by vda_ln_stats_finalize when a row's statistics are not
         // finite, i.e. when a token moved further than 65 504 from its own mean and saturated the fp16 hi plane
-        int32_t* ovf = fold ? (int32_t*)buf("overflow", 1, 4) : nullptr;
-        if (fold && !dry) VDA_HIP(hipMemsetAsync(ovf, 0, 4, s));
-        // The planes hold every token RELATIVE TO ITS OWN MEAN: taken out here, and again by every residual epilogue (a.pos below:
-        // the mean the preceding LayerNorm statistics found), so the operand plane's fp16 rounding is relative to the token's
-        // spread whatever offset the stream carries (tests/_outliers.py "offset": mean / sigma ~ 20 cost 15x the standalone
-        // LayerNorm's error before this). Every reader of the stream is a LayerNorm - invariant to a per-row shift.
-        if (fold && !dry) VDA_TRY(vda_split_center_stats_f32(tok, thi, tlo, lnstat, ENC_LN_EPS, rows, D, s));
-        // ---- frame halves (option enc_split; fp16 ln_fold path). The encoder is exactly per frame: attention mixes the tokens of one
-        // frame only and every GEMM / LayerNorm row is independent. So frames [0, F) and [F, BT) run as two launch chains, half A on the
-        // caller's stream and half B on the handle's lane stream, and each chain's kernels fill the tail rounds, launch boundaries and
-        // small launches the other leaves idle. Every op is a row range of the same buffers, and each GEMM half is dispatched as the
-        // whole-clip GEMM would be (gemm's m_plan): the result is bit-identical to one chain. The head (its motion modules mix frames) runs
-        // after the join at full T. A captured forward keeps one stream (a linear graph); the dry pass takes the uncaptured decision
-        // (the larger launch count, which sizes the dynamic-schedule counters).
-        struct Part {
-            int f0, nf;
-            hipStream_t st;
-        };
-        Part parts[2] = {{0, BT, s}, {0, 0, nullptr}};
-        int nparts = 1;
-        vda_model::Side* lane = nullptr;
-        bool split = fold && !mlp1 && h->enc_split != 0 && BT >= 2;
-        // Option head_lanes (fp16 path; below, after the encoder's join) puts two branches of the head on the same two streams.
-        // Neither option applies (`alone` is false) on a capturing stream or while a forward of this handle on another caller stream
-        // is in flight; head_lanes and head_overlap exclude each other.
-        const bool want_lanes = !dry && prec == VDA_PREC_F16 && h->head_lanes != 0 && !h->head_overlap;
-        bool alone = !capturing;
-        if (!dry && (split || want_lanes))
-            for (auto& kv : h->tails) {
-                if (!alone) break;
-                if (kv.first == s || kv.second == nullptr) continue;
-                if (hipEventQuery(kv.second) != hipSuccess) {
-                    (void)hipGetLastError();      // (hipErrorNotReady: that forward is still running)
-                    alone = false;
-                }
-            }
-        if (!dry) split = split && alone;
-        const bool hlanes = want_lanes && alone;
-        if (split) {
+        ovf = fold ? (int32_t*)buf("overflow", 1, 4) : nullptr;
+        yb = defer ? act("ybuf", (size_t)rows * D) : nullptr;
+        if (fold && !dry) {
+            VDA_HIP(hipMemsetAsync(ovf, 0, 4, s));
+            // The planes hold every token RELATIVE TO ITS OWN MEAN: taken out here, and again by every residual epilogue (res_gemm's
+            // a.pos: the mean the preceding LayerNorm statistics found), so the operand plane's fp16 rounding is relative to the
+            // token's spread whatever offset the stream carries (tests/_outliers.py "offset": mean / sigma ~ 20 cost 15x the standalone
+            // LayerNorm's error before this). Every reader of the stream is a LayerNorm - invariant to a per-row shift.
+            VDA_TRY(vda_split_center_stats_f32(tok, thi, tlo, lnstat, ENC_LN_EPS, rows, D, s));
+        }
+        parts[0] = {0, BT, s};
+        const bool want_split = fold && !mlp1 && h->enc_split != 0 && BT >= 2;
+        alone = !capturing && (dry || !(want_split || want_lanes()) || others_idle());
+        if (want_split && alone) {
             parts[0] = {0, BT / 2, s};
             parts[1] = {BT / 2, BT - BT / 2, s};
             nparts = 2;
             if (!dry) {
-                vda_model::Side& ln = h->lanes[s];
-                VDA_TRY(open_side(ln));
-                lane = &ln;
-                parts[1].st = ln.stream;
-                VDA_HIP(hipEventRecord(ln.fork, s));                   // the centred token planes and their statistics exist
-                VDA_HIP(hipStreamWaitEvent(ln.stream, ln.fork, 0));
+                lane = &h->lanes[s];
+                VDA_TRY(fork(*lane));                                  // the centred token planes and their statistics exist
+                parts[1].st = lane->stream;
             }
         }
-        // fn(part) for every part, each on its own stream; the callers go op by op (A.qkv, B.qkv, A.attention, B.attention, ...) so
-        // that neither queue runs dry on the host side
-        auto each = [&](auto&& fn) -> int {
-            const hipStream_t keep = s;
-            int rc = 0;
-            for (int j = 0; j < nparts && rc == 0; ++j) {
-                s = parts[j].st;
-                rc = fn(parts[j]);
-            }
-            s = keep;
-            return rc;
-        };
-        auto ln_gemm = [&](const std::string& wk, void* out, int epi, int N, const Part& p) -> int {   // LayerNorm(x) @ W^T + b on the hi plane
-            const size_t r0 = (size_t)p.f0 * Nt;
-            vda_gemm_args a = {};
-            a.A = (const h16*)thi + r0 * D, a.W = W(wk + ".weight.ln"), a.out = (h16*)out + r0 * N, a.bias = V(wk + ".c2"), a.gamma = V(wk + ".c1");
-            a.stats = lnstat + r0 * 2;
-            a.M = p.nf * Nt, a.N = N, a.K = D, a.a_mode = VDA_A_DENSE, a.epilogue = epi;
-            return gemm(a, nparts > 1 ? rows : 0);
-        };
-        auto res_gemm = [&](const void* A, const std::string& wk, const std::string& gk, int K, bool stats_next, const Part& p) -> int {   // x += gamma * (A @ W^T + b)
-            const size_t r0 = (size_t)p.f0 * Nt;
-            const int nr = p.nf * Nt, np = D / 64;
-            vda_gemm_args a = {};
-            a.A = (const h16*)A + r0 * K, a.W = W(wk + ".weight"), a.bias = V(wk + ".bias"), a.gamma = V(gk);
-            a.out = (h16*)thi + r0 * D, a.out2 = (h16*)tlo + r0 * D, a.res = a.out, a.res2 = a.out2;
-            a.stats = lnpart + r0 * np * 2;      // the part's own [np, nr, 2] block of partial statistics
-            a.pos = lnstat + r0 * 2;             // re-centre by the mean the LayerNorm before this branch saw
-            a.M = nr, a.N = D, a.K = K, a.a_mode = VDA_A_DENSE, a.epilogue = VDA_EPI_SCALE_RES_SPLIT;
-            VDA_TRY(gemm(a, nparts > 1 ? rows : 0));
-            // (after the last block nothing reads the statistics: that finalize runs for its overflow check alone, 5 us per clip)
-            (void)stats_next;
-            if (!dry) VDA_TRY(vda_ln_stats_finalize(lnpart + r0 * np * 2, lnstat + r0 * 2, ENC_LN_EPS, nr, np, ovf, s));
-            return 0;
-        };
-        // final norm of the part's rows; out is the whole tensor (group > 0: compacted, group - skip rows per frame)
-        auto tap_ln = [&](void* out, int group, int skip, const Part& p) -> int {
-            if (dry) return 0;
-            const size_t r0 = (size_t)p.f0 * Nt, o0 = group > 0 ? (size_t)p.f0 * (Nt / group) * (group - skip) : r0;
-            const int nr = p.nf * Nt;
-            return fold ? vda_layernorm_split_f16((const h16*)thi + r0 * D, (const h16*)tlo + r0 * D, (h16*)out + o0 * D, V("norm.w"), V("norm.b"), ENC_LN_EPS, nr, D,
-                                                  group, skip, s)
-                        : vda_layernorm_f32_f16(tok + r0 * D, (h16*)out + o0 * D, V("norm.w"), V("norm.b"), ENC_LN_EPS, nr, D, group, skip, nullptr, 0, 0, s);
-        };
-        void* yb = defer ? act("ybuf", (size_t)rows * D) : nullptr;
-        auto ln_res = [&](const float* gamma, void* out, const float* w, const float* b, int group, int skip) -> int {
-            if (dry) return 0;
-            return vda_layernorm_residual_f32_f16(tok, yb, gamma, out, w, b, ENC_LN_EPS, rows, D, group, skip, s);
-        };
-        bool xn_ready = false;                 // norm1 of block i already ran (fused with block i-1's fc2 residual)
-        // ---- the part of the head that needs taps 0..2 only (dpt_temporal.py:55-69 for i = 0, 1, 2; :75 motion module 0 on layer_3;
-        // :78-80 layer{1,2,3}_rn): 3.8 of the head's 12.5 TFLOP at ViT-L. Option head_overlap runs it on a SIDE stream as soon as tap 2
-        // exists, under the remaining encoder blocks (ViT-L: blocks 18-23), so that its kernels fill the tail rounds and epilogue
-        // bursts of theirs - what two clips in flight do for a video, inside ONE clip. Same kernels, same arithmetic: bit-identical.
-        const int* ocp = h->ocp;
-        const int Fe = c.features, Fhp = h->Fhp;
-        const int h1 = 4 * ph, w1 = 4 * pw, h2 = 2 * ph, w2 = 2 * pw, h4 = (ph - 1) / 2 + 1, w4 = (pw - 1) / 2 + 1;
-        void *l1r = nullptr, *l2r = nullptr, *l3r = nullptr;
-        // part: 1 = the tap 0 / tap 1 chains (-> l1r, l2r), 2 = the tap 2 chain (-> l3r), 3 = both, in the order of one chain. Its
-        // motion module takes scratch blocks of its own ("e."): with option head_lanes motion module 1 runs beside it.
-        auto head_early = [&](int part = 3) -> int {
-            const std::string keep_sp = sp;
-            sp = "e.";
-            void* l1 = act("l1", (size_t)BT * h1 * w1 * ocp[0]);
-            void* l2 = act("l2", (size_t)BT * h2 * w2 * ocp[1]);
-            void* l3t = nullptr;
-            // option convt_fold: a folded level skips its ConvTranspose here and runs the folded GEMM where layer{i+1}_rn stood
-            const bool f0 = fold_level(0, BT, ph, pw, ocp[0], Fe), f1 = fold_level(1, BT, ph, pw, ocp[1], Fe);
-            void *t0 = nullptr, *t1 = nullptr;
-            if (part & 1) {
-                if (!dry) h->folded[0] = f0, h->folded[1] = f1;
-                t0 = act("t0", (size_t)BT * P * ocp[0]);
-                VDA_TRY(dense(taps[0], W("proj0.w"), t0, VDA_EPI_BIAS_F16, BT * P, ocp[0], D, V("proj0.b")));
-                if (!f0) VDA_TRY(convt(t0, 0, l1, BT, ph, pw, ocp[0]));
-                t1 = act("t1", (size_t)BT * P * ocp[1]);
-                VDA_TRY(dense(taps[1], W("proj1.w"), t1, VDA_EPI_BIAS_F16, BT * P, ocp[1], D, V("proj1.b")));
-                if (!f1) VDA_TRY(convt(t1, 1, l2, BT, ph, pw, ocp[1]));
-            }
-            if (part & 2) {
-                void* l3 = act("l3", (size_t)BT * P * ocp[2]);
-                VDA_TRY(dense(taps[2], W("proj2.w"), l3, VDA_EPI_BIAS_F16, BT * P, ocp[2], D, V("proj2.b")));
-                VDA_TRY(temporal(0, l3, B, T, P, ocp[2], "l3t", &l3t));              // dpt_temporal.py:75
-            }
-            if (part & 1) {
-                l1r = act("l1r", (size_t)BT * h1 * w1 * Fe);
-                if (f0) VDA_TRY(convt_fold(t0, 0, l1r, BT, ph, pw, ocp[0], Fe));
-                else VDA_TRY(conv3x3(l1, "rn1.w", l1r, BT, h1, w1, ocp[0], Fe, VDA_EPI_BIAS_F16, 1, nullptr));
-                l2r = act("l2r", (size_t)BT * h2 * w2 * Fe);
-                if (f1) VDA_TRY(convt_fold(t1, 1, l2r, BT, ph, pw, ocp[1], Fe));
-                else VDA_TRY(conv3x3(l2, "rn2.w", l2r, BT, h2, w2, ocp[1], Fe, VDA_EPI_BIAS_F16, 1, nullptr));
-            }
-            if (part & 2) {
-                l3r = act("l3r", (size_t)BT * P * Fe);
-                VDA_TRY(conv3x3(l3t, "rn3.w", l3r, BT, ph, pw, ocp[2], Fe, VDA_EPI_BIAS_F16, 1, nullptr));
-            }
-            sp = keep_sp;
-            return 0;
-        };
-        bool early_done = false;
-        vda_model::Side* side = nullptr;
         for (int i = 0; i < c.depth; ++i) {
-            const std::string k = "b" + std::to_string(i) + ".";
-            if (fold) {
-                VDA_TRY(each([&](const Part& p) { return ln_gemm(k + "attn.qkv", qkv, VDA_EPI_LN_BIAS_F16, 3 * D, p); }));
-            } else {
-                if (!xn_ready) VDA_TRY(layernorm(tok, xn, V(k + "norm1.weight"), V(k + "norm1.bias"), ENC_LN_EPS, rows, D));
-                xn_ready = false;
-                VDA_TRY(dense(xn, W(k + "attn.qkv.weight"), qkv, VDA_EPI_BIAS_F16, rows, 3 * D, D, V(k + "attn.qkv.bias")));
-            }
-            if (!dry)
-                VDA_TRY(each([&](const Part& p) {
-                    const size_t r0 = (size_t)p.f0 * Nt;
-                    return prec == VDA_PREC_F32 ? vda_attention_f32((const float*)qkv + r0 * 3 * D, (float*)ao + r0 * D, p.nf, Nt, NH, s)
-                                                : vda_attention_f16((const h16*)qkv + r0 * 3 * D, (h16*)ao + r0 * D, p.nf, Nt, NH, s);
-                }));
-            if (fold) {
-                VDA_TRY(each([&](const Part& p) { return res_gemm(ao, k + "attn.proj", k + "ls1.gamma", D, true, p); }));
-            } else if (defer) {
-                VDA_TRY(dense(ao, W(k + "attn.proj.weight"), yb, VDA_EPI_BIAS_F16, rows, D, D, V(k + "attn.proj.bias")));
-                VDA_TRY(ln_res(V(k + "ls1.gamma"), xn, V(k + "norm2.weight"), V(k + "norm2.bias"), 0, 0));
-            } else {
-                VDA_TRY(dense(ao, W(k + "attn.proj.weight"), tok, VDA_EPI_SCALE_RES_F32, rows, D, D, V(k + "attn.proj.bias"), tok, V(k + "ls1.gamma")));
-                VDA_TRY(layernorm(tok, xn, V(k + "norm2.weight"), V(k + "norm2.bias"), ENC_LN_EPS, rows, D));
-            }
-            if (mlp1) {
-                if (!dry)
-                    VDA_TRY(vda_mlp_fused_f16(thi, lnstat, W(k + "mlp.fc1.weight.ln"), V(k + "mlp.fc1.c1"), V(k + "mlp.fc1.c2"), W(k + "mlp.fc2.weight.perm"),
-                                              V(k + "mlp.fc2.bias"), V(k + "ls2.gamma"), thi, tlo, lnpart, rows, D, 4 * D, rows, s));
-            } else if (fold) VDA_TRY(each([&](const Part& p) { return ln_gemm(k + "mlp.fc1", hid, VDA_EPI_LN_GELU_F16, 4 * D, p); }));
-            else VDA_TRY(dense(xn, W(k + "mlp.fc1.weight"), hid, VDA_EPI_BIAS_GELU_F16, rows, 4 * D, D, V(k + "mlp.fc1.bias")));
             bool is_tap = false;
             for (int t = 0; t < 4; ++t) is_tap = is_tap || c.taps[t] == i;
-            const bool last = i + 1 == c.depth;
-            void* tp = (is_tap && ntap < 4) ? act("tap" + std::to_string(ntap), (size_t)BT * P * D) : nullptr;
-            if (fold) {
-                if (mlp1) {
-                    if (!dry) VDA_TRY(vda_ln_stats_finalize(lnpart, lnstat, ENC_LN_EPS, rows, D / 64, ovf, s));
-                } else {
-                    VDA_TRY(each([&](const Part& p) { return res_gemm(hid, k + "mlp.fc2", k + "ls2.gamma", 4 * D, !last, p); }));
-                }
-                if (tp != nullptr) VDA_TRY(each([&](const Part& p) { return tap_ln(tp, Nt, 1, p); }));     // final norm, cls dropped
-            } else if (defer) {
-                VDA_TRY(dense(hid, W(k + "mlp.fc2.weight"), yb, VDA_EPI_BIAS_F16, rows, D, 4 * D, V(k + "mlp.fc2.bias")));
-                if (last && tp != nullptr) {
-                    VDA_TRY(ln_res(V(k + "ls2.gamma"), tp, V("norm.w"), V("norm.b"), Nt, 1));            // residual + final norm, cls dropped
-                } else {
-                    const std::string kn = "b" + std::to_string(last ? i : i + 1) + ".";                   // residual + the next block's norm1
-                    VDA_TRY(ln_res(V(k + "ls2.gamma"), xn, V(kn + "norm1.weight"), V(kn + "norm1.bias"), 0, 0));
-                    xn_ready = true;
-                    if (tp != nullptr) VDA_TRY(layernorm(tok, tp, V("norm.w"), V("norm.b"), ENC_LN_EPS, rows, D, Nt, 1));
-                }
-            } else {
-                VDA_TRY(dense(hid, W(k + "mlp.fc2.weight"), tok, VDA_EPI_SCALE_RES_F32, rows, D, 4 * D, V(k + "mlp.fc2.bias"), tok, V(k + "ls2.gamma")));
-                if (tp != nullptr) VDA_TRY(layernorm(tok, tp, V("norm.w"), V("norm.b"), ENC_LN_EPS, rows, D, Nt, 1));     // final norm, cls dropped
-            }
-            if (tp != nullptr) {
-                if (c.use_clstoken) {
-                    // dpt_temporal.py:56-59: the tap becomes GELU(Linear([patch token, cls])); the final norm above dropped the cls
-                    // row, so norm the whole token matrix again (cls kept) and gather [patch | cls] rows for one K = 2D GEMM
-                    void* full = act("rd_full", (size_t)rows * D);
-                    void* cat = act("rd_cat", (size_t)BT * P * 2 * D);
-                    const std::string kr = "readout" + std::to_string(ntap);
-                    VDA_TRY(each([&](const Part& p) -> int {
-                        const size_t r0 = (size_t)p.f0 * Nt, q0 = (size_t)p.f0 * P;      // (token rows, patch rows) before the part
-                        VDA_TRY(fold ? tap_ln(full, 0, 0, p) : layernorm(tok, full, V("norm.w"), V("norm.b"), ENC_LN_EPS, rows, D));
-                        if (!dry)
-                            VDA_TRY(prec == VDA_PREC_F32 ? vda_readout_concat_f32((const float*)full + r0 * D, (float*)cat + q0 * 2 * D, p.nf, P, D, s)
-                                                         : vda_readout_concat_f16((const h16*)full + r0 * D, (h16*)cat + q0 * 2 * D, p.nf, P, D, s));
-                        return dense((const char*)cat + q0 * 2 * D * ab, W(kr + ".w"), (char*)tp + q0 * D * ab, VDA_EPI_BIAS_GELU_F16, p.nf * P, D, 2 * D,
-                                     V(kr + ".b"), nullptr, nullptr, 0, nparts > 1 ? BT * P : 0);
-                    }));
-                }
-                taps[ntap++] = tp;
-                if (ntap == 3 && !last && !early_done) {
-                    if (dry || !h->head_overlap) {
-                        // (dry pass: the buffers are requested here so that both orders of execution find them laid out)
-                        if (dry) {
-                            VDA_TRY(head_early());
-                            early_done = true;
-                        }
-                    } else {
-                        vda_model::Side& sd = h->sides[s];
-                        VDA_TRY(open_side(sd));
-                        side = &sd;
-                        VDA_HIP(hipEventRecord(sd.fork, s));               // taps 0..2 are behind this point of the caller's stream
-                        VDA_HIP(hipStreamWaitEvent(sd.stream, sd.fork, 0));
-                        if (lane != nullptr) {                              // ... and of the lane's (enc_split: half B's tap rows)
-                            VDA_HIP(hipEventRecord(lane->join, lane->stream));
-                            VDA_HIP(hipStreamWaitEvent(sd.stream, lane->join, 0));
-                        }
-                        hipStream_t main_stream = s;
-                        s = sd.stream;
-                        const int rc = head_early();
-                        s = main_stream;
-                        if (rc != 0) return rc;
-                        VDA_HIP(hipEventRecord(sd.join, sd.stream));
-                        early_done = true;
-                    }
-                }
-            }
+            void* tp = (is_tap && ntap < 4) ? act("tap" + std::to_string(ntap), (size_t)BT * g.P * D) : nullptr;
+            VDA_TRY(fold ? block_split(i, tp) : defer ? block_deferred(i, tp) : block_f32_stream(i, tp));
+            if (tp == nullptr) continue;
+            if (c.use_clstoken) VDA_TRY(readout(tp));
+            taps[ntap++] = tp;
+            if (ntap == 3 && i + 1 != c.depth) VDA_TRY(head_early_under_encoder(taps));
         }
         if (lane != nullptr) {                 // half B's encoder is done before anything later on the caller's stream
             VDA_HIP(hipEventRecord(lane->join, lane->stream));
             VDA_HIP(hipStreamWaitEvent(s, lane->join, 0));
         }
-        if (ntap != 4) {
-            vda_set_error("vda_forward: the configuration's taps are not four distinct block indices below depth");
-            return 1;
+        return 0;
+    }
+
+    // ---- the part of the head that needs taps 0..2 only (dpt_temporal.py:55-69 for i = 0, 1, 2; :75 motion module 0 on layer_3;
+    // :78-80 layer{1,2,3}_rn) -> l1r, l2r, l3r: 3.8 of the head's 12.5 TFLOP at ViT-L.
+    // part: 1 = the tap 0 / tap 1 chains (-> l1r, l2r), 2 = the tap 2 chain (-> l3r), 3 = both, in the order of one chain. Its
+    // motion module takes scratch blocks of its own ("e."): with option head_lanes motion module 1 runs beside it.
+    int head_early(void* const* taps, int part) {
+        On on(*this, s, "e.");
+        const int BT = g.BT, ph = g.ph, pw = g.pw, P = g.P, D = g.D, Fe = g.Fe, h1 = g.h1, w1 = g.w1, h2 = g.h2, w2 = g.w2;
+        const int* ocp = h->ocp;
+        void* l1 = act("l1", (size_t)BT * h1 * w1 * ocp[0]);
+        void* l2 = act("l2", (size_t)BT * h2 * w2 * ocp[1]);
+        void* l3t = nullptr;
+        // option convt_fold: a folded level skips its ConvTranspose here and runs the folded GEMM where layer{i+1}_rn stood
+        const bool f0 = fold_level(0), f1 = fold_level(1);
+        void *t0 = nullptr, *t1 = nullptr;
+        if (part & 1) {
+            if (!dry) h->folded[0] = f0, h->folded[1] = f1;
+            t0 = act("t0", (size_t)BT * P * ocp[0]);
+            VDA_TRY(dense(taps[0], W("proj0.w"), t0, VDA_EPI_BIAS_F16, BT * P, ocp[0], D, V("proj0.b")));
+            if (!f0) VDA_TRY(convt(t0, 0, l1));
+            t1 = act("t1", (size_t)BT * P * ocp[1]);
+            VDA_TRY(dense(taps[1], W("proj1.w"), t1, VDA_EPI_BIAS_F16, BT * P, ocp[1], D, V("proj1.b")));
+            if (!f1) VDA_TRY(convt(t1, 1, l2));
         }
-        // ---- head: reassemble (dpt_temporal.py:55-69), temporal modules on layer_3 / layer_4 (:75-76), layer_rn (:78-81)
-        // ---- option head_lanes: a TASK split of the head's DAG over the caller's stream and the lane stream (idle after the join).
-        // The chain through tap 3 (proj3 -> resize3 -> motion module 1 -> rn4 -> refinenet 4 -> motion module 2) holds the head's
-        // poorly filled launches: 19 x 19 maps, 18 .. 72 % of one round of 256 x 256 tiles, and the bandwidth-bound LayerNorm /
-        // GroupNorm / temporal attention passes between them. Beside it the lane runs what does not depend on it and fills the
-        // grid: head_early, and conv1 of resConfUnit1 of refinenets 3, 2, 1 (it reads l3r / l2r / l1r only; the other input of the
-        // unit enters in conv2's epilogue). Every kernel keeps its rows, its tile plan and its arguments, and the two sides share no
-        // scratch block (Run::sp, and y1[] for the hoisted convs): bit-identical to one chain. The lane's order puts what
-        // refinenet 3 needs first: refinenet 3 waits for that alone (join) and refinenet 2 for the rest (join2). One join before
-        // refinenet 3 for all of it measured 0.18 - 0.20 ms per ViT-L clip slower (profiles/r10/head_lanes/) and is not kept.
-        // The dry pass requests y1[] in every configuration, so the layout does not depend on the option.
+        if (part & 2) {
+            void* l3 = act("l3", (size_t)BT * P * ocp[2]);
+            VDA_TRY(dense(taps[2], W("proj2.w"), l3, VDA_EPI_BIAS_F16, BT * P, ocp[2], D, V("proj2.b")));
+            VDA_TRY(temporal(0, l3, P, ocp[2], "l3t", &l3t));              // dpt_temporal.py:75
+        }
+        if (part & 1) {
+            l1r = act("l1r", (size_t)BT * h1 * w1 * Fe);
+            if (f0) VDA_TRY(convt_fold(t0, 0, l1r));
+            else VDA_TRY(conv3x3(l1, "rn1.w", l1r, BT, h1, w1, ocp[0], Fe, VDA_EPI_BIAS_F16, 1, nullptr));
+            l2r = act("l2r", (size_t)BT * h2 * w2 * Fe);
+            if (f1) VDA_TRY(convt_fold(t1, 1, l2r));
+            else VDA_TRY(conv3x3(l2, "rn2.w", l2r, BT, h2, w2, ocp[1], Fe, VDA_EPI_BIAS_F16, 1, nullptr));
+        }
+        if (part & 2) {
+            l3r = act("l3r", (size_t)BT * P * Fe);
+            VDA_TRY(conv3x3(l3t, "rn3.w", l3r, BT, ph, pw, ocp[2], Fe, VDA_EPI_BIAS_F16, 1, nullptr));
+        }
+        return 0;
+    }
+    // Option head_overlap runs head_early on a SIDE stream as soon as tap 2 exists, under the remaining encoder blocks (ViT-L:
+    // blocks 18-23), so that its kernels fill the tail rounds and epilogue bursts of theirs - what two clips in flight do for a
+    // video, inside ONE clip. Same kernels, same arithmetic: bit-identical. Without the option head_early runs in head(); the dry
+    // pass requests its buffers HERE, so that both orders of execution find them laid out.
+    int head_early_under_encoder(void* const* taps) {
+        if (!dry && !h->head_overlap) return 0;
+        early_done = true;
+        if (dry) return head_early(taps, 3);
+        side = &h->sides[s];
+        VDA_TRY(fork(*side));                                          // taps 0..2 are behind this point of the caller's stream
+        if (lane != nullptr) {                                         // ... and of the lane's (enc_split: half B's tap rows)
+            VDA_HIP(hipEventRecord(lane->join, lane->stream));
+            VDA_HIP(hipStreamWaitEvent(side->stream, lane->join, 0));
+        }
+        {
+            On on(*this, side->stream, sp);
+            VDA_TRY(head_early(taps, 3));
+        }
+        VDA_HIP(hipEventRecord(side->join, side->stream));
+        return 0;
+    }
+    // Option head_lanes: the lane stream's share of the head. Its order puts what refinenet 3 needs first: refinenet 3 waits for
+    // that alone (join) and refinenet 2 for the rest (join2).
+    int head_on_lane(void* const* taps, void* const* y1) {
+        lane = &h->lanes[s];
+        VDA_TRY(fork(*lane));                                          // behind the encoder's join: every tap row exists
+        On on(*this, lane->stream, "e.");
+        VDA_TRY(head_early(taps, 2));
+        VDA_TRY(rcu_conv1(3, 1, l3r, y1[3], g.ph, g.pw));
+        VDA_HIP(hipEventRecord(lane->join, lane->stream));
+        VDA_TRY(head_early(taps, 1));
+        VDA_TRY(rcu_conv1(2, 1, l2r, y1[2], g.h2, g.w2));
+        VDA_TRY(rcu_conv1(1, 1, l1r, y1[1], g.h1, g.w1));
+        VDA_HIP(hipEventRecord(lane->join2, lane->stream));
+        return 0;
+    }
+    // ---- head: reassemble (dpt_temporal.py:55-69), temporal modules on layer_3 / layer_4 (:75-76), layer_rn (:78-81), refinenets
+    // ---- option head_lanes: a TASK split of the head's DAG over the caller's stream and the lane stream (idle after the join).
+    // The chain through tap 3 (proj3 -> resize3 -> motion module 1 -> rn4 -> refinenet 4 -> motion module 2) holds the head's
+    // poorly filled launches: 19 x 19 maps, 18 .. 72 % of one round of 256 x 256 tiles, and the bandwidth-bound LayerNorm /
+    // GroupNorm / temporal attention passes between them. Beside it the lane runs what does not depend on it and fills the
+    // grid: head_early, and conv1 of resConfUnit1 of refinenets 3, 2, 1 (it reads l3r / l2r / l1r only; the other input of the
+    // unit enters in conv2's epilogue). Every kernel keeps its rows, its tile plan and its arguments, and the two sides share no
+    // scratch block (Run::sp, and y1[] for the hoisted convs): bit-identical to one chain. One join before refinenet 3 for all
+    // of the lane's work measured 0.18 - 0.20 ms per ViT-L clip slower (profiles/r10/head_lanes/) and is not kept.
+    int head(void* const* taps, float* depth) {
+        const int BT = g.BT, ph = g.ph, pw = g.pw, P = g.P, Fe = g.Fe, h1 = g.h1, w1 = g.w1, h2 = g.h2, w2 = g.w2, h4 = g.h4, w4 = g.w4;
+        const int* ocp = h->ocp;
+        // (requested in every configuration: the layout does not depend on the option)
         void* y1[4] = {nullptr, act("ref1.y1", (size_t)BT * h1 * w1 * Fe), act("ref2.y1", (size_t)BT * h2 * w2 * Fe), act("ref3.y1", (size_t)BT * P * Fe)};
-        if (hlanes) {
-            vda_model::Side& ln = h->lanes[s];
-            VDA_TRY(open_side(ln));
-            lane = &ln;
-            VDA_HIP(hipEventRecord(ln.fork, s));                       // behind the encoder's join: every tap row exists
-            VDA_HIP(hipStreamWaitEvent(ln.stream, ln.fork, 0));
-            auto on_lane = [&]() -> int {
-                VDA_TRY(head_early(2));
-                VDA_TRY(rcu_conv1(3, 1, l3r, y1[3], BT, ph, pw, Fe));
-                VDA_HIP(hipEventRecord(ln.join, ln.stream));
-                VDA_TRY(head_early(1));
-                VDA_TRY(rcu_conv1(2, 1, l2r, y1[2], BT, h2, w2, Fe));
-                VDA_TRY(rcu_conv1(1, 1, l1r, y1[1], BT, h1, w1, Fe));
-                VDA_HIP(hipEventRecord(ln.join2, ln.stream));
-                return 0;
-            };
-            const hipStream_t keep = s;
-            s = ln.stream, sp = "e.";
-            const int rc = on_lane();
-            s = keep, sp = "";
-            if (rc != 0) return rc;
-        } else if (!early_done) VDA_TRY(head_early());
+        const bool hlanes = want_lanes() && alone;
+        if (hlanes) VDA_TRY(head_on_lane(taps, y1));
+        else if (!early_done) VDA_TRY(head_early(taps, 3));
         else if (side != nullptr) VDA_HIP(hipStreamWaitEvent(s, side->join, 0));     // the side stream's part is done before anything reads it
         void* t3 = act("t3", (size_t)BT * P * ocp[3]);
-        VDA_TRY(dense(taps[3], W("proj3.w"), t3, VDA_EPI_BIAS_F16, BT * P, ocp[3], D, V("proj3.b")));
+        VDA_TRY(dense(taps[3], W("proj3.w"), t3, VDA_EPI_BIAS_F16, BT * P, ocp[3], g.D, V("proj3.b")));
         void* l4 = act("l4", (size_t)BT * h4 * w4 * ocp[3]);
         VDA_TRY(conv3x3(t3, "resize3.w", l4, BT, ph, pw, ocp[3], ocp[3], VDA_EPI_BIAS_F16, 2, V("resize3.b")));
         void* l4t = nullptr;
-        VDA_TRY(temporal(1, l4, B, T, h4 * w4, ocp[3], "l4t", &l4t));
+        VDA_TRY(temporal(1, l4, h4 * w4, ocp[3], "l4t", &l4t));
         void* l4r = act("l4r", (size_t)BT * h4 * w4 * Fe);
         VDA_TRY(conv3x3(l4t, "rn4.w", l4r, BT, h4, w4, ocp[3], Fe, VDA_EPI_BIAS_F16, 1, nullptr));
         void *p4 = nullptr, *p4t = nullptr, *p3 = nullptr, *p3t = nullptr, *p2 = nullptr, *p1 = nullptr;
-        VDA_TRY(fusion(4, l4r, nullptr, BT, h4, w4, ph, pw, Fe, "p4", &p4));
-        VDA_TRY(temporal(2, p4, B, T, P, Fe, "p4t", &p4t));
+        VDA_TRY(fusion(4, l4r, nullptr, h4, w4, ph, pw, "p4", &p4));
+        VDA_TRY(temporal(2, p4, P, Fe, "p4t", &p4t));
         if (hlanes) VDA_HIP(hipStreamWaitEvent(s, lane->join, 0));                   // l3r and y1[3]
-        VDA_TRY(fusion(3, p4t, l3r, BT, ph, pw, h2, w2, Fe, "p3", &p3, true, hlanes ? y1[3] : nullptr));
-        VDA_TRY(temporal(3, p3, B, T, h2 * w2, Fe, "p3t", &p3t));
+        VDA_TRY(fusion(3, p4t, l3r, ph, pw, h2, w2, "p3", &p3, true, hlanes ? y1[3] : nullptr));
+        VDA_TRY(temporal(3, p3, h2 * w2, Fe, "p3t", &p3t));
         if (hlanes) VDA_HIP(hipStreamWaitEvent(s, lane->join2, 0));                    // l2r, l1r, y1[2], y1[1]
-        VDA_TRY(fusion(2, p3t, l2r, BT, h2, w2, h1, w1, Fe, "p2", &p2, true, hlanes ? y1[2] : nullptr));
-        // refinenet1's 2x upsample (util/blocks.py:156-160) is folded into output_conv1 on the fp16 path: path_1 at 8 ph x 8 pw (1.4 GB
-        // per ViT-L clip) never exists; "p1c" is refinenet1's out_conv output at 4 ph x 4 pw (bilinear and the 1x1 conv commute)
-        const bool up_fused = prec == VDA_PREC_F16 && h->oc1_fused != 0 && Fhp <= 128 && Fe % 16 == 0;
-        // option oc1_mix (where up_fused applies): the channel mixing of out_conv + output_conv1 as ONE GEMM at h1 x w1 into z (9 * Fhp
-        // channels, pack-time weight vda_fold_oc1_weight) and the gather-and-add pass vda_oc1_mix_combine_f16; refinenet1 stops after
-        // resConfUnit2 and "p1c" is never written. z of a whole ViT-L clip is 1.6 GB: the pair runs per chunk of mixF frames out of one
-        // z buffer. The dry pass lays out "p1c" and z and counts the launches of both forms whatever the option says.
-        const int mixF = std::min(BT, h->oc1_mix_chunk > 0 ? h->oc1_mix_chunk : vda_oc1_mix_frames());
-        const int ldz = vda_oc1_mix_ldz(Fhp);      // z's row: 9 * Fhp channels (tap, cout), padded where the GEMM planner then tiles better
-        const bool mix_fits = (double)mixF * h1 * w1 * ldz < 2147483647.0;
-        const bool mix = up_fused && !dry && h->oc1_mix != 0 && mix_fits;
-        if (!dry) h->mixed = mix;
-        VDA_TRY(fusion(1, p2, l1r, BT, h1, w1, 2 * h1, 2 * w1, Fe, up_fused ? "p1c" : "p1", &p1, !up_fused, hlanes ? y1[1] : nullptr, mix));
-        // ---- output convs (dpt.py:117-124, dpt_temporal.py:93-100)
-        const int hh = 2 * h1, ww = 2 * w1;
+        VDA_TRY(fusion(2, p3t, l2r, h2, w2, h1, w1, "p2", &p2, true, hlanes ? y1[2] : nullptr));
+        const Oc1 o = oc1_form();
+        if (!dry) h->mixed = o.mix;
+        VDA_TRY(fusion(1, p2, l1r, h1, w1, 2 * h1, 2 * w1, o.up_fused ? "p1c" : "p1", &p1, !o.up_fused, hlanes ? y1[1] : nullptr, o.mix));
+        return output_convs(p1, depth);
+    }
+    // The form of output_conv1. up_fused: refinenet1's 2x upsample (util/blocks.py:156-160) is folded into output_conv1 on the fp16
+    // path: path_1 at 8 ph x 8 pw (1.4 GB per ViT-L clip) never exists; "p1c" is refinenet1's out_conv output at 4 ph x 4 pw (bilinear
+    // and the 1x1 conv commute). mix (option oc1_mix, where up_fused applies): the channel mixing of out_conv + output_conv1 as ONE
+    // GEMM at h1 x w1 into z (9 * Fhp channels, pack-time weight vda_fold_oc1_weight) and the gather-and-add pass
+    // vda_oc1_mix_combine_f16; refinenet1 stops after resConfUnit2 and "p1c" is never written. z of a whole ViT-L clip is 1.6 GB: the
+    // pair runs per chunk of `frames` frames out of one z buffer. The dry pass lays out "p1c" and z and counts the launches of both
+    // forms whatever the option says.
+    struct Oc1 {
+        bool up_fused, fits, mix;
+        int frames, ldz;      // ldz: z's row, 9 * Fhp channels (tap, cout), padded where the GEMM planner then tiles better
+    };
+    Oc1 oc1_form() const {
+        Oc1 o;
+        o.up_fused = prec == VDA_PREC_F16 && h->oc1_fused != 0 && g.Fhp <= 128 && g.Fe % 16 == 0;
+        o.frames = std::min(g.BT, h->oc1_mix_chunk > 0 ? h->oc1_mix_chunk : vda_oc1_mix_frames());
+        o.ldz = vda_oc1_mix_ldz(g.Fhp);
+        o.fits = (double)o.frames * g.h1 * g.w1 * o.ldz < 2147483647.0;
+        o.mix = o.up_fused && !dry && h->oc1_mix != 0 && o.fits;
+        return o;
+    }
+    // ---- output convs (dpt.py:117-124, dpt_temporal.py:93-100) on refinenet1's result p1 -> depth
+    int output_convs(const void* p1, float* depth) {
+        const Oc1 o = oc1_form();
+        const int BT = g.BT, H = g.H, Wd = g.W, Fe = g.Fe, Fhp = g.Fhp, h1 = g.h1, w1 = g.w1, hh = 2 * h1, ww = 2 * w1;
         void* o1 = act("o1", (size_t)BT * hh * ww * Fhp);
-        if (up_fused && mix_fits && (mix || dry)) {
-            void* z = act("oc1_z", (size_t)mixF * h1 * w1 * ldz);
-            for (int f0 = 0; f0 < BT; f0 += mixF) {
-                const int nf = std::min(mixF, BT - f0);
-                VDA_TRY(dense((const h16*)p1 + (size_t)f0 * h1 * w1 * Fe, W("oc1.mix.w"), z, VDA_EPI_BIAS_F16, nf * h1 * w1, ldz, Fe, V("oc1.mix.b")));
-                if (!dry) VDA_TRY(vda_oc1_mix_combine_f16(z, V("oc1.b"), (h16*)o1 + (size_t)f0 * hh * ww * Fhp, nf, h1, w1, Fhp, ldz, s));
+        if (o.up_fused && o.fits && (o.mix || dry)) {
+            void* z = act("oc1_z", (size_t)o.frames * h1 * w1 * o.ldz);
+            for (int f0 = 0; f0 < BT; f0 += o.frames) {
+                const int nf = std::min(o.frames, BT - f0);
+                VDA_TRY(dense((const h16*)p1 + (size_t)f0 * h1 * w1 * Fe, W("oc1.mix.w"), z, VDA_EPI_BIAS_F16, nf * h1 * w1, o.ldz, Fe, V("oc1.mix.b")));
+                if (!dry) VDA_TRY(vda_oc1_mix_combine_f16(z, V("oc1.b"), (h16*)o1 + (size_t)f0 * hh * ww * Fhp, nf, h1, w1, Fhp, o.ldz, s));
             }
         }
-        if (up_fused) {
-            if (!dry && !mix) VDA_TRY(vda_conv3x3_up2_f16(p1, W("oc1.w"), V("oc1.b"), o1, BT, h1, w1, Fe, Fhp, Fhp, s));
+        if (o.up_fused) {
+            if (!dry && !o.mix) VDA_TRY(vda_conv3x3_up2_f16(p1, W("oc1.w"), V("oc1.b"), o1, BT, h1, w1, Fe, Fhp, Fhp, s));
         } else
             VDA_TRY(conv3x3(p1, "oc1.w", o1, BT, hh, ww, Fe, Fhp, VDA_EPI_BIAS_F16, 1, V("oc1.b")));
         if (prec == VDA_PREC_F16) {
@@ -1243,13 +1280,46 @@ struct Run {
             hipLaunchKernelGGL(poison_on_overflow_kernel, dim3(256), dim3(256), 0, s, (const int*)ovf, depth, (long long)BT * H * Wd, (volatile int*)h->ovf_host);
             VDA_LAUNCH_CHECK();
         }
-        if (!dry && !capturing) {
+        return 0;
+    }
+
+    // One forward of the clip: x [B, T, 3, H, W] fp32 -> depth [B, T, H, W] fp32 (dry pass: the layout and the launch count)
+    int forward(const float* x, float* depth) {
+        if (!dry) {                          // (a captured forward stays one linear stream)
+            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+            if (hipStreamIsCapturing(s, &cs) != hipSuccess) {
+                (void)hipGetLastError();          // (e.g. the legacy stream while another stream captures): treated as capturing
+                cs = hipStreamCaptureStatusActive;
+            }
+            capturing = cs != hipStreamCaptureStatusNone;
+        }
+        // dynamic-schedule counters of every GEMM launch below: sized by the dry pass, zeroed here once per forward
+        if (prec == VDA_PREC_F16 && h->dyn_sched) {
+            const int cap = dry ? 4096 : lay->gemm_launches;
+            sched = (int32_t*)buf("sched", (size_t)8 * (cap > 0 ? cap : 1), 4);
+            if (!dry) VDA_HIP(hipMemsetAsync(sched, 0, (size_t)32 * lay->gemm_launches, s));
+        }
+        void* taps[4] = {nullptr, nullptr, nullptr, nullptr};
+        VDA_TRY(encoder(x, taps));
+        if (ntap != 4) {
+            vda_set_error("vda_forward: the configuration's taps are not four distinct block indices below depth");
+            return 1;
+        }
+        VDA_TRY(head(taps, depth));
+        if (!dry && !capturing) {            // the end of the last forward enqueued on this caller stream (others_idle)
             hipEvent_t& tail = h->tails[s];
             if (tail == nullptr) VDA_HIP(hipEventCreateWithFlags(&tail, hipEventDisableTiming));
             VDA_HIP(hipEventRecord(tail, s));
         }
         return 0;
     }
+    // vda_debug_copy: "l1" / "l2" of a forward that ran level lvl folded (option convt_fold) were never written: rebuilt here, into
+    // their own block, from the level's projection with the ConvTranspose GEMM the unfused forward runs - same arguments, same
+    // kernel, same bits
+    int rebuild_level(int lvl) { return convt(act(lvl == 0 ? "t0" : "t1", 0), lvl, act(lvl == 0 ? "l1" : "l2", 0)); }
+    // ... and "p1c" of a forward that ran option oc1_mix: rebuilt from resConfUnit2's output ("fus_r": refinenet1 is its last
+    // writer) with the out_conv GEMM the unfused forward runs
+    int rebuild_p1c() { return dense(act("fus_r", 0), W("ref1.out.w"), act("p1c", 0), VDA_EPI_BIAS_F16, g.BT * g.h1 * g.w1, g.Fe, g.Fe, V("ref1.out.b")); }
 };
 
 int get_layout(vda_model* h, int B, int T, int H, int W, int prec, Layout** out) {
@@ -1257,8 +1327,8 @@ int get_layout(vda_model* h, int B, int T, int H, int W, int prec, Layout** out)
     auto it = h->layouts.find(key);
     if (it == h->layouts.end()) {
         Layout lay;
-        Run r{h, prec, true, &lay, nullptr, prec == VDA_PREC_F32 ? (size_t)4 : (size_t)2};
-        VDA_TRY(r.forward(nullptr, nullptr, B, T, H, W));
+        Run r(h, prec, true, &lay, nullptr, B, T, H, W);
+        VDA_TRY(r.forward(nullptr, nullptr));
         lay.gemm_launches = r.nsched;
         size_t off = 0;
         for (const std::string& n : lay.order) {
@@ -1282,21 +1352,50 @@ int check_shape(const vda_model* h, int B, int T, int H, int W, int prec) {
     return 0;
 }
 
-int head_lanes_default() {
-    static const int v = getenv("VDA_HEAD_LANES") ? atoi(getenv("VDA_HEAD_LANES")) : 1;      // (A/B through an unmodified caller)
-    return v != 0;
+// An on / off option's default from the environment (A/B through an unmodified caller; unset: on). Each default below reads its
+// variable once per process.
+int env_default(const char* var) {
+    const char* e = getenv(var);
+    return e == nullptr || atoi(e) != 0;
 }
-
-int convt_fold_default() {
-    static const int v = getenv("VDA_CONVT_FOLD") ? atoi(getenv("VDA_CONVT_FOLD")) : 1;      // (A/B through an unmodified caller)
-    return v != 0;
-}
-
+int enc_split_default(const vda_model*) { static const int v = env_default("VDA_ENC_SPLIT"); return v; }
+int head_lanes_default(const vda_model*) { static const int v = env_default("VDA_HEAD_LANES"); return v; }
+int convt_fold_default(const vda_model*) { static const int v = env_default("VDA_CONVT_FOLD"); return v; }
 int oc1_mix_default(const vda_model* h) { return vda_oc1_mix_default(h->cfg.features); }
 
-int enc_split_default() {
-    static const int v = getenv("VDA_ENC_SPLIT") ? atoi(getenv("VDA_ENC_SPLIT")) : 1;      // (A/B through an unmodified caller)
-    return v != 0;
+// vda_set_option: the tuning / A-B switches of the launch sequence (see Run). `flag`: the value is stored as value != 0, and where
+// the option has a process default (`dflt`), value < 0 stores that; otherwise the value is stored as given. `relayout`: the
+// workspace layout or the GEMM launch count (dynamic-schedule counters) depends on the option, so the layouts are dropped.
+struct Option {
+    const char* name;
+    int vda_model::*field;
+    bool flag, relayout;
+    int (*dflt)(const vda_model*);
+};
+const Option OPTIONS[] = {
+    // name            field                        flag   relayout  dflt                   default
+    {"residual_in_ln", &vda_model::residual_in_ln, false, true, nullptr},                // 0
+    {"ln_fold", &vda_model::ln_fold, false, true, nullptr},                              // 1
+    {"dyn_sched", &vda_model::dyn_sched, false, true, nullptr},                          // 0
+    {"oc1_fused", &vda_model::oc1_fused, false, true, nullptr},                          // 1
+    {"mlp_fused", &vda_model::mlp_fused, true, true, nullptr},                           // 0 (hid is not allocated with it)
+    {"head_overlap", &vda_model::head_overlap, true, false, nullptr},                    // 0
+    {"enc_split", &vda_model::enc_split, true, true, enc_split_default},                 // 1, or VDA_ENC_SPLIT
+    {"head_lanes", &vda_model::head_lanes, true, false, head_lanes_default},             // 1, or VDA_HEAD_LANES
+    {"convt_fold", &vda_model::convt_fold, true, false, convt_fold_default},             // 1, or VDA_CONVT_FOLD
+    {"oc1_mix", &vda_model::oc1_mix, true, false, oc1_mix_default},                      // vda_oc1_mix_default, or VDA_OC1_MIX
+    {"oc1_mix_chunk", &vda_model::oc1_mix_chunk, false, true, nullptr},                  // 0: frames per z buffer (<= 0: vda_oc1_mix_frames())
+};
+
+// No exception crosses the C ABI: an entry point that can throw (std::map::at, std::string, std::vector) runs inside this
+template <typename R, typename Fn>
+R guarded(const char* entry, R on_throw, Fn&& fn) {
+    try {
+        return fn();
+    } catch (const std::exception& e) {
+        vda_set_error("%s: %s", entry, e.what());
+        return on_throw;
+    }
 }
 
 }  // namespace
@@ -1339,10 +1438,8 @@ extern "C" int vda_create(const vda_config* cfg, vda_model** out) {
     }
     memset(ring, 0, 64);
     h->ovf_host = (volatile int32_t*)ring;
-    h->enc_split = enc_split_default();
-    h->head_lanes = head_lanes_default();
-    h->convt_fold = convt_fold_default();
-    h->oc1_mix = oc1_mix_default(h);
+    for (const Option& o : OPTIONS)
+        if (o.dflt) h->*o.field = o.dflt(h);
     *out = h;
     return 0;
 }
@@ -1509,9 +1606,9 @@ static int vda_forward_impl(vda_model* h, const float* in, float* out, int B, in
     }
     VDA_REQUIRE((size_t)h->ws_bytes >= lay->total, "vda_forward: workspace of %lld bytes, this shape needs %lld (vda_workspace_bytes)",
                 (long long)h->ws_bytes, (long long)lay->total);
-    Run r{h, precision, false, lay, (hipStream_t)stream, precision == VDA_PREC_F32 ? (size_t)4 : (size_t)2};
+    Run r(h, precision, false, lay, (hipStream_t)stream, B, T, H, W);
     h->last_key = {B, T, H, W, precision};
-    return r.forward(in, out, B, T, H, W);
+    return r.forward(in, out);
 }
 
 // Debug / parity hook: copy a named intermediate of the LAST forward (same workspace) into `dst`: "tap0".."tap3" (final-norm'd
@@ -1523,90 +1620,30 @@ static int vda_debug_copy_impl(vda_model* h, const char* name, void* dst, int64_
     auto b = it->second.bufs.find(name);
     VDA_REQUIRE(b != it->second.bufs.end(), "vda_debug_copy: no buffer named %s", name);
     VDA_REQUIRE(bytes > 0 && (size_t)bytes <= b->second.second, "vda_debug_copy: %s holds %lld bytes", name, (long long)b->second.second);
-    // "l1" / "l2" of a forward that ran the level folded (option convt_fold) were never written: rebuilt here, into their own block,
-    // from the level's projection with the ConvTranspose GEMM the unfused forward runs - same arguments, same kernel, same bits
+    // a stage that the last forward's options folded away is rebuilt first (Run::rebuild_level, Run::rebuild_p1c)
+    const std::array<int, 5>& k = h->last_key;
     const int lvl = strcmp(name, "l1") == 0 ? 0 : strcmp(name, "l2") == 0 ? 1 : -1;
-    if (lvl >= 0 && h->last_key[4] == VDA_PREC_F16 && h->folded[lvl]) {
+    const bool level = lvl >= 0 && h->folded[lvl], p1c = strcmp(name, "p1c") == 0 && h->mixed;
+    if (k[4] == VDA_PREC_F16 && (level || p1c)) {
         VDA_TRY(require_device(h, "vda_debug_copy"));
-        Run r{h, VDA_PREC_F16, false, &it->second, (hipStream_t)stream, (size_t)2};
-        const int BT = h->last_key[0] * h->last_key[1], ph = h->last_key[2] / PATCH, pw = h->last_key[3] / PATCH;
-        VDA_TRY(r.convt(r.act(lvl == 0 ? "t0" : "t1", 0), lvl, r.act(name, 0), BT, ph, pw, h->ocp[lvl]));
-    }
-    // "p1c" of a forward that ran option oc1_mix was never written either: rebuilt from resConfUnit2's output ("fus_r": refinenet1 is
-    // its last writer) with the out_conv GEMM the unfused forward runs
-    if (strcmp(name, "p1c") == 0 && h->last_key[4] == VDA_PREC_F16 && h->mixed) {
-        VDA_TRY(require_device(h, "vda_debug_copy"));
-        Run r{h, VDA_PREC_F16, false, &it->second, (hipStream_t)stream, (size_t)2};
-        const int BT = h->last_key[0] * h->last_key[1], ph = h->last_key[2] / PATCH, pw = h->last_key[3] / PATCH, Fe = h->cfg.features;
-        const int keep = h->dyn_sched;            // (a launch outside the forward has no dynamic-schedule counters)
-        h->dyn_sched = 0;
-        const int rc = r.dense(r.act("fus_r", 0), r.W("ref1.out.w"), r.act("p1c", 0), VDA_EPI_BIAS_F16, BT * 16 * ph * pw, Fe, Fe, r.V("ref1.out.b"));
-        h->dyn_sched = keep;
-        VDA_TRY(rc);
+        Run r(h, VDA_PREC_F16, false, &it->second, (hipStream_t)stream, k[0], k[1], k[2], k[3]);
+        VDA_TRY(level ? r.rebuild_level(lvl) : r.rebuild_p1c());
     }
     VDA_HIP(hipMemcpyAsync(dst, (char*)h->ws + b->second.first, (size_t)bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return 0;
 }
 
-// Tuning / A-B switches of the launch sequence: "residual_in_ln" (default 0), "ln_fold" (default 1), "dyn_sched" (default 0), "oc1_fused"
-// (default 1), "mlp_fused" (default 0), "head_overlap" (default 0), "enc_split" (default 1, or VDA_ENC_SPLIT), "head_lanes" (default 1,
-// or VDA_HEAD_LANES), "convt_fold" (default 1, or VDA_CONVT_FOLD), "oc1_mix" (default vda_oc1_mix_default, or VDA_OC1_MIX),
-// "oc1_mix_chunk": see Run::forward.
+// The options, their value conventions and their defaults: the OPTIONS table above.
 extern "C" int vda_set_option(vda_model* h, const char* name, int value) {
     VDA_REQUIRE(h && name, "vda_set_option: null argument");
-    if (strcmp(name, "residual_in_ln") == 0) {
-        h->residual_in_ln = value;
-        h->layouts.clear();                  // the workspace layout depends on it
-        return 0;
-    }
     if (strcmp(name, "profile_min_gflop") == 0) {       // vda_profile_start brackets only launches of at least this many GFLOP
         h->prof.min_flops = 1e9 * value;
         return 0;
     }
-    if (strcmp(name, "dyn_sched") == 0) {
-        h->dyn_sched = value;
-        h->layouts.clear();
-        return 0;
-    }
-    if (strcmp(name, "ln_fold") == 0) {
-        h->ln_fold = value;
-        h->layouts.clear();
-        return 0;
-    }
-    if (strcmp(name, "head_overlap") == 0) {
-        h->head_overlap = value != 0;
-        return 0;
-    }
-    if (strcmp(name, "enc_split") == 0) {                // (< 0: the default, VDA_ENC_SPLIT or 1)
-        h->enc_split = value < 0 ? enc_split_default() : value != 0;
-        h->layouts.clear();                  // the GEMM launch count (dynamic-schedule counters) depends on it
-        return 0;
-    }
-    if (strcmp(name, "head_lanes") == 0) {               // (< 0: the default, VDA_HEAD_LANES or 1). The layout does not depend on it.
-        h->head_lanes = value < 0 ? head_lanes_default() : value != 0;
-        return 0;
-    }
-    if (strcmp(name, "convt_fold") == 0) {               // (< 0: the default, VDA_CONVT_FOLD or 1). The layout does not depend on it.
-        h->convt_fold = value < 0 ? convt_fold_default() : value != 0;
-        return 0;
-    }
-    if (strcmp(name, "oc1_mix") == 0) {                  // (< 0: the default, VDA_OC1_MIX or vda_oc1_mix_default). The layout does not depend on it.
-        h->oc1_mix = value < 0 ? oc1_mix_default(h) : value != 0;
-        return 0;
-    }
-    if (strcmp(name, "oc1_mix_chunk") == 0) {            // frames per z buffer (<= 0: vda_oc1_mix_frames())
-        h->oc1_mix_chunk = value;
-        h->layouts.clear();                  // the z buffer is that many frames
-        return 0;
-    }
-    if (strcmp(name, "mlp_fused") == 0) {
-        h->mlp_fused = value != 0;
-        h->layouts.clear();                  // hid is not allocated with it
-        return 0;
-    }
-    if (strcmp(name, "oc1_fused") == 0) {
-        h->oc1_fused = value;
-        h->layouts.clear();
+    for (const Option& o : OPTIONS) {
+        if (strcmp(name, o.name) != 0) continue;
+        h->*o.field = !o.flag ? value : (value < 0 && o.dflt) ? o.dflt(h) : value != 0;
+        if (o.relayout) h->layouts.clear();
         return 0;
     }
     vda_set_error("vda_set_option: unknown option %s", name);
@@ -1664,64 +1701,21 @@ static int vda_profile_stop_impl(vda_model* h, char* json, int cap) {
 }
 
 extern "C" int vda_load_weight(vda_model* h, const char* name, const void* ptr, const int64_t* dims, int ndim, int dtype) {
-    try {
-        return vda_load_weight_impl(h, name, ptr, dims, ndim, dtype);
-    } catch (const std::exception& e) {        // no exception crosses the C ABI
-        vda_set_error("vda_load_weight: %s", e.what());
-        return 3;
-    }
+    return guarded("vda_load_weight", 3, [&] { return vda_load_weight_impl(h, name, ptr, dims, ndim, dtype); });
 }
-
-extern "C" int vda_finalize_weights(vda_model* h) {
-    try {
-        return vda_finalize_weights_impl(h);
-    } catch (const std::exception& e) {        // no exception crosses the C ABI
-        vda_set_error("vda_finalize_weights: %s", e.what());
-        return 3;
-    }
-}
-
+extern "C" int vda_finalize_weights(vda_model* h) { return guarded("vda_finalize_weights", 3, [&] { return vda_finalize_weights_impl(h); }); }
 extern "C" int vda_prepare(vda_model* h, int B, int T, int H, int W, int precision) {
-    try {
-        return vda_prepare_impl(h, B, T, H, W, precision);
-    } catch (const std::exception& e) {        // no exception crosses the C ABI
-        vda_set_error("vda_prepare: %s", e.what());
-        return 3;
-    }
+    return guarded("vda_prepare", 3, [&] { return vda_prepare_impl(h, B, T, H, W, precision); });
 }
-
 extern "C" int vda_forward(vda_model* h, const float* in, float* out, int B, int T, int H, int W, int precision, vda_stream_t stream) {
-    try {
-        return vda_forward_impl(h, in, out, B, T, H, W, precision, stream);
-    } catch (const std::exception& e) {        // no exception crosses the C ABI
-        vda_set_error("vda_forward: %s", e.what());
-        return 3;
-    }
+    return guarded("vda_forward", 3, [&] { return vda_forward_impl(h, in, out, B, T, H, W, precision, stream); });
 }
-
 extern "C" int vda_debug_copy(vda_model* h, const char* name, void* dst, int64_t bytes, vda_stream_t stream) {
-    try {
-        return vda_debug_copy_impl(h, name, dst, bytes, stream);
-    } catch (const std::exception& e) {        // no exception crosses the C ABI
-        vda_set_error("vda_debug_copy: %s", e.what());
-        return 3;
-    }
+    return guarded("vda_debug_copy", 3, [&] { return vda_debug_copy_impl(h, name, dst, bytes, stream); });
 }
-
 extern "C" int vda_profile_stop(vda_model* h, char* json, int cap) {
-    try {
-        return vda_profile_stop_impl(h, json, cap);
-    } catch (const std::exception& e) {        // no exception crosses the C ABI
-        vda_set_error("vda_profile_stop: %s", e.what());
-        return 3;
-    }
+    return guarded("vda_profile_stop", 3, [&] { return vda_profile_stop_impl(h, json, cap); });
 }
-
 extern "C" int64_t vda_workspace_bytes(vda_model* h, int B, int T, int H, int W, int precision) {
-    try {
-        return vda_workspace_bytes_impl(h, B, T, H, W, precision);
-    } catch (const std::exception& e) {
-        vda_set_error("vda_workspace_bytes: %s", e.what());
-        return -1;
-    }
+    return guarded("vda_workspace_bytes", (int64_t)-1, [&] { return vda_workspace_bytes_impl(h, B, T, H, W, precision); });
 }

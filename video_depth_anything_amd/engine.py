@@ -451,7 +451,7 @@ class Engine:
         p2 = self.fusion(2, p3, l2r, BT, h2, w2, h1, w1, Fe, "p2")
         # fp16 path: refinenet1's 2x upsample is folded into output_conv1 (vda_conv3x3_up2_f16), as csrc/host.hip does by default
         up_fused = not fp32 and Fhp <= 128
-        # option oc1_mix: the z GEMM at h1 x w1 + the combine pass per chunk of frames (csrc/host.hip, Run::forward)
+        # option oc1_mix: the z GEMM at h1 x w1 + the combine pass per chunk of frames (csrc/host.hip, Run::output_convs)
         mixF = min(BT, self.oc1_mix_chunk)
         ldz = _lib.lib.vda_oc1_mix_ldz(Fhp)
         mix = up_fused and self.oc1_mix and mixF * h1 * w1 * ldz < (1 << 31) - 1
