@@ -584,6 +584,31 @@ int vda_mjpeg_decode_u8(const uint8_t* scan, size_t scan_bytes, const int* inter
                         const uint16_t* qtables, int n, int h, int w, int components, int hs, int vs, void* workspace,
                         size_t workspace_bytes, uint8_t* out, size_t out_capacity, int* status, vda_stream_t stream);
 
+/* ---- raw deflate (RFC 1951) of a device buffer, for .npz files (video_depth_anything_amd/deflate.py: deflate_numpy is the contract) ----
+ * in: n device bytes at any byte address. The stream is cut into independent chunks of 16384 input bytes, a workgroup each:
+ *   tokens   a run's first byte is a literal; its other bytes are distance-1 matches of 258 from the front and a rest, one more
+ *            match when 3..257 long, literals when 1 or 2 (zlib's Z_RLE strategy); no match crosses a chunk boundary
+ *   code     a dynamic Huffman block per chunk: lengths at most 15 bits from the counts by integer arithmetic with ties broken by
+ *            (count, symbol) (csrc/deflate_core.h); one distance code; the lengths written one by one in a code-length code built
+ *            the same way, at most 7 bits, without the repeat symbols
+ *   end      end-of-block, then an empty stored block (a sync flush: the chunk ends on a byte with 00 00 FF FF) - except the last
+ *            chunk when final = 1, whose block carries BFINAL instead. A chunk whose coded form would not be smaller than 5 + its
+ *            bytes is one stored block. n = 0 gives 01 00 00 FF FF with final = 1 and no bytes with final = 0.
+ * So a call with final = 0 leaves a byte-aligned open piece, and pieces followed by a final one are one valid stream. out: the
+ * chunks back to back, *length (device int64) bytes of them; crcs: device uint32 per chunk, the CRC-32 (zlib's polynomial) of the
+ * chunk's INPUT bytes, max(1, ceil(n / 16384)) entries (only ceil(n / 16384) are written when final = 0). Deterministic: bits of
+ * neighbouring tokens meet in shared words through integer OR-atomics only.
+ *   vda_deflate_out_bytes(n)       = n + 5 * max(1, ceil(n / 16384))         the capacity `out` needs; the encoder never truncates
+ *   vda_deflate_workspace_bytes(n) = chunks * 16400 + up16(4 chunks) + up16(8 chunks), chunks = max(1, ceil(n / 16384)); device
+ *                                    bytes, contents irrelevant      (both 0 for n > 2^44)
+ * Refused before any launch: a null in (unless n = 0), workspace, out, length or crcs; n > 2^44; final outside {0, 1}; workspace not
+ * 16-byte, length not 8-byte or crcs not 4-byte aligned; workspace_bytes or out_capacity below the bound. Four launches on `stream`
+ * (encode, crc, offsets, pack), no allocation, no synchronisation. */
+size_t vda_deflate_workspace_bytes(size_t n);
+size_t vda_deflate_out_bytes(size_t n);
+int vda_deflate_u8(const uint8_t* in, size_t n, int final, void* workspace, size_t workspace_bytes, uint8_t* out, size_t out_capacity,
+                   long long* length, uint32_t* crcs, vda_stream_t stream);
+
 /* ---- validation losses on the device (the reference's utils/loss_MiDas.py and utils/loss.py: Loss_ssi, Loss_tgm) ---------------
  * What train.py's validation pass ranks checkpoints by, as inference-time arithmetic (no gradients). pred, y: dense fp32
  * [nframes, px] (nframes = B * N, px = H * W); mask: bytes of the same shape, 0 = excluded, or NULL for all valid. Every fp32

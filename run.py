@@ -7,7 +7,8 @@ of uint8 [N,H,W,3] RGB frames, a directory of images, a GIF, a Motion-JPEG .avi 
 frames larger than `--max_res` are scaled down on the device with cv2's 8-bit arithmetic (csrc/resize_u8.hip), with `--stream` a
 block at a time (utils.dc_utils.read_video_blocks), so an HD .avi or .npy keeps its bounded memory; the
 visualisations are mp4 through imageio when present and animated GIFs otherwise, or with `--mjpeg` Motion-JPEG .avi files that
-need no encoder library (the JPEG coding runs on the device too, csrc/mjpeg.hip); `--save_npz` adds <name>_depths.npz.
+need no encoder library (the JPEG coding runs on the device too, csrc/mjpeg.hip); `--save_npz` adds <name>_depths.npz
+(key `depths`, read with np.load; on a GPU its deflate streams are made on the device, csrc/deflate.hip, instead of by zlib on one core).
 <name>_vis carries the reference's colours: depth is mapped through matplotlib's 256-entry inferno table, which ships in
 video_depth_anything_amd/visualize.py (not through the polynomial fit utils/dc_utils.py keeps as save_video's default), and on a
 GPU the mapping itself runs on the device (csrc/visualize.hip) - the same bytes as on the host.
@@ -27,7 +28,7 @@ import numpy as np
 import torch
 
 from utils.dc_utils import read_video_blocks, read_video_frames, reads_in_blocks, save_video
-from video_depth_anything_amd import mjpeg
+from video_depth_anything_amd import deflate, mjpeg
 from video_depth_anything_amd.scale import scaled_size
 from video_depth_anything_amd.visualize import inferno_table
 from video_depth_anything_amd.video_depth import MetricVideoDepthAnything, VideoDepthAnything
@@ -118,6 +119,13 @@ def block_jpegs(blocks, quality, device):
         yield from (mjpeg.encode_jpeg_numpy(b, quality) if device is None else mjpeg.encode_jpeg(b, quality, device))
 
 
+def save_depths_npz(path, depths, device):
+    """<name>_depths.npz, key `depths`, as np.savez_compressed writes it and np.load reads it. On a device the deflate streams are made
+    there (csrc/deflate.hip) instead of by zlib on one core; `depths` may be the memory map --stream left, which is then read block by
+    block. Without a device it IS np.savez_compressed."""
+    return deflate.savez_compressed(path, device=device, depths=depths)
+
+
 if __name__ == '__main__':
     parser = argparse.ArgumentParser(description='Video Depth Anything (MI355X)')
     parser.add_argument('--input_video', type=str, default='./assets/example_videos/davis_rollercoaster.mp4')
@@ -195,7 +203,7 @@ if __name__ == '__main__':
     vis_path = save_video(depths, stem + '_vis.mp4', fps=fps, is_depths=True, grayscale=args.grayscale, palette=inferno_table(),
                           device=vis_device, **d_range, **codec)
     if args.save_npz:
-        np.savez_compressed(stem + '_depths.npz', depths=depths)
+        save_depths_npz(stem + '_depths.npz', depths, io_device)
     if args.save_exr:
         import Imath
         import OpenEXR

@@ -604,6 +604,34 @@ def mjpeg_decode(scan, intervals, tables, qtables, hs, vs, workspace, out, statu
                                   _p(status), _stream(scan)), "vda_mjpeg_decode_u8")
 
 
+# ---- raw deflate of a device buffer (csrc/deflate.hip; deflate.py is the contract and owns the .npz container) --------------------
+def deflate_workspace_bytes(n):
+    return int(lib.vda_deflate_workspace_bytes(n))
+
+
+def deflate_out_bytes(n):
+    """The capacity deflate's `out` needs for n input bytes: no stream of them is longer."""
+    return int(lib.vda_deflate_out_bytes(n))
+
+
+def deflate(data, final, workspace, out, length, crcs):
+    """data uint8 [n] (n may be 0; any byte offset of a larger tensor) -> out uint8 [>= deflate_out_bytes(n)]: the raw deflate stream,
+    length int64 [1] its size, crcs int32 [>= max(1, ceil(n / 16384))] the CRC-32 of every 16384-byte chunk of the INPUT (as
+    unsigned bits); workspace: deflate_workspace_bytes(n) bytes. final=False leaves a byte-aligned piece that a later call continues."""
+    for t, name in ((data, "data"), (workspace, "workspace"), (out, "out")):
+        _req(t, torch.uint8, name)
+    _req(length, torch.int64, "length"), _req(crcs, torch.int32, "crcs")
+    if data.dim() != 1:
+        raise ValueError(f"deflate: data must be one axis of bytes, got {tuple(data.shape)}")
+    n = data.numel()
+    if length.numel() < 1 or crcs.numel() < max(1, -(-n // 16384)):
+        raise ValueError(f"deflate: length holds {length.numel()} entries (needs 1), crcs {crcs.numel()} (needs {max(1, -(-n // 16384))})")
+    if len({t.device for t in (data, workspace, out, length, crcs)}) != 1:
+        raise ValueError("deflate: the operands live on different devices")
+    check(lib.vda_deflate_u8(_p(data), n, 1 if final else 0, _p(workspace), workspace.numel(), _p(out), out.numel(), _p(length), _p(crcs),
+                             _stream(out)), "vda_deflate_u8")
+
+
 # ---- validation losses (csrc/losses.hip; losses.py lays the buffers out) --------------------------------------------------------
 LOSS_STATS = 8               # doubles per frame in `stats` (include/vda.h)
 
