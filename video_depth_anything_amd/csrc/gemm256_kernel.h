@@ -1,5 +1,6 @@
-// Large-tile fp16 MFMA GEMM / implicit-GEMM conv for gfx950: 256 x BN x 64 tiles, 8 waves, one
-// workgroup per CU. This is the kernel the encoder's qkv/proj/fc1/fc2 GEMMs and the head's wide convs run on.
+// Large-tile fp16 MFMA GEMM / implicit-GEMM conv for gfx950 on v_mfma_f32_32x32x16_f16: 256 x BN x 64 tiles, 8 waves, one
+// workgroup per CU, one barrier per K tile. An A/B family: the planner never picks it by default (gemm256s_kernel.h is the same
+// tile on 16x16x32 MFMA, gemm8p_kernel.h its 8-phase schedule). Tile walk, staging pieces and grid rule: gemm_tile.h.
 //
 // Why this shape: with a 128x128 tile every 32 MFMAs per wave need 32 KB staged from L2 into LDS; at MFMA
 // peak that is more than the L2 can deliver, so the small tile is staging-bound. 256x256 halves the staged
@@ -17,12 +18,11 @@
 // applied on the DMA SOURCE address and on the read address. MFMA operands are swapped (W rows as "A",
 // activation rows as "B") so a lane's accumulator registers are runs of 4 consecutive output columns.
 #pragma once
-#include "gemm_epilogue.h"
+#include "gemm_tile.h"
 
 namespace vda_gemm256 {
 
-constexpr int BK = 64;
-constexpr int ROW_BYTES = BK * 2;
+using namespace vda_gemm;
 constexpr int BM = 256;
 constexpr int NW = 8;                 // waves
 constexpr int NT = NW * 64;
@@ -42,28 +42,18 @@ __global__ void __launch_bounds__(NT) gemm256_kernel(const vda_gemm_args p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
 
-    // Persistent workgroups: one per CU, each walks tiles round by round. In round r the 32 workgroups of an
-    // XCD (equal bid % 8) take 32 CONSECUTIVE tiles (N fastest), so concurrently running tiles share A / W panels
-    // in that XCD's L2.
-    const int nbn = (p.N + BN - 1) / BN, nbm = (p.M + BM - 1) / BM;
-    const int ntiles = nbm * nbn;
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int per_xcd = nwg >> 3;                                    // launch guarantees nwg % 8 == 0
-    auto tile_of = [&](int round) { return round * nwg + (bid & 7) * per_xcd + (bid >> 3); };
+    // Persistent workgroups, one per CU (gemm_tile.h): the plain XCD mapping in every round
+    const TileWalk walk = tile_walk<BM, BN>(p);
+    auto tile_of = [&](int round) { return walk.plain(round); };
+    const int ntiles = walk.ntiles;
 
-    // ---- per-lane DMA sources. A piece is 8 rows x 128 B; lane -> (row lrow of the piece, LDS chunk lane & 7).
-    // The swizzled source chunk ((lane&7) ^ ((row>>1)&7)) does not depend on the piece index (pieces are 8 rows
-    // apart, the swizzle has period 16 rows and the wave stride is 64 rows), so it is one lane constant.
-    // Dense / W offsets are recomputed per K tile from the tile origin (3 VALU ops per piece) instead of being
-    // kept in registers; only the conv row decomposition (two divisions per piece) is cached.
+    // ---- per-lane DMA sources (the pieces: gemm_tile.h). Only the conv row decomposition (two divisions per piece) is cached per tile.
     const int lrow = lane >> 3;
     const int src_chk = ((lane & 7) ^ ((((wave & 1) << 2) + (lrow >> 1)) & 7)) * 8;     // halves
     int a_pix[AJ], a_yx[AJ];          // conv: b*H*W, and (oy*stride-1) | (ox*stride-1) << 16
     int tm0 = 0, tn0 = 0;             // origin of the tile being staged
     auto set_sources = [&](int t) {
-        const int bm = t / nbn, bn = t - bm * nbn;
-        tm0 = bm * BM;
-        tn0 = bn * BN;
+        walk.origin<BM, BN>(t, tm0, tn0);
         if constexpr (AMODE == VDA_A_CONV3X3) {
 #pragma unroll
             for (int j = 0; j < AJ; ++j) {
@@ -84,10 +74,7 @@ __global__ void __launch_bounds__(NT) gemm256_kernel(const vda_gemm_args p) {
         const int k0 = kt * BK;
         if constexpr (AMODE == VDA_A_DENSE) {
 #pragma unroll
-            for (int j = 0; j < AJ; ++j) {
-                const int m = min(tm0 + (wave + NW * j) * 8 + lrow, p.M - 1);
-                glds16((const h16*)p.A + (size_t)(unsigned)(m * p.lda + src_chk + k0), buf + (wave + NW * j) * 1024);
-            }
+            for (int j = 0; j < AJ; ++j) stage_a_piece(p, tm0, wave + NW * j, lrow, src_chk, k0, buf);
         } else {
             const int tap = k0 / p.cCin, ci0 = k0 - tap * p.cCin;
             const int ky = tap / 3, kx = tap - ky * 3;
@@ -101,20 +88,13 @@ __global__ void __launch_bounds__(NT) gemm256_kernel(const vda_gemm_args p) {
             }
         }
 #pragma unroll
-        for (int j = 0; j < WJ; ++j) {
-            const int n = min(tn0 + (wave + NW * j) * 8 + lrow, p.N - 1);
-            glds16((const h16*)p.W + (size_t)(unsigned)(n * p.K + src_chk + k0), buf + A_BYTES + (wave + NW * j) * 1024);
-        }
+        for (int j = 0; j < WJ; ++j) stage_w_piece(p, tn0, wave + NW * j, lrow, src_chk, k0, buf + A_BYTES);
     };
 
     // fragment addressing: row = lane & 31 inside a 32-row subtile, k-chunk = 2*step + (lane >> 5)
     const int frow = lane & 31, fh = lane >> 5, fsw = (lane >> 1) & 7;     // ((row >> 1) & 7) with row = subtile*32 + frow
     const int a_off = (wm * WTM + frow) * ROW_BYTES, w_off = A_BYTES + (wn * WTN + frow) * ROW_BYTES;
-    // relu on the activation operand (conv only), branch-free: max(x, 0) or max(x, -inf)
-    const h16 relu_floor = (p.relu_in & VDA_OPT_RELU_IN) ? (h16)0.f : (h16)(-65504.f);
-    h16x8 relu_thr;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) relu_thr[e] = relu_floor;
+    const h16x8 relu_thr = relu_threshold(p);
 
     struct Frags {
         h16x8 a[MI];
@@ -140,8 +120,8 @@ __global__ void __launch_bounds__(NT) gemm256_kernel(const vda_gemm_args p) {
     set_sources(tile);
     stage(0, smem);
     for (int round = 0; tile < ntiles; ++round) {
-        const int bm = tile / nbn, bn = tile - bm * nbn;
-        const int m0 = bm * BM, n0 = bn * BN;
+        int m0, n0;
+        walk.origin<BM, BN>(tile, m0, n0);
 
         f32x16 acc[MI][NJ];
 #pragma unroll
@@ -302,9 +282,7 @@ int launch256(const vda_gemm_args& a, hipStream_t s) {
     static VdaKernelDeviceState dev_state;
     const int num_cu = vda_prepare_kernel(reinterpret_cast<const void*>(&gemm256_kernel<BN, AMODE, EPI>), smem, dev_state);
     if (num_cu < 0) return 2;
-    const int nbm = (a.M + BM - 1) / BM, nbn = (a.N + BN - 1) / BN;
-    const int ntiles = nbm * nbn;
-    const int grid = ntiles < num_cu ? (ntiles + 7) / 8 * 8 : num_cu;     // one persistent workgroup per CU
+    const int grid = persistent_grid(tile_count<BM, BN>(a), num_cu);     // one persistent workgroup per CU
     hipLaunchKernelGGL((gemm256_kernel<BN, AMODE, EPI>), dim3(grid), dim3(NT), smem, s, a);
     VDA_LAUNCH_CHECK();
     return 0;

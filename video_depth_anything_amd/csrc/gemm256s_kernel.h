@@ -1,30 +1,29 @@
-// Large-tile fp16 MFMA GEMM / implicit-GEMM conv for gfx950: 256 x BN x 64 tiles, 8 waves, one
-// workgroup per CU. This is the kernel the encoder's qkv/proj/fc1/fc2 GEMMs and the head's wide convs run on.
+// Large-tile fp16 MFMA GEMM / implicit-GEMM conv for gfx950 on v_mfma_f32_16x16x32_f16: BM x BN x 64 tiles, one barrier per K tile.
+// 256 x 256 / 256 x 128 on 8 waves, 192 x 128 on 6 (one or two workgroups per CU), 192 x 384 on 12. This is the kernel the
+// N = 128-wide cases and ViT-S's N = 384 / 1152 GEMMs run on; the 8-phase schedule of the same tile is gemm8p_kernel.h, the
+// 32x32x16 form gemm256_kernel.h. Tile walk, stagger, staging pieces, tap cursor and grid rule: gemm_tile.h.
 //
 // Why this shape: with a 128x128 tile every 32 MFMAs per wave need 32 KB staged from L2 into LDS; at MFMA
 // peak that is more than the L2 can deliver, so the small tile is staging-bound. 256x256 halves the staged
-// bytes per FLOP (64 KB per 64 MFMAs per wave) and the 128x64 wave tile cuts LDS fragment reads to
-// 0.75 ds_read_b128 per v_mfma_f32_32x32x16_f16.
+// bytes per FLOP. Per 32-deep k step the 128x64 wave tile reads 8 + 4 fragments for 32 MFMAs: 0.375 ds_read_b128 per MFMA.
 //
 // Pipeline (one __syncthreads per 64-deep K tile):
-//   LDS holds two K tiles (2 x 64 KB at BN=256). Fragments are register double-buffered at 16-deep k-step
-//   granularity: while the 8 MFMAs of step t issue, the 6 ds_read_b128 of step t+1 are in flight. The last
-//   step of tile k waits for tile k+1 (issued one whole tile earlier), barriers once, issues the 8
-//   global_load_lds of tile k+2 into the buffer tile k just vacated, and prefetches tile k+1's first
+//   LDS holds two K tiles (2 x 64 KB at BN=256). A K tile is four units of 16 MFMAs (at the 128x64 wave tile): one 32-deep k step
+//   x half of the wave's rows. Fragments are register double-buffered at that granularity: while the MFMAs of one unit issue, the
+//   ds_read_b128 of the next are in flight. The last unit of tile k waits for tile k+1 (issued one whole tile earlier), barriers
+//   once, issues the global_load_lds of tile k+2 into the buffer tile k just vacated, and prefetches tile k+1's first
 //   fragments while its own MFMAs run, so the barrier never exposes an LDS or HBM round trip.
 //
-// LDS image: [rows][8 x 16 B], chunk ^= (row >> 1) & 7 (conflict-free for the 32-row ds_read_b128 fragment),
+// LDS image: [rows][8 x 16 B], chunk ^= (row >> 1) & 7 (conflict-free for the 16-row ds_read_b128 fragment),
 // applied on the DMA SOURCE address and on the read address. MFMA operands are swapped (W rows as "A",
-// activation rows as "B") so a lane's accumulator registers are runs of 4 consecutive output columns.
-// 16x16x32-MFMA variant of gemm256_kernel.h (same tile, DMA, LDS image, persistence and epilogue; the K loop
-// is pipelined in units of 16 MFMAs: one 32-deep k step x half of the wave's rows).
+// activation rows as "B") so a lane's accumulator registers are 4 consecutive output columns.
 #pragma once
-#include "gemm_epilogue.h"
+#include "gemm_tile.h"
 
 namespace vda_gemm256s {
 
-constexpr int BK = 64;
-constexpr int ROW_BYTES = BK * 2;
+using namespace vda_gemm;
+
 // BM = 256 on 8 waves, or (BN = 128 only) BM = 192 on 6 waves (3 x 2, the same 64 x 64 wave tile): the tile for problems whose
 // 256-row tile count sits just above a multiple of the CU count - ViT-S's proj / fc2: 172 x 3 = 516 tiles = 2.016 rounds run as
 // 3; 229 x 3 = 687 tiles of 3/4 the size = 2.68 rounds run as 3 x 0.75 = 2.25.
@@ -57,37 +56,17 @@ __global__ void __launch_bounds__(BN == 384 ? 768 : BM / 32 * 64) gemm256s_kerne
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
 
-    // Persistent workgroups: one per CU, each walks tiles round by round. In round r the 32 workgroups of an
-    // XCD (equal bid % 8) take 32 CONSECUTIVE tiles (N fastest), so concurrently running tiles share A / W panels
-    // in that XCD's L2.
-    const int nbn = (p.N + BN - 1) / BN, nbm = (p.M + BM - 1) / BM;
-    const int ntiles = nbm * nbn;
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int per_xcd = nwg >> 3;                                    // launch guarantees nwg % 8 == 0
-    // last partial round dealt evenly to the XCDs in row-panel groups, as in gemm8p_kernel.h
-    const int full_rounds = ntiles / nwg, rem = ntiles - full_rounds * nwg;
-    const bool deal_last = rem > 0 && full_rounds > 0 && per_xcd % nbn == 0;
-    auto tile_of = [&](int round) {
-        if (deal_last && round == full_rounds) {
-            const int slot = bid >> 3, j = ((slot / nbn) * 8 + (bid & 7)) * nbn + slot % nbn;
-            return j < rem ? round * nwg + j : ntiles;
-        }
-        return round * nwg + (bid & 7) * per_xcd + (bid >> 3);
-    };
+    const TileWalk walk = tile_walk<BM, BN>(p);
+    auto tile_of = [&](int round) { return walk.dealt(round); };
+    const int ntiles = walk.ntiles;
 
-    // ---- per-lane DMA sources. A piece is 8 rows x 128 B; lane -> (row lrow of the piece, LDS chunk lane & 7).
-    // The swizzled source chunk ((lane&7) ^ ((row>>1)&7)) does not depend on the piece index (pieces are 8 rows
-    // apart, the swizzle has period 16 rows and the wave stride is 64 rows), so it is one lane constant.
-    // Dense / W offsets are recomputed per K tile from the tile origin (3 VALU ops per piece) instead of being
-    // kept in registers; only the conv row decomposition (two divisions per piece) is cached.
+    // ---- per-lane DMA sources (the pieces: gemm_tile.h). Only the conv row decomposition (two divisions per piece) is cached per tile.
     const int lrow = lane >> 3;
     const int src_chk = ((lane & 7) ^ ((((wave & 1) << 2) + (lrow >> 1)) & 7)) * 8;     // halves
     int a_pix[AJ], a_yx[AJ];          // conv: b*H*W, and (oy*stride-1) | (ox*stride-1) << 16
     int tm0 = 0, tn0 = 0;             // origin of the tile being staged
     auto set_sources = [&](int t) {
-        const int bm = t / nbn, bn = t - bm * nbn;
-        tm0 = bm * BM;
-        tn0 = bn * BN;
+        walk.origin<BM, BN>(t, tm0, tn0);
         if constexpr (AMODE == VDA_A_CONV3X3) {
 #pragma unroll
             for (int j = 0; j < AJ; ++j) {
@@ -104,36 +83,20 @@ __global__ void __launch_bounds__(BN == 384 ? 768 : BM / 32 * 64) gemm256s_kerne
         }
     };
 
-    // conv: (3x3 tap, 64-channel slice) of the K tile being staged. Set by tap_of() at the tile seams (one integer division by
-    // the runtime channel count), advanced incrementally inside the K loop: the division is a ~40-instruction dependent chain
-    // that would sit between the barrier and the DMA burst of every K tile.
-    int cv_tap = 0, cv_ci0 = 0;
+    TapCursor cur;                      // conv: (3x3 tap, 64-channel slice) of the K tile being staged
     auto tap_of = [&](int kt) {
-        if constexpr (AMODE == VDA_A_CONV3X3) {
-            const int k0 = kt * BK;
-            cv_tap = k0 / p.cCin;
-            cv_ci0 = k0 - cv_tap * p.cCin;
-        }
+        if constexpr (AMODE == VDA_A_CONV3X3) cur.seek(p, kt);
     };
     auto tap_next = [&]() {
-        if constexpr (AMODE == VDA_A_CONV3X3) {
-            cv_ci0 += BK;
-            if (cv_ci0 >= p.cCin) {
-                cv_ci0 = 0;
-                ++cv_tap;
-            }
-        }
+        if constexpr (AMODE == VDA_A_CONV3X3) cur.next(p);
     };
     auto stage = [&](int kt, char* buf) {
         const int k0 = kt * BK;
         if constexpr (AMODE == VDA_A_DENSE) {
 #pragma unroll
-            for (int j = 0; j < AJ; ++j) {
-                const int m = min(tm0 + (wave + NW * j) * 8 + lrow, p.M - 1);
-                glds16((const h16*)p.A + (size_t)(unsigned)(m * p.lda + src_chk + k0), buf + (wave + NW * j) * 1024);
-            }
+            for (int j = 0; j < AJ; ++j) stage_a_piece(p, tm0, wave + NW * j, lrow, src_chk, k0, buf);
         } else {
-            const int tap = cv_tap, ci0 = cv_ci0;
+            const int tap = cur.tap, ci0 = cur.ci0;
             const int ky = (tap * 11) >> 5, kx = tap - ky * 3;   // tap / 3 for tap = 0..8
 #pragma unroll
             for (int j = 0; j < AJ; ++j) {
@@ -147,19 +110,14 @@ __global__ void __launch_bounds__(BN == 384 ? 768 : BM / 32 * 64) gemm256s_kerne
 #pragma unroll
         for (int j = 0; j < WJ; ++j) {
             if (WP % NW != 0 && wave + NW * j >= WP) break;                  // wave-uniform
-            const int n = min(tn0 + (wave + NW * j) * 8 + lrow, p.N - 1);
-            glds16((const h16*)p.W + (size_t)(unsigned)(n * p.K + src_chk + k0), buf + A_BYTES + (wave + NW * j) * 1024);
+            stage_w_piece(p, tn0, wave + NW * j, lrow, src_chk, k0, buf + A_BYTES);
         }
     };
 
     // fragment addressing: row = lane & 15 inside a 16-row subtile, k-chunk = 4*ks + (lane >> 4)
     const int frow = lane & 15, fh = lane >> 4, fsw = (lane >> 1) & 7;     // ((row >> 1) & 7) with row = subtile*16 + frow
     const int a_off = (wm * WTM + frow) * ROW_BYTES, w_off = A_BYTES + (wn * WTN + frow) * ROW_BYTES;
-    // relu on the activation operand (conv only), branch-free: max(x, 0) or max(x, -inf)
-    const h16 relu_floor = (p.relu_in & VDA_OPT_RELU_IN) ? (h16)0.f : (h16)(-65504.f);
-    h16x8 relu_thr;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) relu_thr[e] = relu_floor;
+    const h16x8 relu_thr = relu_threshold(p);
 
     struct AF {
         h16x8 a[MH];
@@ -187,20 +145,13 @@ __global__ void __launch_bounds__(BN == 384 ? 768 : BM / 32 * 64) gemm256s_kerne
 
     int tile = tile_of(0);
     if (tile >= ntiles) return;                        // uniform per workgroup
-    // stagger of the workgroups that sit out the last round (gemm8p_kernel.h): up to 3/4 of a tile time, four phases, free
-    if (!VDA_OPT_FLAG(p.relu_in, VDA_FLAG_NO_STAGGER) && rem > 0 && full_rounds > 0 && tile_of(full_rounds) >= ntiles) {       // VDA_GEMM_STAGGER=0 switches it off
-        // phase by slot: the nbn workgroups of an XCD that share an A row panel land in DIFFERENT phases (keeping them in phase -
-        // VDA_GEMM_STAGGER=2 - is slower than no stagger at all: it is those neighbours' epilogues that collide)
-        const int q = VDA_OPT_FLAG(p.relu_in, VDA_FLAG_STAGGER_PANEL) ? ((bid >> 3) / (nbn <= 8 ? nbn : 8)) & 3 : (bid >> 3) & 3;
-        const int units = (nt * 60 + 260) * q / 4;
-        for (int i = 0; i < units; i += 120) __builtin_amdgcn_s_sleep(120);
-    }
+    stagger_last_round<60>(p, walk, nt, tile_of);      // the workgroups that sit out the last round
     set_sources(tile);
     tap_of(0);
     stage(0, smem);
     for (int round = 0; tile < ntiles; ++round) {
-        const int bm = tile / nbn, bn = tile - bm * nbn;
-        const int m0 = bm * BM, n0 = bn * BN;
+        int m0, n0;
+        walk.origin<BM, BN>(tile, m0, n0);
 
         f32x4 acc[MI][NJ];
 #pragma unroll
@@ -269,9 +220,9 @@ __global__ void __launch_bounds__(BN == 384 ? 768 : BM / 32 * 64) gemm256s_kerne
             stage(0, smem);
         }
 
-        // ---- epilogue. Accumulator register e of subtile (i,j) is row m = lane & 31, column 8*(e>>2) + 4*(lane>>5) + (e&3):
-        // stored straight from this layout a wave instruction would touch 32 rows x 16 B (32 partial lines). Instead each
-        // wave transposes one 32-row x 64-column fp32 block at a time through its own 8 KiB of (idle) pipeline buffer 1
+        // ---- epilogue. Accumulator (mi, nj) holds row 16*mi + (lane & 15), columns 16*nj + 4*(lane >> 4) + e of the wave tile:
+        // stored straight from this layout a wave instruction would touch 16 rows x 64 B (16 partial lines). Instead each
+        // wave transposes one 32-row x 64-column fp32 block (accumulator rows 2i, 2i+1) at a time through its own 8 KiB staging slice
         // (16-byte chunks XOR-swizzled by row: conflict-free both ways) and then owns whole row segments: bias / LayerScale /
         // residual reads and the output stores become contiguous 16-byte accesses covering full 128-byte lines.
         const int bm0 = m0 + wm * WTM, bn0 = n0 + wn * WTN;
@@ -388,9 +339,7 @@ int launch256(const vda_gemm_args& a, hipStream_t s) {
     static VdaKernelDeviceState dev_state;
     const int num_cu = vda_prepare_kernel(reinterpret_cast<const void*>(&gemm256s_kernel<BN, AMODE, EPI, BM, PER_CU>), smem, dev_state);
     if (num_cu < 0) return 2;
-    const int nbm = (a.M + BM - 1) / BM, nbn = (a.N + BN - 1) / BN;
-    const int ntiles = nbm * nbn;
-    const int grid = ntiles < PER_CU * num_cu ? (ntiles + 7) / 8 * 8 : PER_CU * num_cu;     // PER_CU persistent workgroups per CU
+    const int grid = persistent_grid(tile_count<BM, BN>(a), PER_CU * num_cu);     // PER_CU persistent workgroups per CU
     if (PER_CU == 2 && getenv("VDA_DEBUG_OCC")) {           // what the runtime thinks fits on a CU (A/B aid)
         int nb = -1;
         (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gemm256s_kernel<BN, AMODE, EPI, BM, PER_CU>, nthreads, smem);

@@ -1,7 +1,7 @@
 // 8-phase, two-group (ping-pong) schedule of the 256 x 256 x 64 fp16 MFMA GEMM / implicit-GEMM conv for gfx950.
 // Same tile, LDS image (rows of 128 B, 16-byte chunks XOR-swizzled by (row >> 1) & 7 on the DMA SOURCE address and on the
-// read), fragment shapes (v_mfma_f32_16x16x32_f16, swapped operands), persistence and epilogue as gemm8p_kernel.h;
-// what changes is WHEN things are issued:
+// read), fragment shapes (v_mfma_f32_16x16x32_f16, swapped operands), persistence and epilogue as gemm256s_kernel.h (tile walk,
+// stagger, staging pieces, tap cursor and grid rule are written once, in gemm_tile.h); what changes is WHEN things are issued:
 //
 //   * A K tile is four phases of 16 MFMAs: (k-step 0, rows lo), (k0, rows hi), (k1, rows lo), (k1, rows hi) of the wave's
 //     128 x 64 tile. A phase = { ds_read its fragments (8 / 4 / 8 / 4 x b128) ; issue a slice of the LDS-DMA of K tile
@@ -22,12 +22,11 @@
 //   WAR: every reading phase drains lgkmcnt(0) BEFORE its first barrier; a slot is re-staged no earlier than the phase
 //        after its last read (A: last read phase 4 of K tile kt-1, re-staged phase 1 of kt; W: phase 3 -> phase 4).
 #pragma once
-#include "gemm_epilogue.h"
+#include "gemm_tile.h"
 
 namespace vda_gemm8p {
 
-constexpr int BK = 64;
-constexpr int ROW_BYTES = BK * 2;
+using namespace vda_gemm;
 constexpr int BM_MAX = 256;           // the LDS slots are laid out for the 256-row tile (a 192-row tile uses the first 192 rows of each)
 constexpr int NW = 8;                 // waves
 constexpr int NT = NW * 64;
@@ -76,18 +75,10 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
     const int wm = wave / WN, wn = wave % WN;
     const int grp = wave >> 2;                         // wave group: 0 = waves 0..3, 1 = their SIMD partners (rows 128.. of the tile)
 
-    // Persistent workgroups: one per CU, each walks tiles round by round. In round r the 32 workgroups of an
-    // XCD (equal bid % 8) take 32 CONSECUTIVE tiles (N fastest), so concurrently running tiles share A / W panels
-    // in that XCD's L2.
-    const int nbn = (p.N + BN - 1) / BN, nbm = (p.M + BM - 1) / BM;
-    const int ntiles = nbm * nbn;
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int per_xcd = nwg >> 3;                                    // launch guarantees nwg % 8 == 0
-    // The LAST, partial round (ntiles % nwg tiles) is dealt to the XCDs in groups of nbn consecutive tiles (one row panel), round
-    // robin, so that every XCD keeps the same share of busy CUs instead of whole XCDs going idle (needs nbn | per_xcd; otherwise
-    // the plain mapping stays). A workgroup without a tile in that round has one tile time of slack: see the stagger below.
-    const int full_rounds = ntiles / nwg, rem = ntiles - full_rounds * nwg;
-    const bool deal_last = rem > 0 && full_rounds > 0 && per_xcd % nbn == 0;
+    // Persistent workgroups, one per CU (gemm_tile.h): the plain XCD mapping with the last, partial round dealt in row-panel groups.
+    const TileWalk walk = tile_walk<BM, BN>(p);
+    const int nbn = walk.nbn, nbm = walk.nbm, ntiles = walk.ntiles, nwg = walk.nwg, bid = walk.bid, per_xcd = walk.per_xcd;
+    const int full_rounds = walk.full_rounds;
     // L2-BLOCKED tile order: an XCD keeps ONE group of CG column panels for the whole launch (its W slice - 4 x 256 x K x 2 B = 2 MB at
     // K = 1024 - stays in its 4 MB L2) and walks down the row panels, interleaved with the other XCDs of its column group, instead of
     // 32 consecutive tiles per round (N fastest), which at nbn = 16 re-fetches all 8 MB of W past L2 every round (fc1: 832 MB fetched
@@ -112,11 +103,7 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
             const int rp = idx / cgw, cp = (x % cgroups) * cgw + (idx - rp * cgw);
             return rp < nbm ? rp * nbn + cp : ntiles;
         }
-        if (deal_last && round == full_rounds) {
-            const int slot = bid >> 3, j = ((slot / nbn) * 8 + (bid & 7)) * nbn + slot % nbn;
-            return j < rem ? round * nwg + j : ntiles;
-        }
-        return round * nwg + (bid & 7) * per_xcd + (bid >> 3);
+        return walk.dealt(round);
     };
     // FOLD: in the walk above a workgroup keeps its column panel from round to round whenever nbn | nwg (16 | 256) - the one that
     // drew a 16-K-tile phase would run 16-K-tile phases all launch long and the launch would end at ITS pace (4x the lightest). The
@@ -143,18 +130,14 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
     // tiles instead of running its fixed share one shift late: with the static walk a foreign kernel costs ~35 % of its active
     // time (tools/contention.py). The draw for tile i+2 is issued by lane 0 of wave 0 at the top of tile i+1 ... i.e. one tile
     // ahead of its use, and handed to the other waves through LDS at the K loop's last barrier.
-    constexpr bool dyn = DYN;                  // (the launcher picks the instantiation by p.sched != NULL)
+    // (the launcher picks the DYN instantiation by p.sched != NULL)
     const int xq = ntiles >> 3, xr = ntiles & 7;
     const int xb = (bid & 7) * xq + min(bid & 7, xr), xc = xq + ((bid & 7) < xr ? 1 : 0);
-    const bool drawer = dyn && wave == 0;                          // wave-uniform (constant false without DYN)
+    const bool drawer = DYN && wave == 0;                          // wave-uniform (constant false without DYN)
     volatile VDA_LDS_AS int* const sched_slot =
         (volatile VDA_LDS_AS int*)(smem + 3 * A_BYTES + BN * ROW_BYTES + NW * 1024);      // W slot 1, past the statistics slices
 
-    // ---- per-lane DMA sources. A piece is 8 rows x 128 B; lane -> (row lrow of the piece, LDS chunk lane & 7).
-    // The swizzled source chunk ((lane&7) ^ ((row>>1)&7)) does not depend on the piece index (pieces are 8 rows
-    // apart, the swizzle has period 16 rows and the wave stride is 64 rows), so it is one lane constant.
-    // Dense / W offsets are recomputed per K tile from the tile origin (3 VALU ops per piece) instead of being
-    // kept in registers; only the conv row decomposition (two divisions per piece) is cached.
+    // ---- per-lane DMA sources (the pieces: gemm_tile.h). Only the conv row decomposition (two divisions per piece) is cached per tile.
     const int lrow = lane >> 3;
     const int src_chk = ((lane & 7) ^ ((((wave & 1) << 2) + (lrow >> 1)) & 7)) * 8;     // halves
     // conv: per A piece the element offset of the window's top-left tap (+ the lane's swizzled chunk) and a 9-bit mask of the taps
@@ -168,9 +151,7 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
     [[maybe_unused]] const auto a_rsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<void*>(p.A), 0, AMODE == VDA_A_CONV3X3 ? (unsigned)(p.cB * p.cH * p.cW * p.cCin) * 2u : 0u, 0x00020000);
     auto set_sources = [&](int t) {
-        const int bm = t / nbn, bn = t - bm * nbn;
-        tm0 = bm * BM;
-        tn0 = bn * BN;
+        walk.origin<BM, BN>(t, tm0, tn0);
         if constexpr (FOLD) cv_mask = vda_gemm::fold_tap_mask(tn0, min(tn0 + BN, p.N), p.tK, p.tCout);
         if constexpr (AMODE == VDA_A_CONV3X3) {
 #pragma unroll
@@ -202,33 +183,27 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
     // (tap * Cin + ci0, not kt * 64). W(kt) is staged in two halves, the second a phase after the pair has moved on to K tile
     // kt + 1: cv_wk keeps the offset of the K tile whose A was staged last (tap_next) - the prologue's K tiles 0 and 1 set it in
     // tap_of, and tap_of(2), which only positions the pair, leaves it at K tile 1's for that tile's second half.
-    int cv_tap = 0, cv_ci0 = 0;
+    TapCursor cur;
     [[maybe_unused]] int cv_wk = 0;
     auto tap_of = [&](int kt) {
         if constexpr (FOLD) {
             const int idx = kt / cv_cpt;
-            cv_tap = vda_gemm::fold_nth_tap(cv_mask, idx);
-            cv_ci0 = (kt - idx * cv_cpt) * BK;
-            if (kt < 2) cv_wk = cv_tap * p.cCin + cv_ci0;
+            cur.tap = vda_gemm::fold_nth_tap(cv_mask, idx);
+            cur.ci0 = (kt - idx * cv_cpt) * BK;
+            if (kt < 2) cv_wk = cur.tap * p.cCin + cur.ci0;
         } else if constexpr (AMODE == VDA_A_CONV3X3) {
-            const int k0 = kt * BK;
-            cv_tap = k0 / p.cCin;
-            cv_ci0 = k0 - cv_tap * p.cCin;
+            cur.seek(p, kt);
         }
     };
     auto tap_next = [&]() {
-        if constexpr (AMODE == VDA_A_CONV3X3) {
-            if constexpr (FOLD) cv_wk = cv_tap * p.cCin + cv_ci0;
-            cv_ci0 += BK;
-            if (cv_ci0 >= p.cCin) {
-                cv_ci0 = 0;
-                if constexpr (FOLD) {
-                    const int rest = cv_mask >> (cv_tap + 1);
-                    cv_tap = rest ? cv_tap + 1 + __builtin_ctz(rest) : 9;
-                } else {
-                    ++cv_tap;
-                }
+        if constexpr (FOLD) {
+            cv_wk = cur.tap * p.cCin + cur.ci0;
+            if (cur.next_slice(p)) {             // on to the next SET tap of the mask
+                const int rest = cv_mask >> (cur.tap + 1);
+                cur.tap = rest ? cur.tap + 1 + __builtin_ctz(rest) : 9;
             }
+        } else if constexpr (AMODE == VDA_A_CONV3X3) {
+            cur.next(p);
         }
     };
     auto stage_a = [&](int kt, int j0, char* abuf) {
@@ -237,14 +212,11 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
 #pragma unroll
             for (int jj = 0; jj < 2; ++jj) {
                 const int j = j0 + jj;
-                if (j < AJ) {                    // (192-row tile: three pieces, issued 2 + 1)
-                    const int m = min(tm0 + (wave + NW * j) * 8 + lrow, p.M - 1);
-                    glds16((const h16*)p.A + (size_t)(unsigned)(m * p.lda + src_chk + k0), abuf + (wave + NW * j) * 1024);
-                }
+                if (j < AJ) stage_a_piece(p, tm0, wave + NW * j, lrow, src_chk, k0, abuf);      // (192-row tile: three pieces, issued 2 + 1)
             }
         } else {
-            const int tap = cv_tap, ci0 = cv_ci0;            // set by tap_of(kt) / tap_next(): wave-uniform (scalar registers)
-            const int ky = (tap * 11) >> 5, kx = tap - ky * 3;   // tap / 3 for tap = 0..8
+            const int tap = cur.tap, ci0 = cur.ci0;          // set by tap_of(kt) / tap_next(): wave-uniform (scalar registers)
+            const int ky = cur.ky(), kx = tap - ky * 3;
             const int toff = (ky * p.cW + kx) * p.cCin + ci0, bit = 1 << tap;
 #pragma unroll
             for (int jj = 0; jj < 2; ++jj) {
@@ -257,20 +229,13 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
     auto stage_w = [&](int kt, char* wbuf, int j0 = 0, int j1 = BN / 8 / NW) {
         const int k0 = FOLD ? cv_wk : kt * BK;
 #pragma unroll
-        for (int j = j0; j < j1; ++j) {
-            const int n = min(tn0 + (wave + NW * j) * 8 + lrow, p.N - 1);
-            glds16((const h16*)p.W + (size_t)(unsigned)(n * p.K + src_chk + k0), wbuf + (wave + NW * j) * 1024);
-        }
+        for (int j = j0; j < j1; ++j) stage_w_piece(p, tn0, wave + NW * j, lrow, src_chk, k0, wbuf);
     };
 
     // fragment addressing: row = lane & 15 inside a 16-row subtile, k-chunk = 4*ks + (lane >> 4)
     const int frow = lane & 15, fh = lane >> 4, fsw = (lane >> 1) & 7;     // ((row >> 1) & 7) with row = subtile*16 + frow
     const int a_off = (wm * WTM + frow) * ROW_BYTES, w_off = (wn * WTN + frow) * ROW_BYTES;
-    // relu on the activation operand (conv only), branch-free: max(x, 0) or max(x, -inf)
-    const h16 relu_floor = (p.relu_in & VDA_OPT_RELU_IN) ? (h16)0.f : (h16)(-65504.f);
-    h16x8 relu_thr;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) relu_thr[e] = relu_floor;
+    const h16x8 relu_thr = relu_threshold(p);
 
     struct AF {
         h16x8 a[MH];
@@ -341,22 +306,14 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
         }
     };
 
-    int tile = dyn ? ((bid >> 3) < xc ? xb + (bid >> 3) : ntiles) : tile_of(0);
+    int tile = DYN ? ((bid >> 3) < xc ? xb + (bid >> 3) : ntiles) : tile_of(0);
     if (tile >= ntiles) return;                        // uniform per workgroup
-    // Start stagger (VDA_GEMM_STAGGER=1, OFF by default). All workgroups run the same tile time, so their epilogues hit HBM
-    // together (a plain fp16 epilogue stores at 7.8 TB/s aggregate: it is bandwidth-bound only because it is synchronised).
-    // Workgroups that sit out the last round can start up to 3/4 of a tile time late, in four phases, for free - the launch ends
-    // with the others' last tile - and take their epilogues out of phase: -4..-6 us per qkv / fc1 / fc2 launch on some boxes,
-    // nothing on others, and it costs L2 sharing (PMC: +40 % fetched bytes, the workgroups of an XCD no longer read the same W
-    // and A tiles at the same moment) and 2 % with two clips in flight (a sleeping workgroup holds a CU the other stream's
-    // kernel could use). Tile time estimate: 1.6 us per K tile + 8 us, at ~2.1 GHz, in 64-cycle sleep units.
-    if (!dyn && !VDA_OPT_FLAG(p.relu_in, VDA_FLAG_NO_STAGGER) && rem > 0 && full_rounds > 0 && tile_of(full_rounds) >= ntiles) {       // switch off: variant 5 + 16 * 16
-        // phase by slot: the nbn workgroups of an XCD that share an A row panel land in DIFFERENT phases (keeping them in phase -
-        // VDA_GEMM_STAGGER=2 - is slower than no stagger at all: it is those neighbours' epilogues that collide)
-        const int q = VDA_OPT_FLAG(p.relu_in, VDA_FLAG_STAGGER_PANEL) ? ((bid >> 3) / (nbn <= 8 ? nbn : 8)) & 3 : (bid >> 3) & 3;
-        const int units = (nt * 52 + 260) * q / 4;
-        for (int i = 0; i < units; i += 120) __builtin_amdgcn_s_sleep(120);
-    }
+    // Start stagger (gemm_tile.h; VDA_GEMM_STAGGER=1, OFF by default). All workgroups run the same tile time, so their epilogues hit
+    // HBM together (a plain fp16 epilogue stores at 7.8 TB/s aggregate: it is bandwidth-bound only because it is synchronised).
+    // Staggered: -4..-6 us per qkv / fc1 / fc2 launch on some boxes, nothing on others, and it costs L2 sharing (PMC: +40 % fetched
+    // bytes, the workgroups of an XCD no longer read the same W and A tiles at the same moment) and 2 % with two clips in flight (a
+    // sleeping workgroup holds a CU the other stream's kernel could use). Tile time estimate: 1.6 us per K tile + 8 us, at ~2.1 GHz.
+    if constexpr (!DYN) stagger_last_round<52>(p, walk, nt, tile_of);      // switch off: variant 5 + 16 * 16
     load_bias(tile);
     load_stats(tile);
     set_sources(tile);
@@ -397,17 +354,14 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
         };
         if (stamp) stamps[(bid * 16 + (round & 15)) * 4 + 0] = __builtin_readcyclecounter();
         clk(round, 0);
-        const int bm = tile / nbn, bn = tile - bm * nbn;
-        const int m0 = bm * BM, n0 = bn * BN;
+        int m0, n0;
+        walk.origin<BM, BN>(tile, m0, n0);
 
         f32x4 acc[MI][NJ];
 #pragma unroll
         for (int i = 0; i < MI; ++i)
 #pragma unroll
             for (int j = 0; j < NJ; ++j) acc[i][j] = nbias[j];
-        // ReLU on the conv activation operand: in the LOAD section (after the fragments landed, before the barrier), so it
-        // runs under the partner wave's MFMA section instead of delaying this wave's
-        auto relu_a = [&](AF&) {};               // (the ReLU now rides inside the MFMA cluster, see mma)
         auto mma = [&](int half, AF& fa, const WF& fw) {
             if constexpr (SCHED != 2) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -476,14 +430,12 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
                 read_a(ab, 0, 0, fa);
                 if (kt + 1 < nt) stage_w(kt + 1, wb1, WH, WJ);
                 lgkm0();
-                relu_a(fa);
                 bar();
                 mma(0, fa, fw);
                 bar();
                 read_a(ab, 0, 1, fa);
                 if (more) stage_a(kt + 2, 0, ab2);
                 lgkm0();
-                relu_a(fa);
                 bar();
                 mma(1, fa, fw);
                 bar();
@@ -494,7 +446,6 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
                     tap_next();
                 }
                 lgkm0();
-                relu_a(fa);
                 bar();
                 mma(0, fa, fw);
                 bar();
@@ -506,7 +457,6 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 }
                 lgkm0();
-                relu_a(fa);
                 bar();
                 mma(1, fa, fw);
                 bar();
@@ -516,7 +466,6 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
                 read_a(ab, 0, 0, fa);
                 if (more) stage_a(kt + 2, 0, ab2);
                 lgkm0();
-                relu_a(fa);
                 bar();
                 mma(0, fa, fw);
                 bar();
@@ -527,7 +476,6 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
                     tap_next();
                 }
                 lgkm0();
-                relu_a(fa);
                 bar();
                 mma(1, fa, fw);
                 bar();
@@ -535,7 +483,6 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
                 read_w(wb, 1, fw);
                 read_a(ab, 1, 0, fa);
                 lgkm0();
-                relu_a(fa);
                 bar();
                 mma(0, fa, fw);
                 bar();
@@ -548,7 +495,6 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 }
                 lgkm0();
-                relu_a(fa);
                 bar();
                 mma(1, fa, fw);
                 bar();
@@ -584,9 +530,9 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
             stage_w(0, smem + W_BASE);
         }
 
-        // ---- epilogue. Accumulator register e of subtile (i,j) is row m = lane & 31, column 8*(e>>2) + 4*(lane>>5) + (e&3):
-        // stored straight from this layout a wave instruction would touch 32 rows x 16 B (32 partial lines). Instead each
-        // wave transposes one 32-row x 64-column fp32 block at a time through its own 8 KiB of (idle) pipeline buffer 1
+        // ---- epilogue. Accumulator (mi, nj) holds row 16*mi + (lane & 15), columns 16*nj + 4*(lane >> 4) + e of the wave tile:
+        // stored straight from this layout a wave instruction would touch 16 rows x 64 B (16 partial lines). Instead each
+        // wave transposes one 32-row x 64-column fp32 block (accumulator rows 2i, 2i+1) at a time through its own 8 KiB staging slice
         // (16-byte chunks XOR-swizzled by row: conflict-free both ways) and then owns whole row segments: bias / LayerScale /
         // residual reads and the output stores become contiguous 16-byte accesses covering full 128-byte lines.
         const int bm0 = m0 + wm * WTM, bn0 = n0 + wn * WTN;
@@ -750,14 +696,13 @@ template <int BN, int AMODE, int EPI, int SCHED = 1, int BM = 256>
 int launch256(const vda_gemm_args& a, hipStream_t s) {
     constexpr int smem = 3 * BM_MAX * ROW_BYTES + 2 * BN * ROW_BYTES;
     static_assert(smem <= 160 * 1024, "LDS budget");
-    const int nbm = (a.M + BM - 1) / BM, nbn = (a.N + BN - 1) / BN;
-    const int ntiles = nbm * nbn;
+    const int ntiles = tile_count<BM, BN>(a);
     if constexpr (SCHED == 1 && EPI != VDA_EPI_CONVT_FOLD_F16) {      // (the folded mode balances its unequal tiles by the rotated static walk)
         if (a.sched != nullptr) {                 // dynamic tile draw: its own instantiation (see DYN above)
             static VdaKernelDeviceState dyn_state;
             const int ncu = vda_prepare_kernel(reinterpret_cast<const void*>(&gemm8p_kernel<BN, AMODE, EPI, SCHED, BM, true>), smem, dyn_state);
             if (ncu < 0) return 2;
-            hipLaunchKernelGGL((gemm8p_kernel<BN, AMODE, EPI, SCHED, BM, true>), dim3(ntiles < ncu ? (ntiles + 7) / 8 * 8 : ncu), dim3(NT), smem, s, a);
+            hipLaunchKernelGGL((gemm8p_kernel<BN, AMODE, EPI, SCHED, BM, true>), dim3(persistent_grid(ntiles, ncu)), dim3(NT), smem, s, a);
             VDA_LAUNCH_CHECK();
             return 0;
         }
@@ -765,7 +710,7 @@ int launch256(const vda_gemm_args& a, hipStream_t s) {
     static VdaKernelDeviceState dev_state;
     const int num_cu = vda_prepare_kernel(reinterpret_cast<const void*>(&gemm8p_kernel<BN, AMODE, EPI, SCHED, BM, false>), smem, dev_state);
     if (num_cu < 0) return 2;
-    const int grid = ntiles < num_cu ? (ntiles + 7) / 8 * 8 : num_cu;     // one persistent workgroup per CU
+    const int grid = persistent_grid(ntiles, num_cu);     // one persistent workgroup per CU
     hipLaunchKernelGGL((gemm8p_kernel<BN, AMODE, EPI, SCHED, BM, false>), dim3(grid), dim3(NT), smem, s, a);
     VDA_LAUNCH_CHECK();
     return 0;
