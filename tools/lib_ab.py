@@ -9,6 +9,7 @@ import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(REPO, "video_depth_anything_amd")
 what = sys.argv[1] if len(sys.argv) > 1 else "vitl"
+INNER = int(os.environ.get("AB_INNER", "5"))      # forwards per timed round (tools/option_ab2.py's rounds are 10: AB_INNER=10 gives the same rounds)
 paths = {"A": sys.argv[2] if len(sys.argv) > 2 else os.path.join(REPO, "tools", "ab", "libvda_base.so"),
          "B": sys.argv[3] if len(sys.argv) > 3 else os.path.join(PKG, "libvda_hip.so")}
 
@@ -56,7 +57,7 @@ if what in ("vitl", "vits"):
     ts = {k: [] for k in pk}
     for rep in range(7):
         for k in pk:
-            ts[k].append(timed(lambda: models[k].forward(x, fp32=False), 5))
+            ts[k].append(timed(lambda: models[k].forward(x, fp32=False), INNER))
     for k in pk:
         t = sorted(ts[k])[len(ts[k]) // 2]
         print(f"{what} build {k}: {t:.3f} ms/clip ({32e3 / t:.1f} frames/s)   all: {[round(u, 2) for u in ts[k]]}", flush=True)

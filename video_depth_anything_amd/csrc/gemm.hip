@@ -29,9 +29,12 @@ constexpr int NTHREADS = NWAVES * 64;
 
 // FOLD (VDA_EPI_CONVT_FOLD_F16, vda.h; conv A): the K loop visits only the taps the tile's output phases reach, and the epilogue is
 // that one. A kernel of its own (gemm_fold_kernel), so that the other kernels' code and names do not change.
-template <int BM, int BN, int AMODE, bool FOLD>
+// RELU (conv A): the input ReLU is compiled in, a packed max per A fragment whose threshold p.relu_in sets (0, or -65504 = identity).
+// Without it (gemm_plain_kernel: what a conv without an input ReLU runs) the K loop has no max.
+template <int BM, int BN, int AMODE, bool FOLD, bool RELU>
 __device__ __forceinline__ void gemm_tile(const vda_gemm_args& p) {
     static_assert(!FOLD || AMODE == VDA_A_CONV3X3, "the folded mode is a conv A mode");
+    static_assert(RELU || AMODE == VDA_A_CONV3X3, "the form without the max is a conv A form");
     constexpr int WTM = BM / 2, WTN = BN / 2;     // wave tile
     constexpr int MI = WTM / 16, NI = WTN / 16;   // 16x16 subtiles per wave
     constexpr int AJ = BM / 8 / NWAVES;           // 1-KiB DMA pieces per wave, A tile
@@ -118,7 +121,7 @@ __device__ __forceinline__ void gemm_tile(const vda_gemm_args& p) {
     // fragment read offsets: row = lane&15 (so row&7 == lane&7), k-chunk = ks*4 + (lane>>4)
     const int frow = lane & 15, fchk = lane >> 4, fsw = lane & 7;
     const h16 relu_floor = p.relu_in ? (h16)0.f : (h16)(-65504.f);
-    h16x8 relu_thr;
+    [[maybe_unused]] h16x8 relu_thr;
 #pragma unroll
     for (int e = 0; e < 8; ++e) relu_thr[e] = relu_floor;
 
@@ -133,7 +136,7 @@ __device__ __forceinline__ void gemm_tile(const vda_gemm_args& p) {
             for (int i = 0; i < MI; ++i) af[i] = *reinterpret_cast<const h16x8*>(At + i * 16 * ROW_BYTES + coff);
 #pragma unroll
             for (int j = 0; j < NI; ++j) wf[j] = *reinterpret_cast<const h16x8*>(Wt + j * 16 * ROW_BYTES + coff);
-            if constexpr (AMODE == VDA_A_CONV3X3) {
+            if constexpr (AMODE == VDA_A_CONV3X3 && RELU) {
 #pragma unroll
                 for (int i = 0; i < MI; ++i) af[i] = __builtin_elementwise_max(af[i], relu_thr);
             }
@@ -181,19 +184,25 @@ __device__ __forceinline__ void gemm_tile(const vda_gemm_args& p) {
 
 template <int BM, int BN, int AMODE>
 __global__ void __launch_bounds__(NTHREADS) gemm_kernel(const vda_gemm_args p) {
-    gemm_tile<BM, BN, AMODE, false>(p);
+    gemm_tile<BM, BN, AMODE, false, true>(p);
 }
 template <int BM, int BN>
 __global__ void __launch_bounds__(NTHREADS) gemm_fold_kernel(const vda_gemm_args p) {
-    gemm_tile<BM, BN, VDA_A_CONV3X3, true>(p);
+    gemm_tile<BM, BN, VDA_A_CONV3X3, true, true>(p);
+}
+// conv A without an input ReLU, plain or folded (vda_gemm_launch_name reports gemm_kernel / gemm_fold_kernel for either)
+template <int BM, int BN, bool FOLD>
+__global__ void __launch_bounds__(NTHREADS) gemm_plain_kernel(const vda_gemm_args p) {
+    gemm_tile<BM, BN, VDA_A_CONV3X3, FOLD, false>(p);
 }
 
-template <int BM, int BN, int AMODE, bool FOLD = false>
+template <int BM, int BN, int AMODE, bool FOLD = false, bool RELU = true>
 int launch(const vda_gemm_args& a, hipStream_t s) {
     constexpr int smem = 2 * (BM + BN) * ROW_BYTES;
     static VdaKernelDeviceState dev_state;
     void (*const kern)(const vda_gemm_args) = [] {
-        if constexpr (FOLD) return &gemm_fold_kernel<BM, BN>;
+        if constexpr (!RELU) return &gemm_plain_kernel<BM, BN, FOLD>;
+        else if constexpr (FOLD) return &gemm_fold_kernel<BM, BN>;
         else return &gemm_kernel<BM, BN, AMODE>;
     }();
     if (vda_prepare_kernel(reinterpret_cast<const void*>(kern), smem, dev_state) < 0) return 2;
@@ -264,8 +273,12 @@ static int launch_small(const vda_gemm_args& a, hipStream_t s) {
         }
         return rc;
     }
-    if (a.epilogue == VDA_EPI_CONVT_FOLD_F16) return launch<128, 128, VDA_A_CONV3X3, true>(a, s);      // (N = k * k * Cout: never narrow)
-    return narrow ? launch<128, 64, VDA_A_CONV3X3>(a, s) : launch<128, 128, VDA_A_CONV3X3>(a, s);
+    // conv A: the instantiation with the max only where the kernel would have applied the ReLU (p.relu_in != 0; VDA_GEMM_PLAIN_CONV=0: always)
+    const bool relu = a.relu_in || !vda_gemm_plain_conv();
+    if (a.epilogue == VDA_EPI_CONVT_FOLD_F16)                                                          // (N = k * k * Cout: never narrow)
+        return relu ? launch<128, 128, VDA_A_CONV3X3, true>(a, s) : launch<128, 128, VDA_A_CONV3X3, true, false>(a, s);
+    if (relu) return narrow ? launch<128, 64, VDA_A_CONV3X3>(a, s) : launch<128, 128, VDA_A_CONV3X3>(a, s);
+    return narrow ? launch<128, 64, VDA_A_CONV3X3, false, false>(a, s) : launch<128, 128, VDA_A_CONV3X3, false, false>(a, s);
 }
 
 extern "C" int vda_gemm_built(int family, int bm, int bn, int per_cu, int a_mode, int epilogue) {
@@ -307,18 +320,20 @@ struct GemmTuning {
     int small_grid;        // VDA_GEMM_SMALL_GRID (1): the 128-row kernel when 256-row tiles fill at most half of the CUs
     int bn384;             // VDA_GEMM_BN384 (2): where 192 x 384 tiles apply, see plan_one
     int conv_lds;          // VDA_CONV_LDS (1): narrow-output 3x3 convs as a patch-in-LDS direct convolution
+    int plain_conv;        // VDA_GEMM_PLAIN_CONV (1; 0 = A/B): 3x3 convs without relu_in run the instantiation without the max (vda_common.h)
     void read_env() {
         auto env = [](const char* k, long long d) { const char* v = getenv(k); return v ? atoll(v) : d; };
         split = (int)env("VDA_GEMM_SPLIT", 1), r192 = (int)env("VDA_GEMM_R192", 84), big_min_n = (int)env("VDA_GEMM_BIG_MIN_N", 192);
         eight128 = (int)env("VDA_GEMM_8P128", 0), stagger = (int)env("VDA_GEMM_STAGGER", 0), nt_mb = env("VDA_GEMM_NT_MB", 192);
         bm192 = (int)env("VDA_GEMM_BM192", 1), small_grid = (int)env("VDA_GEMM_SMALL_GRID", 1), bn384 = (int)env("VDA_GEMM_BN384", 2);
-        conv_lds = (int)env("VDA_CONV_LDS", 1);
+        conv_lds = (int)env("VDA_CONV_LDS", 1), plain_conv = (int)env("VDA_GEMM_PLAIN_CONV", 1);
     }
 };
 static GemmTuning& tuning() {
     static GemmTuning t = [] { GemmTuning x; x.read_env(); return x; }();
     return t;
 }
+bool vda_gemm_plain_conv() { return tuning().plain_conv != 0; }
 extern "C" int vda_gemm_set_variant(int v) { return tuning().variant = v, 0; }
 extern "C" int vda_gemm_set_debug(int flags) { return tuning().debug = flags & VDA_OPT_BYTE, 0; }
 extern "C" int vda_gemm_reload_tuning(void) { return tuning().read_env(), 0; }

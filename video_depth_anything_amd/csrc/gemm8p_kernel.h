@@ -46,8 +46,19 @@ __device__ __forceinline__ void vm_wait_keep() {
 // tile (the atomic's destination VGPR is re-initialised there and may still be in flight as far as the pass can tell). That wait
 // drains the previous epilogue's whole store burst and the prefetched K tile 0: ~4 k cycles per tile in EVERY launch, found in round 4
 // (tools/gemm_ramp.py + the ISA). The static-schedule kernel (what a single-stream forward runs) now has no atomic in it at all.
-template <int BN, int AMODE, int EPI, int SCHED = 1, int BM = 256, bool DYN = false>
+// AKIND = the A mode of vda.h, or A_CONV3X3_PLAIN: the conv A operand WITHOUT the ReLU on load. The conv instantiations apply the
+// ReLU as a packed max per A fragment in front of its MFMAs, against a threshold the option word sets (0, or -65504 = identity): 64
+// maxes per wave and K tile in the source, 128 v_pk_max_f16 in the ISA (maxnum canonicalises its operand first) beside 64 MFMAs, and
+// the s_nops of the VALU-write -> MFMA-read hazard (DESIGN [r15]: the 256-channel convs run 16 - 20 % faster without). A conv
+// without an input ReLU - every one of the head's but conv1 of the resConfUnits - runs the PLAIN instantiation, whose K loop has no
+// max. An instantiation of its own, picked by launch256 from the option word: the names and the code of the other kernels stay
+// what they were (vda_gemm_launch_name reports A mode 1 for both).
+constexpr int A_CONV3X3_PLAIN = 2;
+template <int BN, int AKIND, int EPI, int SCHED = 1, int BM = 256, bool DYN = false>
 __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
+    constexpr bool RELU = AKIND != A_CONV3X3_PLAIN;
+    constexpr int AMODE = RELU ? AKIND : VDA_A_CONV3X3;
+    static_assert(RELU || (SCHED == 1 && BM == 256), "the conv operand without the max: default schedule, 256-row tiles");
     static_assert(BM == 256 || (BM == 192 && BN == 256 && AMODE == VDA_A_DENSE), "192-row tiles: dense A, 256 columns");
     // FOLD (VDA_EPI_CONVT_FOLD_F16, vda.h): a ConvTranspose folded into the 3x3 conv behind it = a 3x3 conv on the tap grid whose
     // column tile (one output phase at Cout = 256, four at 64) reaches only SOME of the nine taps: the K loop visits the K tiles of
@@ -235,7 +246,7 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
     // fragment addressing: row = lane & 15 inside a 16-row subtile, k-chunk = 4*ks + (lane >> 4)
     const int frow = lane & 15, fh = lane >> 4, fsw = (lane >> 1) & 7;     // ((row >> 1) & 7) with row = subtile*16 + frow
     const int a_off = (wm * WTM + frow) * ROW_BYTES, w_off = (wn * WTN + frow) * ROW_BYTES;
-    const h16x8 relu_thr = relu_threshold(p);
+    [[maybe_unused]] const h16x8 relu_thr = relu_threshold(p);
 
     struct AF {
         h16x8 a[MH];
@@ -367,7 +378,8 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
 #pragma unroll
             for (int i = 0; i < MH; ++i) {
                 // conv ReLU on the activation fragment just before its 4 MFMAs: 4 packed max per fragment ride in the MFMA gaps
-                if constexpr (AMODE == VDA_A_CONV3X3) fa.a[i] = __builtin_elementwise_max(fa.a[i], relu_thr);
+                // (not in the PLAIN instantiation)
+                if constexpr (AMODE == VDA_A_CONV3X3 && RELU) fa.a[i] = __builtin_elementwise_max(fa.a[i], relu_thr);
 #pragma unroll
                 for (int j = 0; j < NJ; ++j) {
                     if (half == 0) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fw.w[j], fa.a[i], acc[i][j], 0, 0, 0);
@@ -693,7 +705,7 @@ __global__ void __launch_bounds__(NT) gemm8p_kernel(const vda_gemm_args p) {
 }
 
 template <int BN, int AMODE, int EPI, int SCHED = 1, int BM = 256>
-int launch256(const vda_gemm_args& a, hipStream_t s) {
+int launch_kind(const vda_gemm_args& a, hipStream_t s) {
     constexpr int smem = 3 * BM_MAX * ROW_BYTES + 2 * BN * ROW_BYTES;
     static_assert(smem <= 160 * 1024, "LDS budget");
     const int ntiles = tile_count<BM, BN>(a);
@@ -714,6 +726,15 @@ int launch256(const vda_gemm_args& a, hipStream_t s) {
     hipLaunchKernelGGL((gemm8p_kernel<BN, AMODE, EPI, SCHED, BM, false>), dim3(grid), dim3(NT), smem, s, a);
     VDA_LAUNCH_CHECK();
     return 0;
+}
+
+// conv A: the instantiation with the max only where the option word asks for the input ReLU
+template <int BN, int AMODE, int EPI, int SCHED = 1, int BM = 256>
+int launch256(const vda_gemm_args& a, hipStream_t s) {
+    if constexpr (AMODE == VDA_A_CONV3X3 && SCHED == 1 && BM == 256) {
+        if (!(a.relu_in & VDA_OPT_RELU_IN) && vda_gemm_plain_conv()) return launch_kind<BN, A_CONV3X3_PLAIN, EPI, SCHED, BM>(a, s);
+    }
+    return launch_kind<BN, AMODE, EPI, SCHED, BM>(a, s);
 }
 
 // One case per epilogue of the family's list (gemm_epilogue.h: the lists the planner plans with); -1 = not built, which the planner

@@ -207,6 +207,9 @@ struct VdaKernelDeviceState {
 // take HALF the chip were measured against two full-grid sequences interleaving freely (tools/two_stream.py, round 4): the capped
 // form loses (ViT-L 2 x 16 frames: 619 against 630 frames/s; two clips: 636 against 652), so nothing in the product sets it.
 extern int g_vda_max_wgs;
+// VDA_GEMM_PLAIN_CONV (1; gemm.hip's tuning, read again by vda_gemm_reload_tuning): a 3x3 conv without relu_in runs the instantiation
+// without the max. 0 = A/B: the instantiation with the max at its identity threshold, what every conv ran before. Same bits either way.
+bool vda_gemm_plain_conv();
 // vda_gemm_args::relu_in as a KERNEL sees it (the option word of a vda_gemm_launch): bit 0 is the caller's field, the rest is set by
 // the planner (gemm.hip). The field, its layout and every bit position are fixed (ctypes.sizeof(GemmArgs), the kernels' code).
 enum : int {
