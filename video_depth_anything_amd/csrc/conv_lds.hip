@@ -1,30 +1,23 @@
 // 3x3 / stride-1 / pad-1 convolution for NARROW outputs (Cout = 32 or 64: the ViT-S head, util/blocks.py:20-32,79-84 and
-// dpt.py:117) on NHWC fp16, as a patch-in-LDS direct convolution instead of an implicit GEMM.
+// dpt.py:117) on NHWC fp16, as a patch-in-LDS direct convolution (conv_patch.h) instead of an implicit GEMM.
 //
 // Why: with 64 output channels the implicit GEMM's tile is 128 x 64 and each 64-deep K tile gives a wave only 16 MFMAs between
-// two barriers, while every input pixel is re-read nine times through L2 (300-450 TFLOP/s measured, tools/gemm_ab.py). Here a
-// workgroup keeps the (8+2) x (32+2) pixel patch it needs in LDS and forms all nine taps from it - the structure of the depth
-// tail (tail.hip), with a generic epilogue:
+// two barriers, while every input pixel is re-read nine times through L2 (300-450 TFLOP/s measured, tools/gemm_ab.py).
 //
-//   workgroup = 8 x 32 output pixels, 4 waves; a wave owns 2 output rows = two 32-pixel MFMA column blocks
-//   pass      = 32 input channels: LDS holds the patch [340 pixels][32 ch] and the weights [9 taps x Cout][32 ch]
-//               (64-byte rows, 16-byte chunks XOR-swizzled by (row >> 2) & 3: conflict-free ds_read_b128), both by LDS-DMA
-//   MFMA      : v_mfma_f32_32x32x16_f16, A = weights [32 cout][16 k], B = patch [16 k][32 pixels]; D[cout][pixel]:
-//               patch row R serves (output row R, ky=0), (R-1, ky=1), (R-2, ky=2)
-//   epilogue  : + bias, + residual(s), ReLU, fp16 NHWC store (a lane owns one pixel and 4 consecutive channels per register group)
-#include "vda_common.h"
+// This file adds to conv_patch.h's 8 x 32 tile and per-pass steps:
+//   conv3x3_lds_kernel      the plain per-pass kernel (4 waves, patch [340 pixels][32 ch] + weights [9 taps x Cout][32 ch] per pass)
+//                           with the generic fp16 epilogue (+ bias, + residual(s), ReLU)
+//   c64::conv3x3_c64_kernel C = 64: persistent, fill waves beside MFMA waves, resident weights, residual prefetch. It takes only
+//                           the geometry from conv_patch.h: with its tile walk, tap group and epilogues written through the shared
+//                           functions it had the same registers and instruction counts but ran 0.5 - 1.5 % slower at 148^2
+//                           (profiles/r16/conv_patch_refactor_ab.txt), so those steps stand here in its own text
+//   the launcher and the coverage rule the GEMM planner asks
+#include "conv_patch.h"
 
 namespace {
 
-constexpr int TH = 8, TW = 32;                 // output tile
-constexpr int PH = TH + 2, PW = TW + 2;        // patch with halo
-constexpr int NPIX = PH * PW;                  // 340
-constexpr int CC = 32;                         // channels per pass
-constexpr int ROWB = CC * 2;                   // 64-byte LDS rows
-constexpr int NP_PATCH = (NPIX + 15) / 16;     // 1-KiB DMA pieces (16 rows x 64 B)
-constexpr int PATCH_BYTES = NP_PATCH * 1024;
-
-__device__ __forceinline__ int swz(int r) { return (r >> 2) & 3; }
+using namespace vda_patch;
+using namespace vda_patch::tile8;
 
 template <int CB>                              // 32-channel output blocks: Cout = 32 * CB
 __global__ void __launch_bounds__(256) conv3x3_lds_kernel(const h16* __restrict__ in, const h16* __restrict__ wt, const float* __restrict__ bias,
@@ -38,124 +31,53 @@ __global__ void __launch_bounds__(256) conv3x3_lds_kernel(const h16* __restrict_
     char* const wl = lds + PATCH_BYTES;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // workgroups are dealt to the 8 XCDs round-robin: give XCD x the contiguous tile range [x * per_xcd, (x+1) * per_xcd)
-    const int per_xcd = gridDim.x >> 3;
-    const int tile = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    const int tile = xcd_tile();
     if (tile >= ntiles) return;                               // uniform per workgroup
-    const int tx = tile % tiles_x, tyb = tile / tiles_x;
-    const int ty = tyb % tiles_y, b = tyb / tiles_y;
-    const int x0 = tx * TW, y0 = ty * TH;
+    const TilePos t = tile_pos<TH, TW>(tile, tiles_x, tiles_y);
     const int px = lane & 31, hh = lane >> 5;
 
     f32x16 acc[2][CB];
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-        for (int cb = 0; cb < CB; ++cb)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[r][cb][e] = 0.f;
+    zero_acc(acc);
 
     const h16 floor_v = relu_in ? (h16)0.f : (h16)(-65504.f);
     h16x8 relu_thr;
 #pragma unroll
     for (int e = 0; e < 8; ++e) relu_thr[e] = floor_v;
 
-    const int lr = lane >> 2, lp = lane & 3;
     for (int c0 = 0; c0 < C; c0 += CC) {
         if (c0 > 0) __syncthreads();                         // everyone done reading the previous pass's patch / weights
-        // weights of this pass: rows R = tap * (32 * CB) + cout, 32 channels each (rows of couts >= N read row N - 1: never stored)
-        for (int piece = wave; piece < NP_W; piece += 4) {
-            const int R = piece * 16 + lr;
-            const int tap = R / (32 * CB), co = min(R - tap * (32 * CB), N - 1);
-            glds16(wt + co * (9 * C) + tap * C + c0 + ((lp ^ swz(R)) << 3), wl + piece * 1024);
-        }
-        // patch of this pass (zero page outside the image = the conv's padding)
-        for (int piece = wave; piece < NP_PATCH; piece += 4) {
-            const int q = piece * 16 + lr;
-            const int py = q / PW, pxx = q - py * PW;
-            const int iy = y0 - 1 + py, ix = x0 - 1 + pxx;
-            const bool ok = q < NPIX && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W;
-            const int sc = (lp ^ swz(q)) << 3;
-            const h16* src = ok ? in + ((b * H + iy) * W + ix) * C + c0 + sc : zero_page + sc;
-            glds16(src, patch + piece * 1024);
-        }
+        stage_weights<CB>(wt, wl, wave, lane, C, N, c0);
+        stage_patch(in, zero_page, patch, wave, lane, t.b, t.y0, t.x0, H, W, C, c0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // LDS-DMA landed before the barrier publishes it
         __syncthreads();
-
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                h16x8 P[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int q = (wave * 2 + j) * PW + px + kx;
-                    P[j] = *reinterpret_cast<const h16x8*>(patch + q * ROWB + (((2 * ks + hh) ^ swz(q)) << 4));
-                    P[j] = __builtin_elementwise_max(P[j], relu_thr);
-                }
-#pragma unroll
-                for (int cb = 0; cb < CB; ++cb) {
-                    h16x8 Wf[3];
-#pragma unroll
-                    for (int ky = 0; ky < 3; ++ky) {
-                        const int R = (ky * 3 + kx) * (32 * CB) + cb * 32 + px;      // A operand: row = cout (lane & 31)
-                        Wf[ky] = *reinterpret_cast<const h16x8*>(wl + R * ROWB + (((2 * ks + hh) ^ swz(R)) << 4));
-                    }
-#pragma unroll
-                    for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                        for (int r = 0; r < 2; ++r) acc[r][cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Wf[ky], P[r + ky], acc[r][cb], 0, 0, 0);
-                }
-            }
-        }
+        mfma_pass<CB, true>(patch, wl, wave, px, hh, relu_thr, acc);
     }
 
-    // epilogue: lane = pixel (lane & 31) of row r; registers 4g..4g+3 of block cb = channels cb*32 + 8g + 4hh .. +3
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
-        const int oy = y0 + wave * 2 + r, ox = x0 + px;
+        const int oy = t.y0 + wave * 2 + r, ox = t.x0 + px;
         if (oy >= H || ox >= W) continue;
-        const size_t row = ((size_t)(b * H + oy) * W + ox) * ldc;
+        const size_t row = ((size_t)(t.b * H + oy) * W + ox) * ldc;
 #pragma unroll
         for (int cb = 0; cb < CB; ++cb)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int n = cb * 32 + 8 * g + 4 * hh;
-                if (n >= N) continue;
-                f32x4 v = {acc[r][cb][4 * g], acc[r][cb][4 * g + 1], acc[r][cb][4 * g + 2], acc[r][cb][4 * g + 3]};
-                if (bias) v += *reinterpret_cast<const f32x4*>(bias + n);
-                if (res) {
-                    const h16x4 a = *reinterpret_cast<const h16x4*>(res + row + n);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] += (float)a[e];
-                }
-                if (res2) {
-                    const h16x4 a = *reinterpret_cast<const h16x4*>(res2 + row + n);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] += (float)a[e];
-                }
-                if (relu_out) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-                }
-                const h16x4 o = {(h16)v[0], (h16)v[1], (h16)v[2], (h16)v[3]};
-                *reinterpret_cast<h16x4*>(out + row + n) = o;
+                if (n < N) store_narrow(acc4(acc[r][cb], g), bias, res, res2, relu_out, out, row, n);
             }
     }
 }
 
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // [r4] The same convolution for C = 64 input channels (every 3x3 conv of the ViT-S head but the fused output_conv1) as a PERSISTENT
-// kernel with SPECIALISED waves - the structure the depth tail got this round (tail.hip), without the interpolation:
+// kernel with SPECIALISED waves:
 //   The kernel above fills 22 KiB of patch and 36 KiB of weights per 32-channel pass and workgroup, waits, runs 72 MFMAs per wave, and
 //   does it again for the second pass: 448 TFLOP/s on the 148^2 maps (115 us), two workgroups per CU.
-//   Here ALL 64 channels of a pixel are one 128-byte LDS row: the whole weight tensor (9 taps x 64 cout x 64 ch = 72 KiB) is loaded ONCE
-//   per workgroup, the (8+2) x (32+2) patch of the NEXT tile (43 KiB) arrives by LDS-DMA from four fill waves while four MFMA waves
-//   (2 output rows each, 144 MFMAs per tile, fragments of group g + 1 requested before the MFMAs of group g) work on the current one;
-//   one barrier per tile. LDS = 72 + 2 x 43 KiB. Rows are swizzled by the pixel's COLUMN ((col >> 1) & 7 on the eight 16-byte chunks:
-//   conflict-free ds_read_b128, fragment addresses = lane constants + immediates).
-//   Same MFMA order per output element as the kernel above (channel half, kx, k-step, ky): bit-identical results
+//   Here ALL 64 channels of a pixel are one 128-byte LDS row: the whole weight tensor (72 KiB) is loaded ONCE per workgroup, the patch of
+//   the NEXT tile (43 KiB) arrives by LDS-DMA from four fill waves while four MFMA waves (144 MFMAs per tile, fragments of group g + 1
+//   requested before the MFMAs of group g) work on the current one; one barrier per tile. LDS = 72 + 2 x 43 KiB, rows swizzled by swz64.
+//   Groups run in the order of the kernel above's two passes (channel half, kx, k-step; ky, row as conv_patch.h's tap_group):
+//   bit-identical results
 //   (tests/test_kernels_gpu.py holds that; vda_conv_lds_set_variant(1) = the kernel above for every shape).
 namespace c64 {
 constexpr int C64 = 64, ROW64 = C64 * 2;       // 128-byte rows
@@ -448,14 +370,14 @@ extern "C" int vda_conv_lds_set_variant(int v) {      // 0 = default (the C = 64
 bool vda_conv3x3_lds_covers(const vda_gemm_args& a) {
     if (a.a_mode != VDA_A_CONV3X3 || a.cStride != 1 || a.N > 64 || a.N % 4 != 0 || a.cCin % CC != 0 || a.ldc % 4 != 0) return false;
     if (a.epilogue != VDA_EPI_BIAS_F16 && a.epilogue != VDA_EPI_BIAS_RELU_F16 && a.epilogue != VDA_EPI_RES_F16) return false;
-    return (long long)((a.cW + TW - 1) / TW) * ((a.cH + TH - 1) / TH) * a.cB < (1ll << 30);
+    int tiles_x, tiles_y;
+    return tile_count(a.cB, a.cH, a.cW, TH, TW, tiles_x, tiles_y) < (1ll << 30);
 }
 
 int vda_conv3x3_lds(const vda_gemm_args& a, hipStream_t s) {
     if (!vda_conv3x3_lds_covers(a)) return -1;
-    const int tiles_x = (a.cW + TW - 1) / TW, tiles_y = (a.cH + TH - 1) / TH;
-    const long long ntiles = (long long)tiles_x * tiles_y * a.cB;
-    const dim3 grid((unsigned)((ntiles + 7) / 8 * 8));
+    int tiles_x, tiles_y;
+    const long long ntiles = tile_count(a.cB, a.cH, a.cW, TH, TW, tiles_x, tiles_y);
     const h16* res = a.epilogue == VDA_EPI_RES_F16 ? (const h16*)a.res : nullptr;
     const h16* res2 = a.epilogue == VDA_EPI_RES_F16 ? (const h16*)a.res2 : nullptr;
     const int relu_out = a.epilogue == VDA_EPI_BIAS_RELU_F16 ? 1 : 0;
@@ -464,37 +386,22 @@ int vda_conv3x3_lds(const vda_gemm_args& a, hipStream_t s) {
         // per-pass kernel (tools/conv_lds_ab.py, profiles/r04/vits_conv_c64_ab.txt): 148^2 with a residual 129 -> 103 us, 74^2 39.4 -> 35.9,
         // 37^2 a tie, 19^2 13.3 -> 11.6; ViT-S forward 8.15 -> 8.05 ms. 32 output channels (not a shape of the model) lose on it
         // (one MFMA wave per SIMD has half the work per tile) and stay on the per-pass kernel.
-        const int cb = a.N <= 32 ? 1 : 2;
-        const int smem = 9 * 32 * cb * c64::ROW64 + 2 * c64::PATCH64;
-        static VdaKernelDeviceState st1, st2;
-        const void* fn = cb == 1 ? reinterpret_cast<const void*>(&c64::conv3x3_c64_kernel<1>) : reinterpret_cast<const void*>(&c64::conv3x3_c64_kernel<2>);
-        const int ncu = vda_prepare_kernel(fn, smem, cb == 1 ? st1 : st2);
+        constexpr int smem = 9 * 32 * 2 * c64::ROW64 + 2 * c64::PATCH64;
+        using KFn = void (*)(const h16*, const h16*, const float*, const h16*, const h16*, h16*, const h16*, int, int, int, int, int, int, int, int, int);
+        // by timing experiment DBG (results invalid): variants 2, 3, 4 = experiments 1, 2, 3; each is prepared as its own function
+        static const KFn fns[4] = {&c64::conv3x3_c64_kernel<2>, &c64::conv3x3_c64_kernel<2, 1>, &c64::conv3x3_c64_kernel<2, 2>, &c64::conv3x3_c64_kernel<2, 3>};
+        static VdaKernelDeviceState dev_state[4];
+        const int v = g_conv_lds_variant >= 2 && g_conv_lds_variant <= 4 ? g_conv_lds_variant - 1 : 0;
+        const int ncu = vda_prepare_kernel(reinterpret_cast<const void*>(fns[v]), smem, dev_state[v]);
         if (ncu < 0) return 2;
-        const int g64 = (int)(ntiles < ncu ? (ntiles + 7) / 8 * 8 : ncu);
-        if (cb == 1)
-            hipLaunchKernelGGL((c64::conv3x3_c64_kernel<1>), dim3(g64), dim3(c64::NT64), smem, s, (const h16*)a.A, (const h16*)a.W, a.bias, res, res2, (h16*)a.out,
-                               (const h16*)a.zero_page, a.cH, a.cW, a.N, a.ldc, a.relu_in & VDA_OPT_RELU_IN, relu_out, tiles_x, tiles_y, (int)ntiles);
-        else if (g_conv_lds_variant == 2)
-            hipLaunchKernelGGL((c64::conv3x3_c64_kernel<2, 1>), dim3(g64), dim3(c64::NT64), smem, s, (const h16*)a.A, (const h16*)a.W, a.bias, res, res2, (h16*)a.out,
-                               (const h16*)a.zero_page, a.cH, a.cW, a.N, a.ldc, a.relu_in & VDA_OPT_RELU_IN, relu_out, tiles_x, tiles_y, (int)ntiles);
-        else if (g_conv_lds_variant == 4)
-            hipLaunchKernelGGL((c64::conv3x3_c64_kernel<2, 3>), dim3(g64), dim3(c64::NT64), smem, s, (const h16*)a.A, (const h16*)a.W, a.bias, res, res2, (h16*)a.out,
-                               (const h16*)a.zero_page, a.cH, a.cW, a.N, a.ldc, a.relu_in & VDA_OPT_RELU_IN, relu_out, tiles_x, tiles_y, (int)ntiles);
-        else if (g_conv_lds_variant == 3)
-            hipLaunchKernelGGL((c64::conv3x3_c64_kernel<2, 2>), dim3(g64), dim3(c64::NT64), smem, s, (const h16*)a.A, (const h16*)a.W, a.bias, res, res2, (h16*)a.out,
-                               (const h16*)a.zero_page, a.cH, a.cW, a.N, a.ldc, a.relu_in & VDA_OPT_RELU_IN, relu_out, tiles_x, tiles_y, (int)ntiles);
-        else
-            hipLaunchKernelGGL((c64::conv3x3_c64_kernel<2>), dim3(g64), dim3(c64::NT64), smem, s, (const h16*)a.A, (const h16*)a.W, a.bias, res, res2, (h16*)a.out,
-                               (const h16*)a.zero_page, a.cH, a.cW, a.N, a.ldc, a.relu_in & VDA_OPT_RELU_IN, relu_out, tiles_x, tiles_y, (int)ntiles);
+        hipLaunchKernelGGL(fns[v], dim3(persistent_grid(ntiles, ncu)), dim3(c64::NT64), smem, s, (const h16*)a.A, (const h16*)a.W, a.bias, res, res2,
+                           (h16*)a.out, (const h16*)a.zero_page, a.cH, a.cW, a.N, a.ldc, a.relu_in & VDA_OPT_RELU_IN, relu_out, tiles_x, tiles_y, (int)ntiles);
         VDA_LAUNCH_CHECK();
         return 0;
     }
-    if (a.N <= 32)
-        hipLaunchKernelGGL((conv3x3_lds_kernel<1>), grid, dim3(256), 0, s, (const h16*)a.A, (const h16*)a.W, a.bias, res, res2, (h16*)a.out,
-                           (const h16*)a.zero_page, a.cH, a.cW, a.cCin, a.N, a.ldc, a.relu_in & VDA_OPT_RELU_IN, relu_out, tiles_x, tiles_y, (int)ntiles);
-    else
-        hipLaunchKernelGGL((conv3x3_lds_kernel<2>), grid, dim3(256), 0, s, (const h16*)a.A, (const h16*)a.W, a.bias, res, res2, (h16*)a.out,
-                           (const h16*)a.zero_page, a.cH, a.cW, a.cCin, a.N, a.ldc, a.relu_in & VDA_OPT_RELU_IN, relu_out, tiles_x, tiles_y, (int)ntiles);
+    const auto fn = a.N <= 32 ? &conv3x3_lds_kernel<1> : &conv3x3_lds_kernel<2>;
+    hipLaunchKernelGGL(fn, dim3(grid8(ntiles)), dim3(256), 0, s, (const h16*)a.A, (const h16*)a.W, a.bias, res, res2, (h16*)a.out, (const h16*)a.zero_page,
+                       a.cH, a.cW, a.cCin, a.N, a.ldc, a.relu_in & VDA_OPT_RELU_IN, relu_out, tiles_x, tiles_y, (int)ntiles);
     VDA_LAUNCH_CHECK();
     return 0;
 }

@@ -2,8 +2,8 @@
 // F.interpolate(scale_factor=2, mode="bilinear", align_corners=True) of refinenet1):
 //     out[B, 2h, 2w, N] = conv3x3( bilinear2x(in[B, h, w, C]) ) + bias          NHWC fp16, N = 32 * CB <= 128
 // as ONE kernel: the upsampled tensor (1.4 GB per ViT-L clip, written once and re-read nine times through L2 by the implicit GEMM)
-// never exists. The structure is the patch-in-LDS direct convolution of conv_lds.hip / tail.hip, re-cut so that every staging
-// step runs UNDER the MFMAs of the step before it:
+// never exists. A patch-in-LDS direct convolution (conv_patch.h: 16 x 32 tile, tile walk, tap group, source-region geometry, fp16
+// epilogues); what this file adds is the cut into 16-channel k-steps so that every staging step runs UNDER the MFMAs of the step before it:
 //
 //   workgroup = 16 x 32 output pixels, 8 waves (one workgroup per CU); a wave owns 2 output rows x all N channels
 //               (acc = 2 x CB x 16 fp32 registers)
@@ -15,18 +15,14 @@
 //     patch[2]  the (16+2) x (32+2) upsampled pixels x 16 ch   <- interpolated from src[] by the VALU ONE step ahead, between
 //               the MFMA groups of the running step (fp32 arithmetic on the four corners, one rounding to fp16: what the
 //               unfused path would have read back from memory, up to the last bit of the fp32 sum)
-//   MFMA      : A = weights [32 cout][16 k], B = patch [16 k][32 pixels], D[cout][pixel]; patch row R serves (output row R,
-//               ky = 0), (R-1, ky = 1), (R-2, ky = 2): per kx a wave reads 4 patch + 3 CB weight fragments for 6 CB MFMAs.
+//   MFMA      : per kx a wave reads 4 patch + 3 CB weight fragments for 6 CB MFMAs.
 //   epilogue  : + bias, fp16 NHWC store.
-#include <type_traits>
-
-#include "vda_common.h"
+#include "conv_patch.h"
 
 namespace {
 
-constexpr int TH = 16, TW = 32;                // output tile
-constexpr int PH = TH + 2, PW = TW + 2;        // patch with halo
-constexpr int NPIX = PH * PW;                  // 612
+namespace vp = vda_patch;
+using namespace vda_patch::tile16;             // TH, TW, PW, NPIX
 constexpr int KC = 16;                         // channels per k-step
 constexpr int ROWB = KC * 2;                   // 32-byte LDS rows
 // source pixels under a patch at scale (h-1)/(2h-1) < 1/2: rows floor(ys*(y0-1)) .. floor(ys*(y0+16)) + 1, i.e. at most
@@ -43,10 +39,9 @@ constexpr int NI = (NITEM + NT - 1) / NT;      // 3 per thread
 
 __device__ __forceinline__ int swz(int r) { return (r >> 3) & 1; }
 __device__ __forceinline__ int lds_off(int row, int chunk) { return row * ROWB + ((chunk ^ swz(row)) << 4); }
-// [r4] the PATCH image is swizzled by the pixel's COLUMN in the patch, (col >> 3) & 1, instead of its row index: conflict-free for the
-// same reason (the lanes of a ds_read_b128 group that share a row-mod-8 are 8 or 24 columns apart), and a reading lane's swizzle then
-// depends on pixel + kx only: the patch fragment addresses of a k-step are 3 lane constants + immediates, the weight fragment addresses
-// one (rows R = 32 (...) + cout: (R >> 3) & 1 = (cout >> 3) & 1), instead of ~70 VALU instructions per k-step and wave.
+// [r4] the PATCH image is swizzled by the pixel's COLUMN in the patch instead of its row index (conv_patch.h): the patch fragment
+// addresses of a k-step are 3 lane constants + immediates, the weight fragment addresses one (rows R = 32 (...) + cout:
+// (R >> 3) & 1 = (cout >> 3) & 1), instead of ~70 VALU instructions per k-step and wave.
 __device__ __forceinline__ int patch_off(int q, int chunk) {
     const int col = q % PW;
     return q * ROWB + ((chunk ^ ((col >> 3) & 1)) << 4);
@@ -65,20 +60,18 @@ __global__ void __launch_bounds__(NT) conv3x3_up2_kernel(const h16* __restrict__
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int H = 2 * h, W = 2 * w;
-    // workgroups are dealt to the 8 XCDs round-robin: give XCD x the contiguous tile range [x * per_xcd, (x+1) * per_xcd)
-    const int per_xcd = gridDim.x >> 3;
-    const int tile = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    const int tile = vp::xcd_tile();
     if (tile >= ntiles) return;                                  // uniform per workgroup
-    const int tx = tile % tiles_x, tyb = tile / tiles_x;
-    const int ty = tyb % tiles_y, b = tyb / tiles_y;
-    const int x0 = tx * TW, y0 = ty * TH;
+    const vp::TilePos t = vp::tile_pos<TH, TW>(tile, tiles_x, tiles_y);
+    const int b = t.b, x0 = t.x0, y0 = t.y0;
     const int px = lane & 31, hh = lane >> 5;
     const bool wide = (N & 7) == 0 && (ldc & 7) == 0 && ((uintptr_t)out & 15) == 0;     // uniform
 
     // ---- geometry (the same for every k-step). align_corners=True: src = dst * (in-1)/(out-1), as lerp_coord() of resample.hip
     const float ys = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f, xs = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f;
-    const int sy0 = min((int)(ys * (float)max(y0 - 1, 0)), h - 1), sx0 = min((int)(xs * (float)max(x0 - 1, 0)), w - 1);
-    int ia[NI], ib[NI];                         // LDS offsets of the four corners (16 bits each)
+    int sy0, sx0;
+    vp::src_origin(ys, xs, y0, x0, h, w, sy0, sx0);
+    unsigned ia[NI], ib[NI];                    // LDS offsets of the four corners (16 bits each)
     float wxs[NI], wys[NI];
     // Entry k of these arrays is item k in waves 0..3 and item k - 1 (mod 3) in waves 4..7: the interpolation slots of a k-step are
     // I M I M I M in the early waves and M I M I M I in the late ones (below), and with the late waves' entries rotated every slot
@@ -98,10 +91,9 @@ __global__ void __launch_bounds__(NT) conv3x3_up2_kernel(const h16* __restrict__
         const int yb = min(ya + 1, h - 1), xb = min(xa + 1, w - 1);
         wys[k] = sy - (float)ya;
         wxs[k] = sx - (float)xa;
-        const int fa = min(max(ya - sy0, 0), SH - 1), fb = min(max(yb - sy0, 0), SH - 1);
-        const int ga = min(max(xa - sx0, 0), SW - 1), gb = min(max(xb - sx0, 0), SW - 1);
-        ia[k] = lds_off(fa * SW + ga, c) | (lds_off(fa * SW + gb, c) << 16);
-        ib[k] = lds_off(fb * SW + ga, c) | (lds_off(fb * SW + gb, c) << 16);
+        const vp::Corners cn = vp::corner_offsets(ya, yb, xa, xb, sy0, sx0, SH, SW, [&](int row) { return (unsigned)lds_off(row, c); });
+        ia[k] = cn.ia;
+        ib[k] = cn.ib;
         if (!ok) ia[k] = ib[k] = ZERO_OFF | (ZERO_OFF << 16);      // outside the image: four reads of the zero chunk = the conv's padding
     }
     // DMA sources: a piece = 32 LDS rows x 32 B; lane -> (row lr of the piece, LDS chunk lp), fetching source chunk lp ^ swz(row)
@@ -139,9 +131,9 @@ __global__ void __launch_bounds__(NT) conv3x3_up2_kernel(const h16* __restrict__
         const int item = tid + NT * (early ? k : (k + NI - 1) % NI), q = item < NITEM ? item >> 1 : NPIX + (lane & 15);
         woff[k] = patch_off(q, item & 1);
     }
-    auto interp_item = [&](int wo, int iav, int ibv, float wx, float wy, const char* sb, char* pb) {
-        const h16x8 a00 = *reinterpret_cast<const h16x8*>(sb + (iav & 0xffff)), a01 = *reinterpret_cast<const h16x8*>(sb + ((unsigned)iav >> 16));
-        const h16x8 a10 = *reinterpret_cast<const h16x8*>(sb + (ibv & 0xffff)), a11 = *reinterpret_cast<const h16x8*>(sb + ((unsigned)ibv >> 16));
+    auto interp_item = [&](int wo, unsigned iav, unsigned ibv, float wx, float wy, const char* sb, char* pb) {
+        const h16x8 a00 = *reinterpret_cast<const h16x8*>(sb + (iav & 0xffffu)), a01 = *reinterpret_cast<const h16x8*>(sb + (iav >> 16));
+        const h16x8 a10 = *reinterpret_cast<const h16x8*>(sb + (ibv & 0xffffu)), a11 = *reinterpret_cast<const h16x8*>(sb + (ibv >> 16));
         const float ux = 1.f - wx, uy = 1.f - wy;
         const float w00 = ux * uy, w01 = wx * uy, w10 = ux * wy, w11 = wx * wy;
         h16x8 o;
@@ -155,12 +147,7 @@ __global__ void __launch_bounds__(NT) conv3x3_up2_kernel(const h16* __restrict__
     };
 
     f32x16 acc[2][CB];
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-        for (int cb = 0; cb < CB; ++cb)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[r][cb][e] = 0.f;
+    vp::zero_acc(acc);
 
     const int nk = C / KC;
     // ---- prologue: weights and source of step 0, source of step 1; patch of step 0. The zero chunk behind each source buffer's
@@ -194,12 +181,7 @@ __global__ void __launch_bounds__(NT) conv3x3_up2_kernel(const h16* __restrict__
         for (int cb = 0; cb < CB; ++cb)
 #pragma unroll
             for (int ky = 0; ky < 3; ++ky) Wf[cb][ky] = *reinterpret_cast<const h16x8*>(wc + wbase + ((ky * 3 + kx) * CB + cb) * 32 * ROWB);
-#pragma unroll
-        for (int cb = 0; cb < CB; ++cb)
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                for (int r = 0; r < 2; ++r) acc[r][cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Wf[cb][ky], P[r + ky], acc[r][cb], 0, 0, 0);
+        vp::tap_group<CB>(P, Wf, acc);
         // ---- the order the scheduler is asked for
         __builtin_amdgcn_sched_group_barrier(0x100, 7, 0);                          // P + the first block's weights
 #pragma unroll
@@ -238,16 +220,13 @@ __global__ void __launch_bounds__(NT) conv3x3_up2_kernel(const h16* __restrict__
     }
     static_assert(NI == 3, "the interpolation items ride on the three kx groups");
 
-    // ---- epilogue: lane = pixel (lane & 31) of row r; registers 4g..4g+3 of block cb = channels cb*32 + 8g + 4hh .. +3
-    // [r4] WIDE form (N, ldc multiples of 8, out 16-byte aligned: every shape the model runs): the two lanes of a pixel (hh = 0 / 1)
-    // hold the interleaved 4-channel groups 8g + 4hh of a 32-channel block; one v_permlane32_swap per register hands the lower lane
-    // channels 0..15 and the upper lane 16..31, and each lane stores 2 x 16 bytes instead of 4 x 8: half the store instructions and
-    // no 8-byte fragments for L2 to merge (the 8-byte form wrote 851 MB for 718 MB of output, profiles/r03).
+    // ---- epilogue (conv_patch.h). [r4] WIDE form (every shape the model runs): half the store instructions and no 8-byte fragments for
+    // L2 to merge (the 8-byte form wrote 851 MB for 718 MB of output, profiles/r03).
     if (wide) {
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
             const int oy = y0 + wave * 2 + r, ox = x0 + px;
-            const bool inb = oy < H && ox < W;                  // (the swaps below run on every lane)
+            const bool inb = oy < H && ox < W;                  // (the swaps run on every lane)
             const size_t row = ((size_t)(b * H + min(oy, H - 1)) * W + min(ox, W - 1)) * ldc;
 #pragma unroll
             for (int cb = 0; cb < CB; ++cb) {
@@ -255,29 +234,11 @@ __global__ void __launch_bounds__(NT) conv3x3_up2_kernel(const h16* __restrict__
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const int n = cb * 32 + 8 * g + 4 * hh;
-                    f32x4 v = {acc[r][cb][4 * g], acc[r][cb][4 * g + 1], acc[r][cb][4 * g + 2], acc[r][cb][4 * g + 3]};
+                    f32x4 v = vp::acc4(acc[r][cb], g);
                     if (bias && n < N) v += *reinterpret_cast<const f32x4*>(bias + n);
-                    const h16x4 o = {(h16)v[0], (h16)v[1], (h16)v[2], (h16)v[3]};
-                    pk[g][0] = reinterpret_cast<const unsigned*>(&o)[0];
-                    pk[g][1] = reinterpret_cast<const unsigned*>(&o)[1];
+                    vp::pack4(pk[g], vp::round4(v, 0));
                 }
-                // A = groups 0, 1; B = groups 2, 3: the upper lanes' A goes to the lower lanes' B and back
-#pragma unroll
-                for (int g = 0; g < 2; ++g)
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) {
-                        const auto sw = __builtin_amdgcn_permlane32_swap(pk[g][e], pk[g + 2][e], false, false);
-                        pk[g][e] = sw[0];
-                        pk[g + 2][e] = sw[1];
-                    }
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {                   // lower lane: channels 8j..8j+7 of the block, upper lane: 16 + 8j ..
-                    const int n = cb * 32 + 16 * hh + 8 * j;
-                    if (inb && n < N) {
-                        const uint4 o = {pk[j][0], pk[j][1], pk[j + 2][0], pk[j + 2][1]};
-                        *reinterpret_cast<uint4*>(out + row + n) = o;
-                    }
-                }
+                vp::store_wide(pk, out, row, cb, hh, inb, N);
             }
         }
         return;
@@ -292,11 +253,7 @@ __global__ void __launch_bounds__(NT) conv3x3_up2_kernel(const h16* __restrict__
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int n = cb * 32 + 8 * g + 4 * hh;
-                if (n >= N) continue;
-                f32x4 v = {acc[r][cb][4 * g], acc[r][cb][4 * g + 1], acc[r][cb][4 * g + 2], acc[r][cb][4 * g + 3]};
-                if (bias) v += *reinterpret_cast<const f32x4*>(bias + n);
-                const h16x4 o = {(h16)v[0], (h16)v[1], (h16)v[2], (h16)v[3]};
-                *reinterpret_cast<h16x4*>(out + row + n) = o;
+                if (n < N) vp::store_narrow(vp::acc4(acc[r][cb], g), bias, nullptr, nullptr, 0, out, row, n);
             }
     }
 }
@@ -308,10 +265,10 @@ int launch_up2(const h16* in, const h16* wt, const float* bias, h16* out, int B,
     static_assert(smem <= 160 * 1024, "LDS budget");
     static VdaKernelDeviceState dev_state;
     if (vda_prepare_kernel(reinterpret_cast<const void*>(&conv3x3_up2_kernel<CB, DBG>), smem, dev_state) < 0) return 2;
-    const int tiles_x = (2 * w + TW - 1) / TW, tiles_y = (2 * h + TH - 1) / TH;
-    const long long ntiles = (long long)tiles_x * tiles_y * B;
+    int tiles_x, tiles_y;
+    const long long ntiles = vp::tile_count(B, 2 * h, 2 * w, TH, TW, tiles_x, tiles_y);
     VDA_REQUIRE(ntiles < (1ll << 30), "vda_conv3x3_up2: too many tiles");
-    hipLaunchKernelGGL((conv3x3_up2_kernel<CB, DBG>), dim3((unsigned)((ntiles + 7) / 8 * 8)), dim3(NT), smem, s, in, wt, bias, out, h, w, C, N, ldc,
+    hipLaunchKernelGGL((conv3x3_up2_kernel<CB, DBG>), dim3(vp::grid8(ntiles)), dim3(NT), smem, s, in, wt, bias, out, h, w, C, N, ldc,
                        tiles_x, tiles_y, (int)ntiles);
     VDA_LAUNCH_CHECK();
     return 0;

@@ -2,46 +2,25 @@
 //     [bilinear align_corners resize h x w -> H x W]  ->  3x3 conv C -> 32 (+bias, ReLU)  ->  1x1 conv 32 -> 1 (+bias, ReLU)
 // as ONE kernel with the input read once. Run as an implicit GEMM this stage re-reads every input pixel nine
 // times through L2 to feed a 32-wide output (staging-bound, 290 TFLOP/s, plus a 2.2 GB upsampled tensor written
-// and read back); here a workgroup keeps the (8+2) x (32+2) pixel patch it needs in LDS and forms all nine taps from it.
+// and read back); here it is a patch-in-LDS direct convolution (conv_patch.h).
 //
-//   workgroup = 8 x 32 output pixels, 4 waves; a wave owns 2 output rows = two 32-pixel MFMA column blocks
-//   pass      = 32 input channels: LDS holds the patch [340 pixels][32 ch] and the weights [9 taps x 32 cout][32 ch]
-//               (64-byte rows; 16-byte chunks XOR-swizzled by (row >> 2) & 3: any 16 consecutive rows of one chunk
-//               cover the sixteen 16-byte slots of a bank row = conflict-free ds_read_b128). 40 KiB -> 3 workgroups
-//               per CU, so one workgroup's fill overlaps its neighbours' MFMA phase.
-//   weights   : LDS-DMA per pass (L2 -> LDS, 18 KiB). Re-reading them from L2 per MFMA made v1 L2-bandwidth-bound.
-//   patch fill: SRC_UP = 0: 16-byte LDS-DMA straight from the tensor (zero page outside the image = conv padding)
-//               SRC_UP = 1: the bilinear resize is evaluated here: 4 gathers from the low-res tensor (offsets and
-//                           weights precomputed once per workgroup), packed-fp16 lerp, ds_write_b128 - the
-//                           upsampled tensor never exists in memory
-//   MFMA      : v_mfma_f32_32x32x16_f16, A = weights [32 cout][16 k], B = patch [16 k][32 pixels]; D[cout][pixel].
-//               Patch row R serves (output row R, ky=0), (R-1, ky=1), (R-2, ky=2): per (kx, k-step) a wave reads
-//               4 patch-row fragments + 3 weight fragments for 6 MFMAs.
-//   epilogue  : bias + ReLU, dot with the 32->1 weights in-lane + one lane^32 exchange, bias + ReLU, fp32 store
-//               (32 consecutive pixels per store instruction = full 128-byte lines)
-//   launch    : 1-D grid, workgroup id -> tile remapped so that the workgroups of one XCD take consecutive tiles
-//               (neighbouring tiles share halo / source pixels in that XCD's L2).
-#include "vda_common.h"
+// This file adds to conv_patch.h's tiles, tile walk, per-pass steps, tap group and source-region geometry:
+//   the bilinear resize as the patch fill (bilinear_coord / bilinear_weights / bilinear8: one arithmetic for both kernels)
+//   depth_tail_kernel<SRC_UP>     v1, 8 x 32 tile, 40 KiB -> 3 workgroups per CU, so one workgroup's fill overlaps its neighbours'
+//                                 MFMA phase. SRC_UP = 0: the patch by LDS-DMA straight from the tensor. SRC_UP = 1: 4 gathers from
+//                                 the low-res tensor per patch pixel (offsets precomputed once per workgroup), packed-fp16 weighted
+//                                 sum, ds_write_b128 - the upsampled tensor never exists in memory
+//   v2::depth_tail_up_kernel<DBG> the resizing form the product runs: persistent, fill waves beside MFMA waves, source region in LDS
+#include "conv_patch.h"
 
 namespace {
 
-constexpr int TH = 8, TW = 32;                 // output tile
-constexpr int PH = TH + 2, PW = TW + 2;        // patch with halo
-constexpr int NPIX = PH * PW;                  // 340
-constexpr int CC = 32;                         // channels per pass
-constexpr int ROWB = CC * 2;                   // 64-byte LDS rows
-constexpr int NP_PATCH = (NPIX + 15) / 16;     // 1-KiB DMA pieces (16 rows x 64 B)
-constexpr int PATCH_BYTES = NP_PATCH * 1024;
+using namespace vda_patch;
+using namespace vda_patch::tile8;
+
 constexpr int NP_W = 9 * 32 / 16;
 constexpr int W_BYTES = NP_W * 1024;
 constexpr int NK = (NPIX + 63) / 64;           // bilinear items per thread and pass
-
-typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
-
-// ds_read_b128 is served 16 lanes at a time against one 256-byte bank row = sixteen 16-byte slots. Row r of 64 bytes puts chunk c
-// at slot 4 * (r & 3) + c: 16 consecutive rows of one chunk must hit 16 different slots, so rows r, r+4, r+8, r+12 need 4 different
-// chunk positions -> XOR with (r >> 2) & 3. (The first version used (r >> 1) & 3: 8 slots hit twice, 44 % conflict cycles measured.)
-__device__ __forceinline__ int swz(int r) { return (r >> 2) & 3; }
 
 // The bilinear sample as ONE weighted sum, a00 w00 + a01 w01 + a10 w10 + a11 w11 in packed fp16 (v_pk_mul + 3 v_pk_fma per channel pair:
 // 16 VALU instructions per 8 channels against 24 for the nested lerp the first version used); the weights are formed in fp32 and
@@ -99,20 +78,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) d
     char* const wl = lds + PATCH_BYTES;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // workgroups are dealt to the 8 XCDs round-robin: give XCD x the contiguous tile range [x * per_xcd, (x+1) * per_xcd)
-    const int per_xcd = gridDim.x >> 3;
-    const int tile = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    const int tile = xcd_tile();
     if (tile >= ntiles) return;                               // uniform per workgroup
-    const int tx = tile % tiles_x, tyb = tile / tiles_x;
-    const int ty = tyb % tiles_y, b = tyb / tiles_y;
-    const int x0 = tx * TW, y0 = ty * TH;
+    const TilePos t = tile_pos<TH, TW>(tile, tiles_x, tiles_y);
+    const int b = t.b, x0 = t.x0, y0 = t.y0;
     const int px = lane & 31, hh = lane >> 5;
 
-    f32x16 acc[2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[r][e] = 0.f;
+    f32x16 acc[2][1];
+    zero_acc(acc);
 
     // ---- bilinear (align_corners=True) geometry of this thread's patch pixels: the same for every pass
     const int ch = tid & 3;                                   // 16-byte chunk (8 channels) of the pass
@@ -135,27 +108,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) d
 
     for (int c0 = 0; c0 < C; c0 += CC) {
         if (c0 > 0) __syncthreads();                         // everyone done reading the previous pass's patch / weights
-        // ---- weights of this pass: rows R = tap * 32 + cout, 32 channels each
-        {
-            const int lr = lane >> 2, lp = lane & 3;
-            for (int piece = wave; piece < NP_W; piece += 4) {
-                const int R = piece * 16 + lr;
-                const int tap = R >> 5, co = R & 31;
-                glds16(w2 + co * (9 * C) + tap * C + c0 + ((lp ^ swz(R)) << 3), wl + piece * 1024);
-            }
-        }
-        // ---- patch of this pass
+        stage_weights<1>(w2, wl, wave, lane, C, 32, c0);
         if constexpr (SRC_UP == 0) {
-            const int lr = lane >> 2, lp = lane & 3;
-            for (int piece = wave; piece < NP_PATCH; piece += 4) {
-                const int q = piece * 16 + lr;
-                const int py = q / PW, pxx = q - py * PW;
-                const int iy = y0 - 1 + py, ix = x0 - 1 + pxx;
-                const bool ok = q < NPIX && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W;
-                const int sc = (lp ^ swz(q)) << 3;
-                const h16* src = ok ? in + ((b * H + iy) * W + ix) * C + c0 + sc : zero_page + sc;
-                glds16(src, patch + piece * 1024);
-            }
+            stage_patch(in, zero_page, patch, wave, lane, b, y0, x0, H, W, C, c0);
         } else {
             // three batches of 2 patch pixels: all 8 gathers of a batch are issued before its first lerp (loads are
             // unconditional - pixels outside the image read the tensor's first bytes and are zeroed afterwards)
@@ -185,28 +140,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) d
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // LDS-DMA landed before the barrier publishes it
         __syncthreads();
 
-        // ---- 3 kx x 2 k-steps: D[cout][pixel] += W2[cout][(ky,kx), c0 + 16ks ..] . patch[row + ky][pixel + kx][..]
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                h16x8 P[4], Wf[3];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int q = (wave * 2 + j) * PW + px + kx;
-                    P[j] = *reinterpret_cast<const h16x8*>(patch + q * ROWB + (((2 * ks + hh) ^ swz(q)) << 4));
-                }
-#pragma unroll
-                for (int ky = 0; ky < 3; ++ky) {
-                    const int R = (ky * 3 + kx) * 32 + px;                  // A operand: row = cout (lane & 31)
-                    Wf[ky] = *reinterpret_cast<const h16x8*>(wl + R * ROWB + (((2 * ks + hh) ^ swz(R)) << 4));
-                }
-#pragma unroll
-                for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                    for (int r = 0; r < 2; ++r) acc[r] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Wf[ky], P[r + ky], acc[r], 0, 0, 0);
-            }
-        }
+        mfma_pass<1, false>(patch, wl, wave, px, hh, h16x8{}, acc);
     }
 
     // ---- epilogue: lane = pixel (lane & 31) of row r; registers = couts 8*(e>>2) + 4*hh + (e&3)
@@ -216,7 +150,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) d
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const int co = 8 * (e >> 2) + 4 * hh + (e & 3);
-            s += fmaxf(acc[r][e] + b2[co], 0.f) * w3[co];
+            s += fmaxf(acc[r][0][e] + b2[co], 0.f) * w3[co];
         }
         s += __shfl_xor(s, 32, 64);
         const int oy = y0 + wave * 2 + r, ox = x0 + px;
@@ -250,7 +184,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) d
 //   arithmetic: the same interpolation, the same MFMA order per output pixel as v1 - results are bit-identical to v1
 //               (tests/test_kernels_gpu.py holds that).
 namespace v2 {
-constexpr int TH2 = 16, TW2 = 32, PH2 = TH2 + 2, PW2 = TW2 + 2, NPIX2 = PH2 * PW2;      // 612
+constexpr int TH2 = tile16::TH, TW2 = tile16::TW, PW2 = tile16::PW, NPIX2 = tile16::NPIX;      // (tile8's names are v1's)
 constexpr int MMA_WAVES = 8, FILL_WAVES = 8, NT2 = (MMA_WAVES + FILL_WAVES) * 64;        // 1024 threads
 constexpr int FILL_T = FILL_WAVES * 64;
 constexpr int NKF = (NPIX2 * 4 + FILL_T - 1) / FILL_T;                                   // 5 items per fill lane and pass
@@ -259,10 +193,8 @@ constexpr int PATCH_BYTES2 = PROWS2 * ROWB;                                     
 constexpr int W_PASS_BYTES = 9 * 32 * ROWB;                                              // 18 KiB per pass
 constexpr int SRC_ROWS = 256, ZERO_OFF = SRC_ROWS * ROWB, SRC_BYTES = ZERO_OFF + ROWB;   // 16 KiB + the zero row
 constexpr int SMEM2 = 2 * W_PASS_BYTES + 2 * PATCH_BYTES2 + 2 * SRC_BYTES;               // 148 KiB
-// patch rows are swizzled by their COLUMN in the patch, (col >> 2) & 3, not by the row index as in v1: conflict-free for the same
-// reason (a ds_read_b128 lane group's 16 columns still land on 16 different 16-byte slots), and a reading lane's swizzle then depends
-// on (pixel + kx) only - the 24 patch fragment addresses of a pass are 6 lane constants + immediates, the 18 weight fragment
-// addresses 2 (v1 recomputes ~4 VALU instructions per fragment and pass)
+// patch rows are swizzled by their COLUMN in the patch, not by the row index as in v1 (conv_patch.h): the 24 patch fragment addresses
+// of a pass are 6 lane constants + immediates, the 18 weight fragment addresses 2 (v1 recomputes ~4 VALU instructions per fragment)
 __device__ __forceinline__ int swzc(int col) { return (col >> 2) & 3; }
 
 // the source rows / columns a 16 x 32 tile's patch can touch, exactly as the kernel computes them (host side: sizes the source region)
@@ -294,23 +226,10 @@ __global__ void __launch_bounds__(NT2) depth_tail_up_kernel(const h16* __restric
     SH &= 0xffff;
     // the XCD's contiguous share of the tiles, dealt to its workgroups tile by tile: the workgroups of an XCD work on neighbouring tiles
     // at any moment (shared halo and source pixels in that XCD's L2)
-    const int per_xcd = gridDim.x >> 3, xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int tb = (int)((long long)ntiles * xcd / 8), te = (int)((long long)ntiles * (xcd + 1) / 8);
-    if (tb + slot >= te) return;                               // uniform per workgroup
-    const int nmy = (te - tb - slot + per_xcd - 1) / per_xcd;
+    const TileShare sh = xcd_share(ntiles);
+    if (sh.tb + sh.slot >= sh.te) return;                      // uniform per workgroup
+    const int per_xcd = sh.per_xcd, nmy = sh.nmy, tile0 = sh.tb + sh.slot;
     const int nu = nmy * npass;                                // units of this workgroup
-    auto bar = [&]() __attribute__((always_inline)) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("" ::: "memory");
-    };
-    // first source row / column under the patch of the tile at (y0, x0)
-    auto src_origin = [&](int y0, int x0, int& sy0, int& sx0) __attribute__((always_inline)) {
-        sy0 = min((int)(ys * (float)max(y0 - 1, 0)), h - 1);
-        sx0 = min((int)(xs * (float)max(x0 - 1, 0)), w - 1);
-    };
 
     if (wave >= MMA_WAVES) {
         // =================================================== fill waves ===================================================
@@ -337,16 +256,15 @@ __global__ void __launch_bounds__(NT2) depth_tail_up_kernel(const h16* __restric
         };
         auto dma_geometry = [&](int t) __attribute__((always_inline)) {
             asm volatile("; source geometry of a new tile" ::: "memory");     // (not speculable: keeps the once-per-tile work behind its branch)
-            const int tx = t % tiles_x, tyb = t / tiles_x;
-            const int ty = tyb % tiles_y, b = tyb / tiles_y;
+            const TilePos p = tile_pos<TH2, TW2>(t, tiles_x, tiles_y);
             int sy0, sx0;
-            src_origin(ty * TH2, tx * TW2, sy0, sx0);
+            src_origin(ys, xs, p.y0, p.x0, h, w, sy0, sx0);
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const int r = (fw + 8 * j) * 16 + lr;
                 const int fy = r / SW, fx = r - fy * SW;
                 const int gy = min(sy0 + fy, h - 1), gx = min(sx0 + fx, w - 1);     // (rows past the region: some valid pixel, never read)
-                s_goff[j] = (unsigned)(((b * h + gy) * w + gx) * C + ch * 8);
+                s_goff[j] = (unsigned)(((p.b * h + gy) * w + gx) * C + ch * 8);
             }
         };
         auto dma_src = [&](int pass, char* sb) __attribute__((always_inline)) {
@@ -366,11 +284,10 @@ __global__ void __launch_bounds__(NT2) depth_tail_up_kernel(const h16* __restric
         BiW bw[NKF];
         auto interp_geometry = [&](int t) __attribute__((always_inline)) {
             asm volatile("; patch geometry of a new tile" ::: "memory");      // (hipcc if-converted ~260 VALU instructions into every pass without it)
-            const int tx = t % tiles_x, tyb = t / tiles_x;
-            const int ty = tyb % tiles_y;
-            const int x0 = tx * TW2, y0 = ty * TH2;
+            const TilePos p = tile_pos<TH2, TW2>(t, tiles_x, tiles_y);
+            const int x0 = p.x0, y0 = p.y0;
             int sy0, sx0;
-            src_origin(y0, x0, sy0, sx0);
+            src_origin(ys, xs, y0, x0, h, w, sy0, sx0);
 #pragma unroll
             for (int k = 0; k < NKF; ++k) {
                 const int q = (ft >> 2) + (FILL_T / 4) * k;
@@ -380,12 +297,11 @@ __global__ void __launch_bounds__(NT2) depth_tail_up_kernel(const h16* __restric
                 int ya, yb, xa, xb;
                 float wx, wy;
                 bilinear_coord(ys, xs, iy, ix, h, w, ya, yb, xa, xb, wx, wy);
-                const int fa = min(max(ya - sy0, 0), SH - 1), fb = min(max(yb - sy0, 0), SH - 1);
-                const int ga = min(max(xa - sx0, 0), SW - 1), gb = min(max(xb - sx0, 0), SW - 1);
                 const unsigned c16 = (unsigned)ch * 16u;
                 const unsigned z = (unsigned)ZERO_OFF + c16;
-                ia[k] = ok ? ((unsigned)(fa * SW + ga) * ROWB + c16) | (((unsigned)(fa * SW + gb) * ROWB + c16) << 16) : (z | (z << 16));
-                ib[k] = ok ? ((unsigned)(fb * SW + ga) * ROWB + c16) | (((unsigned)(fb * SW + gb) * ROWB + c16) << 16) : (z | (z << 16));
+                const Corners cn = ok ? corner_offsets(ya, yb, xa, xb, sy0, sx0, SH, SW, [&](int row) { return (unsigned)row * ROWB + c16; }) : Corners{z | (z << 16), z | (z << 16)};
+                ia[k] = cn.ia;
+                ib[k] = cn.ib;
                 bw[k] = bilinear_weights(wx, wy);
             }
         };
@@ -405,9 +321,9 @@ __global__ void __launch_bounds__(NT2) depth_tail_up_kernel(const h16* __restric
                 *reinterpret_cast<h16x8*>(pb + woff[k]) = bilinear8(a00, a01, a10, a11, bw[k]);
             }
         };
-        // unit v of this workgroup = (tile tb + slot + (v / npass) * per_xcd, pass v % npass); the two sides run at different units
-        int tileD = tb + slot, passD = 0;                      // DMA side: the unit whose source region is fetched next
-        int tileI = tb + slot, passI = 0;                      // interpolation side: the unit whose patch is built next
+        // unit v of this workgroup = (tile tile0 + (v / npass) * per_xcd, pass v % npass); the two sides run at different units
+        int tileD = tile0, passD = 0;                      // DMA side: the unit whose source region is fetched next
+        int tileI = tile0, passI = 0;                      // interpolation side: the unit whose patch is built next
         auto advance = [&](int& t, int& ps) __attribute__((always_inline)) {
             if (++ps == npass) {
                 ps = 0;
@@ -420,7 +336,7 @@ __global__ void __launch_bounds__(NT2) depth_tail_up_kernel(const h16* __restric
         dma_src(0, srcb);
         advance(tileD, passD);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        bar();
+        wg_barrier();
         interp_geometry(tileI);
         interp(srcb, patch);
         advance(tileI, passI);
@@ -430,10 +346,10 @@ __global__ void __launch_bounds__(NT2) depth_tail_up_kernel(const h16* __restric
             advance(tileD, passD);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        bar();
+        wg_barrier();
         if constexpr (DBG >= 4) {                              // TIMING EXPERIMENTS 4..6: the MFMA side alone
             for (int u = 0; u < nu; ++u)
-                if (DBG != 6) bar();
+                if (DBG != 6) wg_barrier();
             return;
         }
         for (int u = 0; u < nu; ++u) {
@@ -452,18 +368,15 @@ __global__ void __launch_bounds__(NT2) depth_tail_up_kernel(const h16* __restric
                 advance(tileI, passI);
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            bar();
+            wg_barrier();
         }
         return;
     }
 
     // ======================================================= MFMA waves =======================================================
     const int px = lane & 31, hh = lane >> 5;
-    f32x16 acc[2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[r][e] = 0.f;
+    f32x16 acc[2][1];
+    zero_acc(acc);
     // fragment addresses: lane constants + immediates
     int pbase[3][2], wbase[2];
 #pragma unroll
@@ -473,20 +386,14 @@ __global__ void __launch_bounds__(NT2) depth_tail_up_kernel(const h16* __restric
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) wbase[ks] = px * ROWB + (((2 * ks + hh) ^ swz(px)) << 4);
     struct Frag {
-        h16x8 P[4], Wf[3];
+        h16x8 P[4], Wf[1][3];
     };
     auto load_frag = [&](int g, const char* pc, const char* wc, Frag& f) __attribute__((always_inline)) {
         const int kx = g >> 1, ks = g & 1;
 #pragma unroll
         for (int j = 0; j < 4; ++j) f.P[j] = *reinterpret_cast<const h16x8*>(pc + pbase[kx][ks] + j * PW2 * ROWB);
 #pragma unroll
-        for (int ky = 0; ky < 3; ++ky) f.Wf[ky] = *reinterpret_cast<const h16x8*>(wc + wbase[ks] + (ky * 3 + kx) * 32 * ROWB);
-    };
-    auto mma = [&](const Frag& f) __attribute__((always_inline)) {
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-            for (int r = 0; r < 2; ++r) acc[r] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.Wf[ky], f.P[r + ky], acc[r], 0, 0, 0);
+        for (int ky = 0; ky < 3; ++ky) f.Wf[0][ky] = *reinterpret_cast<const h16x8*>(wc + wbase[ks] + (ky * 3 + kx) * 32 * ROWB);
     };
     int u = 0;
     auto unit = [&]() __attribute__((always_inline)) {
@@ -504,41 +411,39 @@ __global__ void __launch_bounds__(NT2) depth_tail_up_kernel(const h16* __restric
                 load_frag(g + 1, pc, wc, f[(g + 1) & 1]);
                 __builtin_amdgcn_sched_group_barrier(0x100, 7, 0);      // the next group's fragments are requested first ...
             }
-            mma(f[DBG == 5 ? 0 : g & 1]);                               // (experiment 5: no fragment reads but the first group's)
+            const Frag& fg = f[DBG == 5 ? 0 : g & 1];
+            tap_group<1>(fg.P, fg.Wf, acc);                              // (experiment 5: no fragment reads but the first group's)
             __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);          // ... then this group's six MFMAs
             __builtin_amdgcn_sched_barrier(0);
         }
         ++u;
     };
-    bar();                                                     // (prologue: weights and source of unit 0 landed)
-    bar();                                                     // (prologue: patch of unit 0 built)
-    int tile = tb + slot;
+    wg_barrier();                                              // (prologue: weights and source of unit 0 landed)
+    wg_barrier();                                              // (prologue: patch of unit 0 built)
+    int tile = tile0;
     for (int k = 0; k < nmy; ++k) {
         for (int pass = 0; pass + 1 < npass; ++pass) {
             unit();
-            if (DBG != 6) bar();
+            if (DBG != 6) wg_barrier();
         }
         unit();
-        {
-            // ---- epilogue of the tile: lane = pixel (lane & 31) of row r; registers = couts 8*(e>>2) + 4*hh + (e&3)
-            const int tx = tile % tiles_x, tyb = tile / tiles_x;
-            const int ty = tyb % tiles_y, b = tyb / tiles_y;
+        // ---- epilogue of the tile, the text of v1's: as one shared function hipcc regrouped the b2 / w3 loads and their waits here
+        const TilePos t = tile_pos<TH2, TW2>(tile, tiles_x, tiles_y);
 #pragma unroll
-            for (int r = 0; r < 2; ++r) {
-                float s = 0.f;
+        for (int r = 0; r < 2; ++r) {
+            float s = 0.f;
 #pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const int co = 8 * (e >> 2) + 4 * hh + (e & 3);
-                    s += fmaxf(acc[r][e] + b2[co], 0.f) * w3[co];
-                    acc[r][e] = 0.f;
-                }
-                s += __shfl_xor(s, 32, 64);
-                const int oy = ty * TH2 + wave * 2 + r, ox = tx * TW2 + px;
-                if (hh == 0 && oy < H && ox < W) out[((size_t)b * H + oy) * W + ox] = fmaxf(s + b3, 0.f);
+            for (int e = 0; e < 16; ++e) {
+                const int co = 8 * (e >> 2) + 4 * hh + (e & 3);
+                s += fmaxf(acc[r][0][e] + b2[co], 0.f) * w3[co];
+                acc[r][0][e] = 0.f;
             }
+            s += __shfl_xor(s, 32, 64);
+            const int oy = t.y0 + wave * 2 + r, ox = t.x0 + px;
+            if (hh == 0 && oy < H && ox < W) out[((size_t)t.b * H + oy) * W + ox] = fmaxf(s + b3, 0.f);
         }
         tile += per_xcd;
-        if (DBG != 6) bar();
+        if (DBG != 6) wg_barrier();
     }
 }
 }  // namespace v2
@@ -561,10 +466,9 @@ extern "C" int vda_depth_tail_f16(const void* in, const void* w2, const float* b
     VDA_REQUIRE(B > 0 && h > 0 && w > 0 && H > 0 && W > 0 && C > 0 && C % CC == 0, "vda_depth_tail: bad geometry (C=%d must be a multiple of %d)", C, CC);
     VDA_REQUIRE(((uintptr_t)in & 15) == 0 && ((uintptr_t)w2 & 15) == 0, "vda_depth_tail: 16-byte alignment required");
     VDA_REQUIRE((double)B * h * w * C < 2147483647.0 && (double)B * H * W < 2147483647.0, "vda_depth_tail: tensor exceeds 32-bit element offsets");
-    const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;
-    const long long ntiles = (long long)tiles_x * tiles_y * B;
+    int tiles_x, tiles_y;
+    const long long ntiles = tile_count(B, H, W, TH, TW, tiles_x, tiles_y);
     VDA_REQUIRE(ntiles < (1ll << 30), "vda_depth_tail: too many tiles");
-    const dim3 grid((unsigned)((ntiles + 7) / 8 * 8));
     hipStream_t s = (hipStream_t)stream;
     // align_corners=True scale, computed once on the host (an in-kernel division is not guaranteed the same bits in two kernels)
     const float ys = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f, xs = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f;
@@ -572,8 +476,8 @@ extern "C" int vda_depth_tail_f16(const void* in, const void* w2, const float* b
     // under a 18 x 34 patch to fit 256 pixels - any upsampling by >= ~1.3 does (1.75 everywhere in the product)
     const int SH = v2::src_extent(ys, v2::TH2, -1, H, h), SW = v2::src_extent(xs, v2::TW2, -1, W, w);
     if ((h != H || w != W) && SH * SW <= v2::SRC_ROWS && (g_tail_variant & 7) != 1) {
-        const int tx2 = (W + v2::TW2 - 1) / v2::TW2, ty2 = (H + v2::TH2 - 1) / v2::TH2;
-        const long long nt2 = (long long)tx2 * ty2 * B;
+        int tx2, ty2;
+        const long long nt2 = tile_count(B, H, W, v2::TH2, v2::TW2, tx2, ty2);
         VDA_REQUIRE(nt2 < (1ll << 30), "vda_depth_tail: too many tiles");
         static VdaKernelDeviceState dev_state[8];
         const int dbg = (g_tail_variant >> 4) & 7;              // timing experiments (results invalid), tools/tail_variants.py
@@ -583,19 +487,15 @@ extern "C" int vda_depth_tail_f16(const void* in, const void* w2, const float* b
         const KFn fn = fns[dbg];
         const int ncu = vda_prepare_kernel(reinterpret_cast<const void*>(fn), v2::SMEM2, dev_state[dbg]);
         if (ncu < 0) return 2;
-        const int grid2 = (int)(nt2 < ncu ? (nt2 + 7) / 8 * 8 : ncu);
-        hipLaunchKernelGGL(fn, dim3(grid2), dim3(v2::NT2), v2::SMEM2, s, (const h16*)in, (const h16*)w2, b2, w3, b3, out, h, w, H, W, C,
+        hipLaunchKernelGGL(fn, dim3(persistent_grid(nt2, ncu)), dim3(v2::NT2), v2::SMEM2, s, (const h16*)in, (const h16*)w2, b2, w3, b3, out, h, w, H, W, C,
                            tx2, ty2, (int)nt2, ys, xs, SH | ((g_tail_variant & 8) ? 1 << 16 : 0), SW);
         VDA_LAUNCH_CHECK();
         g_tail_last_kernel = "depth_tail_up_kernel";
         return 0;
     }
-    if (h == H && w == W)
-        hipLaunchKernelGGL((depth_tail_kernel<0>), grid, dim3(256), 0, s, (const h16*)in, (const h16*)w2, b2, w3, b3, out, (const h16*)zero_page, h, w,
-                           H, W, C, tiles_x, tiles_y, (int)ntiles, ys, xs);
-    else
-        hipLaunchKernelGGL((depth_tail_kernel<1>), grid, dim3(256), 0, s, (const h16*)in, (const h16*)w2, b2, w3, b3, out, (const h16*)zero_page, h, w,
-                           H, W, C, tiles_x, tiles_y, (int)ntiles, ys, xs);
+    const auto fn1 = h == H && w == W ? &depth_tail_kernel<0> : &depth_tail_kernel<1>;
+    hipLaunchKernelGGL(fn1, dim3(grid8(ntiles)), dim3(256), 0, s, (const h16*)in, (const h16*)w2, b2, w3, b3, out, (const h16*)zero_page, h, w, H, W, C,
+                       tiles_x, tiles_y, (int)ntiles, ys, xs);
     VDA_LAUNCH_CHECK();
     g_tail_last_kernel = h == H && w == W ? "depth_tail_kernel<0>" : "depth_tail_kernel<1>";
     return 0;
