@@ -11,7 +11,8 @@ equalities can fail) and tests/test_kernels_f32_edges_gpu.py (GPU: the kernels m
 
 The second half does the same for the fp16 GEMM (fp16 operands, fp32 accumulation, fp16 stores: a second condition, see there)
 and tests/test_kernels_f16_edges_gpu.py, and lists that file's launches as shapes (f16_launches) for the planner coverage test
-in tests/test_gemm_plan.py.
+in tests/test_gemm_plan.py. Its "tile seams" part restates the persistent kernels' tile walk (tile_walk) and builds the cases that
+give a workgroup three tiles under vda_set_max_wgs.
 
 The last part builds inputs whose SOFTMAX is exact - one key that wins by 52 bits, or every weight 1 - for the fp16 attention
 kernels and tests/test_attention_edges_gpu.py, with their preconditions (assert_selector_safe, assert_tattn_selector_safe).
@@ -19,6 +20,8 @@ kernels and tests/test_attention_edges_gpu.py, with their preconditions (assert_
 The part after that does it for the fused upsample convolutions (conv_up.hip, tail.hip) and tests/test_upsample_edges_gpu.py: constant
 images, selector weights with a derived bound, dyadic resize scales; a plain restatement of resize + convolution (fused_emulate) in the
 kernels' own operation orders, with the mistakes of FUSED_MUTATIONS built in; replicas of the kernels' source-window arithmetic."""
+import functools
+
 import torch
 import torch.nn.functional as F
 
@@ -297,10 +300,14 @@ DENSE16_CASES = [
 def dense16_inputs(case):
     """Integer operands as fp32 host tensors (each is its own fp16 rounding). A [M, K] in [-3, 3] ({-1, 0, 1} where K >= 448), W in
     [-2, 2]; bias, res, res2 in [-4, 4]; gamma, ln_w, ln_b, mean in [-2, 2]; rstd in {0.5, 1, 2}. (K >= 448: ln_w in {-1, 0, 1} too - with [-2, 2] the LayerNorm-folded
-    reference of the K = 1536 case reaches 1475 = 2950 half-steps, past what fp16 holds at a step of 0.5.)"""
+    reference of the K = 1536 case reaches 1475 = 2950 half-steps, past what fp16 holds at a step of 0.5.)
+    A seam case (below) is narrowed at every K it has, 320 and 576: it has a million outputs and more where DENSE16_CASES' K = 320 case has 68 000,
+    and with A in [-3, 3] and ln_w in [-2, 2] the LayerNorm-folded reference of the first one (M = 4827, N = 256, K = 320) reaches 2124 half-steps - the
+    tail of that many sums, which no other seed would cut."""
     M, N, K, lda, ldc = case
-    s = 5000 + 17 * DENSE16_CASES.index(case)
-    a = 1 if K >= 448 else 3
+    seam = case not in DENSE16_CASES
+    s = seam16_seed(case) if seam else 5000 + 17 * DENSE16_CASES.index(case)
+    a = 1 if K >= 448 or seam else 3
     rstd = torch.tensor([0.5, 1.0, 2.0])[ints((M,), 0, 2, s + 9).long()]
     return dict(A=ints((M, K), -a, a, s), W=ints((N, K), -2, 2, s + 1), bias=ints((N,), -4, 4, s + 2), gamma=ints((N,), -2, 2, s + 3),
                 res=ints((M, N), -4, 4, s + 4), res2=ints((M, N), -4, 4, s + 5), ln_w=ints((K,), -a if a == 1 else -2, a if a == 1 else 2, s + 6), ln_b=ints((K,), -2, 2, s + 7),
@@ -349,7 +356,10 @@ BROADCAST16_CASES = [(300, 136, 128)]
 # one full round and a short last one.  N = 2048: nbn = 8, the L2-blocked walk (it needs a full round); N = 1024: nbn = 4, the last
 # partial round dealt by row panel (per_xcd % nbn == 0); N = 768: nbn = 3, the plain mapping with a partial last round.
 WALK16_N = [2048, 1024, 768]
-WALK16_VARIANTS = [-1, 3, 4, 5, 9, 5 + 16 * 64]
+# 8 (192 x 128) and 11 (the same, two workgroups per CU): M comes from the CU count in 256-row tiles, so 192-row tiles number more and both have
+# more tiles than workgroups too. Not 10: at N = 768 its 192 x 384 tiles number 116 x 2 = 232, fewer than the 256 workgroups, and 384 does not
+# divide the other two widths, where it plans variant 4's 256 x 128 tile. (The seam cases below walk the 192 x 384 tile on a capped grid.)
+WALK16_VARIANTS = [-1, 3, 4, 5, 9, 5 + 16 * 64, 8, 11]
 
 
 def walk16_case(ncu, N):
@@ -376,7 +386,7 @@ PATCH16_CASES = [(130, 1, 72, 128, 72), (130, 1, 136, 128, 144), (43, 6, 72, 128
 
 def patch16_inputs(case):
     fr, P, N, K, ldc = case
-    s = 6000 + 17 * PATCH16_CASES.index(case)
+    s = 6000 + 17 * (PATCH16_CASES + SEAM_PATCH16_CASES).index(case)
     return dict(A=ints((fr * P, K), -3, 3, s), W=ints((N, K), -2, 2, s + 1), bias=ints((N,), -4, 4, s + 2), pos=ints((P + 1, N), -4, 4, s + 3))
 
 
@@ -395,7 +405,7 @@ CONVT16_CASES = [
 
 def convt16_inputs(case, k):
     B, h, w, C, Cp = case
-    s = 6501 + 17 * CONVT16_CASES.index(case) + k          # (seed 6500 has a zero in the last input channel of the 1 x 1 case, k = 4: a dropped k = C - 1 went unseen)
+    s = 6501 + 17 * (CONVT16_CASES + SEAM_CONVT16_CASES).index(case) + k          # (seed 6500 has a zero in the last input channel of the 1 x 1 case, k = 4: a dropped k = C - 1 went unseen)
     return dict(x=ints((B, C, h, w), -3, 3, s), w=ints((C, C, k, k), -2, 2, s + 1), bias=ints((C,), -4, 4, s + 2))
 
 
@@ -419,7 +429,7 @@ def conv16_id(c):
 
 def conv16_inputs(case):
     B, H, W, Cin, Cout, stride, _, _ = case
-    s = 7000 + 17 * CONV16_CASES.index(case)
+    s = 7000 + 17 * (CONV16_CASES + SEAM_CONV16_CASES).index(case)
     Ho, Wo = conv_out_size(H, W, stride)
     return dict(x=ints((B, Cin, H, W), -3, 3, s), w=ints((Cout, Cin, 3, 3), -2, 2, s + 1), bias=ints((Cout,), -4, 4, s + 2),
                 res=ints((B, Ho, Wo, Cout), -4, 4, s + 3), res2=ints((B, Ho, Wo, Cout), -4, 4, s + 4))
@@ -521,7 +531,9 @@ ROWPOS16_ROWS = [0, 127, 128, 191, 192, 255, 256]
 
 def f16_launches(ncu):
     """Every (variant, sched, fields) that tests/test_kernels_f16_edges_gpu.py hands to vda_gemm_f16, in no particular order: the planner
-    coverage test (CPU) walks this list, the GPU file asserts after every launch that the kernel that ran is the one planned."""
+    coverage test (CPU) walks this list, the GPU file asserts after every launch that the kernel that ran is the one planned.
+    (The tile-seam launches run on a capped grid and are planned for it: seam16_launches and pick_cap below, held to the built
+    tables in tests/test_exact_inputs.py.)"""
     for v in VARIANTS16:
         for case in DENSE16_CASES:
             for e in dense16_epis(case):
@@ -547,6 +559,233 @@ def f16_launches(ncu):
                 yield v, True, gemm16_fields(M, N, K, EPI["BIAS_F16"])
     M, N, K = split16_case(ncu)
     yield -1, False, gemm16_fields(M, N, K, EPI["BIAS_F16"])
+
+
+# ------------------------------------------------------------------------------------------------ tile seams: a persistent workgroup's second and third tile
+# The cases above give a persistent workgroup at most one tile on a 256-CU device. Under vda_set_max_wgs(8 or 16) a few thousand rows
+# are three rounds of the capped grid: what passes from one tile to the next (the prefetched K tile 0, the A slot the epilogue staged
+# through, the bias / statistics fragments fetched a tile ahead, the conv row decomposition, the rotated fold walk, the dealt last
+# round) is then under the same equalities. The walk model below restates gemm_tile.h's TileWalk so that the CPU file can assert what
+# each case's launches do - which workgroup runs which tiles in which order - without a GPU.
+FOLD_ROT = 5                          # gemm8p_kernel.h: the folded mode rotates a row panel's columns by FOLD_ROT panels per round
+
+
+def tile_walk(M, N, bm, bn, nwg, fold=False):
+    """gemm_tile.h's TileWalk (plain, dealt, deal_last) for a grid of nwg workgroups, with the FOLD_ROT rotation of gemm8p_kernel.h on
+    request: dict(nbn, nbm, ntiles, nwg, per_xcd, full_rounds, rem, deal_last, tiles), tiles[bid] = the tiles workgroup bid runs, in
+    order (the kernels' loop ends at the first round whose tile is past the end). The L2-blocked order (32 workgroups per XCD) is not
+    modelled: no capped launch takes it."""
+    assert nwg > 0 and nwg % 8 == 0, "persistent grids are multiples of the eight XCDs"
+    nbn, nbm = -(-N // bn), -(-M // bm)
+    ntiles, per_xcd = nbm * nbn, nwg >> 3
+    full_rounds, rem = divmod(ntiles, nwg)
+    deal_last = rem > 0 and full_rounds > 0 and per_xcd % nbn == 0
+
+    def tile_of(bid, rnd):
+        if deal_last and rnd == full_rounds:
+            slot = bid >> 3
+            j = ((slot // nbn) * 8 + (bid & 7)) * nbn + slot % nbn
+            t = rnd * nwg + j if j < rem else ntiles
+        else:
+            t = rnd * nwg + (bid & 7) * per_xcd + (bid >> 3)
+        if fold and t < ntiles:
+            i, j = divmod(t, nbn)
+            t = i * nbn + (j + (i * nbn // nwg) * FOLD_ROT) % nbn
+        return t
+
+    tiles = []
+    for bid in range(nwg):
+        mine, rnd = [], 0
+        while tile_of(bid, rnd) < ntiles:
+            mine.append(tile_of(bid, rnd))
+            rnd += 1
+        tiles.append(mine)
+    return dict(M=M, N=N, bm=bm, bn=bn, nbn=nbn, nbm=nbm, ntiles=ntiles, nwg=nwg, per_xcd=per_xcd, full_rounds=full_rounds, rem=rem, deal_last=deal_last, tiles=tiles)
+
+
+def tile_box(w, t):
+    """(r0, r1, c0, c1): the rows and columns of the matrix that tile t of a tile_walk owns."""
+    i, j = divmod(t, w["nbn"])
+    return i * w["bm"], min((i + 1) * w["bm"], w["M"]), j * w["bn"], min((j + 1) * w["bn"], w["N"])
+
+
+def seam_pairs(w):
+    """[(previous tile, tile)] over every workgroup's tiles of round >= 1: the seams."""
+    return [(a, b) for mine in w["tiles"] for a, b in zip(mine, mine[1:])]
+
+
+def seam16_case(bm, bn, nwg, nbn, K, wide64, pad):
+    """(M, N, K, lda, ldc) for bm x bn tiles on nwg workgroups: two full rounds and a partial third (at least three tiles of it), the
+    partial row tile in the last round. N: wide64 - a multiple of 64 (split, split_pos and GEGLU apply), the last column tile 64 wide
+    where nbn > 1; otherwise one 8-column segment past a tile width (past bn / 2 where nbn == 1). The 192 x 384 tile is forced only
+    for N % 384 == 0: whole column tiles, wide64 alone. Asserted through the model by assert_seam16."""
+    nbm = -(-(2 * nwg + 3) // nbn)
+    M = nbm * bm - 37
+    if bn == 384:
+        assert wide64
+        N = nbn * bn
+    elif wide64:
+        N = bn if nbn == 1 else (nbn - 1) * bn + 64
+    else:
+        N = bn // 2 + 8 if nbn == 1 else (nbn - 1) * bn + 8
+    return (M, N, K, K + 8 * pad, N + 8 * pad)
+
+
+def assert_seam16(case, bm, bn, nwg):
+    """What a seam case is there for, from the model; returns the walk."""
+    M, N, K, lda, ldc = case
+    w = tile_walk(M, N, bm, bn, nwg)
+    assert sorted(t for mine in w["tiles"] for t in mine) == list(range(w["ntiles"])), "the walk covers every tile once"
+    assert w["full_rounds"] == 2 and 0 < w["rem"] < nwg, (case, bm, bn, nwg, w["full_rounds"], w["rem"])
+    assert sorted({len(mine) for mine in w["tiles"]}) == [2, 3], "some workgroups run three tiles, the others sit out the last round"
+    assert w["deal_last"] == ((nwg >> 3) % w["nbn"] == 0)
+    assert M % bm != 0 and N % 8 == 0 and K % 64 == 0 and lda % 8 == 0 and ldc % 8 == 0
+    last_panel = range((w["nbm"] - 1) * w["nbn"], w["ntiles"])
+    assert all(mine.index(t) >= 1 for mine in w["tiles"] for t in mine if t in last_panel), "the partial row tile falls in a round > 0"
+    if w["nbn"] > 1 and N % bn != 0:
+        ragged_after_full = [(a, b) for a, b in seam_pairs(w) if b % w["nbn"] == w["nbn"] - 1 and a % w["nbn"] != w["nbn"] - 1]
+        # nbn | nwg: plain() and dealt() both keep a workgroup in its column (t and t + nwg are congruent mod nbn, and the dealt slot
+        # keeps slot % nbn), so no workgroup can change column tiles at a seam; the modes with nbn = 3 do
+        assert bool(ragged_after_full) == (nwg % w["nbn"] != 0), (case, bm, bn, nwg)
+    return w
+
+
+# (bm, bn, workgroups per CU): the large tiles vda_gemm_built lists for dense A
+SEAM16_TILES = [(256, 256, 1), (256, 128, 1), (192, 128, 1), (192, 128, 2), (192, 384, 1), (192, 256, 1)]
+# (cap, nbn): nbn = 1 on 8 workgroups - the last round dealt (per_xcd % nbn == 0); nbn = 3 - the plain last round; nbn = 2 on 16 - dealt
+# with per_xcd = 2. (Two workgroups per CU: 16 workgroups under cap 8 in all three.)
+SEAM16_MODES = [(8, 1), (8, 3), (16, 2)]
+# what the seam tests force: every variant with a large tile (0 and 7 run the 128-row kernel on dense A)
+SEAM16_VARIANTS = [-1, 1, 2, 3, 4, 5, 9, 8, 10, 11, 5 + 16 * 64]
+
+
+def seam16_specs():
+    """[(bm, bn, per_cu, cap, case)]. Every tile in the three modes with N a multiple of 64, and with the one-segment N in the plain mode
+    (nbn = 3: the one mode in which a workgroup changes its column tile at a seam, so the one in which a ragged tile follows a full one).
+    K steps: 5 (the 8-phase kernel's 3 A slots and 2 W slots out of phase at the seam) and 9; each tile gets both, and lda > K, ldc > N
+    with the segment flavour (the 192 x 384 tile, which has none: with nbn = 3)."""
+    out = []
+    for bm, bn, per_cu in SEAM16_TILES:
+        for cap, nbn in SEAM16_MODES:
+            cap = 8 if per_cu == 2 else cap
+            for wide64 in (True, False):
+                if not wide64 and (bn == 384 or nbn != 3):
+                    continue
+                K = 64 * (9 if nbn == 2 or not wide64 or (bn == 384 and nbn == 3) else 5)
+                pad = not wide64 or (bn == 384 and nbn == 3)
+                out.append((bm, bn, per_cu, cap, seam16_case(bm, bn, per_cu * cap, nbn, K, wide64, pad)))
+    return out
+
+
+SEAM16_SPECS = seam16_specs()
+
+
+def seam16_id(spec):
+    return "tile%dx%dx%d-cap%d-%s" % (spec[:4] + (dense_id(spec[4]),))
+
+
+def seam16_seed(case):
+    """Seeds of dense16_inputs for a seam case (several tiles may share a shape: the same inputs then)."""
+    cases = sorted({s[4] for s in SEAM16_SPECS})
+    return 5300 + 31 * cases.index(case)
+
+
+def seam16_launches(L, spec):
+    """[(variant, epilogue name, family, dyn)] that run spec's case on spec's tile under vda_set_max_wgs(cap), from vda_gemm_plan for cap CUs:
+    a variant whose family is not built for the epilogue plans another tile, on which this case has other rounds - that launch belongs to
+    the spec of that tile, if any. A forced variant that repeats an earlier one's kernel on this tile is left out (8, 10 and 11 fall back
+    to variant 4's 256 x 128 tile, 5 + 16 * 64 to variant 5's 256 x 256 one, for the epilogues their own tile is not built for); the
+    automatic path stays, its option word differs. dyn: the same launch with sched set draws its tiles (8-phase kernel, default K schedule)."""
+    bm, bn, per_cu, cap, case = spec
+    out, seen = [], set()
+    for v in SEAM16_VARIANTS:
+        L.lib.vda_gemm_set_variant(v)
+        for e in dense16_epis(case):
+            f = gemm16_fields(epi=EPI[EPI_OF[e]], **dense16_kw(case, e))
+            rc, recs = plan16(L, f, ncu=cap)
+            if rc == 0 and len(recs) == 1 and recs[0].family != L.FAM_128 and (recs[0].bm, recs[0].bn, recs[0].per_cu) == (bm, bn, per_cu):
+                if (v < 0, recs[0].family, recs[0].ksched, e) in seen:
+                    continue
+                seen.add((v < 0, recs[0].family, recs[0].ksched, e))
+                rc2, dyn = plan16(L, f, ncu=cap, sched=True)
+                out.append((v, e, recs[0].family, bool(rc2 == 0 and len(dyn) == 1 and dyn[0].dyn == 1)))
+    L.lib.vda_gemm_set_variant(-1)
+    return out
+
+
+def pick_cap(L, fields, fold=False):
+    """(cap, record, walk) for a launch of the conv / patch / ConvTranspose / folded seam cases under the current variant: the first of
+    8 and 16 workgroups with at least two full rounds and a partial one on the planned tile, else the first with more than two
+    rounds' worth of tiles (N = 16 column tiles can have no partial round on either); None where the plan is the 128-row kernel
+    or the tiles are too few on both."""
+    found = None
+    for cap in (8, 16):
+        rc, recs = plan16(L, fields, ncu=cap)
+        if rc != 0 or len(recs) != 1 or recs[0].family in (L.FAM_128, L.FAM_CONV_LDS):
+            continue
+        r = recs[0]
+        w = tile_walk(fields["M"], fields["N"], r.bm, r.bn, r.per_cu * cap, fold)
+        if w["full_rounds"] >= 2 and w["rem"] > 0:
+            return cap, r, w
+        if found is None and w["ntiles"] > 2 * w["nwg"]:
+            found = (cap, r, w)
+    return found
+
+
+# patch embed (frames, P, N, K, ldc): P = 37 rows per frame, so frame boundaries fall inside 256-row tiles of every round; five K steps
+SEAM_PATCH16_CASES = [(131, 37, 136, 320, 144), (131, 37, 264, 320, 264)]
+# ConvTranspose (B, h, w, C, Cp), three frames, K = Cp = 128: two K steps. k = 2 (N = 512: 2 or 4 column tiles) on 30 x 30 = 2700 rows = 11 row
+# tiles of 256; k = 4 (N = 2048: 8 or 16 column tiles) on 14 x 14 = 588 rows = 3 row tiles, both frame borders inside tiles of later rounds
+SEAM_CONVT16_CASES = [(3, 30, 30, 120, 128), (3, 14, 14, 120, 128)]
+SEAM_CONVT16 = [(SEAM_CONVT16_CASES[0], 2), (SEAM_CONVT16_CASES[1], 4)]
+# conv3x3 (B, H, W, Cin, Cout, stride, relu_in, ldc): 3 x 41 x 41 = 5043 rows = 20 row tiles of 256, frame borders at rows 1681 and 3362
+SEAM_CONV16_CASES = [
+    (3, 41, 41, 64, 128, 1, True, 128),       # one column tile of either width, the instantiation with the max
+    (3, 41, 41, 64, 128, 1, False, 128),      # ... and the plain one
+    (3, 41, 41, 128, 136, 1, False, 144),     # two K steps per tap; nbn = 1 of 256 / 2 of 128 with a one-segment last tile; ldc > N
+    (3, 41, 41, 64, 264, 1, True, 264),       # nbn = 2 of 256 / 3 of 128; the one shape the automatic path gives a large tile
+    (3, 81, 81, 64, 136, 2, False, 136),      # stride 2 from an 81 x 81 source
+    (3, 81, 81, 64, 136, 2, True, 136),
+    (3, 17, 65, 64, 64, 1, True, 64),         # conv3x3_c64_kernel's: 3 x 3 x 3 = 27 tiles of 8 x 32; on 8 workgroups (one per XCD) the XCD shares are 3 or 4
+]
+SEAM_C64_CASE = SEAM_CONV16_CASES[-1]
+# every variant with a conv family on the large tiles; also what the patch-embed and ConvTranspose epilogues are built on (the 256-row
+# tiles alone: 8, 10, 11 and 5 + 16 * 64 would repeat 4 and 5)
+SEAM_CONV16_VARIANTS = [-1, 1, 2, 3, 4, 5, 9]
+# folded ConvTranspose + conv (k, Cin, Fe, B, H, W): N = k * k * Fe -> nbn = 1, 2 and 4 column tiles of the 8-phase 256 x 256 tile
+SEAM_FOLD_CASES = [(2, 64, 64, 2, 47, 50), (2, 64, 128, 2, 30, 40), (4, 64, 64, 2, 24, 25)]
+SEAM_C64_EPIS = ["bias_f16", "bias_relu", "res", "res_res2"]
+# depth_tail_up_kernel: 3 x 3 x 3 = 27 tiles of 16 x 32 on 8 workgroups
+SEAM_TAILUP_CASE = (3, 17, 33, 33, 65)
+# the L2-blocked walk (32 workgroups per XCD, uncapped) at five K steps
+WALK16_BLOCKED_K = 320
+EPI_CONVT_FOLD_F16 = 13               # include/vda.h (test_exact_inputs.py holds it to _lib)
+
+
+def fold_fields(case):
+    k, Cin, Fe, B, H, W = case
+    return gemm16_fields(B * H * W, k * k * Fe, 9 * Cin, EPI_CONVT_FOLD_F16, lda=9 * Cin, ldc=Fe, conv=(B, H, W, Cin, H, W, 1), convt=(k, H, W, Fe))
+
+
+@functools.lru_cache(maxsize=None)
+def seam_fold_data(case):
+    """(t, Wc, Bc, fp64 reference [B, Fe, k H, k W]) of a folded seam case from tests/_convt_fold_ref.py's integer inputs, with the
+    exactness conditions of tests/test_convt_fold_gpu.py: every composed weight, class bias, intermediate and result an fp16 integer."""
+    import _convt_fold_ref as R
+    k, Cin, Fe, B, H, W = case
+    t, wt, bt, wr = R.exact_inputs(k, Cin, Fe, B, H, W, seed=1000 * k + Cin + Fe + 7 * H + W)
+    ref = R.unfused(t, wt, bt, wr, k)
+    Wc, Bc = R.compose(wt, bt, wr)
+    bound = F.conv_transpose2d(t.abs(), wt.abs(), bt.abs(), stride=k) * 27      # (each output sums at most 27 entries of the ConvTranspose's result)
+    assert_exact_safe_f16([bound], [F.conv_transpose2d(t, wt, bt, stride=k), R.pack(Wc), R.class_bias(Bc), ref])
+    return t, Wc, Bc, ref
+
+
+def fold_as_gemm(ref, k):
+    """[B, Fe, k H, k W] -> the folded GEMM's own [B H W, k k Fe] matrix (column = (py k + px) Fe + co)."""
+    B, Fe, kH, kW = ref.shape
+    H, W = kH // k, kW // k
+    return ref.reshape(B, Fe, H, k, W, k).permute(0, 2, 4, 3, 5, 1).reshape(B * H * W, k * k * Fe)
 
 
 # ================================================================================================ the fp16 attention kernels (attention.hip, temporal.hip)

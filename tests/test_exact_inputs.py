@@ -209,7 +209,7 @@ def test_dense16_case_is_exact_and_sensitive(case):
         assert M == 1 or N == 64 or len(set(sums.flatten().tolist())) > 1, "the partial sums tell column blocks and rows apart"
 
 
-@pytest.mark.parametrize("case", E.BROADCAST16_CASES + [E.walk16_case(256, N) for N in E.WALK16_N] + [E.split16_case(256)], ids=lambda c: "M%d-N%d-K%d" % c)
+@pytest.mark.parametrize("case", E.BROADCAST16_CASES + [E.walk16_case(256, N) for N in E.WALK16_N] + [E.split16_case(256), E.walk16_case(256, 2048)[:2] + (E.WALK16_BLOCKED_K,)], ids=lambda c: "M%d-N%d-K%d" % c)
 def test_walk16_and_broadcast_cases_are_exact_and_sensitive(case):
     """(The broadcast case uses row 0 of the same inputs; the row-split case is checked on sampled rows, as on the GPU.)"""
     M, N, K = case
@@ -229,7 +229,7 @@ def test_walk16_and_broadcast_cases_are_exact_and_sensitive(case):
     assert not torch.equal(lin[:, :256], lin[:, 256:512]) if N >= 512 else True
 
 
-@pytest.mark.parametrize("case", E.PATCH16_CASES, ids=lambda c: "fr%d-P%d-N%d-K%d-ldc%d" % c)
+@pytest.mark.parametrize("case", E.PATCH16_CASES + E.SEAM_PATCH16_CASES, ids=lambda c: "fr%d-P%d-N%d-K%d-ldc%d" % c)
 def test_patch16_case_is_exact_and_sensitive(case):
     fr, P, N, K, ldc = case
     inp = E.patch16_inputs(case)
@@ -245,7 +245,7 @@ def test_patch16_case_is_exact_and_sensitive(case):
 
 
 @pytest.mark.parametrize("k", E.CONVT_K)
-@pytest.mark.parametrize("case", E.CONVT16_CASES, ids=lambda c: "B%d-%dx%d-C%d-Cp%d" % c)
+@pytest.mark.parametrize("case", E.CONVT16_CASES + E.SEAM_CONVT16_CASES, ids=lambda c: "B%d-%dx%d-C%d-Cp%d" % c)
 def test_convt16_case_is_exact_and_sensitive(case, k):
     B, h, w, C, Cp = case
     inp = E.convt16_inputs(case, k)
@@ -262,7 +262,7 @@ def test_convt16_case_is_exact_and_sensitive(case, k):
     differs(last_segments_swapped(ref), ref, "the last two 8-channel segments swapped")
 
 
-@pytest.mark.parametrize("case", E.CONV16_CASES, ids=E.conv16_id)
+@pytest.mark.parametrize("case", E.CONV16_CASES + E.SEAM_CONV16_CASES, ids=E.conv16_id)
 def test_conv16_case_is_exact_and_sensitive(case):
     B, H, W, Cin, Cout, stride, relu_in, ldc = case
     assert Cin % 64 == 0 and Cout % 8 == 0 and ldc % 8 == 0 and ldc >= Cout
@@ -326,6 +326,220 @@ def test_f16_helpers_refuse_what_they_should():
     assert bool(torch.tensor([E.SENTINEL16_BITS], dtype=torch.int16).view(F16).isnan().all()), "the fp16 sentinel is a NaN"
     from video_depth_anything_amd import _lib
     assert all(getattr(_lib, "EPI_" + k) == v for k, v in E.EPI.items()) and len(E.EPI) == 13
+    assert _lib.EPI_CONVT_FOLD_F16 == E.EPI_CONVT_FOLD_F16
+
+
+# ================================================================================================ tile seams: a persistent workgroup's later tiles
+# tests/test_kernels_f16_edges_gpu.py runs the seam cases of tests/_exact.py under vda_set_max_wgs(8 or 16). Here, without a GPU: the
+# walk model says of every case what it is there for (two full rounds and a partial one, the partial row tile in a later round, ...),
+# the planner gives every built large tile its launches, the exactness preconditions hold, and a tile of round >= 1 computed with
+# something its workgroup's PREVIOUS tile left behind - bias, residual / statistics / pos rows, the first K step's A or W rows, the
+# conv row origin, the column of an unrotated fold round - or without its second K step differs from the reference inside that tile.
+@pytest.fixture(scope="module")
+def L():
+    from video_depth_anything_amd import _lib
+    yield _lib
+    _lib.lib.vda_gemm_set_variant(-1)
+
+
+def test_tile_walk_model():
+    """The restatement against hand-walked launches: 19 tiles on 8 workgroups, one column tile (dealt: the last round's three tiles go
+    to XCDs 0, 1, 2); 21 tiles in three columns (plain: XCDs 0..4); 36 tiles in two columns on 16 (dealt by row panel); the folded
+    rotation is a bijection of every round's tiles and moves round 1 by FOLD_ROT columns."""
+    w = E.tile_walk(19 * 256 - 37, 256, 256, 256, 8)
+    assert (w["full_rounds"], w["rem"], w["deal_last"]) == (2, 3, True) and w["tiles"] == [[b, 8 + b] + ([16 + b] if b < 3 else []) for b in range(8)]
+    w = E.tile_walk(7 * 256 - 37, 520, 256, 256, 8)
+    assert (w["nbn"], w["full_rounds"], w["rem"], w["deal_last"]) == (3, 2, 5, False) and w["tiles"][4] == [4, 12, 20] and w["tiles"][5] == [5, 13]
+    w = E.tile_walk(18 * 256 - 37, 264, 256, 256, 16)
+    assert (w["per_xcd"], w["rem"], w["deal_last"]) == (2, 4, True)
+    assert [len(m) for m in w["tiles"]] == [3, 3] + [2] * 6 + [3, 3] + [2] * 6 and w["tiles"][0] == [0, 16, 32] and w["tiles"][8] == [1, 17, 33] and w["tiles"][1] == [2, 18, 34]
+    for nbn in (2, 4):
+        plain, fold = E.tile_walk(2400, nbn * 256, 256, 256, 8), E.tile_walk(2400, nbn * 256, 256, 256, 8, fold=True)
+        for r in range(3):
+            a, b = [m[r] for m in plain["tiles"] if len(m) > r], [m[r] for m in fold["tiles"] if len(m) > r]
+            assert sorted(a) == sorted(b) and (a == b) == (r * E.FOLD_ROT % nbn == 0 or r == 0)
+        assert fold["tiles"][0][1] == 8 + E.FOLD_ROT % nbn
+
+
+@functools.lru_cache(maxsize=None)
+def seam_dense(case):
+    inp = E.dense16_inputs(case)
+    return inp, E.dense16_check(inp), dbl(inp)
+
+
+def seam_index(w, a, b):
+    """Rows / columns of tile b, and those that tile a's origin gives the same places of the tile (clamped as the kernels clamp)."""
+    r0, r1, c0, c1 = E.tile_box(w, b)
+    p0, _, q0, _ = E.tile_box(w, a)
+    return slice(r0, r1), slice(c0, c1), (p0 + torch.arange(r1 - r0)).clamp_max(w["M"] - 1), (q0 + torch.arange(c1 - c0)).clamp_max(w["N"] - 1)
+
+
+@pytest.mark.parametrize("spec", E.SEAM16_SPECS, ids=E.seam16_id)
+def test_seam16_case_is_exact_and_sensitive(L, spec):
+    bm, bn, per_cu, cap, case = spec
+    M, N, K, lda, ldc = case
+    w = E.assert_seam16(case, bm, bn, per_cu * cap)
+    # the planner: every epilogue some family builds on this tile reaches it on this case under some forced variant
+    launches = E.seam16_launches(L, spec)
+    built = {e for e in E.dense16_epis(case) if any(L.lib.vda_gemm_built(fam, bm, bn, per_cu, 0, E.EPI[E.EPI_OF[e]]) for fam in (L.FAM_256, L.FAM_256S, L.FAM_8P))}
+    assert {e for _, e, _, _ in launches} == built and built, sorted(built - {e for _, e, _, _ in launches})
+    assert all(fam == L.FAM_8P for _, _, fam, dyn in launches if dyn)
+    assert any(dyn for *_, dyn in launches) == bool(L.lib.vda_gemm_built(L.FAM_8P, bm, bn, per_cu, 0, 0))
+    inp, ref, d = seam_dense(case)                       # (dense16_check: both exactness conditions for every exact epilogue)
+    assert all(is_f16(v) for v in inp.values())
+    Wf, c1, c2 = E.fold_ln(d)
+    A, W, lin = d["A"], d["W"], ref["bias_f16"]
+    pairs = E.seam_pairs(w)
+    assert len(pairs) == w["nwg"] + w["rem"]
+    nbn, seen_col = w["nbn"], False
+    for a, b in pairs:
+        rows, cols, prow, pcol = seam_index(w, a, b)
+        what = f"tile {b} after tile {a}"
+        assert a // nbn != b // nbn, "every seam changes the row panel"
+        blk = lin[rows, cols]
+        # rows: residual, (mean, rstd) and pos rows of the previous tile
+        assert not torch.equal(d["res"][rows, cols], d["res"][prow][:, cols]) and not torch.equal(d["mean"][rows], d["mean"][prow]) and not torch.equal(d["rstd"][rows], d["rstd"][prow])
+        differs(blk + d["res"][prow][:, cols], ref["res"][rows, cols], f"{what}: the previous tile's residual rows")
+        differs(d["res"][prow][:, cols] + d["gamma"][cols] * blk, ref["scale_res_in_place_gamma"][rows, cols], f"{what}: the previous tile's residual rows (LayerScale)")
+        ln = lambda mean, rstd, k1, k2: rstd[:, None] * (A[rows] @ Wf[cols].t() - mean[:, None] * k1) + k2      # noqa: E731
+        assert torch.equal(ln(d["mean"][rows], d["rstd"][rows], c1[cols], c2[cols]), ref["ln_bias"][rows, cols])
+        differs(ln(d["mean"][prow], d["rstd"][rows], c1[cols], c2[cols]), ref["ln_bias"][rows, cols], f"{what}: the previous tile's mean rows")
+        differs(ln(d["mean"][rows], d["rstd"][prow], c1[cols], c2[cols]), ref["ln_bias"][rows, cols], f"{what}: the previous tile's rstd rows")
+        if "split" in ref:
+            stream = lambda res, res2: res + res2 + d["gamma"][cols] * blk      # noqa: E731
+            differs(stream(d["res"][prow][:, cols], d["res2"][rows, cols]), ref["split"][rows, cols], f"{what}: the previous tile's hi plane rows")
+            differs(stream(d["res"][rows, cols], d["res2"][prow][:, cols]), ref["split"][rows, cols], f"{what}: the previous tile's lo plane rows")
+            differs(ref["split"][rows, cols] - d["mean"][prow][:, None], ref["split_pos"][rows, cols], f"{what}: the previous tile's pos rows")
+        # K steps: the first one from the previous tile's A rows, the second one missing
+        differs(blk + (A[prow, :64] - A[rows, :64]) @ W[cols, :64].t(), blk, f"{what}: K step 0 from the previous tile's A rows")
+        differs(blk - A[rows, 64:128] @ W[cols, 64:128].t(), blk, f"{what}: K step 1 missing")
+        # columns: bias (c1, c2 of the LayerNorm-folded epilogues) and W rows of the previous tile, where the workgroup changes column
+        if a % nbn != b % nbn:
+            seen_col = True
+            assert not torch.equal(d["bias"][cols], d["bias"][pcol]) and not torch.equal(c2[cols], c2[pcol]) and not torch.equal(c1[cols], c1[pcol])
+            differs(blk - d["bias"][cols] + d["bias"][pcol], blk, f"{what}: the previous tile's bias")
+            differs(ln(d["mean"][rows], d["rstd"][rows], c1[pcol], c2[cols]), ref["ln_bias"][rows, cols], f"{what}: the previous tile's c1")
+            differs(ln(d["mean"][rows], d["rstd"][rows], c1[cols], c2[pcol]), ref["ln_bias"][rows, cols], f"{what}: the previous tile's c2")
+            differs(blk + A[rows, :64] @ (W[pcol, :64] - W[cols, :64]).t(), blk, f"{what}: K step 0 from the previous tile's W rows")
+    assert seen_col == (nbn > 1 and w["nwg"] % nbn != 0), "a workgroup changes its column tile at a seam exactly where nbn does not divide the grid"
+
+
+def test_seam16_specs_cover_what_is_stated(L):
+    """Every large dense tile in all three walk modes with both K-step counts; lda > K and ldc > N once per tile at least; the tiles are
+    the ones vda_gemm_built lists."""
+    built = {(bm, bn, pc) for fam in (1, 2, 3) for bm in (192, 256) for bn in (128, 256, 384) for pc in (1, 2) if any(L.lib.vda_gemm_built(fam, bm, bn, pc, 0, e) for e in range(13))}
+    assert built == set(E.SEAM16_TILES)
+    for tile in E.SEAM16_TILES:
+        mine = [s for s in E.SEAM16_SPECS if s[:3] == tile]
+        walks = [E.tile_walk(s[4][0], s[4][1], s[0], s[1], s[2] * s[3]) for s in mine]
+        assert {(w["nbn"], w["deal_last"]) for w in walks} == {(1, True), (3, False), (2, True)}
+        assert {s[4][2] // 64 for s in mine} == {5, 9}
+        assert any(s[4][3] > s[4][2] and s[4][4] > s[4][1] for s in mine)
+        assert any(s[4][1] % 64 == 0 for s in mine) and (tile[1] == 384 or any(s[4][1] % 64 == 8 for s in mine))
+
+
+def seam_walks(L, fields, variants, fold=False):
+    """{(bm, bn, nwg): walk} over the variants' launches of one conv / patch / ConvTranspose / folded seam case (E.pick_cap)."""
+    out = {}
+    for v in variants:
+        L.lib.vda_gemm_set_variant(v)
+        got = E.pick_cap(L, fields, fold)
+        if got is not None:
+            cap, r, w = got
+            assert w["ntiles"] > 2 * r.per_cu * cap
+            out[(r.family, r.bm, r.bn, w["nwg"])] = w
+    L.lib.vda_gemm_set_variant(-1)
+    return out
+
+
+@pytest.mark.parametrize("case", E.SEAM_CONV16_CASES[:-1], ids=E.conv16_id)
+def test_seam_conv16_case_reaches_the_seams(L, case):
+    """(Exactness and the tap / pad / K-step mistakes: test_conv16_case_is_exact_and_sensitive runs on these cases too.)"""
+    B, H, W, Cin, Cout, stride, relu_in, ldc = case
+    kw = E.conv16_kw(case)
+    M, hw = kw["M"], kw["M"] // B
+    walks = seam_walks(L, E.gemm16_fields(epi=E.EPI["BIAS_F16"], **kw), E.SEAM_CONV16_VARIANTS)
+    assert {k[:3] for k in walks} >= {(L.FAM_256, 256, 256), (L.FAM_256, 256, 128), (L.FAM_256S, 256, 256), (L.FAM_256S, 256, 128), (L.FAM_8P, 256, 256), (L.FAM_8P, 256, 128)}
+    inp = E.conv16_inputs(case)
+    lin = E.conv16_refs(dbl(inp), stride, relu_in)["bias_f16"].reshape(M, Cout)
+    bias = inp["bias"].double()
+    for key, w in walks.items():
+        later = {b for _, b in E.seam_pairs(w)}
+        cross = [b for b in later for f in range(1, B) if E.tile_box(w, b)[0] < f * hw < E.tile_box(w, b)[1]]
+        assert cross, f"{key}: no frame border inside a tile of round >= 1"
+        for a, b in E.seam_pairs(w):
+            rows, cols, prow, pcol = seam_index(w, a, b)
+            differs(lin[prow][:, cols], lin[rows, cols], f"{key} tile {b}: rows decoded with the (b, y, x) origin of tile {a}")
+            if a % w["nbn"] != b % w["nbn"]:
+                differs(lin[rows, cols] - bias[cols] + bias[pcol], lin[rows, cols], f"{key} tile {b}: the bias of tile {a}")
+
+
+def test_seam_c64_case(L):
+    """27 tiles of 8 x 32 on the 8 workgroups of vda_set_max_wgs(8): conv3x3_c64_kernel gives XCD x the tiles [27 x / 8, 27 (x + 1) / 8) -
+    three or four each, so both patch buffers and the residual prefetch are reused, by an odd and an even count."""
+    B, H, W, Cin, Cout, stride, relu_in, ldc = E.SEAM_C64_CASE
+    assert (Cin, stride) == (64, 1) and 32 < Cout <= 64
+    ntiles = B * -(-H // 8) * -(-W // 32)
+    shares = [ntiles * (x + 1) // 8 - ntiles * x // 8 for x in range(8)]
+    assert ntiles == 27 and sorted(set(shares)) == [3, 4]
+    L.lib.vda_gemm_set_variant(-1)
+    rc, recs = E.plan16(L, E.gemm16_fields(epi=E.EPI["RES_F16"], **E.conv16_kw(E.SEAM_C64_CASE)), ncu=8)
+    assert rc == 0 and L.launch_name(recs[0]) == "conv3x3_lds_kernel<2>"
+
+
+@pytest.mark.parametrize("case", E.SEAM_PATCH16_CASES, ids=lambda c: "fr%d-P%d-N%d-K%d-ldc%d" % c)
+def test_seam_patch16_case_reaches_the_seams(L, case):
+    fr, P, N, K, ldc = case
+    walks = seam_walks(L, E.gemm16_fields(epi=E.EPI["PATCH_F32"], **E.patch16_kw(case)), E.SEAM_CONV16_VARIANTS)
+    assert {k[0] for k in walks} == {L.FAM_256, L.FAM_256S, L.FAM_8P} and {k[1] for k in walks} == {256}
+    d = dbl(E.patch16_inputs(case))
+    ref = E.patch16_ref(d, P).reshape(fr * P, N)
+    lin = d["A"] @ d["W"].t() + d["bias"]
+    for key, w in walks.items():
+        for rnd in (1, 2):
+            tiles = [m[rnd] for m in w["tiles"] if len(m) > rnd]
+            assert any(E.tile_box(w, t)[0] % P != 0 and E.tile_box(w, t)[0] // P != (E.tile_box(w, t)[1] - 1) // P for t in tiles), f"{key}: no frame boundary inside a tile of round {rnd}"
+        for a, b in E.seam_pairs(w):
+            rows, cols, prow, pcol = seam_index(w, a, b)
+            m = torch.arange(rows.start, rows.stop)
+            assert torch.equal(lin[rows, cols] + d["pos"][1 + m % P][:, cols], ref[rows, cols])
+            differs(lin[rows, cols] + d["pos"][1 + prow % P][:, cols], ref[rows, cols], f"{key} tile {b}: the pos rows of tile {a}")
+
+
+@pytest.mark.parametrize("case,k", E.SEAM_CONVT16, ids=lambda c: "B%d-%dx%d-C%d-Cp%d" % c if isinstance(c, tuple) else "k%d" % c)
+def test_seam_convt16_case_reaches_the_seams(L, case, k):
+    B, h, w_, C, Cp = case
+    walks = seam_walks(L, E.gemm16_fields(epi=E.EPI["CONVT_F16"], **E.convt16_kw(case, k)), E.SEAM_CONV16_VARIANTS)
+    assert {key[0] for key in walks} == {L.FAM_256, L.FAM_256S, L.FAM_8P}
+    d = dbl(E.convt16_inputs(case, k))
+    ref = E.convt_ref(d["x"], d["w"], d["bias"], k)                              # [B, h k, w k, C]
+    G = ref.reshape(B, h, k, w_, k, C).permute(0, 1, 3, 2, 4, 5).reshape(B * h * w_, k * k, C)     # one row per input pixel: what a GEMM row scatters
+    for key, w in walks.items():
+        moves = [(a, b) for a, b in E.seam_pairs(w) if a // w["nbn"] != b // w["nbn"]]       # (16 column tiles on 8 workgroups: every other seam stays in its row panel)
+        assert len(moves) >= w["nwg"]
+        assert any(E.tile_box(w, b)[0] < f * h * w_ < E.tile_box(w, b)[1] for _, b in moves for f in range(1, B)), f"{key}: no frame border inside a tile of round >= 1"
+        for a, b in moves:
+            r0, r1, _, _ = E.tile_box(w, b)
+            p0 = E.tile_box(w, a)[0]
+            prow = (p0 + torch.arange(r1 - r0)).clamp_max(B * h * w_ - 1)
+            differs(G[prow], G[r0:r1], f"{key} tile {b}: scattered with the row map of tile {a}")
+
+
+@pytest.mark.parametrize("case", E.SEAM_FOLD_CASES, ids=lambda c: "k%d-Cin%d-Fe%d-B%d-%dx%d" % c)
+def test_seam_fold_case_reaches_the_seams(L, case):
+    k, Cin, Fe, B, H, W = case
+    f = E.fold_fields(case)
+    walks = seam_walks(L, f, (-1, 5), fold=True)
+    assert {key[:3] for key in walks} == {(L.FAM_8P, 256, 256)} and all(w["full_rounds"] >= 2 and w["nwg"] == 8 for w in walks.values())
+    w = next(iter(walks.values()))
+    plain = E.tile_walk(f["M"], f["N"], 256, 256, 8)
+    t, Wc, Bc, ref = E.seam_fold_data(case)
+    G = E.fold_as_gemm(ref, k)
+    moved = [(p, q) for mp, mq in zip(plain["tiles"], w["tiles"]) for p, q in list(zip(mp, mq))[1:] if p != q]
+    assert bool(moved) == (w["nbn"] > 1), "a rotated round moves tiles exactly where there is more than one column tile"
+    for p, q in moved:
+        (r0, r1, c0, c1), (_, _, u0, u1) = E.tile_box(w, q), E.tile_box(w, p)
+        differs(G[r0:r1, u0:u1], G[r0:r1, c0:c1], f"tile {q}: the column tile of the unrotated round ({p})")
 
 
 # ================================================================================================ the fp16 attention kernels' cases
@@ -635,7 +849,7 @@ def test_tailup_cases_run_the_kernel_they_are_listed_for():
     assert scales == {(0.0, 0.0), (0.5, 0.5), (0.25, 0.25), (0.5, 0.25), (1.0, 0.25), (1.0, 0.5), (2.0, 2.0), (1.5, 0.5)}
 
 
-@pytest.mark.parametrize("case,Cc", [(c, Cc) for c in E.TAILUP_CASES for Cc in E.TAILUP_C] + [(TAILUP_ALL[-1], 32)],
+@pytest.mark.parametrize("case,Cc", [(c, Cc) for c in E.TAILUP_CASES for Cc in E.TAILUP_C] + [(TAILUP_ALL[-1], 32), (E.SEAM_TAILUP_CASE, 32)],
                          ids=lambda v: E.tailup_id(v) if isinstance(v, tuple) else str(v))
 def test_tailup_case_is_exact_and_sensitive(case, Cc):
     B, h, w, H, W = case

@@ -25,7 +25,7 @@ import torch.nn.functional as F
 
 import _exact as E
 from _exact import check_sentinel, guarded, sentinel_out, sentinel_out_f16
-from test_kernels_f16_edges_gpu import L, close_finite, exact, h16  # noqa: F401  (L: fixture)
+from test_kernels_f16_edges_gpu import L, capped, close_finite, exact, h16  # noqa: F401  (L: fixture)
 from test_kernels_gpu import ops, rnd  # noqa: F401  (ops: fixture)
 
 pytestmark = pytest.mark.gpu
@@ -205,6 +205,15 @@ def test_depth_tail_dyadic_resize_more_tiles_than_compute_units(ops, L, variant)
     B, h, w, H, W = case
     assert B * -(-H // 16) * -(-W // 32) > ncu
     run_tailup(ops, L, case, 32, variant)
+
+
+def test_depth_tail_dyadic_resize_tile_seams(ops, L):
+    """The persistent loop's third and fourth tile: 27 tiles of 16 x 32 on the 8 workgroups of vda_set_max_wgs(8). (The test above keeps
+    covering the full grid, where a workgroup has two tiles at the most.)"""
+    B, h, w, H, W = case = E.SEAM_TAILUP_CASE
+    assert B * -(-H // 16) * -(-W // 32) >= 3 * 8 and E.tailup_kernel(case) == E.TAIL_KERNELS[2]
+    with capped(L, 8):
+        run_tailup(ops, L, case, 32, 0)
 
 
 # ---------------------------------------------------------------- vda_bilinear_nhwc_f16 / _f32 at dyadic scales
