@@ -609,6 +609,33 @@ size_t vda_deflate_out_bytes(size_t n);
 int vda_deflate_u8(const uint8_t* in, size_t n, int final, void* workspace, size_t workspace_bytes, uint8_t* out, size_t out_capacity,
                    long long* length, uint32_t* crcs, vda_stream_t stream);
 
+/* ---- OpenEXR scanline files, ZIP compression, one FLOAT channel, from float32 depth (video_depth_anything_amd/exr.py:
+ * encode_exr_numpy is the contract, byte for byte) ----
+ * depth: device float32, frame f's h * w pixels dense at depth + f * frame_stride (frame_stride counts floats). A file is
+ * header_bytes of header (the caller's: exr.exr_header; it depends on w and h only, 277 bytes for the channel Z) followed by the
+ * frame's PAYLOAD, which is what this call makes:
+ *   table    nb = ceil(h / 16) uint64: the position in the FILE of every block (so header_bytes is added)
+ *   blocks   block b: int32 y = 16 b, int32 dataSize, dataSize bytes. Its raw bytes are its min(16, h - 16 b) rows back to back,
+ *            L = 4 w rows bytes. OpenEXR's filter (even bytes, then odd bytes; then every byte but the first replaced by its
+ *            difference to its predecessor plus 128) gives f. f is cut into k = ceil(L / 16384) balanced chunks of
+ *            q = 64 ceil(L / (64 k)) bytes (the last shorter), each coded as vda_deflate_u8 codes a chunk (BFINAL on the block's
+ *            last, a sync flush behind the others); the zlib stream is 78 01, the chunks, the Adler-32 of f big-endian. If that
+ *            stream is strictly shorter than L it is the block's data, otherwise the raw rows are (dataSize = L).
+ * payload: the frames' payloads back to back; offsets: device int64 [frames + 1], frame f's payload is bytes offsets[f] ..
+ * offsets[f + 1] of `payload`. Deterministic. Only the gathered bytes of `depth` are read, any bit pattern is data.
+ *   vda_exr_payload_bytes(frames, h, w)   = frames * (8 nb + 8 nb + 4 w h): every block raw; the capacity `payload` needs
+ *   vda_exr_workspace_bytes(frames, h, w) = chunks * 16400 + 2 up16(4 chunks) + 16 chunks + 2 up16(4 blocks) + up16(8 blocks), with
+ *                                           blocks = frames * nb and chunks = the k of all blocks; device bytes, contents irrelevant
+ *   (both 0 for a size < 1, h or w > 65535 - a block is then below 2^22 bytes and 256 chunks, which the kernels' 32-bit chunk
+ *   arithmetic holds - or more than 2^31 - 1 chunks in all)
+ * Refused before any launch: a null depth, workspace, payload or offsets; frames, h or w < 1; sizes above the cap; frame_stride <
+ * h * w; header_bytes < 0; depth not 4-byte, workspace not 16-byte or offsets not 8-byte aligned; workspace_bytes or
+ * payload_capacity below the bound. Four launches on `stream` (encode, blocks, offsets, pack), no allocation, no synchronisation. */
+size_t vda_exr_workspace_bytes(int frames, int h, int w);
+size_t vda_exr_payload_bytes(int frames, int h, int w);
+int vda_exr_zip_f32(const float* depth, int frames, int h, int w, long long frame_stride, long long header_bytes, void* workspace,
+                    size_t workspace_bytes, uint8_t* payload, size_t payload_capacity, long long* offsets, vda_stream_t stream);
+
 /* ---- validation losses on the device (the reference's utils/loss_MiDas.py and utils/loss.py: Loss_ssi, Loss_tgm) ---------------
  * What train.py's validation pass ranks checkpoints by, as inference-time arithmetic (no gradients). pred, y: dense fp32
  * [nframes, px] (nframes = B * N, px = H * W); mask: bytes of the same shape, 0 = excluded, or NULL for all valid. Every fp32

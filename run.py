@@ -8,7 +8,8 @@ frames larger than `--max_res` are scaled down on the device with cv2's 8-bit ar
 block at a time (utils.dc_utils.read_video_blocks), so an HD .avi or .npy keeps its bounded memory; the
 visualisations are mp4 through imageio when present and animated GIFs otherwise, or with `--mjpeg` Motion-JPEG .avi files that
 need no encoder library (the JPEG coding runs on the device too, csrc/mjpeg.hip); `--save_npz` adds <name>_depths.npz
-(key `depths`, read with np.load; on a GPU its deflate streams are made on the device, csrc/deflate.hip, instead of by zlib on one core).
+(key `depths`, read with np.load; on a GPU its deflate streams are made on the device, csrc/deflate.hip, instead of by zlib on one core); `--save_exr` adds <name>_depths_exr/frame_00000.exr ... (OpenEXR, channel Z, float32, ZIP; on a GPU the
+files are made on the device, csrc/exr.hip, and no OpenEXR library is needed; video_depth_anything_amd.exr.read_exr reads them).
 <name>_vis carries the reference's colours: depth is mapped through matplotlib's 256-entry inferno table, which ships in
 video_depth_anything_amd/visualize.py (not through the polynomial fit utils/dc_utils.py keeps as save_video's default), and on a
 GPU the mapping itself runs on the device (csrc/visualize.hip) - the same bytes as on the host.
@@ -28,7 +29,7 @@ import numpy as np
 import torch
 
 from utils.dc_utils import read_video_blocks, read_video_frames, reads_in_blocks, save_video
-from video_depth_anything_amd import deflate, mjpeg
+from video_depth_anything_amd import deflate, exr, mjpeg
 from video_depth_anything_amd.scale import scaled_size
 from video_depth_anything_amd.visualize import inferno_table
 from video_depth_anything_amd.video_depth import MetricVideoDepthAnything, VideoDepthAnything
@@ -126,6 +127,30 @@ def save_depths_npz(path, depths, device):
     return deflate.savez_compressed(path, device=device, depths=depths)
 
 
+def save_depths_exr(exr_dir, depths, device):
+    """<name>_depths_exr/frame_00000.exr ...: one OpenEXR file per frame, channel Z, float32, ZIP (run.py:64-76). On a device the ZIP
+    blocks are made there (csrc/exr.hip), no OpenEXR library needed; `depths` may be the memory map --stream left, which is then read
+    a block of frames at a time. Without a device: the OpenEXR library when it imports, as the reference; otherwise the host writer of
+    exr.py, whose deflate streams are zlib's."""
+    if device is None:
+        try:
+            import Imath
+            import OpenEXR
+        except ImportError:
+            return exr.write_exr_sequence(depths, exr_dir, device=None)
+        os.makedirs(exr_dir, exist_ok=True)
+        paths = []
+        for i, depth in enumerate(depths):
+            header = OpenEXR.Header(depth.shape[1], depth.shape[0])
+            header["channels"] = {"Z": Imath.Channel(Imath.PixelType(Imath.PixelType.FLOAT))}
+            paths.append(f"{exr_dir}/frame_{i:05d}.exr")
+            f = OpenEXR.OutputFile(paths[-1], header)
+            f.writePixels({"Z": np.ascontiguousarray(depth, np.float32).tobytes()})
+            f.close()
+        return paths
+    return exr.write_exr_sequence(depths, exr_dir, device=device)
+
+
 if __name__ == '__main__':
     parser = argparse.ArgumentParser(description='Video Depth Anything (MI355X)')
     parser.add_argument('--input_video', type=str, default='./assets/example_videos/davis_rollercoaster.mp4')
@@ -205,14 +230,6 @@ if __name__ == '__main__':
     if args.save_npz:
         save_depths_npz(stem + '_depths.npz', depths, io_device)
     if args.save_exr:
-        import Imath
-        import OpenEXR
-        exr_dir = stem + '_depths_exr'
-        os.makedirs(exr_dir, exist_ok=True)
-        for i, depth in enumerate(depths):
-            header = OpenEXR.Header(depth.shape[1], depth.shape[0])
-            header["channels"] = {"Z": Imath.Channel(Imath.PixelType(Imath.PixelType.FLOAT))}
-            f = OpenEXR.OutputFile(f"{exr_dir}/frame_{i:05d}.exr", header)
-            f.writePixels({"Z": depth.tobytes()})
-            f.close()
-    print(f"{depths.shape[0]} frames -> {vis_path}" + (f", {stem}_depths.npz" if args.save_npz else ""))
+        save_depths_exr(stem + '_depths_exr', depths, io_device)
+    print(f"{depths.shape[0]} frames -> {vis_path}" + (f", {stem}_depths.npz" if args.save_npz else "")
+          + (f", {stem}_depths_exr/" if args.save_exr else ""))

@@ -138,6 +138,9 @@ SIGNATURES = {
     "vda_deflate_workspace_bytes": (C.c_size_t, [C.c_size_t]),
     "vda_deflate_out_bytes": (C.c_size_t, [C.c_size_t]),
     "vda_deflate_u8": (_i, [_vp, C.c_size_t, _i, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp]),
+    "vda_exr_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
+    "vda_exr_payload_bytes": (C.c_size_t, [_i, _i, _i]),
+    "vda_exr_zip_f32": (_i, [_vp, _i, _i, _i, _ll, _ll, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp]),
     "vda_loss_lsq_partial": (_i, [_vp, _vp, _vp, _i, _ll, _i, _vp, _vp, _i, _vp]),
     "vda_loss_lsq_finish": (_i, [_vp, _i, _i, _i, C.c_double, _vp, _vp, _vp]),
     "vda_loss_median": (_i, [_vp, _vp, _vp, _i, _ll, _vp, _vp]),

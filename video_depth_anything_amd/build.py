@@ -26,8 +26,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=f
 # the product are each rounded once. visualize.hip restates numpy's float32 (d - d_min) / span * 255: three roundings.
 # losses.hip restates torch's fp64 s * d + t - y (three roundings) and its centred sums. resize_u8.hip, cv2's 8-bit resize, is integer
 # arithmetic behind resize.hip's fp64 source coordinate (d + 0.5) * scale - 0.5: a product and a difference, each rounded.
-# (mjpeg.hip and mjpeg_decode.hip, the JPEG encoder and decoder, and deflate.hip, the deflate encoder, are integer arithmetic from
-# end to end: they reproduce their host twins under the default flags.)
+# (mjpeg.hip and mjpeg_decode.hip, the JPEG encoder and decoder, deflate.hip, the deflate encoder, and exr.hip, the OpenEXR ZIP
+# writer around it, are integer arithmetic from end to end: they reproduce their host twins under the default flags.)
 PER_FILE = {"stitch.hip": ["-ffp-contract=off"], "eval.hip": ["-ffp-contract=off"], "tae.hip": ["-ffp-contract=off"],
             "resize.hip": ["-ffp-contract=off"], "pointcloud.hip": ["-ffp-contract=off"], "visualize.hip": ["-ffp-contract=off"],
             "losses.hip": ["-ffp-contract=off"], "resize_u8.hip": ["-ffp-contract=off"]}

@@ -632,6 +632,35 @@ def deflate(data, final, workspace, out, length, crcs):
                              _stream(out)), "vda_deflate_u8")
 
 
+# ---- OpenEXR ZIP files from float32 depth (csrc/exr.hip; exr.py is the contract and owns the header and the files) --------------
+def exr_workspace_bytes(frames, h, w):
+    return int(lib.vda_exr_workspace_bytes(frames, h, w))
+
+
+def exr_payload_bytes(frames, h, w):
+    """The capacity exr_zip's `payload` needs: every block raw, frames * (16 ceil(h / 16) + 4 w h)."""
+    return int(lib.vda_exr_payload_bytes(frames, h, w))
+
+
+def exr_zip(depth, header_bytes, workspace, payload, offsets):
+    """depth fp32 [frames, h, w] whose frames are dense (any stride between frames, any dword offset of a larger tensor) -> payload
+    uint8 [>= exr_payload_bytes]: per frame the offset table and the blocks of an OpenEXR ZIP file whose header is `header_bytes` long;
+    offsets int64 [frames + 1]: frame f's payload is payload[offsets[f]:offsets[f + 1]]. workspace: exr_workspace_bytes bytes."""
+    if not isinstance(depth, torch.Tensor) or not depth.is_cuda or depth.dtype != F32 or depth.dim() != 3 or depth.numel() == 0:
+        raise ValueError(f"exr_zip: depth must be a cuda fp32 tensor [frames, h, w], got {getattr(depth, 'dtype', type(depth))} "
+                         f"{tuple(getattr(depth, 'shape', ()))} {getattr(depth, 'device', None)}")
+    n, h, w = depth.shape
+    if depth.stride(2) != 1 or depth.stride(1) != w or (n > 1 and depth.stride(0) < h * w):
+        raise ValueError(f"exr_zip: the frames of depth must be dense, got strides {depth.stride()} for {tuple(depth.shape)}")
+    _req(workspace, torch.uint8, "workspace"), _req(payload, torch.uint8, "payload"), _req(offsets, torch.int64, "offsets")
+    if offsets.numel() < n + 1:
+        raise ValueError(f"exr_zip: offsets holds {offsets.numel()} entries, needs {n + 1}")
+    if len({t.device for t in (depth, workspace, payload, offsets)}) != 1:
+        raise ValueError("exr_zip: the operands live on different devices")
+    check(lib.vda_exr_zip_f32(_p(depth), n, h, w, depth.stride(0) if n > 1 else h * w, int(header_bytes), _p(workspace), workspace.numel(),
+                              _p(payload), payload.numel(), _p(offsets), _stream(payload)), "vda_exr_zip_f32")
+
+
 # ---- validation losses (csrc/losses.hip; losses.py lays the buffers out) --------------------------------------------------------
 LOSS_STATS = 8               # doubles per frame in `stats` (include/vda.h)
 
