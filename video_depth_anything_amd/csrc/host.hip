@@ -12,6 +12,7 @@
 // vda_forward (layouts, the resampled pos-embed and the fp32 weight pack are created the first time a shape / precision is
 // seen), so a steady-state forward is graph-capturable.
 #include "vda_common.h"
+#include "weight_table.h"
 #include <string.h>
 #include <algorithm>
 #include <exception>
@@ -23,10 +24,8 @@
 
 namespace {
 
-constexpr int PATCH = 14, POS_GRID = 37, KPATCH = 640, GN_GROUPS = 32, TEMPORAL_HEADS = 8;
+constexpr int GN_GROUPS = 32, TEMPORAL_HEADS = 8;      // (PATCH, POS_GRID, KPATCH, pad64: weight_table.h)
 constexpr float ENC_LN_EPS = 1e-6f, GN_EPS = 1e-6f, TMP_LN_EPS = 1e-5f;
-
-inline int pad64(int c) { return (c + 63) / 64 * 64; }
 
 #define VDA_TRY(expr)            \
     do {                         \
@@ -116,9 +115,7 @@ __global__ void __launch_bounds__(256) poison_on_overflow_kernel(const int* __re
 }
 
 struct Raw {
-    float* d = nullptr;
-    std::vector<int64_t> dims;
-    size_t n = 0;
+    float* d = nullptr;       // the tensor as loaded (its shape: vda_model::spec)
 };
 
 // Optional per-launch timing of the GEMM / conv launches of vda_forward (bench.py's roofline): every `every`-th launch of each
@@ -149,7 +146,8 @@ struct Layout {
 struct vda_model {
     vda_config cfg;
     int device = 0;
-    std::map<std::string, std::vector<int64_t>> spec;
+    std::vector<WEntry> table;                // csrc/weight_table.h: every checkpoint tensor and how it is packed
+    std::map<std::string, std::vector<int64_t>> spec;      // its name -> shape
     std::map<std::string, Raw> raw;
     std::map<std::string, void*> mat[2];      // packed matrices per precision
     std::map<std::string, float*> vec;        // fp32 vectors (biases, affine, LayerScale, PE), shared by both precisions
@@ -211,115 +209,6 @@ struct vda_model {
 
 namespace {
 
-using Spec = std::map<std::string, std::vector<int64_t>>;
-
-// Checkpoint inventory (name -> shape) of the flat fp32 state dict run.py:46 loads: dinov2.py:106-168, dpt.py:60-124,
-// util/blocks.py:20-32,52-58,124-129, motion_module/motion_module.py:84-100,141-161,194, motion_module/attention.py:81-91,333,374.
-void build_spec(const vda_config& c, Spec& s) {
-    const int64_t D = c.embed_dim, F = c.features;
-    const int64_t oc[4] = {c.out_channels[0], c.out_channels[1], c.out_channels[2], c.out_channels[3]};
-    auto put = [&](const std::string& k, std::vector<int64_t> v) { s[k] = std::move(v); };
-    const std::string p = "pretrained.";
-    put(p + "cls_token", {1, 1, D});
-    put(p + "pos_embed", {1, POS_GRID * POS_GRID + 1, D});
-    put(p + "mask_token", {1, D});
-    put(p + "patch_embed.proj.weight", {D, 3, PATCH, PATCH});
-    put(p + "patch_embed.proj.bias", {D});
-    for (int i = 0; i < c.depth; ++i) {
-        const std::string b = p + "blocks." + std::to_string(i) + ".";
-        put(b + "norm1.weight", {D});
-        put(b + "norm1.bias", {D});
-        put(b + "attn.qkv.weight", {3 * D, D});
-        put(b + "attn.qkv.bias", {3 * D});
-        put(b + "attn.proj.weight", {D, D});
-        put(b + "attn.proj.bias", {D});
-        put(b + "ls1.gamma", {D});
-        put(b + "norm2.weight", {D});
-        put(b + "norm2.bias", {D});
-        put(b + "mlp.fc1.weight", {4 * D, D});
-        put(b + "mlp.fc1.bias", {4 * D});
-        put(b + "mlp.fc2.weight", {D, 4 * D});
-        put(b + "mlp.fc2.bias", {D});
-        put(b + "ls2.gamma", {D});
-    }
-    put(p + "norm.weight", {D});
-    put(p + "norm.bias", {D});
-    const std::string h = "head.";
-    for (int i = 0; i < 4; ++i) {
-        put(h + "projects." + std::to_string(i) + ".weight", {oc[i], D, 1, 1});
-        put(h + "projects." + std::to_string(i) + ".bias", {oc[i]});
-    }
-    put(h + "resize_layers.0.weight", {oc[0], oc[0], 4, 4});
-    put(h + "resize_layers.0.bias", {oc[0]});
-    put(h + "resize_layers.1.weight", {oc[1], oc[1], 2, 2});
-    put(h + "resize_layers.1.bias", {oc[1]});
-    put(h + "resize_layers.3.weight", {oc[3], oc[3], 3, 3});
-    put(h + "resize_layers.3.bias", {oc[3]});
-    if (c.use_clstoken)                                             // dpt.py:92-98
-        for (int i = 0; i < 4; ++i) {
-            put(h + "readout_projects." + std::to_string(i) + ".0.weight", {D, 2 * D});
-            put(h + "readout_projects." + std::to_string(i) + ".0.bias", {D});
-        }
-    const std::string sc = h + "scratch.";
-    for (int i = 0; i < 4; ++i) put(sc + "layer" + std::to_string(i + 1) + "_rn.weight", {F, oc[i], 3, 3});
-    for (int i = 1; i <= 4; ++i) {
-        const std::string r = sc + "refinenet" + std::to_string(i) + ".";
-        put(r + "out_conv.weight", {F, F, 1, 1});
-        put(r + "out_conv.bias", {F});
-        for (int u = 1; u <= 2; ++u)
-            for (int cc = 1; cc <= 2; ++cc) {
-                const std::string k = r + "resConfUnit" + std::to_string(u) + ".conv" + std::to_string(cc);
-                put(k + ".weight", {F, F, 3, 3});
-                put(k + ".bias", {F});
-            }
-        if (c.use_bn)                                                // util/blocks.py:60-62 (state_dict keys of nn.BatchNorm2d)
-            for (int u = 1; u <= 2; ++u)
-                for (int cc = 1; cc <= 2; ++cc) {
-                    const std::string k = r + "resConfUnit" + std::to_string(u) + ".bn" + std::to_string(cc) + ".";
-                    put(k + "weight", {F});
-                    put(k + "bias", {F});
-                    put(k + "running_mean", {F});
-                    put(k + "running_var", {F});
-                    put(k + "num_batches_tracked", {});
-                }
-    }
-    put(sc + "output_conv1.weight", {F / 2, F, 3, 3});
-    put(sc + "output_conv1.bias", {F / 2});
-    put(sc + "output_conv2.0.weight", {32, F / 2, 3, 3});
-    put(sc + "output_conv2.0.bias", {32});
-    put(sc + "output_conv2.2.weight", {1, 32, 1, 1});
-    put(sc + "output_conv2.2.bias", {1});
-    const int64_t tc[4] = {oc[2], oc[3], F, F};                     // dpt_temporal.py:42-51
-    for (int m = 0; m < 4; ++m) {
-        const int64_t C = tc[m];
-        const std::string t = h + "motion_modules." + std::to_string(m) + ".temporal_transformer.";
-        put(t + "norm.weight", {C});
-        put(t + "norm.bias", {C});
-        put(t + "proj_in.weight", {C, C});
-        put(t + "proj_in.bias", {C});
-        const std::string tb = t + "transformer_blocks.0.";
-        for (int a = 0; a < 2; ++a) {
-            const std::string ab = tb + "attention_blocks." + std::to_string(a) + ".";
-            put(ab + "to_q.weight", {C, C});
-            put(ab + "to_k.weight", {C, C});
-            put(ab + "to_v.weight", {C, C});
-            put(ab + "to_out.0.weight", {C, C});
-            put(ab + "to_out.0.bias", {C});
-            if (!c.pe_rope) put(ab + "pos_encoder.pe", {1, c.num_frames, C});     // (rope: freqs_cis is not a buffer, motion_module.py:221-224)
-            put(tb + "norms." + std::to_string(a) + ".weight", {C});
-            put(tb + "norms." + std::to_string(a) + ".bias", {C});
-        }
-        put(tb + "ff.net.0.proj.weight", {8 * C, C});
-        put(tb + "ff.net.0.proj.bias", {8 * C});
-        put(tb + "ff.net.2.weight", {C, 4 * C});
-        put(tb + "ff.net.2.bias", {C});
-        put(tb + "ff_norm.weight", {C});
-        put(tb + "ff_norm.bias", {C});
-        put(t + "proj_out.weight", {C, C});
-        put(t + "proj_out.bias", {C});
-    }
-}
-
 int dev_alloc(vda_model* h, size_t bytes, void** out) {
     void* p = nullptr;
     VDA_HIP(hipMalloc(&p, bytes < 256 ? 256 : bytes));
@@ -352,79 +241,95 @@ __global__ void __launch_bounds__(256) fold_bn_kernel(const float* __restrict__ 
     }
 }
 
-// ---- packing of one precision (T = h16 / float); vectors are packed once with the first precision
+// ---- packing of one precision (T = h16 / float); vectors are packed once with the first precision (`vecs`)
+// One row of the table (csrc/weight_table.h) from its fp32 source; the first W_ROWS tensor of a key allocates the key's whole block.
 template <typename T>
-int pack_all(vda_model* h, int prec) {
+int pack_entry(vda_model* h, int prec, bool vecs, const WEntry& e, const float* src) {
+    if (e.kind == W_NONE || (e.is_vec() && !vecs)) return 0;
+    hipStream_t s = nullptr;
+    const size_t elems = e.packed_elems();
+    void* d = nullptr;
+    const auto shared = h->mat[prec].find(e.key);
+    if (e.kind == W_ROWS && shared != h->mat[prec].end()) d = shared->second;
+    else VDA_TRY(dev_alloc(h, elems * (e.is_vec() ? sizeof(float) : sizeof(T)), &d));
+    if (e.is_vec()) h->vec[e.key] = (float*)d;
+    else h->mat[prec][e.key] = d;
+    const int N = e.N(), K = e.K();
+    const dim3 grid(grid_for(e.kind == W_ROWS ? (size_t)N * e.kpad : elems)), block(256);
+    switch (e.kind) {
+    case W_NONE: break;
+    case W_VEC: hipLaunchKernelGGL((pack_matrix_kernel<float>), grid, block, 0, s, src, (float*)d, 1, K, 1, e.kpad); break;
+    case W_MAT: hipLaunchKernelGGL((pack_matrix_kernel<T>), grid, block, 0, s, src, (T*)d, N, K, e.npad, e.kpad); break;
+    case W_ROWS: hipLaunchKernelGGL((pack_matrix_kernel<T>), grid, block, 0, s, src, (T*)d + (size_t)e.row * e.kpad, N, K, N, e.kpad); break;
+    case W_CONV3: hipLaunchKernelGGL((pack_conv3x3_kernel<T>), grid, block, 0, s, src, (T*)d, N, (int)e.shape[1], e.npad, e.kpad); break;
+    case W_CONVT: hipLaunchKernelGGL((pack_convt_kernel<T>), grid, block, 0, s, src, (T*)d, N, (int)e.shape[1], (int)e.shape[2], e.npad); break;
+    case W_CONVT_BIAS: hipLaunchKernelGGL(expand_convt_bias_kernel, grid, block, 0, s, src, (float*)d, K, e.npad / e.kpad, e.kpad); break;
+    case W_GEGLU: hipLaunchKernelGGL((pack_geglu_kernel<T>), grid, block, 0, s, src, (T*)d, N / 2, K); break;
+    case W_GEGLU_BIAS: hipLaunchKernelGGL((pack_geglu_kernel<float>), grid, block, 0, s, src, (float*)d, K / 2, 1); break;
+    }
+    return 0;
+}
+
+// The weights made of SEVERAL tensors, behind the table's rows: the fp16 path's folds (LayerNorm into the Linear behind it, fc2 permuted
+// for the fused MLP, options oc1_mix and convt_fold) and, in both precisions, use_bn's BatchNorm folded into the resConfUnit convs.
+template <typename T>
+int pack_derived(vda_model* h, int prec, bool vecs) {
     const vda_config& c = h->cfg;
     hipStream_t s = nullptr;
     auto raw = [&](const std::string& k) -> const float* { return h->raw.at(k).d; };
-    auto mat = [&](const std::string& key, size_t elems, T** out) -> int {
-        void* p = nullptr;
-        VDA_TRY(dev_alloc(h, elems * sizeof(T), &p));
-        h->mat[prec][key] = p;
-        *out = (T*)p;
-        return 0;
-    };
-    auto lin = [&](const std::string& key, const std::string& name, int N, int K, int Npad, int Kpad) -> int {
-        T* d = nullptr;
-        VDA_TRY(mat(key, (size_t)Npad * Kpad, &d));
-        hipLaunchKernelGGL((pack_matrix_kernel<T>), dim3(grid_for((size_t)Npad * Kpad)), dim3(256), 0, s, raw(name), d, N, K, Npad, Kpad);
-        return 0;
-    };
-    auto conv = [&](const std::string& key, const std::string& name, int Co, int Ci, int Copad, int Cipad) -> int {
-        T* d = nullptr;
-        VDA_TRY(mat(key, (size_t)Copad * 9 * Cipad, &d));
-        hipLaunchKernelGGL((pack_conv3x3_kernel<T>), dim3(grid_for((size_t)Copad * 9 * Cipad)), dim3(256), 0, s, raw(name), d, Co, Ci, Copad, Cipad);
-        return 0;
-    };
-    const bool vecs = h->vec.empty();
-    auto vecp = [&](const std::string& key, const std::string& name, int n, int npad) -> int {
-        if (!vecs) return 0;
-        void* p = nullptr;
-        VDA_TRY(dev_alloc(h, (size_t)npad * sizeof(float), &p));
-        h->vec[key] = (float*)p;
-        hipLaunchKernelGGL((pack_matrix_kernel<float>), dim3(grid_for(npad)), dim3(256), 0, s, raw(name), (float*)p, 1, n, 1, npad);
-        return 0;
-    };
-    const int D = c.embed_dim, Fe = c.features;
-    const int* oc = c.out_channels;
-    const int* ocp = h->ocp;
-    const int Fh = Fe / 2, Fhp = h->Fhp;
-    const std::string p = "pretrained.";
-    VDA_TRY(lin("patch.w", p + "patch_embed.proj.weight", D, 588, D, KPATCH));
-    VDA_TRY(vecp("patch.b", p + "patch_embed.proj.bias", D, D));
-    VDA_TRY(vecp("cls", p + "cls_token", D, D));
-    for (int i = 0; i < c.depth; ++i) {
-        const std::string b = p + "blocks." + std::to_string(i) + ".", k = "b" + std::to_string(i) + ".";
-        VDA_TRY(vecp(k + "norm1.weight", b + "norm1.weight", D, D));
-        VDA_TRY(vecp(k + "norm1.bias", b + "norm1.bias", D, D));
-        VDA_TRY(vecp(k + "norm2.weight", b + "norm2.weight", D, D));
-        VDA_TRY(vecp(k + "norm2.bias", b + "norm2.bias", D, D));
-        VDA_TRY(vecp(k + "attn.qkv.bias", b + "attn.qkv.bias", 3 * D, 3 * D));
-        VDA_TRY(vecp(k + "attn.proj.bias", b + "attn.proj.bias", D, D));
-        VDA_TRY(vecp(k + "mlp.fc1.bias", b + "mlp.fc1.bias", 4 * D, 4 * D));
-        VDA_TRY(vecp(k + "mlp.fc2.bias", b + "mlp.fc2.bias", D, D));
-        VDA_TRY(vecp(k + "ls1.gamma", b + "ls1.gamma", D, D));
-        VDA_TRY(vecp(k + "ls2.gamma", b + "ls2.gamma", D, D));
-        VDA_TRY(lin(k + "attn.qkv.weight", b + "attn.qkv.weight", 3 * D, D, 3 * D, D));
-        VDA_TRY(lin(k + "attn.proj.weight", b + "attn.proj.weight", D, D, D, D));
-        VDA_TRY(lin(k + "mlp.fc1.weight", b + "mlp.fc1.weight", 4 * D, D, 4 * D, D));
-        VDA_TRY(lin(k + "mlp.fc2.weight", b + "mlp.fc2.weight", D, 4 * D, D, 4 * D));
-        if constexpr (std::is_same<T, h16>::value) {
+    auto n = [](int i) { return std::to_string(i); };
+    const int D = c.embed_dim, Fe = c.features, Fh = Fe / 2, Fhp = h->Fhp;
+    const int *oc = c.out_channels, *ocp = h->ocp;
+    const std::string hd = "head.", sc = hd + "scratch.";
+    if constexpr (std::is_same<T, h16>::value) {
+        auto mat = [&](const std::string& key, size_t elems, T** out) -> int {
+            void* p = nullptr;
+            VDA_TRY(dev_alloc(h, elems * sizeof(T), &p));
+            h->mat[prec][key] = p;
+            *out = (T*)p;
+            return 0;
+        };
+        auto vec = [&](const std::string& key, size_t elems, float** out) -> int {
+            void* p = nullptr;
+            VDA_TRY(dev_alloc(h, elems * sizeof(float), &p));
+            h->vec[key] = *out = (float*)p;
+            return 0;
+        };
+        // (the head's composed weights first: their kernels are the long ones, and run while the host allocates for the blocks)
+        // option oc1_mix: output_conv1 composed with refinenet1's out_conv (vda_fold_oc1_weight), fp16 path only. oc1.w / .b and
+        // ref1.out.* stay: the fp32 path, the option's off setting and vda_debug_copy's rebuild of "p1c" run them.
+        {
+            T* d = nullptr;
+            float* bp = nullptr;
+            const int ldz = vda_oc1_mix_ldz(Fhp);
+            VDA_TRY(mat("oc1.mix.w", (size_t)ldz * Fe, &d));
+            VDA_TRY(vec("oc1.mix.b", ldz, &bp));
+            VDA_TRY(vda_fold_oc1_weight(raw(sc + "output_conv1.weight"), raw(sc + "refinenet1.out_conv.weight"), raw(sc + "refinenet1.out_conv.bias"), d, bp, Fh, Fe, Fhp, ldz, s));
+        }
+        // option convt_fold: resize_layers[i] composed with layer{i+1}_rn (vda_fold_convt_weight), fp16 path only. resize{i}.w / .b
+        // stay: the fp32 path, the option's off setting and vda_debug_copy's rebuild of "l1" / "l2" run the unfused pair.
+        for (int i = 0; i < 2; ++i) {
+            const int kk = i == 0 ? 4 : 2;
+            const std::string k = "rn" + n(i + 1) + ".fold", rs = hd + "resize_layers." + n(i);
+            T* d = nullptr;
+            float* bp = nullptr;
+            VDA_TRY(mat(k + ".w", (size_t)kk * kk * Fe * 9 * ocp[i], &d));
+            VDA_TRY(vec(k + ".b", (size_t)kk * kk * 9 * Fe, &bp));
+            VDA_TRY(vda_fold_convt_weight(raw(rs + ".weight"), raw(rs + ".bias"), raw(sc + "layer" + n(i + 1) + "_rn.weight"), d, bp, kk, oc[i], oc[i], Fe, ocp[i], s));
+        }
+        for (int i = 0; i < c.depth; ++i) {
+            const std::string b = "pretrained.blocks." + n(i) + ".", k = "b" + n(i) + ".";
             // LayerNorm folded into the Linear behind it (vda.h, VDA_EPI_LN_*): W * diag(ln_w) in fp16, c1 = its row sums, c2 = b + W.ln_b
-            const char* pairs[2][3] = {{"attn.qkv", "norm1", nullptr}, {"mlp.fc1", "norm2", nullptr}};
-            const int outs[2] = {3 * D, 4 * D};
+            const char* pairs[2][2] = {{"attn.qkv", "norm1"}, {"mlp.fc1", "norm2"}};
             for (int j = 0; j < 2; ++j) {
                 const std::string lk = pairs[j][0], nk = pairs[j][1];
+                const int out = (int)h->spec.at(b + lk + ".weight")[0];
                 T* d = nullptr;
-                VDA_TRY(mat(k + lk + ".weight.ln", (size_t)outs[j] * D, &d));
-                void *c1 = nullptr, *c2 = nullptr;
-                VDA_TRY(dev_alloc(h, (size_t)outs[j] * sizeof(float), &c1));
-                VDA_TRY(dev_alloc(h, (size_t)outs[j] * sizeof(float), &c2));
-                h->vec[k + lk + ".c1"] = (float*)c1;
-                h->vec[k + lk + ".c2"] = (float*)c2;
-                VDA_TRY(vda_fold_ln_weight(raw(b + lk + ".weight"), raw(b + lk + ".bias"), raw(b + nk + ".weight"), raw(b + nk + ".bias"), d, (float*)c1,
-                                           (float*)c2, outs[j], D, s));
+                float *c1 = nullptr, *c2 = nullptr;
+                VDA_TRY(mat(k + lk + ".weight.ln", (size_t)out * D, &d));
+                VDA_TRY(vec(k + lk + ".c1", out, &c1));
+                VDA_TRY(vec(k + lk + ".c2", out, &c2));
+                VDA_TRY(vda_fold_ln_weight(raw(b + lk + ".weight"), raw(b + lk + ".bias"), raw(b + nk + ".weight"), raw(b + nk + ".bias"), d, c1, c2, out, D, s));
             }
             // the fused MLP kernel (vda_mlp_fused_f16; widths it is built for) takes fc2's weight with its hidden columns permuted
             if (vda_mlp_fused_supported(D, 4 * D)) {
@@ -434,144 +339,39 @@ int pack_all(vda_model* h, int prec) {
             }
         }
     }
-    VDA_TRY(vecp("norm.w", p + "norm.weight", D, D));
-    VDA_TRY(vecp("norm.b", p + "norm.bias", D, D));
-    const std::string hd = "head.";
-    if (c.use_clstoken)
-        for (int i = 0; i < 4; ++i) {
-            const std::string n = hd + "readout_projects." + std::to_string(i) + ".0", k = "readout" + std::to_string(i);
-            VDA_TRY(lin(k + ".w", n + ".weight", D, 2 * D, D, 2 * D));
-            VDA_TRY(vecp(k + ".b", n + ".bias", D, D));
-        }
-    for (int i = 0; i < 4; ++i) {
-        const std::string n = hd + "projects." + std::to_string(i), k = "proj" + std::to_string(i);
-        VDA_TRY(lin(k + ".w", n + ".weight", oc[i], D, ocp[i], D));
-        VDA_TRY(vecp(k + ".b", n + ".bias", oc[i], ocp[i]));
-    }
-    for (int i = 0; i < 2; ++i) {
-        const int kk = i == 0 ? 4 : 2, cp = ocp[i];
-        const std::string n = hd + "resize_layers." + std::to_string(i), k = "resize" + std::to_string(i);
-        T* d = nullptr;
-        VDA_TRY(mat(k + ".w", (size_t)kk * kk * cp * cp, &d));
-        hipLaunchKernelGGL((pack_convt_kernel<T>), dim3(grid_for((size_t)kk * kk * cp * cp)), dim3(256), 0, s, raw(n + ".weight"), d, oc[i], oc[i], kk, cp);
-        if (vecs) {
-            void* bp = nullptr;
-            VDA_TRY(dev_alloc(h, (size_t)kk * kk * cp * sizeof(float), &bp));
-            h->vec[k + ".b"] = (float*)bp;
-            hipLaunchKernelGGL(expand_convt_bias_kernel, dim3((kk * kk * cp + 255) / 256), dim3(256), 0, s, raw(n + ".bias"), (float*)bp, oc[i], kk * kk, cp);
-        }
-    }
-    VDA_TRY(conv("resize3.w", hd + "resize_layers.3.weight", oc[3], oc[3], ocp[3], ocp[3]));
-    VDA_TRY(vecp("resize3.b", hd + "resize_layers.3.bias", oc[3], ocp[3]));
-    const std::string sc = hd + "scratch.";
-    for (int i = 0; i < 4; ++i)
-        VDA_TRY(conv("rn" + std::to_string(i + 1) + ".w", sc + "layer" + std::to_string(i + 1) + "_rn.weight", Fe, oc[i], Fe, ocp[i]));
-    if constexpr (std::is_same<T, h16>::value) {
-        // option oc1_mix: output_conv1 composed with refinenet1's out_conv (vda_fold_oc1_weight), fp16 path only. oc1.w / .b and
-        // ref1.out.* below stay: the fp32 path, the option's off setting and vda_debug_copy's rebuild of "p1c" run them.
-        {
-            T* d = nullptr;
-            const int ldz = vda_oc1_mix_ldz(Fhp);
-            VDA_TRY(mat("oc1.mix.w", (size_t)ldz * Fe, &d));
-            void* bp = nullptr;
-            VDA_TRY(dev_alloc(h, (size_t)ldz * sizeof(float), &bp));
-            h->vec["oc1.mix.b"] = (float*)bp;
-            VDA_TRY(vda_fold_oc1_weight(raw(sc + "output_conv1.weight"), raw(sc + "refinenet1.out_conv.weight"), raw(sc + "refinenet1.out_conv.bias"), d, (float*)bp,
-                                        Fh, Fe, Fhp, ldz, s));
-        }
-        // option convt_fold: resize_layers[i] composed with layer{i+1}_rn (vda_fold_convt_weight), fp16 path only. resize{i}.w / .b
-        // above stay: the fp32 path, the option's off setting and vda_debug_copy's rebuild of "l1" / "l2" run the unfused pair.
-        for (int i = 0; i < 2; ++i) {
-            const int kk = i == 0 ? 4 : 2;
-            const std::string k = "rn" + std::to_string(i + 1) + ".fold";
-            T* d = nullptr;
-            VDA_TRY(mat(k + ".w", (size_t)kk * kk * Fe * 9 * ocp[i], &d));
-            void* bp = nullptr;
-            VDA_TRY(dev_alloc(h, (size_t)kk * kk * 9 * Fe * sizeof(float), &bp));
-            h->vec[k + ".b"] = (float*)bp;
-            VDA_TRY(vda_fold_convt_weight(raw(hd + "resize_layers." + std::to_string(i) + ".weight"), raw(hd + "resize_layers." + std::to_string(i) + ".bias"),
-                                          raw(sc + "layer" + std::to_string(i + 1) + "_rn.weight"), d, (float*)bp, kk, oc[i], oc[i], Fe, ocp[i], s));
-        }
-    }
-    for (int i = 1; i <= 4; ++i) {
-        const std::string r = sc + "refinenet" + std::to_string(i) + ".", k = "ref" + std::to_string(i) + ".";
-        VDA_TRY(lin(k + "out.w", r + "out_conv.weight", Fe, Fe, Fe, Fe));
-        VDA_TRY(vecp(k + "out.b", r + "out_conv.bias", Fe, Fe));
+    if (!c.use_bn) return 0;
+    for (int i = 1; i <= 4; ++i)
         for (int u = 1; u <= 2; ++u)
             for (int cc = 1; cc <= 2; ++cc) {
-                const std::string rn = r + "resConfUnit" + std::to_string(u) + ".conv" + std::to_string(cc);
-                const std::string kn = k + "rcu" + std::to_string(u) + ".c" + std::to_string(cc);
-                if (c.use_bn) {
-                    // the folded fp32 conv replaces the raw one for packing (kept under its own key: a re-pack in the other
-                    // precision finds it again; a re-load of the state dict overwrites it)
-                    const std::string bn = r + "resConfUnit" + std::to_string(u) + ".bn" + std::to_string(cc) + ".";
-                    Raw& fw = h->raw[rn + ".weight.bn"];
-                    Raw& fb = h->raw[rn + ".bias.bn"];
-                    if (fw.d == nullptr) {
-                        void *pw = nullptr, *pb = nullptr;
-                        VDA_TRY(dev_alloc(h, (size_t)Fe * Fe * 9 * sizeof(float), &pw));
-                        VDA_TRY(dev_alloc(h, (size_t)Fe * sizeof(float), &pb));
-                        fw.d = (float*)pw, fw.n = (size_t)Fe * Fe * 9;
-                        fb.d = (float*)pb, fb.n = Fe;
-                    }
-                    hipLaunchKernelGGL(fold_bn_kernel, dim3(grid_for((size_t)Fe * Fe * 9)), dim3(256), 0, s, raw(rn + ".weight"), raw(rn + ".bias"), raw(bn + "weight"),
-                                       raw(bn + "bias"), raw(bn + "running_mean"), raw(bn + "running_var"), fw.d, fb.d, Fe, Fe * 9);
-                    VDA_TRY(conv(kn + ".w", rn + ".weight.bn", Fe, Fe, Fe, Fe));
-                    VDA_TRY(vecp(kn + ".b", rn + ".bias.bn", Fe, Fe));
-                    continue;
+                // the folded fp32 conv replaces the raw one for packing (kept under its own key: a re-pack in the other
+                // precision finds it again; a re-load of the state dict overwrites it)
+                const std::string r = sc + "refinenet" + n(i) + ".resConfUnit" + n(u), rn = r + ".conv" + n(cc), bn = r + ".bn" + n(cc) + ".";
+                const std::string kn = "ref" + n(i) + ".rcu" + n(u) + ".c" + n(cc);
+                const WEntry w{rn + ".weight.bn", h->spec.at(rn + ".weight"), W_CONV3, kn + ".w", Fe, Fe, 0};
+                const WEntry b{rn + ".bias.bn", h->spec.at(rn + ".bias"), W_VEC, kn + ".b", 1, Fe, 0};
+                Raw& fw = h->raw[w.name];
+                Raw& fb = h->raw[b.name];
+                if (fw.d == nullptr) {
+                    void *pw = nullptr, *pb = nullptr;
+                    VDA_TRY(dev_alloc(h, (size_t)w.numel() * sizeof(float), &pw));
+                    VDA_TRY(dev_alloc(h, (size_t)b.numel() * sizeof(float), &pb));
+                    fw.d = (float*)pw, fb.d = (float*)pb;
                 }
-                VDA_TRY(conv(kn + ".w", rn + ".weight", Fe, Fe, Fe, Fe));
-                VDA_TRY(vecp(kn + ".b", rn + ".bias", Fe, Fe));
+                hipLaunchKernelGGL(fold_bn_kernel, dim3(grid_for((size_t)w.numel())), dim3(256), 0, s, raw(rn + ".weight"), raw(rn + ".bias"), raw(bn + "weight"),
+                                   raw(bn + "bias"), raw(bn + "running_mean"), raw(bn + "running_var"), fw.d, fb.d, w.N(), w.K());
+                VDA_TRY(pack_entry<T>(h, prec, vecs, w, fw.d));
+                VDA_TRY(pack_entry<T>(h, prec, vecs, b, fb.d));
             }
-    }
-    VDA_TRY(conv("oc1.w", sc + "output_conv1.weight", Fh, Fe, Fhp, Fe));
-    VDA_TRY(vecp("oc1.b", sc + "output_conv1.bias", Fh, Fhp));
-    VDA_TRY(conv("oc2.w", sc + "output_conv2.0.weight", 32, Fh, 32, Fhp));
-    VDA_TRY(vecp("oc2.b", sc + "output_conv2.0.bias", 32, 32));
-    VDA_TRY(vecp("oc3.w", sc + "output_conv2.2.weight", 32, 32));
-    const int tc[4] = {ocp[2], ocp[3], Fe, Fe};
-    for (int m = 0; m < 4; ++m) {
-        const int Cc = tc[m];
-        const std::string t = hd + "motion_modules." + std::to_string(m) + ".temporal_transformer.", k = "tm" + std::to_string(m) + ".";
-        VDA_TRY(vecp(k + "gn.w", t + "norm.weight", Cc, Cc));
-        VDA_TRY(vecp(k + "gn.b", t + "norm.bias", Cc, Cc));
-        VDA_TRY(lin(k + "in.w", t + "proj_in.weight", Cc, Cc, Cc, Cc));
-        VDA_TRY(vecp(k + "in.b", t + "proj_in.bias", Cc, Cc));
-        VDA_TRY(lin(k + "out.w", t + "proj_out.weight", Cc, Cc, Cc, Cc));
-        VDA_TRY(vecp(k + "out.b", t + "proj_out.bias", Cc, Cc));
-        const std::string tb = t + "transformer_blocks.0.";
-        for (int a = 0; a < 2; ++a) {
-            const std::string ab = tb + "attention_blocks." + std::to_string(a) + ".", ka = k + "a" + std::to_string(a) + ".";
-            T* d = nullptr;
-            VDA_TRY(mat(ka + "qkv.w", (size_t)3 * Cc * Cc, &d));                 // to_q | to_k | to_v fused to one [3C, C]
-            const char* names[3] = {"to_q.weight", "to_k.weight", "to_v.weight"};
-            for (int j = 0; j < 3; ++j)
-                hipLaunchKernelGGL((pack_matrix_kernel<T>), dim3(grid_for((size_t)Cc * Cc)), dim3(256), 0, s, raw(ab + names[j]),
-                                   d + (size_t)j * Cc * Cc, Cc, Cc, Cc, Cc);
-            VDA_TRY(lin(ka + "out.w", ab + "to_out.0.weight", Cc, Cc, Cc, Cc));
-            VDA_TRY(vecp(ka + "out.b", ab + "to_out.0.bias", Cc, Cc));
-            if (!c.pe_rope) VDA_TRY(vecp(ka + "pe", ab + "pos_encoder.pe", c.num_frames * Cc, c.num_frames * Cc));
-            VDA_TRY(vecp(ka + "ln.w", tb + "norms." + std::to_string(a) + ".weight", Cc, Cc));
-            VDA_TRY(vecp(ka + "ln.b", tb + "norms." + std::to_string(a) + ".bias", Cc, Cc));
-        }
-        VDA_TRY(vecp(k + "ffln.w", tb + "ff_norm.weight", Cc, Cc));
-        VDA_TRY(vecp(k + "ffln.b", tb + "ff_norm.bias", Cc, Cc));
-        {
-            T* d = nullptr;
-            VDA_TRY(mat(k + "ff1.w", (size_t)8 * Cc * Cc, &d));
-            hipLaunchKernelGGL((pack_geglu_kernel<T>), dim3(grid_for((size_t)8 * Cc * Cc)), dim3(256), 0, s, raw(tb + "ff.net.0.proj.weight"), d, 4 * Cc, Cc);
-            if (vecs) {
-                void* bp = nullptr;
-                VDA_TRY(dev_alloc(h, (size_t)8 * Cc * sizeof(float), &bp));
-                h->vec[k + "ff1.b"] = (float*)bp;
-                hipLaunchKernelGGL((pack_geglu_kernel<float>), dim3(grid_for((size_t)8 * Cc)), dim3(256), 0, s, raw(tb + "ff.net.0.proj.bias"), (float*)bp, 4 * Cc, 1);
-            }
-        }
-        VDA_TRY(lin(k + "ff2.w", tb + "ff.net.2.weight", Cc, 4 * Cc, Cc, 4 * Cc));
-        VDA_TRY(vecp(k + "ff2.b", tb + "ff.net.2.bias", Cc, Cc));
-    }
+    return 0;
+}
+
+template <typename T>
+int pack_all(vda_model* h, int prec) {
+    const bool vecs = h->vec.empty();
+    for (const WEntry& e : h->table) VDA_TRY(pack_entry<T>(h, prec, vecs, e, h->raw.at(e.name).d));
+    VDA_TRY(pack_derived<T>(h, prec, vecs));
     VDA_HIP(hipGetLastError());
-    VDA_HIP(hipStreamSynchronize(s));
+    VDA_HIP(hipStreamSynchronize(nullptr));
     h->packed[prec] = true;
     return 0;
 }
@@ -1420,9 +1220,11 @@ extern "C" int vda_create(const vda_config* cfg, vda_model** out) {
         vda_set_error("vda_create: no HIP device (this library has no CPU path)");
         return 2;
     }
-    for (int i = 0; i < 4; ++i) h->ocp[i] = pad64(cfg->out_channels[i]);
-    h->Fhp = (cfg->features / 2 + 31) / 32 * 32;      // output_conv1's width: only the depth tail (32-channel passes) consumes it
-    build_spec(h->cfg, h->spec);
+    WeightTable table(h->cfg);                        // csrc/weight_table.h: one row per checkpoint tensor, and the padded widths
+    for (int i = 0; i < 4; ++i) h->ocp[i] = table.ocp[i];
+    h->Fhp = table.Fhp;
+    h->table = std::move(table.rows);
+    for (const WEntry& e : h->table) h->spec[e.name] = e.shape;
     if (dev_alloc(h, 256, &h->zero_page) != 0 || hipMemset(h->zero_page, 0, 256) != hipSuccess) {
         for (void* p : h->owned) (void)hipFree(p);
         delete h;
@@ -1486,8 +1288,6 @@ static int vda_load_weight_impl(vda_model* h, const char* name, const void* ptr,
         void* p = nullptr;
         VDA_TRY(dev_alloc(h, n * sizeof(float), &p));
         r.d = (float*)p;
-        r.dims = want;
-        r.n = n;
     }
     VDA_HIP(hipMemcpy(r.d, ptr, n * sizeof(float), hipMemcpyDefault));       // host or device source
     h->finalized = false;
