@@ -213,8 +213,15 @@ int vda_layernorm_f32_f32(const float* in, float* out, const float* w, const flo
  * vda_ln_stats_finalize: partial[np, r, 2] (sum, centred sum of squares per 64 columns, as VDA_EPI_SCALE_RES_SPLIT writes them)
  *   -> stat[r] = (mean, rstd), combined in column order (Chan et al.), D = 64*np. overflow (device int32, may be NULL) is set to 1
  *   when a row's statistics are not finite: the fp16 planes hold a token only up to 65 504 from its own mean (the reference's
- *   stream is fp32, block.py:105-106, and has no such limit); a saturated plane shows as an infinite / NaN sum here.
+ *   stream is fp32, block.py:105-106, and has no such limit). A saturated element is hi = +-inf, lo = -+inf. The partials of the
+ *   step that saturates are finite wherever the producer takes them from its fp32 values (the 256- and 192-row GEMM tiles,
+ *   vda_mlp_fused_f16) and not finite where it re-reads the stored planes (the 128-row tiles); in either case the NEXT
+ *   VDA_EPI_SCALE_RES_SPLIT GEMM over those planes reads hi + lo = NaN back and leaves NaN partials, which raise the flag here.
+ *   Planes that no such GEMM reads again (after the last block) are checked by their reader, vda_layernorm_split_check_f16.
  * vda_layernorm_split_f16: LayerNorm of x = hi + lo (fp32 statistics), fp16 out, group/skip as vda_layernorm_f32_f16 (the taps).
+ * vda_layernorm_split_check_f16: the same kernel, same bits out; overflow (device int32, may be NULL) is set to 1 when a row it
+ *   normalises (not one that group/skip drops) holds a saturated element. Finite planes never raise it. Never cleared here.
+ *   The handle's forward runs every tap through it: a forward whose depth depends on a saturated element returns status 4 and NaN.
  * vda_fold_ln_weight: pack-time fold of LayerNorm's affine into the Linear that follows it: Wf[n,k] = fp16(W[n,k]*ln_w[k]),
  *   c1[n] = sum_k Wf[n,k] (of the ROUNDED values, fp32), c2[n] = b[n] + sum_k W[n,k]*ln_b[k] (fp32; b may be NULL). */
 int vda_split_stats_f32(const float* x, void* hi, void* lo, float* stat, float eps, int rows, int D, vda_stream_t stream);
@@ -222,6 +229,8 @@ int vda_split_center_stats_f32(const float* x, void* hi, void* lo, float* stat, 
 int vda_ln_stats_finalize(const float* partial, float* stat, float eps, int rows, int np, int32_t* overflow, vda_stream_t stream);
 int vda_layernorm_split_f16(const void* hi, const void* lo, void* out, const float* w, const float* b, float eps,
                             int rows, int D, int group, int skip, vda_stream_t stream);
+int vda_layernorm_split_check_f16(const void* hi, const void* lo, void* out, const float* w, const float* b, float eps,
+                                  int rows, int D, int group, int skip, int32_t* overflow, vda_stream_t stream);
 int vda_fold_ln_weight(const float* W, const float* bias, const float* ln_w, const float* ln_b, void* Wf, float* c1, float* c2,
                        int N, int K, vda_stream_t stream);
 

@@ -73,6 +73,7 @@ SIGNATURES = {
     "vda_split_center_stats_f32": (_i, [_vp, _vp, _vp, _vp, _f, _i, _i, _vp]),
     "vda_ln_stats_finalize": (_i, [_vp, _vp, _f, _i, _i, _vp, _vp]),
     "vda_layernorm_split_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _vp]),
+    "vda_layernorm_split_check_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _vp, _vp]),
     "vda_fold_ln_weight": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "vda_fold_convt_weight": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "vda_fold_oc1_weight": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),

@@ -720,17 +720,21 @@ struct Run {
         a.pos = lnstat + r0 * 2;             // re-centre by the mean the LayerNorm before this branch saw
         a.M = nr, a.N = D, a.K = K, a.a_mode = VDA_A_DENSE, a.epilogue = VDA_EPI_SCALE_RES_SPLIT;
         VDA_TRY(gemm(a, nparts > 1 ? g.rows : 0));
-        // (after the last block nothing reads the statistics: that finalize runs for its overflow check alone, 5 us per clip)
+        // (after the last block nothing reads the statistics: that finalize runs for its overflow check alone, 5 us per clip. It
+        // sees what this GEMM read back - a plane the last attn.proj saturated; what this GEMM itself saturates has finite
+        // partials in the row-layout families and is reported by the reader of its planes: the next res_gemm, or tap_ln)
         if (!dry) VDA_TRY(vda_ln_stats_finalize(lnpart + r0 * np * 2, lnstat + r0 * 2, ENC_LN_EPS, nr, np, ovf, s));
         return 0;
     }
-    // the encoder's final norm of the part's rows; out is the whole tensor (group > 0: compacted, group - skip rows per frame)
+    // the encoder's final norm of the part's rows; out is the whole tensor (group > 0: compacted, group - skip rows per frame).
+    // On the split stream it raises the forward's overflow flag for a saturated row it normalises: after the last block it is the
+    // only reader of the planes, so a token that the last fc2 (or the fused MLP) pushed out of range is reported here or nowhere.
     int tap_ln(void* out, int group, int skip, const Part& p) {
         if (!fold) return layernorm(tok, out, V("norm.w"), V("norm.b"), ENC_LN_EPS, g.rows, g.D, group, skip);   // (one part: the clip)
         if (dry) return 0;
         const size_t r0 = (size_t)p.f0 * g.Nt, o0 = group > 0 ? (size_t)p.f0 * (g.Nt / group) * (group - skip) : r0;
-        return vda_layernorm_split_f16((const h16*)thi + r0 * g.D, (const h16*)tlo + r0 * g.D, (h16*)out + o0 * g.D, V("norm.w"), V("norm.b"), ENC_LN_EPS,
-                                       p.nf * g.Nt, g.D, group, skip, s);
+        return vda_layernorm_split_check_f16((const h16*)thi + r0 * g.D, (const h16*)tlo + r0 * g.D, (h16*)out + o0 * g.D, V("norm.w"), V("norm.b"),
+                                             ENC_LN_EPS, p.nf * g.Nt, g.D, group, skip, ovf, s);
     }
     int ln_res(const float* gamma, void* out, const float* w, const float* b, int group, int skip) {
         if (dry) return 0;
@@ -868,8 +872,9 @@ struct Run {
         tlo = fold ? buf("tok_lo", (size_t)rows * D, 2) : nullptr;
         lnpart = fold ? f32("ln_part", (size_t)rows * (D / 64) * 2) : nullptr;
         lnstat = fold ? f32("ln_stat", (size_t)rows * 2) : nullptr;
-        // overflow flag of this forward (see vda_model::ovf_host): raised by vda_ln_stats_finalize when a row's statistics are not
-        // finite, i.e. when a token moved further than 65 504 from its own mean and saturated the fp16 hi plane
+        // overflow flag of this forward (see vda_model::ovf_host): a token that moved further than 65 504 from its own mean saturates
+        // the fp16 planes (hi = +-inf, lo = -+inf). Raised by whatever reads such a row back: vda_ln_stats_finalize after the next
+        // residual GEMM (non-finite statistics), and the tap LayerNorm (tap_ln) for the rows it normalises
         ovf = fold ? (int32_t*)buf("overflow", 1, 4) : nullptr;
         yb = defer ? act("ybuf", (size_t)rows * D) : nullptr;
         if (fold && !dry) {

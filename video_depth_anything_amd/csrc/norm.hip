@@ -263,14 +263,17 @@ __global__ void __launch_bounds__(256) groupnorm_apply_kernel(const T* __restric
 // ---------------------------------------------------------------- LayerNorm folded into the neighbouring GEMMs
 // The fp32 residual stream of the encoder is kept as two fp16 planes, x = hi + lo (vda.h, VDA_EPI_SCALE_RES_SPLIT).
 //   MODE 0 (vda_split_stats_f32): fp32 rows -> hi, lo planes + stat[row] = (mean, rstd): the entry into the split stream.
-//   MODE 1 (vda_layernorm_split_f16): LayerNorm(hi + lo) * w + b -> fp16, group / skip as layernorm_kernel (the taps).
+//   MODE 1 (vda_layernorm_split_f16, vda_layernorm_split_check_f16): LayerNorm(hi + lo) * w + b -> fp16, group / skip as
+//           layernorm_kernel (the taps). overflow (optional): set to 1 when a row that is normalised - not a skipped one - holds a
+//           saturated element (hi = +-inf, lo = -+inf: hi + lo = NaN, and so is the row's mean). A finite row cannot raise it: D <=
+//           2048 elements of at most 2 * 65 504 sum to less than 2^29, their centred squares to less than 2^46.
 //   MODE 2 (vda_split_center_stats_f32): as MODE 0 with the row's mean taken out: hi + lo = x - mean(x), stat[row] = (0, rstd).
 // The steps of layernorm_kernel around its own loader (fp32 or hi + lo) and, for MODE 0 / 2, its own writer (planes + stat).
 template <int LPR, int NCH, int MODE>
 __global__ void __launch_bounds__(256) ln_split_kernel(const float* __restrict__ xin, const h16* __restrict__ hin, const h16* __restrict__ lin,
                                                        h16* __restrict__ o0, h16* __restrict__ o1, float* __restrict__ stat,
                                                        const float* __restrict__ w, const float* __restrict__ b, float eps, int rows, int D,
-                                                       int group, int skip) {
+                                                       int group, int skip, int* __restrict__ overflow) {
     const int lane = threadIdx.x & 63, nchunk = D >> 3;
     const RowLanes p = row_lanes<LPR>(lane, rows);
     const size_t base = (size_t)(p.row_ok ? p.row : 0) * D;
@@ -290,6 +293,7 @@ __global__ void __launch_bounds__(256) ln_split_kernel(const float* __restrict__
     if (!p.row_ok) return;
     const int orow = MODE == 1 ? out_row(p.row, group, skip) : p.row;
     if (orow < 0) return;
+    if (MODE == 1 && overflow != nullptr && p.sub == 0 && !(__builtin_isfinite(mean) && __builtin_isfinite(rstd))) *overflow = 1;   // (same value from every writer)
     // MODE 2: the planes hold x - mean (the mean of what they hold is 0 up to fp32 rounding: 1e-7 of the row's spread)
     const float ctr = MODE == 2 ? mean : 0.f;
     if (MODE != 1 && p.sub == 0) *reinterpret_cast<float2*>(stat + 2 * (size_t)p.row) = float2{mean - ctr, rstd};
@@ -315,9 +319,12 @@ __global__ void __launch_bounds__(256) ln_split_kernel(const float* __restrict__
 
 // partial[np, r, 2] = (sum, centred sum of squares) per 64 columns -> stat[r] = (mean, rstd); pairwise update in column order
 // (Chan, Golub, LeVeque): no E[x^2] - mean^2 cancellation, fixed order.
-// overflow (optional): set to 1 when a row's mean or m2 is not finite. The partials come from the producing GEMM's fp32 values, not
-// from the fp16 planes it stores, so the step in which a plane first saturates (an element beyond 65 504 of the token's mean) still
-// has finite statistics; the flag rises one step later, when a GEMM has read hi + lo = inf - inf back into its partials.
+// overflow (optional): set to 1 when a row's mean or m2 is not finite. The row-layout GEMM families and the fused MLP kernel take
+// the partials from their fp32 values, not from the fp16 planes they store, so the step in which a plane first saturates (an element
+// beyond 65 504 of the token's mean: hi = +-inf, lo = -+inf) still has FINITE statistics there; only the 128-row kernel, whose
+// partials are re-read from the stored planes, shows it at once. Otherwise the flag rises one step later, when a residual GEMM has
+// read hi + lo = NaN back into its partials. After the last block's fc2 there is no such GEMM: the tap LayerNorm, the one
+// remaining reader of the planes, reports that step (ln_split_kernel's overflow).
 __global__ void __launch_bounds__(64) ln_stats_finalize_kernel(const float* __restrict__ partial, float* __restrict__ stat, float eps, int rows, int np,
                                                                int* __restrict__ overflow) {
     const int r = blockIdx.x * 64 + threadIdx.x;          // one wave per workgroup: 685 workgroups for a ViT-L clip, every CU gets some
@@ -432,12 +439,12 @@ extern "C" int vda_layernorm_f32_f32(const float* in, float* out, const float* w
 // The three entries of ln_split_kernel; each passes the operands its MODE reads and NULL for the rest.
 template <int MODE>
 static int ln_split_launch(const char* name, const float* xin, const h16* hin, const h16* lin, h16* o0, h16* o1, float* stat, const float* w,
-                           const float* b, float eps, int rows, int D, int group, int skip, vda_stream_t stream) {
+                           const float* b, float eps, int rows, int D, int group, int skip, vda_stream_t stream, int32_t* overflow = nullptr) {
     if (MODE == 1 ? ln_check(name, rows, D, group, skip, {hin, lin, o0, w, b}) : ln_check(name, rows, D, group, skip, {xin, o0, o1})) return 1;
     VDA_REQUIRE(MODE == 1 || (stat != nullptr && ((uintptr_t)stat & 7) == 0), "%s: stat must be an 8-byte aligned pointer", name);
     ln_ladder(rows, D, [&](auto lpr, auto nch, dim3 grid) {
         hipLaunchKernelGGL((ln_split_kernel<lpr(), nch(), MODE>), grid, dim3(256), 0, (hipStream_t)stream, xin, hin, lin, o0, o1, stat, w, b,
-                           eps, rows, D, group, skip);
+                           eps, rows, D, group, skip, (int*)overflow);
     });
     VDA_LAUNCH_CHECK();
     return 0;
@@ -455,6 +462,13 @@ extern "C" int vda_layernorm_split_f16(const void* hi, const void* lo, void* out
                                        int group, int skip, vda_stream_t stream) {
     return ln_split_launch<1>("vda_layernorm_split_f16", nullptr, (const h16*)hi, (const h16*)lo, (h16*)out, nullptr, nullptr, w, b, eps, rows, D,
                               group, skip, stream);
+}
+
+extern "C" int vda_layernorm_split_check_f16(const void* hi, const void* lo, void* out, const float* w, const float* b, float eps, int rows,
+                                             int D, int group, int skip, int32_t* overflow, vda_stream_t stream) {
+    VDA_REQUIRE(((uintptr_t)overflow & 3) == 0, "vda_layernorm_split_check_f16: overflow must be a 4-byte aligned pointer");
+    return ln_split_launch<1>("vda_layernorm_split_check_f16", nullptr, (const h16*)hi, (const h16*)lo, (h16*)out, nullptr, nullptr, w, b, eps, rows,
+                              D, group, skip, stream, overflow);
 }
 
 extern "C" int vda_ln_stats_finalize(const float* partial, float* stat, float eps, int rows, int np, int32_t* overflow, vda_stream_t stream) {

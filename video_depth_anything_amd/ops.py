@@ -149,6 +149,13 @@ def layernorm_split(hi, lo, out, w, b, eps, rows, D, group=0, skip=0):
     check(lib.vda_layernorm_split_f16(_p(hi), _p(lo), _p(out), _p(w), _p(b), eps, rows, D, group, skip, _stream(hi)), "vda_layernorm_split_f16")
 
 
+def layernorm_split_check(hi, lo, out, w, b, eps, rows, D, group=0, skip=0, overflow=None):
+    """layernorm_split, and overflow[0] (int32, None = not asked) = 1 when a row it normalises holds a saturated element."""
+    _req(hi, F16, "hi"), _req(lo, F16, "lo"), _req(out, F16, "out"), _req(w, F32, "w"), _req(b, F32, "b"), _req(overflow, torch.int32, "overflow")
+    check(lib.vda_layernorm_split_check_f16(_p(hi), _p(lo), _p(out), _p(w), _p(b), eps, rows, D, group, skip, _p(overflow), _stream(hi)),
+          "vda_layernorm_split_check_f16")
+
+
 def fold_ln_weight(W, bias, ln_w, ln_b, Wf, c1, c2, N, K):
     """Wf = fp16(W * ln_w[None, :]), c1 = Wf.float().sum(1), c2 = bias + W @ ln_b (pack time)."""
     for t, n in ((W, "W"), (bias, "bias"), (ln_w, "ln_w"), (ln_b, "ln_b"), (c1, "c1"), (c2, "c2")):
