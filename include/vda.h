@@ -339,7 +339,8 @@ int vda_head_out_f32_f32(const float* in, const float* w, float bias, float* out
 int vda_depth_tail_f16(const void* in, const void* w2, const float* b2, const float* w3, float b3, float* out,
                        const void* zero_page, int B, int h, int w, int H, int W, int C, vda_stream_t stream);
 /* A/B switch of the resizing form: 0 (default) = the persistent kernel with the weights resident in LDS (C <= 128), 1 = the round-1
- * kernel (one 8 x 32 tile per workgroup). Same arithmetic, bit-identical results. */
+ * kernel (one 8 x 32 tile per workgroup). Same arithmetic, bit-identical results. 8 = the persistent kernel without its fill waves'
+ * raised priority (timing A/B), 9 = 1 and 8 together. Any other value is refused: non-zero, vda_last_error names it, setting unchanged. */
 int vda_depth_tail_set_variant(int v);
 /* The kernel the last vda_depth_tail_f16 of this thread launched ("" before the first): "depth_tail_kernel<0>" (no resize),
  * "depth_tail_kernel<1>" (resize, one 8 x 32 tile per workgroup) or "depth_tail_up_kernel" (resize, persistent). */
@@ -352,7 +353,7 @@ const char* vda_depth_tail_last_kernel(void);
  * The interpolated pixels are rounded to fp16 once, exactly as vda_bilinear_nhwc_f16 would have stored them. */
 int vda_conv3x3_up2_f16(const void* in, const void* w, const float* bias, void* out, int B, int h, int wd, int C, int N, int ldc,
                         vda_stream_t stream);
-/* Timing experiments of the fused kernel at N > 64 (results invalid): 1 = no interpolation, 2 = no MFMA groups; 0 = the kernel. */
+/* The fused kernel has one form: 0 is the only accepted value, any other is refused (non-zero, vda_last_error names it). */
 int vda_conv3x3_up2_set_variant(int v);
 
 /* ---- The same layer with the channel mixing at HALF resolution (option "oc1_mix"). refinenet1's out_conv (1x1: Wo [Fe, Fe], bo), the
@@ -378,7 +379,8 @@ int vda_oc1_mix_ldz(int Fhp);
 int vda_oc1_mix_frames(void);
 int vda_oc1_mix_default(int features);
 /* The LDS-patch 3x3 convolution behind vda_gemm_f16 (N <= 64, stride 1): 0 (default) = the persistent C = 64 kernel where it applies,
- * 1 = the per-pass kernel for every shape. Bit-identical results; A/B only. */
+ * 1 = the per-pass kernel for every shape. Bit-identical results; A/B only. Any other value is refused: non-zero, vda_last_error
+ * names it, setting unchanged. */
 int vda_conv_lds_set_variant(int v);
 
 /* uint8 RGB frames [n,H,W,3] (already at network size) -> normalised fp32 NCHW

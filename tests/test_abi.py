@@ -75,6 +75,32 @@ def test_depth_tail_last_kernel_needs_no_gpu(libpath):
     assert b"null" in lib.vda_last_error() and lib.vda_depth_tail_last_kernel() == b""
 
 
+@pytest.mark.parametrize("setter,accepted,refused", [
+    ("vda_depth_tail_set_variant", (0, 1, 8, 9), (2, 16, 0x70, -1)),
+    ("vda_conv_lds_set_variant", (0, 1), (2, 4)),
+    ("vda_conv3x3_up2_set_variant", (0,), (1, 2)),
+])
+def test_variant_switches_refuse_unknown_codes_without_a_gpu(libpath, setter, accepted, refused):
+    """The three A/B switches take their documented codes and nothing else: a refused code returns non-zero, vda_last_error names the
+    entry point and the value, and the switch can be set again afterwards (a refusal stores nothing). No launch, no HIP call."""
+    from video_depth_anything_amd import _lib
+    lib = _lib.lib
+    fn = getattr(lib, setter)
+    try:
+        for v in accepted:
+            assert fn(v) == 0, (setter, v)
+        last = accepted[-1]
+        for v in refused:
+            assert fn(last) == 0
+            assert fn(v) != 0, (setter, v)
+            msg = lib.vda_last_error().decode()
+            assert setter in msg and re.search(rf"(?<![\d-]){v}(?!\d)", msg.replace(setter, "")), msg
+            assert ", ".join(str(a) for a in accepted) in msg, msg          # the accepted codes are spelled out
+            assert fn(0) == 0
+    finally:
+        assert fn(0) == 0
+
+
 def test_cpp_host_demo_builds_and_links(libpath):
     """examples/host_demo.cpp (a C++ host of the handle API) compiles against include/vda.h and links against the library;
     argument checking happens before any HIP call."""

@@ -1,8 +1,8 @@
-"""ViT-S 64 -> 64 conv at 148^2 under vda_conv_lds_set_variant values (0 persistent, 1 per-pass, 2 / 3 timing experiments), one process."""
+"""ViT-S 64 -> 64 conv at 148^2 under vda_conv_lds_set_variant values (0 persistent, 1 per-pass), one process, interleaved."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from video_depth_anything_amd import ops, _lib
-vs = [int(a) for a in (sys.argv[1] if len(sys.argv) > 1 else "0,1,2,3").split(",")]
+vs = [int(a) for a in (sys.argv[1] if len(sys.argv) > 1 else "0,1").split(",")]
 g = torch.Generator(device="cuda").manual_seed(0)
 B, hw, C, N = 32, 148, 64, 64
 x = torch.randn(B, hw, hw, C, device="cuda", generator=g).half()

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Whole forward under different values of one library-wide switch, one process, interleaved, results asserted bit-identical.
 usage: debug_ab.py [vitl|vits] valueA,valueB,... [setter]     setter: vda_gemm_set_debug (default: diagnostic switches of the 8-phase
-kernel), vda_depth_tail_set_variant (0 persistent / 1 round-1 kernel), vda_conv_up_set_variant, ..."""
+kernel), vda_depth_tail_set_variant (0 persistent / 1 round-1 kernel), vda_conv_lds_set_variant (0 persistent / 1 per-pass kernel), ..."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from video_depth_anything_amd import _lib

@@ -1,5 +1,6 @@
-"""Fused depth tail at the ViT-L shape under a list of vda_depth_tail_set_variant values (debug / timing experiments), one process, interleaved.
-usage: tail_variants.py 0,1,16"""
+"""Fused depth tail at the ViT-L shape under a list of vda_depth_tail_set_variant values (0 persistent, 1 round-1 kernel, 8 / 9 = the same
+without the fill waves' raised priority), one process, interleaved.
+usage: tail_variants.py 0,1,8"""
 import torch, sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from video_depth_anything_amd import ops, _lib

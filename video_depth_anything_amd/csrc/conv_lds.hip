@@ -79,6 +79,8 @@ __global__ void __launch_bounds__(256) conv3x3_lds_kernel(const h16* __restrict_
 //   Groups run in the order of the kernel above's two passes (channel half, kx, k-step; ky, row as conv_patch.h's tap_group):
 //   bit-identical results
 //   (tests/test_kernels_gpu.py holds that; vda_conv_lds_set_variant(1) = the kernel above for every shape).
+//   (Timing experiments without the patch DMA, the epilogue traffic or the MFMAs once lived here as template arms; their results are
+//   in profiles/r04/vits_conv_c64_ab.txt and DESIGN.md, and the last commit that holds their code is d12d6d3.)
 namespace c64 {
 constexpr int C64 = 64, ROW64 = C64 * 2;       // 128-byte rows
 constexpr int NP64 = (NPIX + 7) / 8;           // 43 DMA pieces of 8 rows
@@ -86,7 +88,7 @@ constexpr int PATCH64 = NP64 * 1024;           // 43 KiB
 constexpr int MMA_W = 4, FILL_W = 4, NT64 = (MMA_W + FILL_W) * 64;
 __device__ __forceinline__ int swz64(int col) { return (col >> 1) & 7; }
 
-template <int CB, int DBG = 0>
+template <int CB>
 __global__ void __launch_bounds__(NT64) conv3x3_c64_kernel(const h16* __restrict__ in, const h16* __restrict__ wt, const float* __restrict__ bias,
                                                            const h16* __restrict__ res, const h16* __restrict__ res2, h16* __restrict__ out,
                                                            const h16* __restrict__ zero_page, int H, int W, int N, int ldc, int relu_in,
@@ -126,7 +128,6 @@ __global__ void __launch_bounds__(NT64) conv3x3_c64_kernel(const h16* __restrict
             const int tx = t % tiles_x, tyb = t / tiles_x;
             const int ty = tyb % tiles_y, b = tyb / tiles_y;
             const int x0 = tx * TW, y0 = ty * TH;
-            if constexpr (DBG == 1) return;                    // TIMING EXPERIMENT 1: no patch DMA
             for (int piece = fw; piece < NP64; piece += FILL_W) {
                 const int q = piece * 8 + lr;
                 const int py = q / PW, pxx = q - py * PW;
@@ -187,7 +188,6 @@ __global__ void __launch_bounds__(NT64) conv3x3_c64_kernel(const h16* __restrict
             for (int ky = 0; ky < 3; ++ky) f.Wf[cb][ky] = *reinterpret_cast<const h16x8*>(wl + wbase[ks] + ((ky * 3 + kx) * (32 * CB) + cb * 32) * ROW64);
     };
     auto mma = [&](Frag& f) __attribute__((always_inline)) {
-        if constexpr (DBG == 3) return;                        // TIMING EXPERIMENT 3: no MFMAs (fill + epilogue + barriers)
         // (the input ReLU is applied where the fragment is USED: at the load it would make the wave wait for the prefetch it just issued)
 #pragma unroll
         for (int j = 0; j < 4; ++j) f.P[j] = __builtin_elementwise_max(f.P[j], relu_thr);
@@ -198,7 +198,7 @@ __global__ void __launch_bounds__(NT64) conv3x3_c64_kernel(const h16* __restrict
 #pragma unroll
                 for (int r = 0; r < 2; ++r) acc[r][cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.Wf[cb][ky], f.P[r + ky], acc[r][cb], 0, 0, 0);
     };
-    const bool wide = DBG != 2 && (N & 7) == 0 && (ldc & 7) == 0 && (((uintptr_t)out | (uintptr_t)res | (uintptr_t)res2) & 15) == 0;      // uniform
+    const bool wide = (N & 7) == 0 && (ldc & 7) == 0 && (((uintptr_t)out | (uintptr_t)res | (uintptr_t)res2) & 15) == 0;      // uniform
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // (this wave's share of the weights)
     bar();
     int tile = tb + slot;
@@ -240,7 +240,7 @@ __global__ void __launch_bounds__(NT64) conv3x3_c64_kernel(const h16* __restrict
         // interleaved 4-channel groups 8g + 4hh; one v_permlane32_swap per register gives the lower lane channels 0..15 of the block and
         // the upper lane 16..31, so residuals are READ and the result is WRITTEN 16 bytes per lane (the residual registers are swapped
         // back into the accumulator layout first: the swap is its own inverse). With 8-byte accesses the epilogue was the whole kernel:
-        // 110 of 132 us at 148^2 (vda_conv_lds_set_variant 3), in this kernel and in the per-pass one alike.
+        // 110 of 132 us at 148^2 (the no-epilogue-traffic arm this kernel had up to commit d12d6d3), in this kernel and in the per-pass one alike.
         const int tx = tile % tiles_x, tyb = tile / tiles_x;
         const int ty = tyb % tiles_y, b = tyb / tiles_y;
 #pragma unroll
@@ -331,7 +331,7 @@ __global__ void __launch_bounds__(NT64) conv3x3_c64_kernel(const h16* __restrict
                     f32x4 v = {acc[r][cb][4 * gq], acc[r][cb][4 * gq + 1], acc[r][cb][4 * gq + 2], acc[r][cb][4 * gq + 3]};
 #pragma unroll
                     for (int e = 0; e < 4; ++e) acc[r][cb][4 * gq + e] = 0.f;
-                    if (!inb || n >= N || DBG == 2) continue;          // (TIMING EXPERIMENT 2: no epilogue memory traffic)
+                    if (!inb || n >= N) continue;
                     if (bias) v += *reinterpret_cast<const f32x4*>(bias + n);
                     if (res) {
                         const h16x4 a = *reinterpret_cast<const h16x4*>(res + row + n);
@@ -362,6 +362,7 @@ __global__ void __launch_bounds__(NT64) conv3x3_c64_kernel(const h16* __restrict
 
 static int g_conv_lds_variant = 0;
 extern "C" int vda_conv_lds_set_variant(int v) {      // 0 = default (the C = 64 kernel where it applies), 1 = conv3x3_lds_kernel for every shape (A/B)
+    VDA_REQUIRE(v == 0 || v == 1, "vda_conv_lds_set_variant: unknown variant %d (accepted: 0, 1)", v);
     g_conv_lds_variant = v;
     return 0;
 }
@@ -387,14 +388,10 @@ int vda_conv3x3_lds(const vda_gemm_args& a, hipStream_t s) {
         // 37^2 a tie, 19^2 13.3 -> 11.6; ViT-S forward 8.15 -> 8.05 ms. 32 output channels (not a shape of the model) lose on it
         // (one MFMA wave per SIMD has half the work per tile) and stay on the per-pass kernel.
         constexpr int smem = 9 * 32 * 2 * c64::ROW64 + 2 * c64::PATCH64;
-        using KFn = void (*)(const h16*, const h16*, const float*, const h16*, const h16*, h16*, const h16*, int, int, int, int, int, int, int, int, int);
-        // by timing experiment DBG (results invalid): variants 2, 3, 4 = experiments 1, 2, 3; each is prepared as its own function
-        static const KFn fns[4] = {&c64::conv3x3_c64_kernel<2>, &c64::conv3x3_c64_kernel<2, 1>, &c64::conv3x3_c64_kernel<2, 2>, &c64::conv3x3_c64_kernel<2, 3>};
-        static VdaKernelDeviceState dev_state[4];
-        const int v = g_conv_lds_variant >= 2 && g_conv_lds_variant <= 4 ? g_conv_lds_variant - 1 : 0;
-        const int ncu = vda_prepare_kernel(reinterpret_cast<const void*>(fns[v]), smem, dev_state[v]);
+        static VdaKernelDeviceState dev_state;
+        const int ncu = vda_prepare_kernel(reinterpret_cast<const void*>(&c64::conv3x3_c64_kernel<2>), smem, dev_state);
         if (ncu < 0) return 2;
-        hipLaunchKernelGGL(fns[v], dim3(persistent_grid(ntiles, ncu)), dim3(c64::NT64), smem, s, (const h16*)a.A, (const h16*)a.W, a.bias, res, res2,
+        hipLaunchKernelGGL(c64::conv3x3_c64_kernel<2>, dim3(persistent_grid(ntiles, ncu)), dim3(c64::NT64), smem, s, (const h16*)a.A, (const h16*)a.W, a.bias, res, res2,
                            (h16*)a.out, (const h16*)a.zero_page, a.cH, a.cW, a.N, a.ldc, a.relu_in & VDA_OPT_RELU_IN, relu_out, tiles_x, tiles_y, (int)ntiles);
         VDA_LAUNCH_CHECK();
         return 0;

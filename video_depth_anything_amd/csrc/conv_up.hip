@@ -17,6 +17,8 @@
 //               unfused path would have read back from memory, up to the last bit of the fp32 sum)
 //   MFMA      : per kx a wave reads 4 patch + 3 CB weight fragments for 6 CB MFMAs.
 //   epilogue  : + bias, fp16 NHWC store.
+// (Timing experiments that skipped the interpolation or the MFMA groups once lived here as template arms; their results are in
+// DESIGN.md, and the last commit that holds their code is d12d6d3.)
 #include "conv_patch.h"
 
 namespace {
@@ -47,7 +49,7 @@ __device__ __forceinline__ int patch_off(int q, int chunk) {
     return q * ROWB + ((chunk ^ ((col >> 3) & 1)) << 4);
 }
 
-template <int CB, int DBG = 0>
+template <int CB>
 __global__ void __launch_bounds__(NT) conv3x3_up2_kernel(const h16* __restrict__ in, const h16* __restrict__ wt, const float* __restrict__ bias,
                                                          h16* __restrict__ out, int h, int w, int C, int N, int ldc, int tiles_x,
                                                          int tiles_y, int ntiles) {
@@ -142,7 +144,6 @@ __global__ void __launch_bounds__(NT) conv3x3_up2_kernel(const h16* __restrict__
         *reinterpret_cast<h16x8*>(pb + wo) = o;
     };
     auto interp = [&](int k, const char* sb, char* pb) {
-        if constexpr (DBG == 1) return;                        // TIMING EXPERIMENT 1 (results invalid): no interpolation
         interp_item(woff[k], ia[k], ib[k], wxs[k], wys[k], sb, pb);
     };
 
@@ -172,7 +173,6 @@ __global__ void __launch_bounds__(NT) conv3x3_up2_kernel(const h16* __restrict__
     for (int kx = 0; kx < 3; ++kx) pbase[kx] = (wave * 2 * PW + px + kx) * ROWB + ((hh ^ (((px + kx) >> 3) & 1)) << 4);
     const int wbase = lds_off(px, hh);
     auto mfma_group = [&](int kx, const char* pc, const char* wc) {
-        if constexpr (DBG == 2) return;                        // TIMING EXPERIMENT 2 (results invalid): no MFMA groups
         h16x8 P[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) P[i] = *reinterpret_cast<const h16x8*>(pc + pbase[kx] + i * PW * ROWB);
@@ -258,17 +258,16 @@ __global__ void __launch_bounds__(NT) conv3x3_up2_kernel(const h16* __restrict__
     }
 }
 
-static int g_up2_variant = 0;
-template <int CB, int DBG = 0>
+template <int CB>
 int launch_up2(const h16* in, const h16* wt, const float* bias, h16* out, int B, int h, int w, int C, int N, int ldc, hipStream_t s) {
     constexpr int smem = 2 * (9 * CB * 1024 + PATCH_BYTES + SRC_BYTES);
     static_assert(smem <= 160 * 1024, "LDS budget");
     static VdaKernelDeviceState dev_state;
-    if (vda_prepare_kernel(reinterpret_cast<const void*>(&conv3x3_up2_kernel<CB, DBG>), smem, dev_state) < 0) return 2;
+    if (vda_prepare_kernel(reinterpret_cast<const void*>(&conv3x3_up2_kernel<CB>), smem, dev_state) < 0) return 2;
     int tiles_x, tiles_y;
     const long long ntiles = vp::tile_count(B, 2 * h, 2 * w, TH, TW, tiles_x, tiles_y);
     VDA_REQUIRE(ntiles < (1ll << 30), "vda_conv3x3_up2: too many tiles");
-    hipLaunchKernelGGL((conv3x3_up2_kernel<CB, DBG>), dim3(vp::grid8(ntiles)), dim3(NT), smem, s, in, wt, bias, out, h, w, C, N, ldc,
+    hipLaunchKernelGGL(conv3x3_up2_kernel<CB>, dim3(vp::grid8(ntiles)), dim3(NT), smem, s, in, wt, bias, out, h, w, C, N, ldc,
                        tiles_x, tiles_y, (int)ntiles);
     VDA_LAUNCH_CHECK();
     return 0;
@@ -276,8 +275,9 @@ int launch_up2(const h16* in, const h16* wt, const float* bias, h16* out, int B,
 
 }  // namespace
 
+// One kernel family, nothing to switch: the entry point stays for the ABI and accepts the default code alone.
 extern "C" int vda_conv3x3_up2_set_variant(int v) {
-    g_up2_variant = v;
+    VDA_REQUIRE(v == 0, "vda_conv3x3_up2_set_variant: unknown variant %d (accepted: 0)", v);
     return 0;
 }
 
@@ -294,7 +294,5 @@ extern "C" int vda_conv3x3_up2_f16(const void* in, const void* w, const float* b
     const h16 *ip = (const h16*)in, *wp = (const h16*)w;
     if (N <= 32) return launch_up2<1>(ip, wp, bias, (h16*)out, B, h, wd, C, N, ldc, s);
     if (N <= 64) return launch_up2<2>(ip, wp, bias, (h16*)out, B, h, wd, C, N, ldc, s);
-    if (g_up2_variant == 1) return launch_up2<4, 1>(ip, wp, bias, (h16*)out, B, h, wd, C, N, ldc, s);      // timing experiments (tools/conv_up_variants.py)
-    if (g_up2_variant == 2) return launch_up2<4, 2>(ip, wp, bias, (h16*)out, B, h, wd, C, N, ldc, s);
     return launch_up2<4>(ip, wp, bias, (h16*)out, B, h, wd, C, N, ldc, s);
 }

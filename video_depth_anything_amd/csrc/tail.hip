@@ -10,7 +10,9 @@
 //                                 MFMA phase. SRC_UP = 0: the patch by LDS-DMA straight from the tensor. SRC_UP = 1: 4 gathers from
 //                                 the low-res tensor per patch pixel (offsets precomputed once per workgroup), packed-fp16 weighted
 //                                 sum, ds_write_b128 - the upsampled tensor never exists in memory
-//   v2::depth_tail_up_kernel<DBG> the resizing form the product runs: persistent, fill waves beside MFMA waves, source region in LDS
+//   v2::depth_tail_up_kernel      the resizing form the product runs: persistent, fill waves beside MFMA waves, source region in LDS
+// (Six timing experiments that cut phases out of v2 once lived here as template arms; their results are in
+// profiles/r04/depth_tail_v2.txt and DESIGN.md, and the last commit that holds their code is d12d6d3.)
 #include "conv_patch.h"
 
 namespace {
@@ -211,7 +213,6 @@ inline int src_extent(float scale, int tile, int halo_lo, int out_n, int in_n) {
     return ext;
 }
 
-template <int DBG>
 __global__ void __launch_bounds__(NT2) depth_tail_up_kernel(const h16* __restrict__ in, const h16* __restrict__ w2, const float* __restrict__ b2,
                                                             const float* __restrict__ w3, float b3, float* __restrict__ out, int h, int w, int H,
                                                             int W, int C, int tiles_x, int tiles_y, int ntiles, float ys, float xs, int SH, int SW) {
@@ -306,18 +307,10 @@ __global__ void __launch_bounds__(NT2) depth_tail_up_kernel(const h16* __restric
             }
         };
         auto interp = [&](const char* sb, char* pb) __attribute__((always_inline)) {
-            if constexpr (DBG == 1) return;                    // TIMING EXPERIMENT 1: no interpolation (DMA + barriers only)
 #pragma unroll
             for (int k = 0; k < NKF; ++k) {
                 const h16x8 a00 = *reinterpret_cast<const h16x8*>(sb + (ia[k] & 0xffffu)), a01 = *reinterpret_cast<const h16x8*>(sb + (ia[k] >> 16));
                 const h16x8 a10 = *reinterpret_cast<const h16x8*>(sb + (ib[k] & 0xffffu)), a11 = *reinterpret_cast<const h16x8*>(sb + (ib[k] >> 16));
-                if constexpr (DBG == 3) {                      // TIMING EXPERIMENT 3: the LDS traffic of the interpolation without its arithmetic
-                    uint4 x = *reinterpret_cast<const uint4*>(&a00);
-                    const uint4 y = *reinterpret_cast<const uint4*>(&a01), z = *reinterpret_cast<const uint4*>(&a10), t = *reinterpret_cast<const uint4*>(&a11);
-                    x.x ^= y.x ^ z.x ^ t.x; x.y ^= y.y ^ z.y ^ t.y; x.z ^= y.z ^ z.z ^ t.z; x.w ^= y.w ^ z.w ^ t.w;
-                    *reinterpret_cast<uint4*>(pb + woff[k]) = x;
-                    continue;
-                }
                 *reinterpret_cast<h16x8*>(pb + woff[k]) = bilinear8(a00, a01, a10, a11, bw[k]);
             }
         };
@@ -347,11 +340,6 @@ __global__ void __launch_bounds__(NT2) depth_tail_up_kernel(const h16* __restric
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         wg_barrier();
-        if constexpr (DBG >= 4) {                              // TIMING EXPERIMENTS 4..6: the MFMA side alone
-            for (int u = 0; u < nu; ++u)
-                if (DBG != 6) wg_barrier();
-            return;
-        }
         for (int u = 0; u < nu; ++u) {
             // patch of unit u + 1 from source[(u + 1) & 1] (landed before the barrier behind us)
             // first the DMA - weights of unit u + 1 (its ring slot was last read in unit u - 1), source of unit u + 2 into the region
@@ -397,22 +385,18 @@ __global__ void __launch_bounds__(NT2) depth_tail_up_kernel(const h16* __restric
     };
     int u = 0;
     auto unit = [&]() __attribute__((always_inline)) {
-        if constexpr (DBG == 2) {                              // TIMING EXPERIMENT 2: no MFMA phase (the fill waves' own pace)
-            ++u;
-            return;
-        }
         const char* const pc = patch + (u & 1) * PATCH_BYTES2;
         const char* const wc = wring + (u & 1) * W_PASS_BYTES;
         Frag f[2];
         load_frag(0, pc, wc, f[0]);
 #pragma unroll
         for (int g = 0; g < 6; ++g) {
-            if (g + 1 < 6 && DBG != 5) {
+            if (g + 1 < 6) {
                 load_frag(g + 1, pc, wc, f[(g + 1) & 1]);
                 __builtin_amdgcn_sched_group_barrier(0x100, 7, 0);      // the next group's fragments are requested first ...
             }
-            const Frag& fg = f[DBG == 5 ? 0 : g & 1];
-            tap_group<1>(fg.P, fg.Wf, acc);                              // (experiment 5: no fragment reads but the first group's)
+            const Frag& fg = f[g & 1];
+            tap_group<1>(fg.P, fg.Wf, acc);
             __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);          // ... then this group's six MFMAs
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -424,7 +408,7 @@ __global__ void __launch_bounds__(NT2) depth_tail_up_kernel(const h16* __restric
     for (int k = 0; k < nmy; ++k) {
         for (int pass = 0; pass + 1 < npass; ++pass) {
             unit();
-            if (DBG != 6) wg_barrier();
+            wg_barrier();
         }
         unit();
         // ---- epilogue of the tile, the text of v1's: as one shared function hipcc regrouped the b2 / w3 loads and their waits here
@@ -443,15 +427,16 @@ __global__ void __launch_bounds__(NT2) depth_tail_up_kernel(const h16* __restric
             if (hh == 0 && oy < H && ox < W) out[((size_t)t.b * H + oy) * W + ox] = fmaxf(s + b3, 0.f);
         }
         tile += per_xcd;
-        if (DBG != 6) wg_barrier();
+        wg_barrier();
     }
 }
 }  // namespace v2
 
 }  // namespace
 
-static int g_tail_variant = 0;
+static int g_tail_variant = 0;      // bit 0: v1 for every shape (A/B); bit 3: fill-wave priority off (A/B)
 extern "C" int vda_depth_tail_set_variant(int v) {
+    VDA_REQUIRE((v & ~9) == 0, "vda_depth_tail_set_variant: unknown variant %d (accepted: 0, 1, 8, 9)", v);
     g_tail_variant = v;
     return 0;
 }
@@ -475,19 +460,14 @@ extern "C" int vda_depth_tail_f16(const void* in, const void* w2, const float* b
     // v2: persistent, specialised waves, source region staged in LDS (tools/tail_bench.py; variant 1 = v1 for A/B). Needs the region
     // under a 18 x 34 patch to fit 256 pixels - any upsampling by >= ~1.3 does (1.75 everywhere in the product)
     const int SH = v2::src_extent(ys, v2::TH2, -1, H, h), SW = v2::src_extent(xs, v2::TW2, -1, W, w);
-    if ((h != H || w != W) && SH * SW <= v2::SRC_ROWS && (g_tail_variant & 7) != 1) {
+    if ((h != H || w != W) && SH * SW <= v2::SRC_ROWS && !(g_tail_variant & 1)) {
         int tx2, ty2;
         const long long nt2 = tile_count(B, H, W, v2::TH2, v2::TW2, tx2, ty2);
         VDA_REQUIRE(nt2 < (1ll << 30), "vda_depth_tail: too many tiles");
-        static VdaKernelDeviceState dev_state[8];
-        const int dbg = (g_tail_variant >> 4) & 7;              // timing experiments (results invalid), tools/tail_variants.py
-        using KFn = void (*)(const h16*, const h16*, const float*, const float*, float, float*, int, int, int, int, int, int, int, int, float, float, int, int);
-        static const KFn fns[8] = {&v2::depth_tail_up_kernel<0>, &v2::depth_tail_up_kernel<1>, &v2::depth_tail_up_kernel<2>, &v2::depth_tail_up_kernel<3>,
-                                   &v2::depth_tail_up_kernel<4>, &v2::depth_tail_up_kernel<5>, &v2::depth_tail_up_kernel<6>, &v2::depth_tail_up_kernel<0>};
-        const KFn fn = fns[dbg];
-        const int ncu = vda_prepare_kernel(reinterpret_cast<const void*>(fn), v2::SMEM2, dev_state[dbg]);
+        static VdaKernelDeviceState dev_state;
+        const int ncu = vda_prepare_kernel(reinterpret_cast<const void*>(&v2::depth_tail_up_kernel), v2::SMEM2, dev_state);
         if (ncu < 0) return 2;
-        hipLaunchKernelGGL(fn, dim3(persistent_grid(nt2, ncu)), dim3(v2::NT2), v2::SMEM2, s, (const h16*)in, (const h16*)w2, b2, w3, b3, out, h, w, H, W, C,
+        hipLaunchKernelGGL(v2::depth_tail_up_kernel, dim3(persistent_grid(nt2, ncu)), dim3(v2::NT2), v2::SMEM2, s, (const h16*)in, (const h16*)w2, b2, w3, b3, out, h, w, H, W, C,
                            tx2, ty2, (int)nt2, ys, xs, SH | ((g_tail_variant & 8) ? 1 << 16 : 0), SW);
         VDA_LAUNCH_CHECK();
         g_tail_last_kernel = "depth_tail_up_kernel";

@@ -57,19 +57,6 @@ def _req(t, dtype, name):
         raise ValueError(f"{name}: expected contiguous cuda {dtype}, got {t.dtype} {t.device} contiguous={t.is_contiguous()}")
 
 
-# Optional per-launch timing (bench.py): when PROFILE is a GemmProfile, every `every`-th GEMM launch of each
-# (shape, epilogue) is bracketed by two events recorded on the launch stream; all launches are counted. Bracketing
-# every launch costs ~1 ms per ViT-L clip in event packets (measured), 1 in 4 keeps the timed region honest.
-class GemmProfile:
-    def __init__(self, every=4):
-        self.every = every
-        self.seen = {}          # (M, N, K, epilogue, a_mode) -> launches so far
-        self.launches = {}      # kernel name -> [launches, algorithmic flops]
-        self.samples = []       # (kernel name, algorithmic flops, start event, stop event)
-
-
-PROFILE = None
-
 _zero_pages = {}
 
 
@@ -108,25 +95,7 @@ def gemm(A, W, out, epi, *, M, N, K, lda=None, ldc=None, bias=None, res=None, re
         a.tK, a.tH, a.tW, a.tCout = convt
     if W.numel() < N * K:
         raise ValueError("W smaller than N*K")
-    prof = PROFILE
-    if prof is None:
-        check(fn(C.byref(a), _stream(A)), f"{fname} M={M} N={N} K={K} epi={epi} conv={conv} lda={a.lda} ldc={a.ldc}" if _TRACE else fname)
-        return
-    key = (M, N, K, epi, a.a_mode)
-    n = prof.seen.get(key, 0)
-    prof.seen[key] = n + 1
-    timed = n % prof.every == 0
-    if timed:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(fn(C.byref(a), _stream(A)), fname)
-    name = lib.vda_gemm_last_kernel().decode() if A.dtype == F16 else "gemm_f32_kernel"
-    tot = prof.launches.setdefault(name, [0, 0.0])
-    tot[0] += 1
-    tot[1] += 2.0 * M * N * K
-    if timed:
-        e1.record()
-        prof.samples.append((name, 2.0 * M * N * K, e0, e1))
+    check(fn(C.byref(a), _stream(A)), f"{fname} M={M} N={N} K={K} epi={epi} conv={conv} lda={a.lda} ldc={a.ldc}" if _TRACE else fname)
 
 
 def split_stats(x, hi, lo, stat, eps, rows, D, center=False):
