@@ -65,6 +65,19 @@ def test_tensor_in_gives_payload_and_lengths_and_writes_nothing_else(shape):
     assert (got[:GUARD] == FILL).all() and (got[GUARD + total:] == FILL).all()
 
 
+@pytest.mark.parametrize("shape", [(5, 16, 24, 3), (5, 9, 17)], ids=["rgb", "gray"])
+def test_numpy_in_staged_two_frames_at_a_time(shape, monkeypatch):
+    """Five frames through a staging block of two (2, 2, 1): the twin's list, and the list of the call that takes them at once."""
+    from video_depth_anything_amd import mjpeg
+    x = np.random.default_rng(shape).integers(0, 256, size=shape, dtype=np.uint8)
+    want = mjpeg.encode_jpeg_numpy(x, 90)
+    at_once = mjpeg.encode_jpeg(x, 90, device="cuda")
+    monkeypatch.setattr(mjpeg, "_BLOCK_BYTES", 2 * x[0].nbytes)
+    staged = mjpeg.encode_jpeg(x, 90, device="cuda")
+    assert isinstance(staged, list) and [len(j) for j in staged] == [len(j) for j in want]
+    assert staged == want and staged == at_once
+
+
 def test_two_calls_give_identical_bytes():
     """The bits of neighbouring blocks meet in shared words through OR-atomics, whose result does not depend on their order."""
     from video_depth_anything_amd import mjpeg

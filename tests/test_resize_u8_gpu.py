@@ -64,6 +64,17 @@ def test_device_resize_is_the_twin_byte_for_byte(src, dst, c):
     assert np.array_equal(resize_frames(torch.from_numpy(x).cuda(), *dst).cpu().numpy(), want)      # a second launch: the same bytes
 
 
+def test_numpy_in_staged_two_frames_at_a_time(monkeypatch):
+    """Five frames through a staging block of two (2, 2, 1): the twin's bytes, and the bytes of the call that takes them at once."""
+    from video_depth_anything_amd import scale
+    x, want = frames(5, 9, 17, 3), twin(5, (9, 17), (14, 11), 3)
+    at_once = scale.resize_frames(x, 14, 11)
+    monkeypatch.setattr(scale, "_BLOCK_BYTES", 2 * x[0].nbytes)
+    staged = scale.resize_frames(x, 14, 11)
+    report_difference(staged, want, "staged")
+    assert isinstance(staged, np.ndarray) and np.array_equal(staged, want) and np.array_equal(staged, at_once)
+
+
 @pytest.mark.parametrize("c", [1, 3], ids=["gray", "rgb"])
 def test_widths_around_a_workgroups_tile(c):
     """Output rows one pixel under, at and one pixel over the bytes a workgroup covers, and an exact multiple of them."""

@@ -31,6 +31,8 @@ import zlib
 
 import numpy as np
 
+from .staging import Staged, cuda_device, frames_per_block
+
 CHUNK = 16384
 NLIT = 286                      # literal/length symbols: 0..255 literals, 256 end of block, 257..285 lengths
 MAX_BITS = 15
@@ -321,44 +323,43 @@ def combine_chunk_crcs(crcs, n, crc=0):
 _BLOCK_BYTES = 1 << 25                # input bytes staged at a time by deflate's numpy path: a multiple of CHUNK
 
 
-class _Stager:
-    """The buffers of the numpy path, allocated once per stream: a pinned host block, its device twin, the encoder's outputs."""
+class _Encoder:
+    """vda_deflate_u8's workspace and outputs for inputs of up to `cap` bytes on `dev`, allocated once, and the call."""
 
-    def __init__(self, dev, block):
+    def __init__(self, dev, cap):
         import torch
         from . import ops
-        assert block % CHUNK == 0 and block > 0
-        self.block, self.dev = block, dev
-        self.host = torch.empty(block, dtype=torch.uint8).pin_memory()
-        self.dev_in = torch.empty(block, dtype=torch.uint8, device=dev)
-        self.work = torch.empty(ops.deflate_workspace_bytes(block), dtype=torch.uint8, device=dev)
-        self.payload = torch.empty(ops.deflate_out_bytes(block), dtype=torch.uint8, device=dev)
+        self.ops = ops
+        self.work = torch.empty(ops.deflate_workspace_bytes(cap), dtype=torch.uint8, device=dev)
+        self.payload = torch.empty(ops.deflate_out_bytes(cap), dtype=torch.uint8, device=dev)
         self.length = torch.empty(1, dtype=torch.int64, device=dev)
-        self.crcs = torch.empty(n_chunks(block), dtype=torch.int32, device=dev)
+        self.crcs = torch.empty(n_chunks(cap), dtype=torch.int32, device=dev)
+
+    def __call__(self, x, final):
+        """(the stream: a view of the payload, its length, the CRC-32 of x's bytes) of a device uint8 [n]."""
+        self.ops.deflate(x, final, self.work, self.payload, self.length, self.crcs)
+        ln, n = int(self.length.item()), x.numel()
+        per_chunk = (self.crcs[:-(-n // CHUNK)].cpu().numpy().astype(np.int64) & 0xFFFFFFFF).tolist()
+        return self.payload[:ln], ln, combine_chunk_crcs(per_chunk, n)
+
+
+class _Stager:
+    """The numpy path for inputs of up to n bytes, at most `block` bytes at a time (staging.Staged): its buffers are allocated once
+    per stream or file."""
+
+    def __init__(self, dev, block, n):
+        import torch
+        assert block % CHUNK == 0 and block > 0
+        block = CHUNK * frames_per_block(-(-n // CHUNK), CHUNK, block)     # no more than the chunks n fills
+        self.staged, self.encode = Staged(block, (), torch.uint8, dev), _Encoder(dev, block)
 
     def pieces(self, b, final):
-        """(stream bytes, per-chunk CRCs, input bytes) of every block of the uint8 array (or memory map) `b`."""
-        from . import ops
-        n = b.size
-        for lo in range(0, max(n, 1), self.block):
-            m = min(self.block, n - lo)
-            last = lo + m >= n
-            if not (final and last) and m == 0:
-                return
-            np.copyto(self.host.numpy()[:m], b[lo:lo + m])
-            self.dev_in[:m].copy_(self.host[:m], non_blocking=True)
-            ops.deflate(self.dev_in[:m], final and last, self.work, self.payload, self.length, self.crcs)
-            ln = int(self.length.item())
-            k = n_chunks(m, final and last)
-            yield self.payload[:ln].cpu().numpy().tobytes(), (self.crcs[:k].cpu().numpy().astype(np.int64) & 0xFFFFFFFF).tolist(), m
-
-
-def _cuda_device(device):
-    import torch
-    dev = torch.device("cuda" if device is None else device)
-    if dev.type != "cuda":
-        raise ValueError(f"deflate: needs a cuda device, got {device!r}; deflate_numpy is the host twin")
-    return dev
+        """(stream bytes, CRC-32 of the input, input bytes) of every block of the uint8 array (or memory map) `b`."""
+        if final and b.size == 0:                                           # one chunk of no bytes
+            yield self.encode(self.staged.dev[:0], True)[0].cpu().numpy().tobytes(), 0, 0
+        for lo, m, x in self.staged.blocks(b):
+            stream, _, crc = self.encode(x, final and lo + m >= b.size)
+            yield stream.cpu().numpy().tobytes(), crc, m
 
 
 def deflate(data, device="cuda", final=True, block_bytes=None):
@@ -367,32 +368,22 @@ def deflate(data, device="cuda", final=True, block_bytes=None):
     returns (payload uint8 tensor, length, crc32) on its device and stream; only the length and the per-chunk CRCs (4 bytes per
     16 KiB) cross to the host."""
     import torch
-    from . import ops
     if isinstance(data, torch.Tensor):
         if not data.is_cuda:
             raise ValueError("deflate: takes a cuda tensor, bytes or a numpy array; deflate_numpy is the host twin")
         x = data.contiguous().reshape(-1).view(torch.uint8)
-        n = x.numel()
         with torch.cuda.device(x.device):
-            work = torch.empty(ops.deflate_workspace_bytes(n), dtype=torch.uint8, device=x.device)
-            payload = torch.empty(ops.deflate_out_bytes(n), dtype=torch.uint8, device=x.device)
-            length = torch.empty(1, dtype=torch.int64, device=x.device)
-            crcs = torch.empty(n_chunks(n), dtype=torch.int32, device=x.device)
-            ops.deflate(x, final, work, payload, length, crcs)
-            ln = int(length.item())
-            per_chunk = (crcs[:-(-n // CHUNK)].cpu().numpy().astype(np.int64) & 0xFFFFFFFF).tolist()
-            return payload[:ln], ln, combine_chunk_crcs(per_chunk, n)
-    dev = _cuda_device(device)
+            return _Encoder(x.device, x.numel())(x, final)
+    dev = cuda_device(device, "deflate", "deflate_numpy")
     b = _as_bytes(data)
     block = _BLOCK_BYTES if block_bytes is None else int(block_bytes)
     if block < CHUNK or block % CHUNK:
         raise ValueError(f"deflate: block_bytes must be a positive multiple of {CHUNK}, got {block_bytes!r}")
     with torch.cuda.device(dev):
-        st = _Stager(dev, min(block, max(CHUNK, -(-b.size // CHUNK) * CHUNK)))
         out, crc = [], 0
-        for piece, crcs, m in st.pieces(b, final):
+        for piece, piece_crc, m in _Stager(dev, block, b.size).pieces(b, final):
             out.append(piece)
-            crc = combine_chunk_crcs(crcs if m else [], m, crc)
+            crc = crc32_combine(crc, piece_crc, m)
         return b"".join(out), crc
 
 
@@ -422,11 +413,6 @@ def _twin_pieces(b, block):
     for lo in range(0, max(b.size, 1), block):
         piece = np.asarray(b[lo:lo + block])
         yield deflate_numpy(piece, final=lo + block >= b.size), zlib.crc32(piece), piece.size
-
-
-def _device_pieces(b, stager):
-    for piece, crcs, m in stager.pieces(b, True):
-        yield piece, combine_chunk_crcs(crcs if m else [], m), m
 
 
 def write_npz(path, arrays, pieces, zip64_limit=ZIP64_LIMIT):
@@ -497,9 +483,9 @@ def savez_compressed(path, device="cuda", _zip64_limit=ZIP64_LIMIT, _twin=False,
         write_npz(path, arrays, lambda b: _twin_pieces(b, block), _zip64_limit)
         return path
     import torch
-    dev = _cuda_device(device)
+    dev = cuda_device(device, "deflate", "deflate_numpy")
     largest = max([np.asarray(a).nbytes if not isinstance(a, np.ndarray) else a.nbytes for a in arrays.values()] + [0])
     with torch.cuda.device(dev):
-        stager = _Stager(dev, min(block, max(CHUNK, -(-largest // CHUNK) * CHUNK)))
-        write_npz(path, arrays, lambda b: _device_pieces(b, stager), _zip64_limit)
+        stager = _Stager(dev, block, largest)
+        write_npz(path, arrays, lambda b: stager.pieces(b, True), _zip64_limit)
     return path

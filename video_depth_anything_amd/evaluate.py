@@ -28,6 +28,8 @@ vda_tae_*; the contract is in DESIGN.md 6d). `evaluate_tae_numpy` is its host tw
 """
 import numpy as np
 
+from .staging import cuda_device, one_device
+
 METRICS = ("abs_relative_difference", "squared_relative_difference", "rmse_linear", "delta1_acc", "delta2_acc", "delta3_acc")
 EVAL_T = 256                 # threads per block of the two passes (csrc/eval.hip EV_T)
 LSQ_MAX_BLOCKS = 1024        # pass 1: blocks per call
@@ -82,9 +84,7 @@ def resize_prediction(pred, size, device="cuda"):
     H, W = (int(v) for v in size)
     if pred.dtype != torch.float32 or pred.ndim != 3 or pred.numel() == 0 or H < 1 or W < 1:
         raise ValueError(f"resize_prediction: pred must be a non-empty float32 [N,h,w] and size positive, got {pred.dtype} {tuple(pred.shape)} to {(H, W)}")
-    dev = pred.device if pred.is_cuda else torch.device(device)
-    if dev.type != "cuda":
-        raise ValueError(f"resize_prediction: needs a cuda device, got {device!r}")
+    dev = pred.device if pred.is_cuda else cuda_device(device, "resize_prediction")
     with torch.cuda.device(dev):
         x = pred.to(dev).contiguous()
         if (H, W) == tuple(x.shape[1:]):
@@ -166,17 +166,6 @@ def _as_tensor(a, name, dtypes, what):
     return a
 
 
-def _one_device(tensors, device, what):
-    """The device the CUDA tensors among `tensors` (None entries skipped) share, or torch.device(device) when none is on a device."""
-    import torch
-
-    on_dev = [t.device for t in tensors if t is not None and t.is_cuda]
-    dev = on_dev[0] if on_dev else torch.device(device)
-    if dev.type != "cuda" or any(d != dev for d in on_dev):
-        raise ValueError(f"{what}: needs one cuda device, got {device!r} / {[str(d) for d in on_dev]}")
-    return dev
-
-
 def _chunk_feeds(pred, gt, dev, size):
     """(pred_chunk, gt_chunk): frames lo .. hi-1 on the device, the prediction at gt's `size` (deterministic: the same bits every pass)."""
     on_device = lambda t, lo, hi: t[lo:hi].to(dev, non_blocking=False).contiguous()  # noqa: E731
@@ -210,7 +199,7 @@ def evaluate_depth(pred, gt, max_depth, max_eval_len=None, device="cuda", chunk_
     pred = _as_tensor(pred, "pred", (torch.float32,), "evaluate_depth")
     gt = _as_tensor(gt, "gt", (torch.float32, torch.float64), "evaluate_depth")
     pred, gt = _check_pair(pred, gt, max_eval_len, resize)
-    dev = _one_device((pred, gt), device, "evaluate_depth")
+    dev = one_device((pred, gt), device, "evaluate_depth")
     N, H, W = gt.shape
     px = H * W
     step = N if chunk_frames is None else int(chunk_frames)
@@ -344,7 +333,7 @@ def evaluate_tae(pred, gt, K, poses, max_depth, mask=None, device="cuda", chunk_
     gt = _as_tensor(gt, "gt", (torch.float32, torch.float64), "evaluate_tae")
     mask = None if mask is None else _as_tensor(mask, "mask", (torch.bool, torch.uint8), "evaluate_tae")
     cam_host = _check_tae(pred, gt, K, poses, mask, resize)
-    dev = _one_device((pred, gt, mask), device, "evaluate_tae")
+    dev = one_device((pred, gt, mask), device, "evaluate_tae")
     N, H, W = gt.shape
     px, P = H * W, N - 1
     if px >= 2 ** 31 - 1:

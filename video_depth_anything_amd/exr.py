@@ -22,7 +22,7 @@ import zlib
 
 import numpy as np
 
-from . import deflate
+from . import deflate, staging
 
 MAGIC = b"\x76\x2f\x31\x01"
 VERSION = 2
@@ -135,14 +135,6 @@ def encode_exr_numpy(depth, compress=None, info=None):
 
 
 # ------------------------------------------------------------------------------------------------------------------ the device
-def _cuda_device(device):
-    import torch
-    dev = torch.device("cuda" if device is None else device)
-    if dev.type != "cuda":
-        raise ValueError(f"exr: needs a cuda device, got {device!r}; encode_exr_numpy is the host twin")
-    return dev
-
-
 def _frames3(depths):
     if depths.ndim == 2:
         depths = depths[None]
@@ -151,17 +143,21 @@ def _frames3(depths):
     return depths
 
 
-def _encode_tensor(x, header_bytes):
-    """(payload uint8, offsets int64 [frames + 1]) of a cuda fp32 [n, h, w] tensor with dense frames, on its device and stream."""
-    import torch
-    from . import ops
-    n, h, w = x.shape
-    with torch.cuda.device(x.device):
-        work = torch.empty(ops.exr_workspace_bytes(n, h, w), dtype=torch.uint8, device=x.device)
-        payload = torch.empty(ops.exr_payload_bytes(n, h, w), dtype=torch.uint8, device=x.device)
-        offsets = torch.empty(n + 1, dtype=torch.int64, device=x.device)
-        ops.exr_zip(x, header_bytes, work, payload, offsets)
-    return payload, offsets
+class _Encoder:
+    """vda_exr_zip_f32's workspace and outputs for up to `cap` frames of h x w on `dev`, allocated once, and the call."""
+
+    def __init__(self, dev, cap, h, w):
+        import torch
+        from . import ops
+        self.ops = ops
+        self.work = torch.empty(ops.exr_workspace_bytes(cap, h, w), dtype=torch.uint8, device=dev)
+        self.payload = torch.empty(ops.exr_payload_bytes(cap, h, w), dtype=torch.uint8, device=dev)
+        self.offsets = torch.empty(cap + 1, dtype=torch.int64, device=dev)
+
+    def __call__(self, x, header_bytes):
+        """(payload uint8, offsets int64 [frames + 1]) of a cuda fp32 [n, h, w] tensor with dense frames, n <= cap."""
+        self.ops.exr_zip(x, header_bytes, self.work, self.payload, self.offsets)
+        return self.payload, self.offsets[:x.shape[0] + 1]
 
 
 def _dense(x):
@@ -178,48 +174,36 @@ def _files_of(payload, offsets, head):
 
 
 def _iter_files(depths, device, frames_per_block):
-    """The files of the frames, a staging block at a time. device None: the host writer with zlib.compress."""
+    """The files of the frames, a block of frames at a time: a cuda tensor is read in place, a host array goes through
+    staging.Staged. device None: the host writer with zlib.compress."""
     import torch
-    if isinstance(depths, torch.Tensor) and depths.is_cuda:
-        x = _frames3(depths)
-        if x.dtype != torch.float32:
-            x = x.float()
-        x = _dense(x)
-        n, h, w = x.shape
-        head = exr_header(w, h)
-        step = max(1, _STAGE_BYTES // (4 * h * w)) if frames_per_block is None else int(frames_per_block)
-        if step < 1:
-            raise ValueError(f"exr: frames_per_block must be at least 1, got {frames_per_block!r}")
-        for lo in range(0, n, step):
-            yield from _files_of(*_encode_tensor(x[lo:lo + step], len(head)), head)
-        return
-    if isinstance(depths, torch.Tensor):
-        depths = depths.numpy()
-    d = _frames3(depths if isinstance(depths, np.ndarray) else np.asarray(depths))
+    on_device = isinstance(depths, torch.Tensor) and depths.is_cuda
+    if on_device:
+        d = _frames3(depths)
+        d = _dense(d if d.dtype == torch.float32 else d.float())
+        dev = d.device
+    else:
+        if isinstance(depths, torch.Tensor):
+            depths = depths.numpy()
+        d = _frames3(depths if isinstance(depths, np.ndarray) else np.asarray(depths))
+        if device is None:
+            for frame in d:
+                yield encode_exr_numpy(frame, compress=zlib.compress)
+            return
+        dev = staging.cuda_device(device, "exr", "encode_exr_numpy")
     n, h, w = d.shape
-    if device is None:
-        for i in range(n):
-            yield encode_exr_numpy(d[i], compress=zlib.compress)
-        return
-    dev = _cuda_device(device)
-    from . import ops
     head = exr_header(w, h)
-    step = max(1, _STAGE_BYTES // (4 * h * w)) if frames_per_block is None else int(frames_per_block)
+    step = staging.frames_per_block(n, 4 * h * w, _STAGE_BYTES) if frames_per_block is None else min(int(frames_per_block), n)
     if step < 1:
         raise ValueError(f"exr: frames_per_block must be at least 1, got {frames_per_block!r}")
-    step = min(step, n)
     with torch.cuda.device(dev):
-        host = torch.empty((step, h, w), dtype=torch.float32).pin_memory()
-        dev_in = torch.empty((step, h, w), dtype=torch.float32, device=dev)
-        work = torch.empty(ops.exr_workspace_bytes(step, h, w), dtype=torch.uint8, device=dev)
-        payload = torch.empty(ops.exr_payload_bytes(step, h, w), dtype=torch.uint8, device=dev)
-        offsets = torch.empty(step + 1, dtype=torch.int64, device=dev)
-        for lo in range(0, n, step):
-            m = min(step, n - lo)
-            np.copyto(host.numpy()[:m], d[lo:lo + m], casting="same_kind")          # a memory map is read here, m frames of it
-            dev_in[:m].copy_(host[:m], non_blocking=True)
-            ops.exr_zip(dev_in[:m], len(head), work, payload, offsets)
-            yield from _files_of(payload, offsets[:m + 1], head)
+        encode = _Encoder(dev, step, h, w)
+        if on_device:
+            views = (d[lo:lo + step] for lo in range(0, n, step))
+        else:                                                                 # a memory map is read here, a block of it at a time
+            views = (x for _, _, x in staging.Staged(step, (h, w), torch.float32, dev).blocks(d, casting="same_kind"))
+        for x in views:
+            yield from _files_of(*encode(x, len(head)), head)
 
 
 def encode_exr(depths, device="cuda", frames_per_block=None):
@@ -233,10 +217,11 @@ def encode_exr(depths, device="cuda", frames_per_block=None):
         if x.dtype != torch.float32:
             raise ValueError(f"encode_exr: a cuda tensor must be float32, got {x.dtype}")
         x = _dense(x)
-        return _encode_tensor(x, len(exr_header(x.shape[2], x.shape[1])))
+        with torch.cuda.device(x.device):
+            return _Encoder(x.device, *x.shape)(x, len(exr_header(x.shape[2], x.shape[1])))
     if isinstance(depths, torch.Tensor):
         raise ValueError("encode_exr: takes a cuda tensor or a numpy array; encode_exr_numpy is the host twin")
-    _cuda_device(device)
+    staging.cuda_device(device, "exr", "encode_exr_numpy")
     return list(_iter_files(depths, device, frames_per_block))
 
 

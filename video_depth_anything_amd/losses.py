@@ -26,7 +26,7 @@ CPU path. The contract is in DESIGN.md 6g; in short, with every float32 value wi
 """
 import numpy as np
 
-from .evaluate import _one_device
+from .staging import one_device
 
 VARIANTS = ("lsq", "mad")
 LOSS_T = 256                 # threads per block of the reductions (csrc/losses.hip LS_T)
@@ -186,7 +186,7 @@ def _device_inputs(pred, y, mask, device, what):
 
     shape = _shape_checks(pred, y, mask, what)
     ts = [_as_tensor(pred), _as_tensor(y)] + ([] if mask is None else [_as_tensor(mask)])
-    dev = _one_device(ts, device, what)
+    dev = one_device(ts, device, what)
     with torch.cuda.device(dev):
         ts = [t.detach().to(dev).reshape(shape).contiguous() for t in ts]
         m = None

@@ -28,6 +28,8 @@ import struct
 
 import numpy as np
 
+from . import staging
+
 # ------------------------------------------------------------------------------------------------------------ ITU T.81 Annex K
 _QL = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
        18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99)
@@ -263,39 +265,25 @@ def encode_jpeg(frames, quality=90, device=None):
     lengths int64 [N] their sizes; frame i is jpeg_header(h, w, channels, quality) + payload[sum(lengths[:i]) :][: lengths[i]].
     A numpy array or memory map gives the list of complete JPEGs, the frames staged a block at a time (`device`, default "cuda")."""
     import torch
-    is_tensor = isinstance(frames, torch.Tensor)
-    if not is_tensor and not isinstance(frames, np.ndarray):
+    if not isinstance(frames, (torch.Tensor, np.ndarray)):
         frames = np.asarray(frames)
     n, h, w, ch = _check_frames(frames)
     _check_quality(quality)
-    if is_tensor and not frames.is_cuda:
-        raise ValueError("mjpeg: encode_jpeg takes a cuda tensor or a numpy array; encode_jpeg_numpy is the host twin")
-    dev = frames.device if is_tensor else torch.device("cuda" if device is None else device)
-    if dev.type != "cuda":
-        raise ValueError(f"mjpeg: needs a cuda device, got {device!r}; encode_jpeg_numpy is the host twin")
+    is_tensor, dev = staging.placement(frames, device, "mjpeg", "encode_jpeg_numpy", "encode_jpeg")
     from . import ops
     qt = _device_tables(quality, ch)
     with torch.cuda.device(dev):
-        if is_tensor:
-            x = frames.contiguous()
-            work = torch.empty(ops.mjpeg_workspace_bytes(n, h, w, ch), dtype=torch.uint8, device=dev)
-            payload = torch.empty(ops.mjpeg_out_bytes(n, h, w, ch), dtype=torch.uint8, device=dev)
-            lengths = torch.empty(n, dtype=torch.int64, device=dev)
-            ops.mjpeg_encode(x, qt, work, payload, lengths)
-            return payload, lengths
-        head = jpeg_header(h, w, ch, quality)
-        b = max(1, min(n, _BLOCK_BYTES // (h * w * ch)))
-        host_in = torch.empty((b, h, w) + ((3,) if ch == 3 else ()), dtype=torch.uint8).pin_memory()
-        dev_in = torch.empty_like(host_in, device=dev)
+        b = n if is_tensor else staging.frames_per_block(n, h * w * ch, _BLOCK_BYTES)          # frames per call
         work = torch.empty(ops.mjpeg_workspace_bytes(b, h, w, ch), dtype=torch.uint8, device=dev)
         payload = torch.empty(ops.mjpeg_out_bytes(b, h, w, ch), dtype=torch.uint8, device=dev)
         lengths = torch.empty(b, dtype=torch.int64, device=dev)
+        if is_tensor:
+            ops.mjpeg_encode(frames.contiguous(), qt, work, payload, lengths)
+            return payload, lengths
+        head = jpeg_header(h, w, ch, quality)
         out = []
-        for i in range(0, n, b):
-            m = min(b, n - i)
-            np.copyto(host_in.numpy()[:m], frames[i:i + m])
-            dev_in[:m].copy_(host_in[:m], non_blocking=True)
-            ops.mjpeg_encode(dev_in[:m], qt, work, payload, lengths)
+        for _, m, x in staging.Staged(b, frames.shape[1:], torch.uint8, dev).blocks(frames):
+            ops.mjpeg_encode(x, qt, work, payload, lengths)
             out += split_payload(head, payload, lengths[:m])
         return out
 
@@ -882,9 +870,7 @@ def decode_jpeg(jpegs, device="cuda", to_host=True):
     jpegs = [bytes(j) for j in jpegs]
     if not jpegs:
         raise ValueError("mjpeg: no frames")
-    dev = torch.device("cuda" if device is None else device)
-    if dev.type != "cuda":
-        raise ValueError(f"mjpeg: needs a cuda device, got {device!r}; decode_jpeg_numpy is the host twin")
+    dev = staging.cuda_device(device, "mjpeg", "decode_jpeg_numpy")
     from . import ops
     groups = _device_groups(jpegs)
     first = groups[0][0]

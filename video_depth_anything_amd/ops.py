@@ -57,6 +57,21 @@ def _req(t, dtype, name):
         raise ValueError(f"{name}: expected contiguous cuda {dtype}, got {t.dtype} {t.device} contiguous={t.is_contiguous()}")
 
 
+def _same_device(what, *tensors):
+    if len({t.device for t in tensors if t is not None}) != 1:
+        raise ValueError(f"{what}: the operands live on different devices")
+
+
+def _host_array(a, dtype, size, name, what, form=None):
+    """`a` must be a contiguous host numpy array of `dtype` and `size`: the number of entries, or the shape with None for any
+    extent. `form` words the error where "array of size entries" does not."""
+    import numpy as np
+    ok = isinstance(a, np.ndarray) and a.dtype == dtype and a.flags.c_contiguous
+    got, want = ((a.size,), (size,)) if ok and isinstance(size, int) else (getattr(a, "shape", ()), size)
+    if not ok or len(got) != len(want) or any(w not in (None, g) for g, w in zip(got, want)):
+        raise ValueError(f"{what}: {name} must be {form or f'a contiguous host {np.dtype(dtype).name} array of {size} entries'}")
+
+
 _zero_pages = {}
 
 
@@ -493,8 +508,7 @@ def pointcloud(depth, rgb, records, counts, workspace, fx, fy, cx, cy, max_depth
     _req(workspace, torch.uint8, "workspace")
     if depth.dim() != 3 or depth.numel() == 0 or tuple(rgb.shape) != tuple(depth.shape) + (3,):
         raise ValueError(f"pointcloud: depth {tuple(depth.shape)} and rgb {tuple(rgb.shape)} must be [n,h,w] and [n,h,w,3]")
-    if len({t.device for t in (depth, rgb, records, counts, workspace)}) != 1:
-        raise ValueError("pointcloud: the operands live on different devices")
+    _same_device("pointcloud", depth, rgb, records, counts, workspace)
     n, h, w = depth.shape
     if counts.numel() < n or records.numel() < n * pointcloud_frame_stride(h, w, record_f32):
         raise ValueError(f"pointcloud: counts ({counts.numel()}) or records ({records.numel()} bytes) too small for {n} frames of {h} x {w}")
@@ -514,8 +528,7 @@ def depth_vis(depth, minmax, lut, out, n=None):
         raise ValueError(f"depth_vis: bad sizes (n={n} of {depth.numel()} pixels, minmax {minmax.numel()}, out {out.numel()} bytes)")
     if lut is not None and tuple(lut.shape) != (256, 3):
         raise ValueError(f"depth_vis: lut must be [256,3], got {tuple(lut.shape)}")
-    if len({t.device for t in (depth, minmax, out) + (() if lut is None else (lut,))}) != 1:
-        raise ValueError("depth_vis: the operands live on different devices")
+    _same_device("depth_vis", depth, minmax, out, lut)
     check(lib.vda_depth_vis_u8(_p(depth), n, _p(minmax), _p(lut), _p(out), _stream(depth)), "vda_depth_vis_u8")
 
 
@@ -538,12 +551,10 @@ def mjpeg_encode(frames, qtables, workspace, out, lengths):
         raise ValueError(f"mjpeg_encode: frames must be [n,h,w,3] or [n,h,w] and not empty, got {tuple(frames.shape)}")
     n, h, w = frames.shape[:3]
     ch = 3 if frames.dim() == 4 else 1
-    if not isinstance(qtables, np.ndarray) or qtables.dtype != np.uint16 or qtables.size != 64 * (2 if ch == 3 else 1) or not qtables.flags.c_contiguous:
-        raise ValueError(f"mjpeg_encode: qtables must be a contiguous host uint16 array of {64 * (2 if ch == 3 else 1)} entries")
+    _host_array(qtables, np.uint16, 64 * (2 if ch == 3 else 1), "qtables", "mjpeg_encode")
     if lengths.numel() < n:
         raise ValueError(f"mjpeg_encode: lengths holds {lengths.numel()} entries, needs {n}")
-    if len({t.device for t in (frames, workspace, out, lengths)}) != 1:
-        raise ValueError("mjpeg_encode: the operands live on different devices")
+    _same_device("mjpeg_encode", frames, workspace, out, lengths)
     check(lib.vda_mjpeg_encode_u8(_p(frames), n, h, w, ch, qtables.ctypes.data_as(C.c_void_p), _p(workspace), workspace.numel(), _p(out), out.numel(),
                                   _p(lengths), _stream(frames)), "vda_mjpeg_encode_u8")
 
@@ -564,16 +575,12 @@ def mjpeg_decode(scan, intervals, tables, qtables, hs, vs, workspace, out, statu
         raise ValueError(f"mjpeg_decode: out must be [n,h,w,3] or [n,h,w] and not empty, got {tuple(out.shape)}")
     n, h, w = out.shape[:3]
     ch = 3 if out.dim() == 4 else 1
-    if not isinstance(intervals, np.ndarray) or intervals.dtype != np.int32 or intervals.ndim != 2 or intervals.shape[1] != 5 or not intervals.flags.c_contiguous:
-        raise ValueError("mjpeg_decode: intervals must be a contiguous host int32 array [k,5]")
-    if not isinstance(tables, np.ndarray) or tables.dtype != TABLES_DTYPE or tables.size != 1:
-        raise ValueError("mjpeg_decode: tables must be one host record of mjpeg.TABLES_DTYPE")
-    if not isinstance(qtables, np.ndarray) or qtables.dtype != np.uint16 or qtables.size != 64 * ch or not qtables.flags.c_contiguous:
-        raise ValueError(f"mjpeg_decode: qtables must be a contiguous host uint16 array of {64 * ch} entries")
+    _host_array(intervals, np.int32, (None, 5), "intervals", "mjpeg_decode", "a contiguous host int32 array [k,5]")
+    _host_array(tables, TABLES_DTYPE, 1, "tables", "mjpeg_decode", "one host record of mjpeg.TABLES_DTYPE")
+    _host_array(qtables, np.uint16, 64 * ch, "qtables", "mjpeg_decode")
     if status.numel() < n:
         raise ValueError(f"mjpeg_decode: status holds {status.numel()} entries, needs {n}")
-    if len({t.device for t in (scan, workspace, out, status)}) != 1:
-        raise ValueError("mjpeg_decode: the operands live on different devices")
+    _same_device("mjpeg_decode", scan, workspace, out, status)
     tables = np.ascontiguousarray(tables)
     check(lib.vda_mjpeg_decode_u8(_p(scan), scan.numel(), intervals.ctypes.data_as(C.c_void_p), intervals.shape[0], tables.ctypes.data_as(C.c_void_p),
                                   qtables.ctypes.data_as(C.c_void_p), n, h, w, ch, hs, vs, _p(workspace), workspace.numel(), _p(out), out.numel(),
@@ -602,8 +609,7 @@ def deflate(data, final, workspace, out, length, crcs):
     n = data.numel()
     if length.numel() < 1 or crcs.numel() < max(1, -(-n // 16384)):
         raise ValueError(f"deflate: length holds {length.numel()} entries (needs 1), crcs {crcs.numel()} (needs {max(1, -(-n // 16384))})")
-    if len({t.device for t in (data, workspace, out, length, crcs)}) != 1:
-        raise ValueError("deflate: the operands live on different devices")
+    _same_device("deflate", data, workspace, out, length, crcs)
     check(lib.vda_deflate_u8(_p(data), n, 1 if final else 0, _p(workspace), workspace.numel(), _p(out), out.numel(), _p(length), _p(crcs),
                              _stream(out)), "vda_deflate_u8")
 
@@ -631,8 +637,7 @@ def exr_zip(depth, header_bytes, workspace, payload, offsets):
     _req(workspace, torch.uint8, "workspace"), _req(payload, torch.uint8, "payload"), _req(offsets, torch.int64, "offsets")
     if offsets.numel() < n + 1:
         raise ValueError(f"exr_zip: offsets holds {offsets.numel()} entries, needs {n + 1}")
-    if len({t.device for t in (depth, workspace, payload, offsets)}) != 1:
-        raise ValueError("exr_zip: the operands live on different devices")
+    _same_device("exr_zip", depth, workspace, payload, offsets)
     check(lib.vda_exr_zip_f32(_p(depth), n, h, w, depth.stride(0) if n > 1 else h * w, int(header_bytes), _p(workspace), workspace.numel(),
                               _p(payload), payload.numel(), _p(offsets), _stream(payload)), "vda_exr_zip_f32")
 
@@ -648,8 +653,7 @@ def _loss_planes(pred, y, mask, what):
     if pred.dim() < 3 or pred.shape != y.shape or pred.numel() == 0 or (mask is not None and mask.shape != pred.shape):
         raise ValueError(f"{what}: pred {tuple(pred.shape)}, y {tuple(y.shape)} and mask "
                          f"{None if mask is None else tuple(mask.shape)} must be one non-empty [..,H,W]")
-    if len({t.device for t in (pred, y) + (() if mask is None else (mask,))}) != 1:
-        raise ValueError(f"{what}: the operands live on different devices")
+    _same_device(what, pred, y, mask)
     H, W = pred.shape[-2:]
     return pred.numel() // (H * W), H, W
 

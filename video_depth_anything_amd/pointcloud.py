@@ -161,15 +161,13 @@ class _Unprojector:
 
     def __init__(self, frames, h, w, fx, fy, cx, cy, max_depth, dtype, device):
         import torch
-        from . import ops
+        from . import ops, staging
         self.ops, self.torch = ops, torch
         self.rs = _record_size(dtype)
         self.f32 = dtype == "float32"
         self.h, self.w = h, w
         self.fx, self.fy, self.cx, self.cy, self.max_depth = _intrinsics(h, w, fx, fy, cx, cy, max_depth)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError(f"pointcloud: needs a cuda device, got {device!r}")
+        self.device = staging.cuda_device(device, "pointcloud")
         self.stride = ops.pointcloud_frame_stride(h, w, self.f32)
         with torch.cuda.device(self.device):
             self.records = torch.empty(frames * self.stride, dtype=torch.uint8, device=self.device)
@@ -188,11 +186,11 @@ class _Unprojector:
 
 
 def _device_of(depths, frames, device):
+    """The device the cuda tensors among depths and frames share; `device` when neither is on one."""
     import torch
-    for t in (depths, frames):
-        if isinstance(t, torch.Tensor) and t.is_cuda:
-            return t.device
-    return torch.device(device)
+    from . import staging
+    on_dev = [t for t in (depths, frames) if isinstance(t, torch.Tensor) and t.is_cuda]
+    return staging.one_device(on_dev, device, "pointcloud") if on_dev else device
 
 
 def unproject(depths, frames, fx, fy, cx=None, cy=None, max_depth=None, dtype="float64", device="cuda"):

@@ -15,6 +15,7 @@ so the device reproduces it byte for byte. Equal sizes give the input back; an e
 """
 import numpy as np
 
+from . import staging
 from .evaluate import _axis_taps
 
 COEF_ONE = 2048                              # cv2's INTER_RESIZE_COEF_SCALE = 1 << 11
@@ -75,32 +76,21 @@ def resize_frames(frames, H, W, device="cuda"):
     the source is ever on the device. Anything but uint8, a host tensor or a device that is not cuda is an error: there is no CPU
     path behind this name."""
     import torch
-    is_tensor = isinstance(frames, torch.Tensor)
-    if not is_tensor and not isinstance(frames, np.ndarray):
+    if not isinstance(frames, (torch.Tensor, np.ndarray)):
         frames = np.asarray(frames)
     H, W = int(H), int(W)
     _check(frames, H, W, "resize_frames")
-    if is_tensor and not frames.is_cuda:
-        raise ValueError("resize_frames: takes a cuda tensor or a numpy array; resize_frames_numpy is the host twin")
-    dev = frames.device if is_tensor else torch.device("cuda" if device is None else device)
-    if dev.type != "cuda":
-        raise ValueError(f"resize_frames: needs a cuda device, got {device!r}; resize_frames_numpy is the host twin")
+    is_tensor, dev = staging.placement(frames, device, "resize_frames", "resize_frames_numpy")
     from . import ops
     n, (h, w), tail = frames.shape[0], frames.shape[1:3], tuple(frames.shape[3:])
     with torch.cuda.device(dev):
-        if is_tensor:
-            out = torch.empty((n, H, W) + tail, dtype=torch.uint8, device=dev)
-            ops.resize_linear_u8(frames.contiguous(), out)
-            return out
-        b = max(1, min(n, _BLOCK_BYTES // (h * w * (3 if tail else 1))))
-        host_in = torch.empty((b, h, w) + tail, dtype=torch.uint8).pin_memory()
-        dev_in = torch.empty_like(host_in, device=dev)
+        b = n if is_tensor else staging.frames_per_block(n, h * w * (3 if tail else 1), _BLOCK_BYTES)      # frames per call
         dev_out = torch.empty((b, H, W) + tail, dtype=torch.uint8, device=dev)
+        if is_tensor:
+            ops.resize_linear_u8(frames.contiguous(), dev_out)
+            return dev_out
         out = np.empty((n, H, W) + tail, np.uint8)
-        for i in range(0, n, b):
-            m = min(b, n - i)
-            np.copyto(host_in.numpy()[:m], frames[i:i + m])
-            dev_in[:m].copy_(host_in[:m], non_blocking=True)
-            ops.resize_linear_u8(dev_in[:m], dev_out[:m])
-            out[i:i + m] = dev_out[:m].cpu().numpy()                        # synchronises: host_in is free again
+        for i, m, x in staging.Staged(b, (h, w) + tail, torch.uint8, dev).blocks(frames):
+            ops.resize_linear_u8(x, dev_out[:m])
+            out[i:i + m] = dev_out[:m].cpu().numpy()
         return out

@@ -23,6 +23,8 @@ vda_minmax_accum_f32 on the same stream, which never takes a NaN. A given range 
 """
 import numpy as np
 
+from . import staging
+
 _BLOCK_PIXELS = 1 << 25                       # pixels staged at a time by the numpy paths: 128 MB of depth, 96 MB of colour
 
 _INFERNO = bytes.fromhex(
@@ -64,7 +66,7 @@ def _check(depths):
 
 
 def _blocks(n, px):
-    b = max(1, min(n, _BLOCK_PIXELS // px))
+    b = staging.frames_per_block(n, px, _BLOCK_PIXELS)
     return [slice(i, min(i + b, n)) for i in range(0, n, b)]
 
 
@@ -115,16 +117,11 @@ def colorize(depths, d_min=None, d_max=None, grayscale=False, palette=None, devi
     through one bounded pair of staging buffers a block at a time (`device`, default "cuda"), so a video that does not fit in
     memory or in one allocation still works."""
     import torch
-    is_tensor = isinstance(depths, torch.Tensor)
-    if not is_tensor and not isinstance(depths, np.ndarray):
+    if not isinstance(depths, (torch.Tensor, np.ndarray)):
         depths = np.asarray(depths)
     shape = _check(depths)
     table = None if grayscale else _table(palette)
-    if is_tensor and not depths.is_cuda:
-        raise ValueError("visualize: colorize takes a cuda tensor or a numpy array; colorize_numpy is the host twin")
-    dev = depths.device if is_tensor else torch.device("cuda" if device is None else device)
-    if dev.type != "cuda":
-        raise ValueError(f"visualize: needs a cuda device, got {device!r}; colorize_numpy is the host twin")
+    is_tensor, dev = staging.placement(depths, device, "visualize", "colorize_numpy", "colorize")
     from . import ops
     ch = 1 if grayscale else 3
     out_shape = shape + (() if grayscale else (3,))
@@ -149,17 +146,15 @@ def colorize(depths, d_min=None, d_max=None, grayscale=False, palette=None, devi
         blocks = _blocks(n, px)
         lo, hi = _host_range(frames, blocks, d_min, d_max)
         minmax = torch.tensor([float(lo), float(hi)], dtype=torch.float32, device=dev)
-        cap = (blocks[0].stop - blocks[0].start) * px
-        host_in, host_out = torch.empty(cap, dtype=torch.float32).pin_memory(), torch.empty(cap * ch, dtype=torch.uint8).pin_memory()
-        dev_in, dev_out = torch.empty(cap, dtype=torch.float32, device=dev), torch.empty(cap * ch, dtype=torch.uint8, device=dev)
+        staged = staging.Staged(blocks[0].stop, frames.shape[1:], torch.float32, dev)
+        host_out = torch.empty(staged.cap * px * ch, dtype=torch.uint8).pin_memory()
+        dev_out = torch.empty(staged.cap * px * ch, dtype=torch.uint8, device=dev)
         out = np.empty(frames.shape + (() if grayscale else (3,)), dtype=np.uint8)
         flat_out = out.reshape(n, px * ch)
-        for b in blocks:
-            m = (b.stop - b.start) * px
-            np.copyto(host_in.numpy()[:m].reshape((b.stop - b.start,) + frames.shape[1:]), frames[b])
-            dev_in[:m].copy_(host_in[:m], non_blocking=True)
-            ops.depth_vis(dev_in, minmax, lut, dev_out, n=m)
-            host_out[:m * ch].copy_(dev_out[:m * ch], non_blocking=True)
+        for i, m, x in staged.blocks(frames):
+            k = m * px * ch
+            ops.depth_vis(x, minmax, lut, dev_out)
+            host_out[:k].copy_(dev_out[:k], non_blocking=True)
             torch.cuda.current_stream().synchronize()
-            np.copyto(flat_out[b].reshape(-1), host_out.numpy()[:m * ch])
+            np.copyto(flat_out[i:i + m].reshape(-1), host_out.numpy()[:k])
         return out.reshape(out_shape)
